@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: rendered rays/s of the ray-marching hot path at 480x640 x 128 samples.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N>1 without a torchrun environment: this process starts N fresh children (python -m torch.distributed.run, one
         rank per GPU) BEFORE it touches the GPU and relays rank 0's line; launched by torch.distributed.run it is a rank.
     python bench.py --config c5 [--gpus N]                 BASELINE config C5 (8 objects, mixed resolution, N=256):
@@ -10,8 +10,16 @@
 A step = one pass of the hot path over one full 480x640 image per GPU through the product API
 (Graph.render_by_slices, mode='val': fused ray-gen + bounds + stratified samples -> fused
 posenc + static/transient/light MLP -> per-ray composite), synthetic Duck-like scene, inputs
-resident in HBM.  Images shard by batch across GPUs (weak scaling, no data-path collective: rays
-are independent).  Rank 0 prints ONE JSON line with the contract fields plus
+resident in HBM, the stratified jitter drawn from a fixed seed (same arguments, same inputs).
+Images shard by batch across GPUs (weak scaling, no data-path collective: rays are independent,
+SURVEY 8e).
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and nothing else.
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned as DIR/<key>.npy
+(float32): the per-ray maps whole, the per-sample maps (alpha_*, density) at a fixed seeded sample of
+DUMP_RAYS rays (numpy RandomState(DUMP_SEED), sorted ray indices).
+--full: everything else, in the same line (untimed legs, after the timed steps):
   roofline     : the dominant kernel (fused MLP, MFMA-bound), algorithmic FLOP / HIP-event time; its FLAT scalar members also
                  carry the clock held under the kernel (clock_ghz), the exact-fp32 kernel (exact_fp32_*), the HBM-bound kernels
                  (hbm_<kernel>_frac / _ms / _traffic_ratio) and the training iteration at the BASELINE size (train_c3_*)
@@ -38,6 +46,8 @@ MLP_FLOP_PER_SAMPLE = 1_821_184          # 2 x 910,592 MAC
 MFMA_PEAK_TFLOPS = {"fp32": 157.3, "f16x3": 2500.0}
 TRAIN_FLOP_PER_SAMPLE = 3_220_992        # recording forward (1,821,184) + backward of the two heads (SURVEY 8d / DESIGN 4)
 ISSUED_PER_ALGORITHMIC = {"fp32": 1, "f16x3": 3}    # f16x3 issues hi*hi + hi*lo + lo*hi per product
+SEED = 0                                 # torch's generators (stratified jitter: Philox seeded by torch.initial_seed())
+DUMP_RAYS, DUMP_SEED = 8192, 0           # --dump-outputs: rays kept of the per-sample maps (8192 x 128 x 4 floats = 16 MB)
 
 
 def build_scene(device, seed):
@@ -601,6 +611,27 @@ def emit(line):
     out.flush()
 
 
+def dump_outputs(out_dir, ret):
+    """--dump-outputs: the maps render_by_slices returned in the last timed step as out_dir/<key>.npy (float32).  Per-ray maps
+    [1, H*W, c] whole (17 MB); per-sample maps [1, H*W, N(, 2)] at the DUMP_RAYS rays a RandomState(DUMP_SEED) draw picks (sorted),
+    which keeps the files under 64 MB together.  Keys the render left None (not materialised) are not written."""
+    from texpose_amd.graph import RENDER_KEYS
+    os.makedirs(out_dir, exist_ok=True)
+    rays = np.sort(np.random.RandomState(DUMP_SEED).choice(H * W, DUMP_RAYS, replace=False))
+    written = {}
+    for k in RENDER_KEYS:
+        v = ret[k]
+        if v is None:
+            continue
+        v = v.detach()
+        if v.dim() >= 3 and v.shape[2] == N_SAMPLES:
+            v = v[:, torch.from_numpy(rays).to(v.device)]
+        a = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = list(a.shape)
+    return written
+
+
 def spawn_ranks(n_gpus, argv):
     """`python bench.py --gpus N` without a torchrun environment: start N fresh rank processes as CHILDREN
     (python -m torch.distributed.run, rendezvous on 127.0.0.1 with a free port), pass their output through and return the
@@ -621,10 +652,16 @@ def spawn_ranks(n_gpus, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training leg (train iters/s)")
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (one 480x640 image per GPU each)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<key>.npy (float32; per-sample maps "
+                         "at a fixed seeded sample of rays)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs: MFMA / HBM rooflines, exact-fp32 and per-ray-only renders, clock probe, "
+                         "training legs, masked evaluation, trained weights, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the training leg (train iters/s)")
     ap.add_argument("--precision", choices=["f16x3", "fp32"], default="f16x3",
                     help="MLP arithmetic: f16x3 = split-fp16 products on the f16 matrix cores (fp32-grade accuracy, "
                          "default); fp32 = exact fp32 MFMA")
@@ -634,6 +671,10 @@ def main():
     ap.add_argument("--spawn-check", action="store_true",
                     help="launcher self-test without a GPU: the ranks meet in a gloo all-reduce and rank 0 prints the world size")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.config != "c2":
+        ap.error("--dump-outputs applies to the c2 workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # driver-style call `python bench.py --gpus N`: nothing in this process has touched the GPU yet (importing torch
@@ -685,6 +726,7 @@ def main():
     from texpose_amd import dist as tdist
     ranks_seen = tdist.ranks_seen(device=device)                    # SUM all-reduce of ones: RCCL's own view of the job (1 rank: 1)
 
+    torch.manual_seed(SEED)                                         # the jitter's Philox seed: same inputs from run to run
     sc, params, emb_t, emb_l = build_scene(device, seed=rank)       # one image per rank
     graph, opt = make_graph(device, params, emb_t, emb_l, args.precision)
     pose, intr = sc["pose"].to(device), sc["intr"].to(device)
@@ -720,8 +762,10 @@ def main():
 
     for _ in range(args.warmup):
         ret = step()
-    ops.mlp_forward = timing_into(mlp_events)
-    ops.raygen, ops.composite_fwd = timing_into(raygen_events, orig_raygen), timing_into(comp_events, orig_comp)
+    if args.full:
+        # the rooflines of --full: HIP events around the MLP, ray-gen and composite launches of the timed steps
+        ops.mlp_forward = timing_into(mlp_events)
+        ops.raygen, ops.composite_fwd = timing_into(raygen_events, orig_raygen), timing_into(comp_events, orig_comp)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -735,6 +779,36 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
+    value = world * H * W * args.steps / dt
+    headline = {
+        "metric": "rendered rays/sec (480x640x128 samples) + train iters/sec",
+        "value": value,
+        "unit": "rays/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "dtype": "f32" if args.precision == "fp32" else "f32 carried as 2xf16 (f16x3 products, f32 accumulate)",
+        "data": "synthetic",
+        "config": {"workload": "Duck-like synthetic scene 480x640, 128 samples/ray, batch=1 image per GPU, "
+                               "forward render (render_by_slices mode='val', all pixels), per-sample outputs "
+                               "materialised", "rays_per_step_per_gpu": H * W, "samples_per_ray": N_SAMPLES,
+                   "mlp_precision": args.precision,
+                   "parallelism": "images sharded across %d GPU(s), no collective" % world},
+    }
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, ret)
+    if not args.full:
+        ops.check_mlp_status(device)
+        if rank == 0:
+            emit(dict(headline, full=False, dumped=dumped))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     mlp_ms = float(np.mean([a.elapsed_time(b) for a, b in mlp_events]))
     launches_per_step = len(mlp_events) / args.steps
     samples_per_launch = H * W * N_SAMPLES / launches_per_step
@@ -867,7 +941,6 @@ def main():
             legs_failed.append("a leg on another rank")
 
     if rank == 0:
-        value = world * H * W * args.steps / dt
         rl = roofline(args.precision, mlp_ms, samples_per_launch)
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
@@ -928,28 +1001,14 @@ def main():
             if "error" not in cpu:
                 line["gpu_over_cpu"] = value / cpu["value"]
         line["legs_failed"] = list(legs_failed)
+        line.update(headline)
         line.update({
-            "metric": "rendered rays/sec (480x640x128 samples) + train iters/sec",
-            "value": value,
-            "unit": "rays/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
             # BASELINE.md holds no published number for this metric (section 1); the figure beside it that north_star asks for is the
             # CPU path timed on this box's host cores in this very run (>= 20x is north_star's bar), so that ratio is reported here
             "vs_baseline": (value / cpu["value"]) if cpu is not None and "error" not in cpu else None,
             "vs_baseline_note": "no published reference number exists (BASELINE.md section 1): value / cpu_baseline.value of this run",
-            "dtype": "f32" if args.precision == "fp32" else "f32 carried as 2xf16 (f16x3 products, f32 accumulate)",
-            "data": "synthetic",
-            "config": {"workload": "Duck-like synthetic scene 480x640, 128 samples/ray, batch=1 image per GPU, "
-                                   "forward render (render_by_slices mode='val', all pixels), per-sample outputs "
-                                   "materialised", "rays_per_step_per_gpu": H * W, "samples_per_ray": N_SAMPLES,
-                       "mlp_precision": args.precision,
-                       "parallelism": "images sharded across %d GPU(s), no collective" % world},
+            "full": True,
+            "dumped": dumped,
             "roofline": rl,
         })
         r3 = lambda v: None if v is None else float("%.4g" % v)

@@ -294,6 +294,41 @@ def test_bench_byte_model_and_host_topology():
     assert sockets >= 1 and 1 <= phys <= avail and isinstance(model, str)
 
 
+def test_bench_dump_outputs_and_step_arguments(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): every map render_by_slices returns as float32 .npy, the per-sample maps at the same
+    fixed sample of rays every time, under 64 MB in all; bench.py refuses a run without timed steps."""
+    import importlib.util
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from texpose_amd.graph import RENDER_KEYS
+    HW, N = bench.H * bench.W, bench.N_SAMPLES
+    ramp = lambda *s: torch.arange(HW, dtype=torch.float32).view(1, HW, *([1] * len(s))).expand(1, HW, *s)
+    ret = AttrDict({k: ramp(3) for k in RENDER_KEYS})
+    for k in ("opacity", "opacity_static", "opacity_transient", "uncert", "depth"):
+        ret[k] = ramp(1)
+    ret.alpha_static, ret.density = ramp(N), ramp(N, 2)
+    ret.alpha_transient = None                                       # (not materialised: not written)
+    a, b = tmp_path / "a", tmp_path / "b"
+    shapes = bench.dump_outputs(str(a), ret)
+    assert bench.dump_outputs(str(b), ret) == shapes
+    assert sorted(shapes) == sorted(k for k in RENDER_KEYS if k != "alpha_transient")
+    assert shapes["rgb"] == [1, HW, 3] and shapes["density"] == [1, bench.DUMP_RAYS, N, 2]
+    total = 0
+    for k in shapes:
+        x, y = np.load(a / (k + ".npy")), np.load(b / (k + ".npy"))
+        assert x.dtype == np.float32 and list(x.shape) == shapes[k] and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 * 2 ** 20
+    rays = np.load(a / "alpha_static.npy")[0, :, 0]
+    assert len(np.unique(rays)) == bench.DUMP_RAYS and np.all(np.diff(rays) > 0) and rays[-1] < HW
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_disc_step_schedule_structure_and_eligibility():
     """texpose_amd/disc_step.py (K16) covers the [conv4s2, InstanceNorm, LeakyReLU]* + full-map ladders (patch 16 / 32) and says
     why not for the others; it is never eligible for CPU tensors (the caller keeps its autograd form there), and the prefetch

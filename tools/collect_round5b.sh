@@ -4,7 +4,7 @@ T=${1:-r5c}
 mkdir -p gpurun_out/$T
 export TMPDIR=/tmp
 O=gpurun_out/$T
-( time timeout 1500 python bench.py > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_wall.txt
+( time timeout 1500 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_wall.txt
 python3 tools/chain_probe.py 50 > $O/chain_probe.txt 2>&1
 python3 tools/boundary_probe.py 64 > $O/boundary_probe.txt 2>&1
 ( echo "## strict (the calling stream waits for both optimiser steps)"; python3 tools/linear_timeline.py 50 2>&1 | tail -16

@@ -4,9 +4,9 @@ T=${1:-r6}
 mkdir -p gpurun_out/$T
 export TMPDIR=/tmp
 O=gpurun_out/$T
-( time timeout 1500 python bench.py > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_wall.txt
+( time timeout 1500 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_wall.txt
 # the same command under rocprofv3 --kernel-trace --stats (kernel averages must agree with the line's HIP-event figures)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof/stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof/stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
 f=$(find $O/prof/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv
 # fabric traffic of the two MLP forward kernels (one counter per pass; KiB, FETCH_SIZE x2 on gfx950) + issue-side counters of the f16x3 one
 pass() { local name=$1 prec=$2; shift 2

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from texpose_amd.gan_modules import Discriminator, PerceptualLoss
 from texpose_amd.graph import Graph
