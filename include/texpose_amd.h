@@ -26,7 +26,7 @@ extern "C" {
 
 typedef void* tp_stream_t; /* hipStream_t */
 
-#define TP_ABI_VERSION 13
+#define TP_ABI_VERSION 14
 
 int tp_abi_version(void);
 const char* tp_last_error(void);
@@ -143,7 +143,8 @@ size_t tp_mlp_packed_bytes(void);
 /* Which parts to (re)pack: the trunk is frozen, the heads change every optimiser step. */
 enum { TP_PACK_TRUNK = 1, TP_PACK_HEADS = 2, TP_PACK_ALL = 3,
        TP_PACK_F16X3 = 4 /* OR-ed in: build the split-fp16 (hi+lo) stream of the TP_MLP_F16X3 forward; same size */,
-       TP_PACK_RAYBIAS = 8 /* OR-ed in with TP_PACK_F16X3: the stream variant of tp_mlp_fwd_args.ray_bias (same buffer size) */ };
+       TP_PACK_RAYBIAS = 8 /* OR-ed in with TP_PACK_F16X3 or TP_PACK_F16: the stream variant of tp_mlp_fwd_args.ray_bias (same buffer size) */,
+       TP_PACK_F16 = 16 /* OR-ed in: build the single-fp16 stream of the TP_MLP_F16 forward (inference only); same buffer size */ };
 int tp_mlp_pack(const tp_mlp_weights* w /*host struct of device ptrs*/, int parts, void* packed, tp_stream_t stream);
 /* Training (TP_MLP_F16X3): everything that is rebuilt from the HEAD weights after an optimiser step, in one launch: the head chunks
  * and head biases of the f16x3 forward stream `packed` (what tp_mlp_pack(TP_PACK_HEADS | TP_PACK_F16X3) writes) and, when packed_t is
@@ -172,14 +173,15 @@ typedef struct tp_mlp_fwd_args {
   float* uncert;           /* [B,R,N,1]   out */
   float* saved;            /* optional activations for tp_mlp_bwd (tp_mlp_saved_bytes) or NULL */
   void* workspace;         /* tp_mlp_workspace_bytes */
-  int precision;           /* TP_MLP_FP32 (exact fp32 MFMA) or TP_MLP_F16X3 (packed with TP_PACK_F16X3) */
-  int* status;             /* TP_MLP_F16X3: device word, bit 0 is set if an activation left the fp16 range */
-  unsigned int* act_max;   /* TP_MLP_F16X3, optional (may be NULL): device word that receives, by atomic max, the fp32 bit
+  int precision;           /* TP_MLP_FP32 (exact fp32 MFMA), TP_MLP_F16X3 (packed with TP_PACK_F16X3) or TP_MLP_F16 (packed with
+                              TP_PACK_F16; no `saved`, no `density_noise`: inference only) */
+  int* status;             /* TP_MLP_F16X3 / TP_MLP_F16: device word, bit 0 is set if an activation left the fp16 range */
+  unsigned int* act_max;   /* TP_MLP_F16X3 / TP_MLP_F16, optional (may be NULL): device word that receives, by atomic max, the fp32 bit
                               pattern of the largest hidden activation handed to the matrix cores in this call (post-ReLU,
                               its fp16 hi part: 11 significant bits).  The range guard fires at 6e4; this word says how far
                               below it a network runs.  Zero it before the calls to be covered. */
-  float* ray_bias;         /* optional (NULL = off).  TP_MLP_F16X3 without `saved`, input form A, N % 128 == 0 (every 128-sample tile
-                              lies inside one ray), `packed` built with TP_PACK_F16X3 | TP_PACK_RAYBIAS: device scratch of
+  float* ray_bias;         /* optional (NULL = off).  TP_MLP_F16X3 or TP_MLP_F16 without `saved`, input form A, N % 128 == 0 (every
+                              128-sample tile lies inside one ray), `packed` built with TP_PACK_F16X3 (TP_PACK_F16) | TP_PACK_RAYBIAS: device scratch of
                               tp_mlp_ray_bias_bytes(B, R).  The inputs of mlp_rgb.0 that are constant along a ray (view encoding 27,
                               light code 48 of its 334 columns; reference layers/nerf_static_transient_light.py:104-118) and the
                               transient code of mlp_trans.0 (:127-129) are then contracted once per ray / image in fp32 by a
@@ -193,7 +195,12 @@ size_t tp_mlp_ray_bias_bytes(int B, int R);
  * accumulated in fp32 on the f16 matrix cores (16x the fp32-MFMA rate / 3).  Measured error vs an fp64 oracle is
  * within 1.3x of plain fp32.  Requires |activation| < 6e4 (see `status`).  With `saved` it writes
  * the same fp32 activation record as TP_MLP_FP32 (the backward kernels do not depend on how the forward was computed). */
-enum { TP_MLP_FP32 = 0, TP_MLP_F16X3 = 1 };
+/* TP_MLP_F16 (inference only, not fp32-grade): ONE fp16 product per multiply-add with fp32 accumulation on the f16 matrix cores,
+ * 3x fewer MFMAs than TP_MLP_F16X3 and half the weight stream.  The 256-wide layers (trunk, hidden layers of both heads, and the
+ * encoding / latent inputs that feed them) use weights rounded to fp16 (nearest even) once at pack time and activations rounded
+ * to fp16 (nearest even) as they are consumed -- about 2^-11 relative per operand.  The narrow output layers (density, transient,
+ * rgb) and the per-ray bias pre-kernels keep the TP_MLP_F16X3 arithmetic.  Range guard as TP_MLP_F16X3 (`status`, `act_max`). */
+enum { TP_MLP_FP32 = 0, TP_MLP_F16X3 = 1, TP_MLP_F16 = 2 };
 
 int tp_mlp_fwd(const tp_mlp_fwd_args* args, tp_stream_t stream);
 
@@ -284,14 +291,15 @@ typedef struct tp_render_eval_args {
   const void* packed;      /* tp_mlp_pack output for `precision` */
   const float* lat_trans;  /* [B,16] */
   const float* lat_light;  /* [B,48] */
-  int precision;           /* TP_MLP_FP32 or TP_MLP_F16X3 */
+  int precision;           /* TP_MLP_FP32, TP_MLP_F16X3 or TP_MLP_F16 */
   int* status;             /* as in tp_mlp_fwd_args (may be NULL) */
   float min_uncert;
   void* workspace;         /* tp_render_eval_workspace_bytes(B, R, N) */
   float* out_ray;          /* [B*R,14] out, layout of tp_composite_args.out_ray */
   float* alpha_static;     /* [B*R,N] out or NULL */
   float* alpha_transient;  /* [B*R,N] out or NULL */
-  int packed_ray_bias;     /* non-zero: `packed` is the TP_PACK_F16X3 | TP_PACK_RAYBIAS stream (precision TP_MLP_F16X3, N % 128 == 0) and
+  int packed_ray_bias;     /* non-zero: `packed` is the TP_PACK_F16X3 (TP_PACK_F16) | TP_PACK_RAYBIAS stream (precision TP_MLP_F16X3
+                              or TP_MLP_F16, N % 128 == 0) and
                               the MLP runs in its ray-bias form (tp_mlp_fwd_args.ray_bias; the scratch is part of `workspace`) */
 } tp_render_eval_args;
 size_t tp_render_eval_workspace_bytes(int B, int R, int N);   /* (includes the ray-bias scratch) */

@@ -1,0 +1,52 @@
+"""The inference-only single-product MLP arithmetic (arch.mlp_precision = "f16") at the levels that need no GPU: options, the
+precision tables of the Python layer and the constants of the C header."""
+import os
+import re
+
+import pytest
+
+from texpose_amd import ops
+from texpose_amd.nerf import NeRF
+from texpose_amd.options import default_options
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "texpose_amd.h")
+
+
+def _opt(**arch):
+    opt = default_options(H=16, W=16, device="cpu")
+    for k, v in arch.items():
+        setattr(opt.arch, k, v)
+    return opt
+
+
+def test_nerf_accepts_f16_for_rendering():
+    nerf = NeRF(_opt(mlp_precision="f16"))
+    assert nerf.precision == "f16" and nerf.train_precision == "f16x3"
+
+
+def test_nerf_rejects_f16_for_training():
+    with pytest.raises(ValueError, match="inference-only"):
+        NeRF(_opt(mlp_train_precision="f16"))
+
+
+def test_precision_tables_know_f16():
+    assert ops.PRECISIONS["f16"] == ops.MLP_F16 == 2
+    assert ops.PRECISIONS["fp32"] == 0 and ops.PRECISIONS["f16x3"] == 1
+    assert ops.ray_bias_applies("f16", 128, False, True)
+    assert not ops.ray_bias_applies("f16", 64, False, True)
+    assert not ops.ray_bias_applies("f16", 128, True, True)
+    assert not ops.ray_bias_applies("f16", 128, False, False)
+
+
+def _enum(name):
+    m = re.search(r"\b%s\s*=\s*(\d+)" % name, open(HEADER).read())
+    assert m, name
+    return int(m.group(1))
+
+
+def test_header_constants_match_python():
+    assert _enum("TP_MLP_F16") == ops.MLP_F16
+    assert _enum("TP_PACK_F16") == ops.PACK_F16
+    assert _enum("TP_MLP_F16X3") == ops.MLP_F16X3 and _enum("TP_PACK_RAYBIAS") == ops.PACK_RAYBIAS
+    flags = (ops.PACK_TRUNK, ops.PACK_HEADS, ops.PACK_F16X3, ops.PACK_RAYBIAS, ops.PACK_F16)
+    assert len({f for f in flags}) == len(flags) and all(f & ops.PACK_F16 == 0 for f in flags[:-1])

@@ -59,6 +59,8 @@ class _Mlp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, nerf, need_grad, density_noise, lat_trans, lat_light, center, ray, depth, points, ray_unit, *head_params):
         precision = nerf.train_precision if need_grad else nerf.precision
+        if density_noise is not None and precision in ops.INFERENCE_ONLY_PRECISIONS:
+            precision = nerf.train_precision          # (a train-mode forward without autograd: density noise is a training input)
         # evaluation renders with whole tiles inside one ray: view / light / transient inputs as a per-ray bias (ops.ray_bias_applies)
         rb = ops.ray_bias_applies(precision, depth.numel() // (center.shape[0] * center.shape[1]) if center is not None else 0,
                                   bool(need_grad), center is not None)

@@ -746,6 +746,152 @@ def gen_dg_finish(src):
     return L
 
 
+# ====================================================================================================== SINGLE PRODUCT ("f16")
+# The inference-only arithmetic TP_MLP_F16 (mlp_fwd_f16x3.hip, mlp_fwd_f16x3_kernel<.., F16 = true>): ONE v_mfma_f32_32x32x16_f16 per
+# (k-step, tile) pair, fp16 weights (rounded to nearest once at pack time, no 2^8 pre-scale) times fp16 activations (rounded to
+# nearest by v_cvt_pk_f16_f32 while the consuming layer's MFMAs issue), fp32 accumulation.  Stream (mlp_layout.h, "f16 stream"):
+# the same 32 KiB chunks and 3-slot ring, a chunk holds FOUR k-steps (hi only): pair q = 8 s + t at byte q * 1024, so a 256 -> 256
+# layer is 4 chunks / 128 MFMAs instead of 8 / 384.  The fragment ring v[160:191] becomes 8 slots of 4 registers (pair q in slot
+# q % 8, refilled right after its MFMA with pair q + 8): on block entry it holds the chunk's first 8 KiB in both formats, so the
+# f16x3-format HEAD chunks of this stream (the narrow layers keep the f16x3 arithmetic) run through the unchanged HEAD block, and
+# the INIT / STASH / RESTORE blocks are shared as they stand (the biases in LDS are simply not pre-scaled).
+# LDS waits are counted EXACTLY per MFMA (an issue-order model of this block's LDS operations), vmcnt at the publish point likewise.
+def F16(slot):
+    return VB + 4 * slot
+
+
+class Lgkm:
+    """issue-order model of the LDS operations of one block: which ring slot waits for which read"""
+    def __init__(self):
+        self.n, self.done, self.slot = 0, 0, {}
+
+    def lds(self, e, ins, slot=None):
+        e(ins)
+        if slot is not None:
+            self.slot[slot] = self.n
+        self.n += 1
+
+    def need(self, e, slot):
+        i = self.slot.get(slot)
+        if i is None or i < self.done:
+            return
+        younger = min(self.n - i - 1, 15)
+        e("s_waitcnt lgkmcnt(%d)" % younger)
+        self.done = self.n - younger
+
+    def drained(self):
+        self.done = self.n
+
+
+def conv16(src_base, tile, g, reg):
+    """5 VALU: elements 2g, 2g+1 of source tile `tile` -> one packed word (RNE), ReLU, range guard"""
+    a = src_base + 16 * tile + 2 * g
+    return ["v_accvgpr_read_b32 v%d, a%d" % (T, a),
+            "v_accvgpr_read_b32 v%d, a%d" % (T + 1, a + 1),
+            "v_cvt_pk_f16_f32 v%d, v%d, v%d" % (reg, T, T + 1),
+            "v_pk_max_f16 v%d, v%d, 0" % (reg, reg),
+            "v_pk_max_f16 %%[amax], %%[amax], v%d" % reg]
+
+
+def conv16_tile(src_base, tile, reg0):
+    """a whole source tile (2 k-steps) -> registers reg0 .. reg0 + 7: word g = registers 2g, 2g + 1 of the tile"""
+    out = []
+    for g in range(8):
+        out += conv16(src_base, tile, g, reg0 + g)
+    return out
+
+
+def chunk16(e, lg, ci, ks, dst, bop, fill, tail=None):
+    """one chunk of ks k-steps (8 ks MFMAs, pair q = 8 s + t -> destination tile t) at position ci of the block.
+      bop(s)   -> B operand (4 registers) of k-step s
+      fill(q)  -> instructions for the gap after MFMA q (VALU / LDS reads into the accumulator file: (ins, is_lds))
+      tail     -> lines after the chunk's last gap
+    Per gap, in issue order: the DMA piece (if any), the publish point (before the first read of the next chunk), the ring refill,
+    then `fill`."""
+    n = 8 * ks
+    cur, nxt, dma = ci % 3, (ci + 1) % 3, (ci + 2) % 3
+    per = n // 8                           # MFMAs per DMA piece
+    vm = 0
+    for q in range(n):
+        s, t = q >> 3, q & 7
+        lg.need(e, q % 8)
+        e(mfma(ar(dst, t), vr(F16(q % 8)), bop(s)))
+        if q % per == 0:
+            dma_piece(e, q // per, dma)
+            vm += 1
+        if q == n - 8:
+            publish(e, vm)
+            lg.drained()
+        p = q + 8
+        addr, off = (VR + cur, p * 1024) if p < n else (VR + nxt, (p - n) * 1024)
+        lg.lds(e, "ds_read_b128 %s, v%d offset:%d" % (vr(F16(q % 8)), addr, off), slot=q % 8)
+        for ins, is_lds in fill(q):
+            if is_lds:
+                lg.lds(e, ins)
+            else:
+                e(ins)
+    for ins in (tail or []):
+        e(ins)
+
+
+def gen_wide16(src, dst):
+    """256 -> 256 layer, one product per pair: 4 chunks, 128 MFMAs.  Chunk c contracts source tiles 2c (k-steps 0, 1) and 2c + 1
+    (k-steps 2, 3) from bank c & 1 (XB[b] + 0..7 / + 8..15).  Tile 0 is converted in the prologue; during MFMAs 0..14 of chunk c
+    tile 2c + 1 is converted into the upper half of the same bank (first read by MFMA 16), during MFMAs 16..30 tile 2c + 2 into the
+    lower half of the other bank (first read by the next chunk).  A converted source tile is re-seeded with the next layer's bias
+    (%[nbias], four LDS reads straight into its accumulator registers): tile 2c in gaps 1..4 of chunk c, tile 2c + 1 in gaps 17..20."""
+    L = []
+    e = L.append
+    lg = Lgkm()
+    ring_prologue(e)
+    for ins in conv16_tile(src, 0, XB[0]):
+        e(ins)
+    for ins in dma_base():
+        e(ins)
+    for c in range(4):
+        b = c & 1
+        cv1 = split_even(conv16_tile(src, 2 * c + 1, XB[b] + 8), 15)
+        cv2 = split_even(conv16_tile(src, 2 * c + 2, XB[b ^ 1]), 15) if c < 3 else [[] for _ in range(15)]
+
+        def seed(tile, k):
+            return ("ds_read_b128 a[%d:%d], %%[nbias] offset:%d" % (src + 16 * tile + 4 * k, src + 16 * tile + 4 * k + 3,
+                                                                   tile * 64 + k * 16), True)
+
+        def fill(q, c=c, cv1=cv1, cv2=cv2):
+            out = []
+            if 1 <= q <= 4:
+                out.append(seed(2 * c, q - 1))
+            if 17 <= q <= 20:
+                out.append(seed(2 * c + 1, q - 17))
+            if q < 15:
+                out += [(i, False) for i in cv1[q]]
+            elif 16 <= q < 31:
+                out += [(i, False) for i in cv2[q - 16]]
+            return out
+
+        tail = advance_dch() + dma_base() if c < 3 else []
+        chunk16(e, lg, c, 4, dst, lambda s, b=b: vr(XB[b] + 4 * s), fill, tail)
+    ring_epilogue(e, 4)
+    return L
+
+
+def gen_extra16(dst, ks):
+    """one chunk of ks (1 or 4) extra k-steps; B operands = the hi halves of the LDS stage at %[stage] + s * 8192 (the stage keeps its
+    f16x3 layout; the lo halves are not read)"""
+    L = []
+    e = L.append
+    lg = Lgkm()
+    ring_prologue(e)
+    for s in range(ks):
+        e("ds_read_b128 %s, %%[stage] offset:%d" % (vr(XB[0] + 4 * s), s * 8192))
+    for ins in dma_base():
+        e(ins)
+    e("s_waitcnt lgkmcnt(0)")
+    chunk16(e, lg, 0, ks, dst, lambda s: vr(XB[0] + 4 * s), lambda q: [])
+    ring_epilogue(e, 1)
+    return L
+
+
 def emit_macro(out, name, comment, lines):
     out.append("// " + comment)
     out.append("#define %s \\" % name)
@@ -778,6 +924,12 @@ def main():
     out.append("#define TP_HEADTAB_OFFSETS {%s}" % ", ".join(str(v) for v in HEADTAB_SIGMA + HEADTAB_TRANS + HEADTAB_RGB))
     emit_macro(out, "TP_ASM_STASH_Q", "set Q -> v[32:159]", gen_stash(SET["Q"]))
     emit_macro(out, "TP_ASM_RESTORE_P", "v[32:159] -> set P", gen_restore(SET["P"]))
+    # single-product (TP_MLP_F16) blocks; HEAD / INIT / STASH / RESTORE / HEADV are shared with the f16x3 forward
+    for s, d in (("Q", "P"), ("P", "Q")):
+        emit_macro(out, "TP_ASM_WIDE16_%s%s" % (s, d), "f16: 256 -> 256 layer: set %s -> set %s" % (s, d), gen_wide16(SET[s], SET[d]))
+    for d in ("P", "Q"):
+        for ks in (1, 4):
+            emit_macro(out, "TP_ASM_EXTRA16_%d_%s" % (ks, d), "f16: %d extra k-step(s) into set %s" % (ks, d), gen_extra16(SET[d], ks))
     # data gradient: the 34-chunk transposed stream
     emit_macro(out, "TP_ASM_DG_NARROW_P", "data gradient: set P = W3^T d (one k-step)", gen_dg_narrow(SET["P"]))
     emit_macro(out, "TP_ASM_DG_WIDE_PQ", "data gradient: set Q = W^T gated(set P), recording gated(set P)", gen_dg_wide(SET["P"], SET["Q"]))

@@ -597,8 +597,8 @@ extern "C" int tp_mlp_fwd(const tp_mlp_fwd_args* a, tp_stream_t stream) {
              "null pointer");
   TP_REQUIRE(a->B > 0 && a->R > 0 && a->N > 0, "bad sizes");
   TP_REQUIRE((a->center && a->ray && a->depth) || (a->points && a->ray_unit), "need (center,ray,depth) or (points,ray_unit)");
-  TP_REQUIRE(a->precision == TP_MLP_FP32 || a->precision == TP_MLP_F16X3, "unknown precision");
-  if (a->precision == TP_MLP_F16X3) {
+  TP_REQUIRE(a->precision == TP_MLP_FP32 || a->precision == TP_MLP_F16X3 || a->precision == TP_MLP_F16, "unknown precision");
+  if (a->precision == TP_MLP_F16X3 || a->precision == TP_MLP_F16) {      // (both arithmetics live in mlp_fwd_f16x3.hip)
     const int64_t tiles = ((int64_t)a->B * a->R * a->N + kTileSamples - 1) / kTileSamples;
     return tp_launch_mlp_fwd_f16x3(a, persistent_grid(tiles), (hipStream_t)stream);
   }

@@ -403,6 +403,20 @@ __device__ __forceinline__ void asm_wide(Pipe& p, Frag& f, Guard& amax, const As
   TP_RING_DONE;
 }
 
+// single-product arithmetic (TP_MLP_F16, gen_wide_asm.py "SINGLE PRODUCT"): the same layer on the f16 stream, 4 chunks of 32 MFMAs
+template <bool SRC_Q>
+__device__ __forceinline__ void asm_wide16(Pipe& p, Frag& f, Guard& amax, const AsmCtx& c, int next_li) {
+  TP_RING_LOCALS;
+  const unsigned nbias = c.bias0 + (unsigned)next_li * 1024u;
+  if constexpr (SRC_Q)
+    asm volatile(TP_ASM_WIDE16_QP : TP_RING(f), TP_RING_STATE, [amax] "+v"(amax.m)
+                 : TP_RING_INPUTS(c), [nbias] "v"(nbias) : TP_ASM_CLOBBERS, "memory", "scc");
+  else
+    asm volatile(TP_ASM_WIDE16_PQ : TP_RING(f), TP_RING_STATE, [amax] "+v"(amax.m)
+                 : TP_RING_INPUTS(c), [nbias] "v"(nbias) : TP_ASM_CLOBBERS, "memory", "scc");
+  TP_RING_DONE;
+}
+
 // ---- recording variants (training): the block that CONSUMES a layer's accumulators also writes its activation record
 // (gen_wide_asm.py, "recording variants").  Addresses of this lane in the wave's private 4 KB staging tile -- the wave's OWN
 // slices of the first four 4 KB blocks of the input stage, dead while a WIDE / HEAD block runs -- and in the record block.
@@ -475,11 +489,26 @@ __device__ __forceinline__ void asm_extra(Pipe& p, Frag& f, const AsmCtx& c, int
   TP_RING_DONE;
 }
 
-// narrow output layer over relu(set P) (SRC_P) or relu(set Q): accumulator tile (still scaled by 2^8)
-template <bool SRC_P>
-__device__ __forceinline__ f32x16 asm_head(Pipe& p, Frag& f, Guard& amax, const AsmCtx& c) {
+// single-product arithmetic: KS (1 or 4) extra k-steps of the stage (hi halves only) in one chunk of the f16 stream
+template <int KS, bool DST_P>
+__device__ __forceinline__ void asm_extra16(Pipe& p, Frag& f, const AsmCtx& c, int ks0) {
   TP_RING_LOCALS;
-  const float kinv = kInvScale;
+  const unsigned stage = c.stage0 + (unsigned)ks0 * 8192u;
+#define TP_EXTRA16(TXT)                                                                                                \
+  asm volatile(TXT : TP_RING(f), TP_RING_STATE : TP_RING_INPUTS(c), [stage] "v"(stage) : TP_ASM_CLOBBERS, "memory", "scc")
+  if constexpr (KS == 1 && DST_P) TP_EXTRA16(TP_ASM_EXTRA16_1_P);
+  else if constexpr (KS == 4 && DST_P) TP_EXTRA16(TP_ASM_EXTRA16_4_P);
+  else if constexpr (KS == 1) TP_EXTRA16(TP_ASM_EXTRA16_1_Q);
+  else TP_EXTRA16(TP_ASM_EXTRA16_4_Q);
+#undef TP_EXTRA16
+  TP_RING_DONE;
+}
+
+// narrow output layer over relu(set P) (SRC_P) or relu(set Q): accumulator tile (still scaled by 2^8).  `kinv`: scale of the source
+// set (2^-8 for the f16x3 sets; 1 for the unscaled sets of the single-product arithmetic, whose head chunks are f16x3 chunks)
+template <bool SRC_P>
+__device__ __forceinline__ f32x16 asm_head(Pipe& p, Frag& f, Guard& amax, const AsmCtx& c, float kinv = kInvScale) {
+  TP_RING_LOCALS;
   const unsigned mask = 0xFFFFE000u;
   f32x16 acc;
   if constexpr (SRC_P)
@@ -597,10 +626,17 @@ __device__ __forceinline__ float pick3(int c, float a0, float a1, float a2) {
 // RB ("ray bias", evaluation only): the stream of chunk_desc_rb (mlp_layout.h).  Every tile lies inside one ray (N % 128 == 0); the
 // accumulators of R0 / T0 are seeded with the per-ray / per-image bias the pre-kernels below left in P.ray_bias, nothing is staged for
 // T0 and R0, and R0's only extra k-step re-reads x from k-step 3 of the encoding stage.
-template <bool SAVE, bool RB = false>
+// F16 (TP_MLP_F16, inference only): the single-product arithmetic on the f16 stream (mlp_layout.h) -- the 256-wide layers and their
+// extra inputs run the WIDE16 / EXTRA16 blocks, the sets are NOT scaled by 2^8 (unscaled biases, weights and ray-bias seeds), the narrow
+// output layers are the f16x3 ones (HEAD over an unscaled set: kinv = 1; the fp32 VALU head of the ray-bias form with its table
+// scaled by 2^8), so the head epilogue is unchanged.  Everything else -- schedule, ring, staging, stash, status words -- is shared.
+template <bool SAVE, bool RB = false, bool F16 = false>
 __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
   static_assert(!(SAVE && RB), "the ray-bias stream has no recording variant");
-  constexpr int NCH = RB ? kNumChunksRB : kNumChunks;
+  static_assert(!(SAVE && F16), "the single-product arithmetic is inference only");
+  constexpr int NCH = F16 ? (RB ? kNumChunks16RB : kNumChunks16) : (RB ? kNumChunksRB : kNumChunks);
+  constexpr int BIAS_NCH = RB ? kNumChunksRB : kNumChunks;      // (the f16 streams keep their bias / aux blocks where f16x3 does)
+  constexpr float kSetScale = F16 ? 1.0f : (float)(1 << kF16WeightShift);    // accumulator sets hold  scale * (W x + b)
 #define TP_CTX asm_ctx_now(P.packed, NCH)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -611,14 +647,15 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
   p.stream = P.packed; p.lds = lds; p.chunk = 0; p.buf = 0; p.wave = __builtin_amdgcn_readfirstlane(wave); p.lane = lane;
   // wide-layer biases are kept pre-scaled by 2^8 (exact): they seed the accumulators of the scaled products
   for (int i = tid; i < kBiasFloats; i += kThreads)
-    bias_lds[i] = P.packed[(size_t)NCH * kChunkFloats + i] * (i < kHeadBiasOff ? (float)(1 << kF16WeightShift) : 1.0f);
+    bias_lds[i] = P.packed[(size_t)BIAS_NCH * kChunkFloats + i] * (i < kHeadBiasOff ? kSetScale : 1.0f);
   if constexpr (RB) {
     // the nine rows of the narrow output layers (fp32, lane-read order) into the parts of the input stage / save area this kernel
     // does not use: k-step 4 of the stage and slot 6 of the save area (gen_wide_asm.py: HEADTAB_*)
     constexpr int kHeadTabOff[kRbHeadRows] = TP_HEADTAB_OFFSETS;
     const float* tab = P.packed + kRbAuxOff + kRbAuxHeads;
     for (int i = tid; i < kRbHeadRows * 256; i += kThreads)
-      *reinterpret_cast<float*>(reinterpret_cast<char*>(st) + kHeadTabOff[i >> 8] + (i & 255) * 4) = tab[i];
+      *reinterpret_cast<float*>(reinterpret_cast<char*>(st) + kHeadTabOff[i >> 8] + (i & 255) * 4) =
+          tab[i] * ((float)(1 << kF16WeightShift) / kSetScale);      // (F16: 2^8, exact, so the head sums come back scaled as in f16x3)
   }
   dma_chunk(p, 0, 0);
   dma_chunk(p, 1, 1);
@@ -670,8 +707,9 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         // per thread each.  The blocks that read them (T2 re-seeds set Q for R0, L7 re-seeds set P for T0) are many barriers away;
         // the previous tile's reads of these two blocks lie before its last barriers.
         const int64_t qt = (tile * 128) / P.N;                 // (wave-uniform: the tile's ray)
-        bias_lds[R0 * 256 + tid] = P.ray_bias[(size_t)P.B * 512 + (size_t)qt * 256 + tid];
-        bias_lds[T0 * 256 + tid] = P.ray_bias[(size_t)(qt / P.R) * 512 + tid];
+        // (the pre-kernels scale by 2^8; F16 sets are unscaled: * 2^-8, exact)
+        bias_lds[R0 * 256 + tid] = P.ray_bias[(size_t)P.B * 512 + (size_t)qt * 256 + tid] * (kSetScale * kInvScale);
+        bias_lds[T0 * 256 + tid] = P.ray_bias[(size_t)(qt / P.R) * 512 + tid] * (kSetScale * kInvScale);
       }
     }
     asm_init<false>(TP_CTX, L1);       // set Q for L1 (set P was re-seeded for L0 by the previous tile's last layer)
@@ -707,8 +745,8 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         a0 = (which == 1 && hh) ? h5.r4 : h5.r0; a1 = h5.r1; a2 = h5.r2; a3 = h5.r3;
       } else {
         f32x16 a;
-        if constexpr (which == 2) a = asm_head<false>(p, frag, amax, TP_CTX);
-        else a = asm_head<true>(p, frag, amax, TP_CTX);
+        if constexpr (which == 2) a = asm_head<false>(p, frag, amax, TP_CTX, 1.0f / kSetScale);
+        else a = asm_head<true>(p, frag, amax, TP_CTX, 1.0f / kSetScale);
         TR_END(7, h);
         a0 = a[0]; a1 = a[1]; a2 = a[2]; a3 = a[3];
       }
@@ -757,6 +795,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         // (T0 <- L7 = trunk feature, values only; T1 <- T0; T2 <- T1; R1 <- R0; R2 <- R1.  R0 re-reads the restored feature)
         if constexpr (REC == 2) asm_wide_rec<true, false>(p, frag, amax, TP_CTX, next_li, rec_ctx_now(P.saved, tile, SV_FEAT));
         else if constexpr (REC == 1) asm_wide_rec<EVEN, true>(p, frag, amax, TP_CTX, next_li, rec_ctx_now(P.saved, tile, li - 1 - L7));
+        else if constexpr (F16) asm_wide16<EVEN>(p, frag, amax, TP_CTX, next_li);
         else asm_wide<EVEN>(p, frag, amax, TP_CTX, next_li);
         TR_END(3, w);
       }
@@ -803,8 +842,12 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         }
         TR_END(5, pe);
         TR_BEGIN(w);
-        asm_extra<2, true>(p, frag, TP_CTX, 0);
-        asm_extra<2, true>(p, frag, TP_CTX, 2);
+        if constexpr (F16) {
+          asm_extra16<4, true>(p, frag, TP_CTX, 0);
+        } else {
+          asm_extra<2, true>(p, frag, TP_CTX, 0);
+          asm_extra<2, true>(p, frag, TP_CTX, 2);
+        }
         TR_END(3, w);
       } else if (RB && EVEN && li == T0) {
         // (the transient code is in the layer's per-image bias)
@@ -822,7 +865,8 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         }
         TR_END(6, r0s);
         TR_BEGIN(w);
-        asm_extra<1, false>(p, frag, TP_CTX, 3);          // [PE slots 48..59 (zero weights) | x | 0] as staged for L0
+        if constexpr (F16) asm_extra16<1, false>(p, frag, TP_CTX, 3);
+        else asm_extra<1, false>(p, frag, TP_CTX, 3);          // [PE slots 48..59 (zero weights) | x | 0] as staged for L0
         TR_END(3, w);
       } else if (EVEN && li == T0) {
         TR_BEGIN(t0s);
@@ -832,7 +876,8 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         for (int jj = 0; jj < 8; ++jj) stage(st, tid, 0, jj, P.lat_trans[bt * 16 + 8 * hh + jj]);
         TR_END(13, t0s);
         TR_BEGIN(w);
-        asm_extra<1, true>(p, frag, TP_CTX, 0);
+        if constexpr (F16) asm_extra16<1, true>(p, frag, TP_CTX, 0);
+        else asm_extra<1, true>(p, frag, TP_CTX, 0);
         TR_END(3, w);
       } else if (!EVEN && li == R0) {
         // [ray_unit | PE(ray_unit) | x | light] in natural column order, 78 of 80 slots
@@ -914,9 +959,14 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         }
         TR_END(6, r0s);
         TR_BEGIN(w);
-        asm_extra<2, false>(p, frag, TP_CTX, 0);
-        asm_extra<2, false>(p, frag, TP_CTX, 2);
-        asm_extra<1, false>(p, frag, TP_CTX, 4);
+        if constexpr (F16) {
+          asm_extra16<4, false>(p, frag, TP_CTX, 0);
+          asm_extra16<1, false>(p, frag, TP_CTX, 4);
+        } else {
+          asm_extra<2, false>(p, frag, TP_CTX, 0);
+          asm_extra<2, false>(p, frag, TP_CTX, 2);
+          asm_extra<1, false>(p, frag, TP_CTX, 4);
+        }
         TR_END(3, w);
       }
 
@@ -1497,7 +1547,7 @@ int tp_launch_mlp_dgrad_f16x3(const tp_mlp_bwd_args* a, float* dz, unsigned int*
 
 extern "C" size_t tp_mlp_ray_bias_bytes(int B, int R) { return ((size_t)B * 512 + (size_t)B * R * 256) * sizeof(float); }
 
-// launched by tp_mlp_fwd (mlp_fwd.hip) when args->precision == TP_MLP_F16X3
+// launched by tp_mlp_fwd (mlp_fwd.hip) when args->precision == TP_MLP_F16X3 or TP_MLP_F16
 int tp_launch_mlp_fwd_f16x3(const tp_mlp_fwd_args* a, int grid, hipStream_t stream) {
   Params P;
   P.packed = (const float*)a->packed;
@@ -1510,6 +1560,9 @@ int tp_launch_mlp_fwd_f16x3(const tp_mlp_fwd_args* a, int grid, hipStream_t stre
   P.status = a->status; P.act_max = a->act_max; P.ray_bias = a->ray_bias;
   P.density_noise = a->density_noise;
   TP_REQUIRE(a->ray_bias == nullptr || a->density_noise == nullptr, "tp_mlp_fwd: density_noise (train mode) does not go with ray_bias (evaluation)");
+  const bool f16 = a->precision == TP_MLP_F16;
+  TP_REQUIRE(!f16 || (a->saved == nullptr && a->density_noise == nullptr),
+             "tp_mlp_fwd: TP_MLP_F16 is inference only (no activation record `saved`, no `density_noise`)");
   static unsigned long long attr_devices = 0;
   if (tp::first_use_on_device(attr_devices)) {
     hipError_t e = hipFuncSetAttribute((const void*)mlp_fwd_f16x3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
@@ -1517,6 +1570,10 @@ int tp_launch_mlp_fwd_f16x3(const tp_mlp_fwd_args* a, int grid, hipStream_t stre
       e = hipFuncSetAttribute((const void*)mlp_fwd_f16x3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void*)mlp_fwd_f16x3_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)mlp_fwd_f16x3_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)mlp_fwd_f16x3_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e != hipSuccess) { tp::set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
   }
   if (a->ray_bias != nullptr) {
@@ -1530,8 +1587,16 @@ int tp_launch_mlp_fwd_f16x3(const tp_mlp_fwd_args* a, int grid, hipStream_t stre
     hipLaunchKernelGGL(rb_image_bias_kernel, dim3(a->B), dim3(256), 0, stream, P.packed, a->lat_trans, a->lat_light, img);
     hipLaunchKernelGGL(rb_ray_bias_kernel, dim3((unsigned)((n_rays + kRbRays - 1) / kRbRays)), dim3(256), 0, stream, P.packed, a->ray,
                        a->R, n_rays, (const float*)img, per_ray);
+    if (f16) {
+      hipLaunchKernelGGL((mlp_fwd_f16x3_kernel<false, true, true>), dim3(grid), dim3(kThreads), kLdsBytes, stream, P);
+      return tp::check_launch("tp_mlp_fwd(f16, ray bias)");
+    }
     hipLaunchKernelGGL((mlp_fwd_f16x3_kernel<false, true>), dim3(grid), dim3(kThreads), kLdsBytes, stream, P);
     return tp::check_launch("tp_mlp_fwd(f16x3, ray bias)");
+  }
+  if (f16) {
+    hipLaunchKernelGGL((mlp_fwd_f16x3_kernel<false, false, true>), dim3(grid), dim3(kThreads), kLdsBytes, stream, P);
+    return tp::check_launch("tp_mlp_fwd(f16)");
   }
   if (P.saved != nullptr)
     hipLaunchKernelGGL(mlp_fwd_f16x3_kernel<true>, dim3(grid), dim3(kThreads), kLdsBytes, stream, P);

@@ -278,3 +278,70 @@ TP_HD void chunk16_src(const ChunkDesc& d, int idx, int& part, int& row, int& co
 }
 
 }  // namespace tp_layout
+
+// ================================================================================================
+// f16 stream (TP_PACK_F16, inference-only TP_MLP_F16 forward): ONE fp16 weight per product, rounded to nearest once at pack time, not
+// pre-scaled.  Same 32 KiB chunks and execution order as the f16x3 stream, but a wide chunk carries FOUR k-steps (hi only):
+//     half index = ((s*8 + t)*64 + lane)*8 + j,   s = 0..3, t = output tile 0..7,  lane = (i = out row in tile t, h)
+// so a 256-input layer is 4 chunks instead of 8.  GEN chunk `sub` (0..3) contracts source tiles 2 sub + (s >> 1), k-step s & 1 of
+// that tile (acc_feat16).  Extra-input chunks hold stage k-steps 4 sub .. 4 sub + 3 (slot = 16 (4 sub + s) + 8 h + j, the stage of the
+// f16x3 kernel); the 1-k-step chunks (X8, RBX, the fifth k-step of X40) leave k-steps 1..3 zero.  HEAD chunks keep the f16x3 format
+// (hi + lo, weights * 2^kF16WeightShift): the narrow output layers keep the f16x3 arithmetic.
+//   plain:     L0 ENC | L1..L3 4 GEN each | L4 4 GEN + ENC | L5, L6 | L7: HEAD (density) + 4 GEN | T0 4 GEN + X8 | T1, T2 | T3 HEAD |
+//              R0 4 GEN + 2 X40 | R1, R2 | R3 HEAD  = 60 chunks
+//   ray bias:  the same without HEAD and X8 chunks and with one RBX chunk instead of the two X40 = 55 chunks
+// The bias block (unscaled) and, for the ray-bias variant, the aux block sit where the f16x3 stream of the same variant keeps them
+// (after kNumChunks / kNumChunksRB chunks), so the per-ray bias pre-kernels read both streams alike; every stream fits kPackedFloats.
+// ================================================================================================
+namespace tp_layout {
+
+constexpr int kNumChunks16 = 60;
+constexpr int kNumChunks16RB = 55;
+constexpr int kFirstHeadChunk16 = 31;      // chunks >= this belong to the trainable heads (T*, R*)
+constexpr int kFirstHeadChunk16RB = 30;
+static_assert(kNumChunks16 <= kNumChunksRB, "the f16 stream ends before the bias / aux blocks of either f16x3 variant");
+
+TP_HD ChunkDesc chunk_desc_f16(int c, int rb) {
+  if (c == 0) return {CK_ENC, W_FEAT0 + 0, 0, 0, 0, 63};
+  if (c < 13) { int l = 1 + (c - 1) / 4; return {CK_GEN, W_FEAT0 + l, (c - 1) % 4, 0, 0, 256}; }
+  if (c < 17) return {CK_GEN, W_FEAT0 + 4, c - 13, 0, 0, 319};
+  if (c == 17) return {CK_ENC, W_FEAT0 + 4, 0, 0, 256, 319};
+  if (c < 26) { int l = 5 + (c - 18) / 4; return {CK_GEN, W_FEAT0 + l, (c - 18) % 4, 0, 0, 256}; }
+  if (rb) {
+    if (c < 30) return {CK_GEN, W_FEAT0 + 7, c - 26, 1, 0, 256};
+    if (c < 34) return {CK_GEN, W_TRANS0 + 0, c - 30, 0, 0, 272};
+    if (c < 42) { int l = 1 + (c - 34) / 4; return {CK_GEN, W_TRANS0 + l, (c - 34) % 4, 0, 0, 256}; }
+    if (c < 46) return {CK_GEN, W_RGB0 + 0, c - 42, 0, 0, 334};
+    if (c == 46) return {CK_RBX, W_RGB0 + 0, 0, 0, 256, 334};
+    int l = 1 + (c - 47) / 4;
+    return {CK_GEN, W_RGB0 + l, (c - 47) % 4, 0, 0, 256};
+  }
+  if (c == 26) return {CK_HEAD, W_FEAT0 + 7, 1, 0, 0, 256};
+  if (c < 31) return {CK_GEN, W_FEAT0 + 7, c - 27, 1, 0, 256};
+  if (c < 35) return {CK_GEN, W_TRANS0 + 0, c - 31, 0, 0, 272};
+  if (c == 35) return {CK_X8, W_TRANS0 + 0, 0, 0, 256, 272};
+  if (c < 44) { int l = 1 + (c - 36) / 4; return {CK_GEN, W_TRANS0 + l, (c - 36) % 4, 0, 0, 256}; }
+  if (c == 44) return {CK_HEAD, W_TRANS0 + 3, 5, 0, 0, 256};
+  if (c < 49) return {CK_GEN, W_RGB0 + 0, c - 45, 0, 0, 334};
+  if (c < 51) return {CK_X40, W_RGB0 + 0, c - 49, 0, 256, 334};
+  if (c < 59) { int l = 1 + (c - 51) / 4; return {CK_GEN, W_RGB0 + l, (c - 51) % 4, 0, 0, 256}; }
+  return {CK_HEAD, W_RGB0 + 3, 3, 0, 0, 256};
+}
+
+// (row, col) of the weight matrix for half `idx` (0..16383) of a non-HEAD chunk of the f16 stream; row = -1 for a zero pad
+TP_HD void chunk_f16_src(const ChunkDesc& d, int idx, int& row, int& col) {
+  const int j = idx & 7, lane = (idx >> 3) & 63, i = lane & 31, h = lane >> 5;
+  const int t = (idx >> 9) & 7, s = idx >> 12;
+  row = -1; col = 0;
+  int k;
+  if (d.kind == CK_GEN) k = acc_feat16(2 * d.sub + (s >> 1), s & 1, h, j);
+  else if (d.kind == CK_ENC) k = enc_slot_col(s * 16 + 8 * h + j);
+  else if (d.kind == CK_X8) k = s == 0 ? x8_slot_col(8 * h + j) : -1;
+  else if (d.kind == CK_RBX) k = (s == 0 && h == 1 && j >= 4 && j <= 6) ? 27 + (j - 4) : -1;
+  else k = x40_slot_col((d.sub * 4 + s) * 16 + 8 * h + j);
+  if (k < 0) return;
+  row = d.row_off + 32 * t + i;
+  col = d.col_off + k;
+}
+
+}  // namespace tp_layout

@@ -39,6 +39,29 @@ __global__ void pack16_kernel(W w, int chunk0, int chunk1, _Float16* __restrict_
   }
 }
 
+// f16 stream (mlp_layout.h): one fp16 per weight, rounded to nearest, unscaled; its HEAD chunks are f16x3 chunks (hi + lo of W * 2^shift)
+__global__ void pack_f16_kernel(W w, int chunk0, int chunk1, _Float16* __restrict__ out, int rb) {
+  const int64_t n = (int64_t)(chunk1 - chunk0) * kChunkHalves;
+  const float scale = (float)(1 << kF16WeightShift);
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int c = chunk0 + (int)(e / kChunkHalves), idx = (int)(e % kChunkHalves);
+    const ChunkDesc d = chunk_desc_f16(c, rb);
+    _Float16 v;
+    if (d.kind == CK_HEAD) {
+      int part, row, col;
+      chunk16_src(d, idx, part, row, col);
+      const float x = row < 0 ? 0.0f : w.w[d.mat][(int64_t)row * d.in_dim + col] * scale;
+      const _Float16 hi = (_Float16)x;
+      v = part == 0 ? hi : (_Float16)(x - (float)hi);
+    } else {
+      int row, col;
+      chunk_f16_src(d, idx, row, col);
+      v = (_Float16)(row < 0 ? 0.0f : w.w[d.mat][(int64_t)row * d.in_dim + col]);
+    }
+    out[(int64_t)c * kChunkHalves + idx] = v;
+  }
+}
+
 // ray-bias stream: the transposed fp32 columns of mlp_rgb.0 / mlp_trans.0 that the per-ray bias pre-kernel contracts (mlp_layout.h)
 __global__ void pack_rb_aux_kernel(W w, float* __restrict__ out, int trunk, int heads) {
   float* aux = out + kRbAuxOff;
@@ -171,9 +194,11 @@ extern "C" int tp_mlp_pack_heads_f16x3(const tp_mlp_weights* p, void* packed, vo
 
 extern "C" int tp_mlp_pack(const tp_mlp_weights* p, int parts, void* packed, tp_stream_t stream) {
   TP_REQUIRE(p && packed, "null pointer");
-  TP_REQUIRE((parts & ~(TP_PACK_ALL | TP_PACK_F16X3 | TP_PACK_RAYBIAS)) == 0 && (parts & TP_PACK_ALL) != 0, "bad parts mask");
+  TP_REQUIRE((parts & ~(TP_PACK_ALL | TP_PACK_F16X3 | TP_PACK_RAYBIAS | TP_PACK_F16)) == 0 && (parts & TP_PACK_ALL) != 0, "bad parts mask");
   const int rb = (parts & TP_PACK_RAYBIAS) ? 1 : 0;
-  TP_REQUIRE(!rb || (parts & TP_PACK_F16X3), "TP_PACK_RAYBIAS is a variant of the TP_PACK_F16X3 stream");
+  const bool f16 = (parts & TP_PACK_F16) != 0;
+  TP_REQUIRE(!(f16 && (parts & TP_PACK_F16X3)), "TP_PACK_F16 and TP_PACK_F16X3 are different streams");
+  TP_REQUIRE(!rb || (parts & (TP_PACK_F16X3 | TP_PACK_F16)), "TP_PACK_RAYBIAS is a variant of the TP_PACK_F16X3 / TP_PACK_F16 stream");
   W w;
   for (int i = 0; i < 8; ++i) { w.w[W_FEAT0 + i] = p->feat_w[i]; w.b[W_FEAT0 + i] = p->feat_b[i]; }
   for (int i = 0; i < 4; ++i) {
@@ -185,11 +210,14 @@ extern "C" int tp_mlp_pack(const tp_mlp_weights* p, int parts, void* packed, tp_
     const bool is_trunk = i < 8;
     if ((is_trunk && trunk) || (!is_trunk && heads)) TP_REQUIRE(w.w[i] && w.b[i], "null weight pointer");
   }
-  const int nch = rb ? kNumChunksRB : kNumChunks;
-  const int first_head = rb ? kFirstHeadChunkRB : kFirstHeadChunk;
-  const int c0 = trunk ? 0 : first_head, c1 = heads ? nch : first_head;
+  const int nch = rb ? kNumChunksRB : kNumChunks;              // (also where the f16 stream keeps its bias / aux blocks)
+  const int first_head = f16 ? (rb ? kFirstHeadChunk16RB : kFirstHeadChunk16) : (rb ? kFirstHeadChunkRB : kFirstHeadChunk);
+  const int nch_stream = f16 ? (rb ? kNumChunks16RB : kNumChunks16) : nch;
+  const int c0 = trunk ? 0 : first_head, c1 = heads ? nch_stream : first_head;
   const int w0 = trunk ? 0 : kFirstHeadWide, w1 = heads ? kNumWide : kFirstHeadWide;
-  if (parts & TP_PACK_F16X3)
+  if (f16)
+    hipLaunchKernelGGL(pack_f16_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w, c0, c1, (_Float16*)packed, rb);
+  else if (parts & TP_PACK_F16X3)
     hipLaunchKernelGGL(pack16_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w, c0, c1, (_Float16*)packed, rb);
   else
     hipLaunchKernelGGL(pack_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w, c0, c1, (float*)packed);

@@ -43,7 +43,8 @@ extern "C" int tp_render_eval(const tp_render_eval_args* a, tp_stream_t stream) 
   m.rgb = (float*)(ws + l.rgb); m.density = (float*)(ws + l.density); m.uncert = (float*)(ws + l.uncert);
   m.saved = nullptr; m.workspace = ws + l.mlp_ws; m.precision = a->precision; m.status = a->status;
   if (a->packed_ray_bias) {
-    TP_REQUIRE(a->precision == TP_MLP_F16X3 && N % 128 == 0, "tp_render_eval: packed_ray_bias needs TP_MLP_F16X3 and N % 128 == 0");
+    TP_REQUIRE((a->precision == TP_MLP_F16X3 || a->precision == TP_MLP_F16) && N % 128 == 0,
+               "tp_render_eval: packed_ray_bias needs TP_MLP_F16X3 or TP_MLP_F16 and N % 128 == 0");
     m.ray_bias = (float*)(ws + l.ray_bias);
   }
   if (int rc = tp_mlp_fwd(&m, stream)) return rc;

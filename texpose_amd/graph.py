@@ -178,20 +178,20 @@ class Graph(torch.nn.Module):
         return ret
 
     def _range_guarded(self, opt, device, render_image):
-        """``render_image()`` renders one whole image with the MLP kernel currently selected.  The f16x3 kernel raises a
+        """``render_image()`` renders one whole image with the MLP kernel currently selected.  The f16x3 / f16 kernels raise a
         device flag if an activation left the fp16 range; the flag is read (and cleared) once per image -- one host
         sync per ~0.2 s image -- and a flagged image is rendered again, in the same call, with the exact-fp32 kernel.
         The caller never has to catch and retry.  ``opt.arch.mlp_range_check = 'off'`` skips the read (the flag then
         stays set for ops.check_mlp_status)."""
         out = render_image()
         nerf = self.nerf
-        if "f16x3" not in (nerf.precision, nerf.train_precision) or opt.arch.get("mlp_range_check", "sync") == "off" \
+        if not set(ops.F16_RANGE_PRECISIONS) & {nerf.precision, nerf.train_precision} or opt.arch.get("mlp_range_check", "sync") == "off" \
                 or torch.cuda.is_current_stream_capturing():
             return out
         if ops.take_mlp_status(device) & 1:
             self.range_fallbacks = getattr(self, "range_fallbacks", 0) + 1
             if self.range_fallbacks == 1:
-                warnings.warn("texpose_amd: an activation left the fp16 range of the f16x3 MLP kernel; the image was "
+                warnings.warn("texpose_amd: an activation left the fp16 range of the f16x3 / f16 MLP kernel; the image was "
                               "re-rendered with the exact-fp32 kernel (arch.mlp_precision='fp32' avoids the double work)")
             keep = nerf.precision, nerf.train_precision
             nerf.precision = nerf.train_precision = "fp32"

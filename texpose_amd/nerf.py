@@ -54,9 +54,10 @@ class NeRF(torch.nn.Module):
         self.mlp_trans = stack(opt.arch.layers_trans, feat_dim + opt.nerf.N_latent_trans)
         if opt.c2f is not None:
             self.progress = torch.nn.Parameter(torch.tensor(0.))
-        # forward arithmetic: "f16x3" (split-fp16 products on the f16 matrix cores, fp32-grade accuracy) or "fp32"
-        # (exact fp32 MFMA).  `precision` is used without autograd, `train_precision` for the recording forward of a
-        # training step (the backward kernels are fp32 MFMA either way and consume the same activation record)
+        # forward arithmetic: "f16x3" (split-fp16 products on the f16 matrix cores, fp32-grade accuracy), "fp32"
+        # (exact fp32 MFMA) or, for `precision` only, "f16" (single fp16 products, inference only: ~2^-11 relative per operand,
+        # for view synthesis into 8-bit images).  `precision` is used without autograd, `train_precision` for the recording
+        # forward of a training step (the backward kernels are fp32 MFMA either way and consume the same activation record)
         self.precision = opt.arch.get("mlp_precision", "f16x3")
         self.train_precision = opt.arch.get("mlp_train_precision", "f16x3")
         # compute units the weight-gradient launch of the backward fills (tp_mlp_bwd_args.wgrad_cus; 0 = all): a training step that runs
@@ -70,6 +71,9 @@ class NeRF(torch.nn.Module):
         self.density_noise_override = None       # tests: the [B,R,N] standard-normal draw of the next train-mode forward
         if self.precision not in ops.PRECISIONS or self.train_precision not in ops.PRECISIONS:
             raise ValueError("arch.mlp_precision / mlp_train_precision must be one of %s" % list(ops.PRECISIONS))
+        if self.train_precision in ops.INFERENCE_ONLY_PRECISIONS:
+            raise ValueError("arch.mlp_train_precision=%r: that MLP arithmetic is inference-only (it has no recording forward); "
+                             "use it as arch.mlp_precision and train with 'f16x3' or 'fp32'" % self.train_precision)
         self._packed = {}
         self._versions = {}
         self._packed_t, self._packed_t_ver = None, None     # transposed f16x3 head image of the backward (packed_weights)
@@ -175,9 +179,10 @@ class NeRF(torch.nn.Module):
     def packed_weights(self, precision: str = "fp32", for_training: bool = False, ray_bias: bool = False) -> torch.Tensor:
         """MFMA-ordered weight stream for ``precision``, re-packed lazily: trunk once (frozen), heads when an
         optimiser step or a load_state_dict bumped a parameter version.  ``for_training`` (a recording f16x3 forward whose
-        backward will run): the same launch also writes the transposed head image of that backward.  ``ray_bias``: the f16x3 stream
-        variant of ops.mlp_forward(..., ray_bias=True), kept beside the plain one."""
-        assert not (ray_bias and (for_training or precision != "f16x3"))
+        backward will run): the same launch also writes the transposed head image of that backward.  ``ray_bias``: the f16x3 / f16
+        stream variant of ops.mlp_forward(..., ray_bias=True), kept beside the plain one."""
+        assert not (ray_bias and (for_training or precision not in ops.F16_RANGE_PRECISIONS))
+        assert not (for_training and precision in ops.INFERENCE_ONLY_PRECISIONS)
         key = precision + ("+ray_bias" if ray_bias else "")
         vt, vh = self._version_keys()
         dev = next(self.parameters()).device

@@ -24,9 +24,13 @@ PIX_COORDS, PIX_INDEX = 0, 1
 BOUNDS_MAP, BOUNDS_AABB, BOUNDS_NONE = 0, 1, 2
 JITTER_MID, JITTER_GIVEN, JITTER_PHILOX = 0, 1, 2
 DEPTH_PARAMS = {"metric": 0, "inverse": 1}          # options nerf.depth.param -> TP_DEPTH_*
-PACK_TRUNK, PACK_HEADS, PACK_ALL, PACK_F16X3, PACK_RAYBIAS = 1, 2, 3, 4, 8
-MLP_FP32, MLP_F16X3 = 0, 1
-PRECISIONS = {"fp32": MLP_FP32, "f16x3": MLP_F16X3}
+PACK_TRUNK, PACK_HEADS, PACK_ALL, PACK_F16X3, PACK_RAYBIAS, PACK_F16 = 1, 2, 3, 4, 8, 16
+MLP_FP32, MLP_F16X3, MLP_F16 = 0, 1, 2
+# "f16": single fp16 products with fp32 accumulation, inference only (include/texpose_amd.h, TP_MLP_F16)
+PRECISIONS = {"fp32": MLP_FP32, "f16x3": MLP_F16X3, "f16": MLP_F16}
+# the arithmetics whose forward raises the fp16 range flag (mlp_status) and whose training forms do not exist
+F16_RANGE_PRECISIONS = ("f16x3", "f16")
+INFERENCE_ONLY_PRECISIONS = ("f16",)
 
 COMPOSITE_RAY_FIELDS = (("rgb", 0, 3), ("rgb_static", 3, 6), ("rgb_transient", 6, 9), ("depth", 9, 10),
                         ("opacity", 10, 11), ("opacity_static", 11, 12), ("opacity_transient", 12, 13),
@@ -222,8 +226,8 @@ def packed_bytes() -> int:
 def pack_weights(state: Dict[str, Tensor], packed: Optional[Tensor] = None, parts: int = PACK_ALL,
                  prefix: str = "", precision: str = "fp32", ray_bias: bool = False) -> Tensor:
     """state: reference state-dict style mapping (``mlp_feat.0.weight`` ...) of CUDA tensors.
-    precision 'f16x3' builds the split-fp16 stream for the fast forward (same size); ``ray_bias``: its variant for
-    mlp_forward(..., ray_bias=True) (tp_mlp_fwd_args.ray_bias)."""
+    precision 'f16x3' builds the split-fp16 stream for the fast forward, 'f16' the single-fp16 stream of the inference-only
+    forward (same size); ``ray_bias``: their variant for mlp_forward(..., ray_bias=True) (tp_mlp_fwd_args.ray_bias)."""
     lib = _lib.load()
     w = MlpWeights()
     keep = []
@@ -242,7 +246,7 @@ def pack_weights(state: Dict[str, Tensor], packed: Optional[Tensor] = None, part
     dev = keep[0].device
     if packed is None:
         packed = torch.empty(packed_bytes() // 4, device=dev)
-    flags = parts | (PACK_F16X3 if PRECISIONS[precision] == MLP_F16X3 else 0) | (PACK_RAYBIAS if ray_bias else 0)
+    flags = parts | {MLP_FP32: 0, MLP_F16X3: PACK_F16X3, MLP_F16: PACK_F16}[PRECISIONS[precision]] | (PACK_RAYBIAS if ray_bias else 0)
     check(lib.tp_mlp_pack(C.byref(w), flags, packed.data_ptr(), _stream()), "tp_mlp_pack")
     return packed
 
@@ -408,7 +412,9 @@ def mlp_forward(packed: Tensor, lat_trans: Tensor, lat_light: Tensor, *, center:
     a.rgb, a.density, a.uncert = rgb.data_ptr(), density.data_ptr(), uncert.data_ptr()
     a.saved, a.workspace = _ptr(saved), ws.data_ptr()
     a.precision = PRECISIONS[precision]
-    if a.precision == MLP_F16X3:
+    if precision in INFERENCE_ONLY_PRECISIONS and (save or density_noise is not None):
+        raise ValueError("mlp_forward: precision %r is inference only (no save=True, no density_noise)" % precision)
+    if precision in F16_RANGE_PRECISIONS:
         a.status = mlp_status(dev).data_ptr()
         a.act_max = _act_max_ptr(dev)
     rb = None
@@ -426,10 +432,10 @@ def mlp_forward(packed: Tensor, lat_trans: Tensor, lat_light: Tensor, *, center:
 
 
 def ray_bias_applies(precision: str, n_samples_per_ray: int, save: bool, center_form: bool) -> bool:
-    """The f16x3 forward can take the ray-constant inputs of mlp_rgb.0 / mlp_trans.0 as a per-ray bias (tp_mlp_fwd_args.ray_bias)
-    when no activation record is written, rays come as (center, ray, depth) and every 128-sample tile lies inside one ray.
-    TP_NO_RAY_BIAS=1 switches it off (same-box A/B)."""
-    return (precision == "f16x3" and not save and center_form and n_samples_per_ray % 128 == 0
+    """The f16x3 and f16 forwards can take the ray-constant inputs of mlp_rgb.0 / mlp_trans.0 as a per-ray bias
+    (tp_mlp_fwd_args.ray_bias) when no activation record is written, rays come as (center, ray, depth) and every 128-sample tile
+    lies inside one ray.  TP_NO_RAY_BIAS=1 switches it off (same-box A/B)."""
+    return (precision in F16_RANGE_PRECISIONS and not save and center_form and n_samples_per_ray % 128 == 0
             and not knobs.K.no_ray_bias)
 
 
@@ -992,7 +998,7 @@ def render_eval(packed: Tensor, intr: Tensor, pose: Tensor, ray_idx: Tensor, z_n
                 rand: Optional[Tensor] = None, with_alphas: bool = False, ray_bias: bool = False, ndc: bool = False,
                 depth_param: str = "metric"):
     """The C ABI's one-call evaluation render (tp_render_eval: ray-gen + MLP + composite, intermediates in one workspace).
-    ``ray_bias``: ``packed`` is the ray-bias stream (pack_weights(..., ray_bias=True); f16x3, n_samples % 128 == 0).
+    ``ray_bias``: ``packed`` is the ray-bias stream (pack_weights(..., ray_bias=True); f16x3 or f16, n_samples % 128 == 0).
     Returns out_ray [B,R,14] (COMPOSITE_RAY_FIELDS) and, if asked, (alpha_static, alpha_transient) [B,R,N].  The Python
     mirror (Graph.render) launches the same three kernels itself; this entry point exists for non-Python hosts."""
     lib = _lib.load()
@@ -1016,7 +1022,7 @@ def render_eval(packed: Tensor, intr: Tensor, pose: Tensor, ray_idx: Tensor, z_n
     a.packed, a.lat_trans, a.lat_light = packed.data_ptr(), lat_trans.data_ptr(), lat_light.data_ptr()
     a.precision, a.min_uncert = PRECISIONS[precision], float(min_uncert)
     a.packed_ray_bias = 1 if ray_bias else 0
-    a.status = mlp_status(dev).data_ptr() if precision == "f16x3" else None
+    a.status = mlp_status(dev).data_ptr() if precision in F16_RANGE_PRECISIONS else None
     ws = torch.empty(int(lib.tp_render_eval_workspace_bytes(B, R, n_samples)) // 4 + 64, device=dev)
     out = torch.empty(B, R, 14, device=dev)
     a.workspace, a.out_ray = ws.data_ptr(), out.data_ptr()
