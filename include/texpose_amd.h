@@ -193,7 +193,10 @@ typedef struct tp_mlp_fwd_args {
 size_t tp_mlp_ray_bias_bytes(int B, int R);
 /* TP_MLP_F16X3: every fp32 operand is split into hi + lo fp16 (22-bit significand) and hi*hi + hi*lo + lo*hi is
  * accumulated in fp32 on the f16 matrix cores (16x the fp32-MFMA rate / 3).  Measured error vs an fp64 oracle is
- * within 1.3x of plain fp32.  Requires |activation| < 6e4 (see `status`).  With `saved` it writes
+ * within 1.3x of plain fp32.  Requires |activation| < 6e4 (see `status`) and |weight| < 2^8 (the stream
+ * holds W * 2^8 in fp16; a larger weight overflows, unflagged).  The 1.3x holds while the lo halves are normal fp16 numbers: where a
+ * layer's weights all lie below ~2^-11 or its activations all below 2^-3, the contract is rtol 1e-4 / atol 1e-6 of fp32 and 32x
+ * fp32's error (measured up to 18x).  With `saved` it writes
  * the same fp32 activation record as TP_MLP_FP32 (the backward kernels do not depend on how the forward was computed). */
 /* TP_MLP_F16 (inference only, not fp32-grade): ONE fp16 product per multiply-add with fp32 accumulation on the f16 matrix cores,
  * 3x fewer MFMAs than TP_MLP_F16X3 and half the weight stream.  The 256-wide layers (trunk, hidden layers of both heads, and the

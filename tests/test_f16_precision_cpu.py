@@ -4,6 +4,7 @@ import os
 import re
 
 import pytest
+import torch
 
 from texpose_amd import ops
 from texpose_amd.nerf import NeRF
@@ -50,3 +51,30 @@ def test_header_constants_match_python():
     assert _enum("TP_MLP_F16X3") == ops.MLP_F16X3 and _enum("TP_PACK_RAYBIAS") == ops.PACK_RAYBIAS
     flags = (ops.PACK_TRUNK, ops.PACK_HEADS, ops.PACK_F16X3, ops.PACK_RAYBIAS, ops.PACK_F16)
     assert len({f for f in flags}) == len(flags) and all(f & ops.PACK_F16 == 0 for f in flags[:-1])
+
+
+@pytest.mark.parametrize("k", [13, -6])
+def test_per_layer_rescaling_preserves_the_network(k):
+    """tests/f16_emulation.rescale (ReLU's positive homogeneity), which the range-guard tests use to move one layer's activations:
+    for every hidden output the fp64 oracle of the rescaled network equals the plain one to rounding, that layer's activations (and
+    only its) move by 2^k; and a lifted latent code (its columns / 2^c, the code * 2^c) changes nothing either"""
+    from f16_emulation import HIDDEN, emulate_f16, hidden_maxima, rays, rescale
+    from oracle import texpose_oracle as O
+    params = O.make_params(61)
+    _, _, _, pts, unit, lt, ll = rays(7, 2, 3, 5)
+    plain = emulate_f16(params, pts, unit, lt, ll, rounded=False)
+    m0 = hidden_maxima(params, pts, unit, lt, ll)
+    for layer in HIDDEN:
+        p = rescale(params, {layer: k})
+        assert sum(not torch.equal(p[n], params[n]) for n in p) in (3, 4), layer      # producer weight + bias, the consumers
+        out = emulate_f16(p, pts, unit, lt, ll, rounded=False)
+        for a, b in zip(out, plain):
+            assert float((a - b).abs().max()) <= 1e-12 * max(1.0, float(b.abs().max())), layer
+        m = hidden_maxima(p, pts, unit, lt, ll)
+        for name in HIDDEN:
+            want = m0[name] * 2.0 ** k if name == layer else m0[name]
+            assert abs(m[name] - want) <= 1e-12 * want, (layer, name, m[name], want)
+    p = rescale(params, {"lat_trans": 5, "lat_light": 5, "mlp_feat.7": 3})
+    out = emulate_f16(p, pts, unit, lt * 32, ll * 32, rounded=False)
+    for a, b in zip(out, plain):
+        assert float((a - b).abs().max()) <= 1e-12

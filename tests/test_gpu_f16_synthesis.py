@@ -10,11 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from f16_emulation import emulate_f16, posenc64 as _posenc64, rays as _rays, rel_l2
 from oracle import texpose_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-WIDE_OUT = 256
 
 
 def dev():
@@ -24,11 +23,6 @@ def dev():
 
 def cu(t):
     return t.to(dev())
-
-
-def rel_l2(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 @pytest.fixture(scope="module")
@@ -51,58 +45,6 @@ def _graph(params, n_train=5, emb_seed=77, H=16, W=16, N=8, precision="f16"):
         g.latent_vars_trans.weight.copy_(torch.from_numpy(ers.normal(size=(n_train, 16)).astype(np.float32)))
         g.latent_vars_light.weight.copy_(torch.from_numpy(ers.normal(size=(n_train, 48)).astype(np.float32)))
     return g, opt
-
-
-def _posenc64(x, L):
-    freq = (2 ** torch.arange(L, dtype=torch.float32)) * np.pi
-    spec = (x.float()[..., None] * freq).double()          # the fp32-rounded argument the kernel encodes
-    return torch.stack([spec.sin(), spec.cos()], dim=-2).reshape(*x.shape[:-1], -1)
-
-
-def emulate_f16(params, points, ray_unit, lat_trans, lat_light, ray_bias=False, rounded=True):
-    """The oracle in fp64 with the operands of every 256-wide layer rounded to fp16 (nearest even): weights and inputs of
-    mlp_feat.0-7 (without the density row of mlp_feat.7), mlp_rgb.0-2, mlp_trans.0-2.  The narrow output layers stay exact.
-    ``ray_bias``: the ray-constant columns (mlp_rgb.0 view encoding 256..282 and light code 286..333, mlp_trans.0 transient code
-    256..271) are contracted unrounded, as the per-ray bias pre-kernels do.  ``rounded=False``: no rounding at all (fp64 oracle)."""
-    p64 = {k: v.double() for k, v in params.items()}
-    names = {id(v): k for k, v in p64.items()}
-    exact_cols = {"mlp_rgb.0.weight": list(range(256, 283)) + list(range(286, 334)), "mlp_trans.0.weight": list(range(256, 272))}
-    lin = torch.nn.functional.linear
-
-    def linear(x, w, b=None):
-        name = names.get(id(w), "")
-        if w.shape[0] < WIDE_OUT or not rounded:
-            return lin(x, w, b)                                   # narrow output layer: exact
-        keep = torch.zeros(w.shape[1], dtype=torch.bool)
-        if ray_bias and name in exact_cols:
-            keep[exact_cols[name]] = True
-        xr = torch.where(keep, x, x.half().double())
-        wr = torch.where(keep, w, w.half().double())
-        out = lin(xr, wr, b)
-        if w.shape[0] == WIDE_OUT + 1:                            # mlp_feat.7: row 0 is the density head
-            out[..., 0] = lin(x, w[:1], None if b is None else b[:1])[..., 0]
-        return out
-
-    saved = O.posenc, torch.nn.functional.linear
-    O.posenc, torch.nn.functional.linear = _posenc64, linear
-    try:
-        with torch.no_grad():
-            return O.mlp_forward(p64, points.double(), ray_unit.double(), lat_trans.double(), lat_light.double())
-    finally:
-        O.posenc, torch.nn.functional.linear = saved
-
-
-def _rays(seed, B, R, N):
-    """form-A inputs (center, ray, depth) and the points / unit directions the kernel derives from them in fp32"""
-    rs = np.random.RandomState(seed)
-    center = torch.from_numpy(rs.uniform(-0.3, 0.3, size=(B, R, 3)).astype(np.float32))
-    ray = torch.from_numpy(rs.normal(size=(B, R, 3)).astype(np.float32))
-    depth = torch.from_numpy(np.sort(rs.uniform(0.2, 1.4, size=(B, R, N)), axis=-1).astype(np.float32))
-    pts = center[:, :, None] + ray[:, :, None] * depth[..., None]
-    unit = (ray / ray.norm(dim=-1, keepdim=True).clamp_min(1e-12))[:, :, None].expand(B, R, N, 3).contiguous()
-    lt = torch.from_numpy(rs.normal(size=(B, 16)).astype(np.float32))
-    ll = torch.from_numpy(rs.normal(size=(B, 48)).astype(np.float32))
-    return center, ray, depth, pts, unit, lt, ll
 
 
 # ------------------------------------------------------------------------------------------ 1. arithmetic pinned
@@ -130,6 +72,79 @@ def test_f16_kernel_matches_fp16_operand_emulation(ops, form):
         err, budget = rel_l2(a, e), rel_l2(e, x)
         print(form, name, "rel-L2 vs fp16-operand emulation %.2e (emulation vs exact arithmetic %.2e)" % (err, budget))
         assert err <= bar and err <= 0.5 * budget, (form, name, err, budget)
+
+
+def _check_vs_emulation(tag, out, emu, exact):
+    """the bars and rule of test_f16_kernel_matches_fp16_operand_emulation on each output AND on each channel of rgb / density
+    (channel 0 static, 1 transient: the transient channels come from the head that also gives uncert, so they get its bar)"""
+    res = []
+    for a, e, x, name, bar in zip(out, emu, exact, ("rgb", "density", "uncert"), (1e-4, 1e-4, 2e-4)):
+        parts = [(name, a, e, x, bar)]
+        if name != "uncert":
+            parts += [("%s[%d]" % (name, c), a[..., c], e[..., c], x[..., c], (1e-4, 2e-4)[c]) for c in (0, 1)]
+        for what, a_, e_, x_, bar_ in parts:
+            err, budget = rel_l2(a_, e_), rel_l2(e_, x_)
+            print(tag, what, "rel-L2 vs fp16-operand emulation %.2e (bar %.0e, emulation vs exact arithmetic %.2e)" % (err, bar_, budget))
+            res.append((what, err, bar_, budget))
+    for what, err, bar_, budget in res:
+        assert err <= bar_ and err <= 0.5 * budget, (tag, what, err, bar_, budget)
+
+
+@pytest.mark.parametrize("B,R,N", [(3, 45, 1), (1, 77, 5), (3, 13, 33), (1, 9, 100), (3, 7, 100)])
+def test_f16_plain_tiling_edges_match_emulation(ops, B, R, N):
+    """plain stream, forms A and B: S % 128 != 0 tails, tiles that straddle rays and images (distinct latents per image), N = 1 and N
+    not a multiple of the 32-sample wave tile.  Form A and form B are bit-identical (as test_mlp_vs_oracle_forms asks of fp32)."""
+    params = O.make_params(43)
+    center, ray, depth, pts, unit, lt, ll = _rays(B * 1000 + R * 10 + N, B, R, N)
+    assert not ops.ray_bias_applies("f16", N, False, True)
+    packed = ops.pack_weights({k: cu(v) for k, v in params.items()}, precision="f16")
+    ops.mlp_status(dev()).zero_()
+    out_a = ops.mlp_forward(packed, cu(lt), cu(ll), center=cu(center), ray=cu(ray), depth=cu(depth), precision="f16")
+    out_b = ops.mlp_forward(packed, cu(lt), cu(ll), points=cu(pts), ray_unit=cu(unit), precision="f16")
+    ops.check_mlp_status(dev())
+    for a, b, name in zip(out_a, out_b, ("rgb", "density", "uncert")):
+        assert torch.equal(a, b), ("form A vs form B", name)
+    _check_vs_emulation("B=%d R=%d N=%d" % (B, R, N), out_a, emulate_f16(params, pts, unit, lt, ll),
+                        emulate_f16(params, pts, unit, lt, ll, rounded=False))
+
+
+@pytest.mark.parametrize("B,R,N", [(1, 1, 128), (1, 31, 256), (3, 11, 128), (3, 11, 256), (1, 33, 256), (1, 65, 128)])
+def test_f16_ray_bias_partial_ray_blocks_match_emulation(ops, B, R, N):
+    """ray-bias stream with B*R in {1, 31, 33, 65}: the per-ray pre-kernel's last 32-ray block (kRbRays) is partial, and with B = 3
+    a block spans images (per-image light code)"""
+    params = O.make_params(44)
+    center, ray, depth, pts, unit, lt, ll = _rays(B * 1000 + R * 10 + N // 128, B, R, N)
+    assert ops.ray_bias_applies("f16", N, False, True)
+    packed = ops.pack_weights({k: cu(v) for k, v in params.items()}, precision="f16", ray_bias=True)
+    ops.mlp_status(dev()).zero_()
+    out = ops.mlp_forward(packed, cu(lt), cu(ll), center=cu(center), ray=cu(ray), depth=cu(depth), precision="f16", ray_bias=True)
+    ops.check_mlp_status(dev())
+    _check_vs_emulation("ray bias B=%d R=%d N=%d" % (B, R, N), out, emulate_f16(params, pts, unit, lt, ll, ray_bias=True),
+                        emulate_f16(params, pts, unit, lt, ll, ray_bias=True, rounded=False))
+
+
+@pytest.mark.parametrize("rb", [False, True], ids=["plain", "ray_bias"])
+def test_f16_many_tiles_persistent(ops, rb):
+    """the f16 twin of test_mlp_many_tiles_persistent: >= 3x the CU count in tiles and a tile count that is not a multiple of the
+    grid, so every workgroup runs several tiles and wraps its weight stream (60 / 55 chunks) from the last chunk back to chunk 0;
+    a strided subset of rays against the emulation, and bit-identical repeat runs"""
+    B, R, N = 2, 1201, 128
+    n_tiles, cus = B * R * N // 128, torch.cuda.get_device_properties(dev()).multi_processor_count
+    assert n_tiles >= 3 * cus and n_tiles % cus, (n_tiles, cus)
+    params = O.make_params(45)
+    center, ray, depth, pts, unit, lt, ll = _rays(17, B, R, N)
+    packed = ops.pack_weights({k: cu(v) for k, v in params.items()}, precision="f16", ray_bias=rb)
+    ops.mlp_status(dev()).zero_()
+    args = dict(center=cu(center), ray=cu(ray), depth=cu(depth), precision="f16", ray_bias=rb)
+    out = ops.mlp_forward(packed, cu(lt), cu(ll), **args)
+    again = ops.mlp_forward(packed, cu(lt), cu(ll), **args)
+    ops.check_mlp_status(dev())
+    for a, b, name in zip(out, again, ("rgb", "density", "uncert")):
+        assert torch.equal(a, b), ("run to run", name)
+    sel = torch.arange(R - 1, -1, -47).flip(0)                    # (the last ray, i.e. the last tile of each image, included)
+    emu = emulate_f16(params, pts[:, sel], unit[:, sel], lt, ll, ray_bias=rb)
+    exact = emulate_f16(params, pts[:, sel], unit[:, sel], lt, ll, ray_bias=rb, rounded=False)
+    _check_vs_emulation("%d tiles on %d CUs, %s" % (n_tiles, cus, "ray bias" if rb else "plain"), [o.cpu()[:, sel] for o in out], emu, exact)
 
 
 # ------------------------------------------------------------------------------------------ 2. accuracy vs the fp64 oracle
@@ -324,3 +339,65 @@ def test_f16_precision_leaves_training_render_and_backward_unchanged(ops):
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     assert all(torch.equal(x, y) for x, y in zip(a[2], b[2]))
     assert torch.equal(a[3], b[3])
+
+
+# ------------------------------------------------------------------------------------------ 7. stream packing: partial repacks
+@pytest.mark.parametrize("part", ["heads", "trunk"])
+@pytest.mark.parametrize("precision,rb", [("f16", False), ("f16", True), ("f16x3", False), ("f16x3", True)],
+                         ids=["f16", "f16_ray_bias", "f16x3", "f16x3_ray_bias"])
+def test_partial_repack_equals_full_pack(ops, precision, rb, part):
+    """pack(A, ALL) then pack(B, part) == pack({A outside part, B inside it}, ALL), bit for bit, from zero-filled buffers: the part's
+    chunk range (kFirstHeadChunk16 / ...RB for f16), its biases, head scalars and aux rows are rewritten and nothing else is.
+    (B is passed whole: a repack that read the other part would show as a difference.)"""
+    pa, pb = O.make_params(51), O.make_params(52)
+    mask = ops.PACK_HEADS if part == "heads" else ops.PACK_TRUNK
+    mixed = {k: (pb if k.startswith("mlp_feat") == (part == "trunk") else pa)[k] for k in pa}
+    n = ops.packed_bytes() // 4
+    got, want = torch.zeros(n, device=dev()), torch.zeros(n, device=dev())
+    ops.pack_weights({k: cu(v) for k, v in pa.items()}, packed=got, precision=precision, ray_bias=rb)
+    ops.pack_weights({k: cu(v) for k, v in pb.items()}, packed=got, parts=mask, precision=precision, ray_bias=rb)
+    ops.pack_weights({k: cu(v) for k, v in mixed.items()}, packed=want, precision=precision, ray_bias=rb)
+    diff = (got.view(torch.int32) != want.view(torch.int32)).nonzero()
+    assert diff.numel() == 0, ("first differing float", int(diff[0]), "of", n)
+    full_a, full_b = ({k: cu(v) for k, v in p.items()} for p in (pa, pb))
+    full_a = ops.pack_weights(full_a, packed=torch.zeros(n, device=dev()), precision=precision, ray_bias=rb)
+    full_b = ops.pack_weights(full_b, packed=torch.zeros(n, device=dev()), precision=precision, ray_bias=rb)
+    assert not torch.equal(got, full_a) and not torch.equal(got, full_b)
+
+
+def test_f16_render_after_training_step_uses_current_heads(ops):
+    """NeRF.packed_weights repacks only the heads of the cached f16 streams (PACK_HEADS | PACK_F16) when an optimiser step bumped a
+    head version -- what a training run does when it renders a validation view with precision = "f16".  One eager f16x3 training
+    step, then f16 renders (plain stream at N = 64, ray-bias stream at N = 128) through the cached streams must be bit-identical to
+    those of a freshly built graph loaded with the stepped weights."""
+    H, W, B = 16, 16, 1
+    sc = O.synthetic_scene(H, W, B=B, seed=2)
+    params = O.make_params(53)
+    rs = np.random.RandomState(4)
+    idx = cu(torch.from_numpy(rs.randint(0, H * W, size=(B, 97)).astype(np.int64)))
+    dr = (cu(sc["z_near"])[:, :, None], cu(sc["z_far"])[:, :, None])
+    g, opt = _graph(params, H=H, W=W, N=16, precision="f16")
+    opt.nerf.sample_stratified = False
+    opt.nerf.density_noise_reg = None
+
+    def render(graph, N):
+        opt.nerf.sample_intvs = N
+        with torch.no_grad():
+            return graph.render(opt, cu(sc["pose"]), intr=cu(sc["intr"]), ray_idx=idx, depth_range=dr, sample_idx=None, mode="val")
+
+    before = {N: render(g, N) for N in (64, 128)}                   # builds and caches both f16 streams
+    heads = [p for _, p in g.nerf.head_parameters()]
+    optim = torch.optim.Adam(heads, lr=1e-2)
+    opt.nerf.sample_intvs = 16
+    coords = cu(torch.from_numpy(rs.uniform(-0.8, 0.8, size=(B, 4, 4, 2)).astype(np.float32)))
+    ret = g.render(opt, cu(sc["pose"]), intr=cu(sc["intr"]), ray_idx=coords, depth_range=dr, sample_idx=cu(torch.tensor([1])),
+                   mode="train")
+    (ret.rgb.sum() + ret.density[..., 1].mean()).backward()
+    optim.step()
+    fresh, _ = _graph({k: v.detach().cpu() for k, v in g.nerf.state_dict().items() if k.startswith("mlp_")}, H=H, W=W, N=16)
+    for N in (64, 128):
+        got, want = render(g, N), render(fresh, N)
+        assert not torch.equal(got["rgb"], before[N]["rgb"]), N          # the step changed what is rendered
+        for name, _, _ in ops.COMPOSITE_RAY_FIELDS:
+            assert torch.equal(got[name], want[name]), (N, name)
+    ops.check_mlp_status(dev())
