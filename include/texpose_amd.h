@@ -26,7 +26,7 @@ extern "C" {
 
 typedef void* tp_stream_t; /* hipStream_t */
 
-#define TP_ABI_VERSION 14
+#define TP_ABI_VERSION 15
 
 int tp_abi_version(void);
 const char* tp_last_error(void);
@@ -776,6 +776,37 @@ int tp_disc_tail_bwd(const tp_disc_tail_args* args, tp_stream_t stream);
 int tp_disc_tail_bwd_bwd(const tp_disc_tail_args* args, tp_stream_t stream);
 int tp_disc_tail_fwd_pair(const tp_disc_tail_args* a, const tp_disc_tail_args* b, tp_stream_t stream);
 int tp_disc_tail_bwd_pair(const tp_disc_tail_args* a, const tp_disc_tail_args* b, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K19  hard mesh rasteriser for the surfel maps of the adaptation loops (rgbsyn_<loop>, nocs_<loop>, normal_<loop>)
+ * ref: compute_surfelinfo.py:37-56,100-140, tools/mvrenderer.py:33-180,695-730 (PyTorch3D, faces_per_pixel = 1),
+ *      compute_box.py:41-60.  One face per pixel: the minimum of (view-space z, face index), so the result does not
+ *      depend on the order faces are visited in.  OpenCV pinhole: x_c = R X + t, (u, v) = (K x_c)[:2] / (K x_c)[2];
+ *      pixel (row i, column j) is sampled at (j + 0.5, i + 0.5); covered iff all three barycentrics are > 0 (either
+ *      winding); degenerate faces and faces with a vertex at z <= 0 are dropped.  Background: zbuf = -1, face = -1,
+ *      rgb = nocs = normal = 0.  rgb / nocs: perspective-correct interpolation of vcolor / of the vertices normalised as
+ *      ((v - nocs_center) / nocs_scale + 1) / 2.  normal: compute_surfelinfo.normal_from_depth of zbuf (object frame,
+ *      third component negated, border and zbuf <= 0 zero).  Three launches; every output except zbuf may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_mesh_raster_args {
+  const float* verts;      /* [V,3] object frame, mm */
+  const int32_t* faces;    /* [F,3] vertex indices (out-of-range indices drop the face) */
+  const float* vcolor;     /* [V,3] in [0,1]; may be NULL when rgb is NULL */
+  float nocs_center[3];    /* host values: per-axis vertex mean */
+  float nocs_scale[3];     /* host values: per-axis max |v - mean| (> 0 when nocs is requested) */
+  const float* pose;       /* [B,3,4] [R|t] object -> camera, t in mm */
+  const float* intr;       /* [B,3,3] */
+  int B, H, W, V, F;
+  int normals_from_zbuf;   /* non-zero: only the normal stage runs, on zbuf as given (an input); verts / faces / V / F unused */
+  float* zbuf;             /* [B,H,W] out: view-space z in mm, -1 on background */
+  int32_t* face;           /* [B,H,W] out or NULL: face index, -1 on background */
+  float* rgb;              /* [B,H,W,3] out or NULL */
+  float* nocs;             /* [B,H,W,3] out or NULL */
+  float* normal;           /* [B,H,W,3] out or NULL */
+  void* workspace;         /* tp_mesh_raster_workspace_bytes(B, H, W, F) bytes, 16-byte aligned */
+} tp_mesh_raster_args;
+size_t tp_mesh_raster_workspace_bytes(int B, int H, int W, int F);
+int tp_mesh_raster(const tp_mesh_raster_args* args, tp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TEXPOSE_AMD_LIB selects another build of the SAME library (e.g. the `make trace` diagnostic build); never a fallback
 LIB_PATH = os.environ.get("TEXPOSE_AMD_LIB") or os.path.join(_HERE, "libtexpose_amd.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 # Every symbol include/texpose_amd.h declares (checked by tests/test_capi_cpu.py).
 SYMBOLS = (
@@ -38,6 +38,7 @@ SYMBOLS = (
     "tp_skinny_linear_fwd", "tp_skinny_linear_wgrad", "tp_skinny_linear_dgrad",
     "tp_disc_tail_workspace_bytes", "tp_disc_tail_fwd", "tp_disc_tail_bwd", "tp_disc_tail_bwd_bwd", "tp_disc_tail_fwd_pair", "tp_disc_tail_bwd_pair",
     "tp_feat_chain_workspace", "tp_feat_chain_packed_floats", "tp_feat_chain_pack", "tp_feat_chain",
+    "tp_mesh_raster_workspace_bytes", "tp_mesh_raster",
 )
 
 vp = C.c_void_p
@@ -204,6 +205,12 @@ class RenderEvalArgs(C.Structure):
                 ("alpha_transient", vp), ("packed_ray_bias", C.c_int)]
 
 
+class MeshRasterArgs(C.Structure):
+    _fields_ = [("verts", vp), ("faces", vp), ("vcolor", vp), ("nocs_center", C.c_float * 3), ("nocs_scale", C.c_float * 3),
+                ("pose", vp), ("intr", vp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("V", C.c_int), ("F", C.c_int),
+                ("normals_from_zbuf", C.c_int), ("zbuf", vp), ("face", vp), ("rgb", vp), ("nocs", vp), ("normal", vp), ("workspace", vp)]
+
+
 class TexposeLibraryError(RuntimeError):
     pass
 
@@ -319,6 +326,8 @@ def load() -> C.CDLL:
         sig(name, [C.POINTER(DiscTailArgs), C.POINTER(DiscTailArgs), vp])
     for name in ("tp_disc_tail_fwd", "tp_disc_tail_bwd", "tp_disc_tail_bwd_bwd"):
         sig(name, [C.POINTER(DiscTailArgs), vp])
+    sig("tp_mesh_raster_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t)
+    sig("tp_mesh_raster", [C.POINTER(MeshRasterArgs), vp])
     _lib = lib
     return lib
 

@@ -1034,6 +1034,71 @@ def render_eval(packed: Tensor, intr: Tensor, pose: Tensor, ray_idx: Tensor, z_n
     return (out, alphas) if with_alphas else out
 
 
+# ------------------------------------------------------------------------------------------ K19
+@_on_tensor_device
+def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: int, W: int, vcolor: Optional[Tensor] = None,
+                nocs_norm: Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]] = None,
+                face_ids: bool = True, normals: bool = True) -> Dict[str, Tensor]:
+    """Hard rasterisation of one mesh at B poses (tp_mesh_raster).  verts [V,3] and pose [B,3,4] ([R|t], t) in the same units (mm),
+    faces [F,3] int, intr [B,3,3] or [3,3].  Returns zbuf [B,H,W] (-1 on background) and, as asked, face [B,H,W] int32, rgb
+    (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3]."""
+    lib = _lib.load()
+    verts, pose = _f32(verts, "verts"), _f32(pose, "pose")
+    if pose.dim() == 2:
+        pose = pose[None]
+    B = pose.shape[0]
+    intr = _f32(intr, "intr")
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3).contiguous()
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    V, F = verts.shape[0], faces.shape[0]
+    if verts.shape != (V, 3) or faces.shape != (F, 3) or pose.shape != (B, 3, 4) or intr.shape != (B, 3, 3):
+        raise ValueError("mesh_raster: verts [V,3], faces [F,3], pose [B,3,4], intr [B,3,3] expected")
+    if F == 0 or V == 0:
+        raise ValueError("mesh_raster: empty mesh")
+    dev = verts.device
+    a = _lib.MeshRasterArgs()
+    a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
+    out = {"zbuf": torch.empty(B, H, W, device=dev)}
+    if face_ids:
+        out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
+    if vcolor is not None:
+        vcolor = _f32(vcolor, "vcolor")
+        if vcolor.shape != (V, 3):
+            raise ValueError("mesh_raster: vcolor [V,3] expected")
+        a.vcolor = vcolor.data_ptr()
+        out["rgb"] = torch.empty(B, H, W, 3, device=dev)
+    if nocs_norm is not None:
+        a.nocs_center = (C.c_float * 3)(*[float(x) for x in nocs_norm[0]])
+        a.nocs_scale = (C.c_float * 3)(*[float(x) for x in nocs_norm[1]])
+        out["nocs"] = torch.empty(B, H, W, 3, device=dev)
+    if normals:
+        out["normal"] = torch.empty(B, H, W, 3, device=dev)
+    ws = torch.empty(max(1, int(lib.tp_mesh_raster_workspace_bytes(B, H, W, F)) // 4), device=dev)
+    a.zbuf, a.face, a.rgb = out["zbuf"].data_ptr(), _ptr(out.get("face")), _ptr(out.get("rgb"))
+    a.nocs, a.normal, a.workspace = _ptr(out.get("nocs")), _ptr(out.get("normal")), ws.data_ptr()
+    check(lib.tp_mesh_raster(C.byref(a), _stream()), "tp_mesh_raster")
+    return out
+
+
+@_on_tensor_device
+def normals_from_depth(depth: Tensor, pose: Tensor, intr: Tensor) -> Tensor:
+    """The normal stage of tp_mesh_raster alone (compute_surfelinfo.normal_from_depth) on a given depth [B,H,W] (mm, <= 0 background),
+    pose [B,3,4] (t in mm), intr [B,3,3] -> normal [B,H,W,3]."""
+    lib = _lib.load()
+    depth, pose, intr = _f32(depth, "depth"), _f32(pose, "pose"), _f32(intr, "intr")
+    B, H, W = depth.shape
+    if pose.shape != (B, 3, 4) or intr.shape != (B, 3, 3):
+        raise ValueError("normals_from_depth: depth [B,H,W], pose [B,3,4], intr [B,3,3] expected")
+    normal = torch.empty(B, H, W, 3, device=depth.device)
+    a = _lib.MeshRasterArgs()
+    a.pose, a.intr, a.zbuf, a.normal = pose.data_ptr(), intr.data_ptr(), depth.data_ptr(), normal.data_ptr()
+    a.B, a.H, a.W, a.normals_from_zbuf = B, H, W, 1
+    check(lib.tp_mesh_raster(C.byref(a), _stream()), "tp_mesh_raster")
+    return normal
+
+
 # ------------------------------------------------------------------------------------------ K11
 _conv_counters = {}          # (device index, stream) -> zero-filled int32 tensor (the kernels leave it zero)
 _conv_counters_retired = []  # outgrown counter tensors: a captured hipGraph may still hold their address -- never freed

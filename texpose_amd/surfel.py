@@ -1,0 +1,225 @@
+"""Surfel maps of the adaptation loops: the synthetic RGB / mask, NOCS and normal maps that the reference renders with PyTorch3D
+(compute_surfelinfo.py:60-140) and its data layer reads back (data/lm.py:196-253), rendered by the HIP rasteriser (tp_mesh_raster).
+
+load_ply (numpy only), SurfelRenderer (one mesh, batches of predicted poses), write_surfel_frame (the reference's files).
+Conventions and what differs from PyTorch3D: DESIGN.md section 11."""
+from __future__ import annotations
+
+import os
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .options import AttrDict
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f):
+    if f.readline().strip() != b"ply":
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError("PLY header without end_header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":                               # ("list", count type, item type, name)
+                elements[-1][2].append(("list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]], tok[4]))
+            else:
+                elements[-1][2].append(("scalar", _PLY_TYPES[tok[1]], None, tok[2]))
+        elif tok[0] == "end_header":
+            break
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"unsupported PLY format {fmt!r}")
+    return fmt, elements
+
+
+def _read_binary_element(buf: memoryview, pos: int, count: int, props, endian: str):
+    """-> (dict name -> array (scalars) or list of arrays (lists), new position)."""
+    if all(kind == "scalar" for kind, _, _, _ in props):
+        dt = np.dtype([(name, endian + t) for _, t, _, name in props])
+        rec = np.frombuffer(buf, dtype=dt, count=count, offset=pos)
+        return {name: rec[name] for _, _, _, name in props}, pos + count * dt.itemsize
+    # lists: try the common case of one constant length first (one structured read), else walk the records
+    if count > 0:
+        fields, p = [], pos
+        for kind, t, it, name in props:
+            if kind == "scalar":
+                fields.append((name, endian + t))
+                p += np.dtype(t).itemsize
+            else:
+                n = int(np.frombuffer(buf, dtype=endian + t, count=1, offset=p)[0])
+                fields += [("__n_" + name, endian + t), (name, endian + it, (n,))]
+                p += np.dtype(t).itemsize + n * np.dtype(it).itemsize
+        dt = np.dtype(fields)
+        if pos + count * dt.itemsize <= len(buf):
+            rec = np.frombuffer(buf, dtype=dt, count=count, offset=pos)
+            if all((rec["__n_" + name] == rec.dtype[name].shape[0]).all() for kind, _, _, name in props if kind == "list"):
+                out = {name: (rec[name] if kind == "scalar" else rec[name].reshape(count, -1)) for kind, _, _, name in props}
+                return out, pos + count * dt.itemsize
+    out = {name: [] for _, _, _, name in props}
+    for _ in range(count):
+        for kind, t, it, name in props:
+            v = np.frombuffer(buf, dtype=endian + t, count=1, offset=pos)[0]
+            pos += np.dtype(t).itemsize
+            if kind == "list":
+                n = int(v)
+                out[name].append(np.frombuffer(buf, dtype=endian + it, count=n, offset=pos))
+                pos += n * np.dtype(it).itemsize
+            else:
+                out[name].append(v)
+    for kind, _, _, name in props:
+        if kind == "scalar":
+            out[name] = np.asarray(out[name])
+    return out, pos
+
+
+def _read_ascii_element(lines, count: int, props):
+    out = {name: [] for _, _, _, name in props}
+    for _ in range(count):
+        tok = next(lines).split()
+        k = 0
+        for kind, t, it, name in props:
+            if kind == "list":
+                n = int(tok[k])
+                out[name].append(np.asarray(tok[k + 1:k + 1 + n], dtype=it))
+                k += 1 + n
+            else:
+                out[name].append(float(tok[k]) if t[0] == "f" else int(tok[k]))
+                k += 1
+    for kind, t, _, name in props:
+        if kind == "scalar":
+            out[name] = np.asarray(out[name], dtype=t)
+    return out
+
+
+def _triangulate(polys) -> np.ndarray:
+    """Faces from a [F,n] array or a list of index arrays: triangles as they are, polygons (quads) as fans (0, k, k+1)."""
+    if isinstance(polys, np.ndarray) and polys.ndim == 2:
+        n = polys.shape[1]
+        if n < 3:
+            return np.zeros((0, 3), dtype=np.int32)
+        tris = [polys[:, [0, k, k + 1]] for k in range(1, n - 1)]
+        return np.stack(tris, axis=1).reshape(-1, 3).astype(np.int32)
+    tris = []
+    for p in polys:
+        for k in range(1, len(p) - 1):
+            tris.append((p[0], p[k], p[k + 1]))
+    return np.asarray(tris, dtype=np.int64).reshape(-1, 3).astype(np.int32)
+
+
+def load_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """ASCII or binary PLY (BOP `models/obj_*.ply` included) -> verts [V,3] float32, faces [F,3] int32 (quads / polygons split into
+    triangles), vcolor [V,3] float32 in [0,1] (uchar colours / 255) or None.  Vertex properties are found by name; faces come from a
+    `vertex_indices` / `vertex_index` list."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f)
+        body = f.read()
+    data = {}
+    if fmt == "ascii":
+        lines = iter(ln for ln in body.decode("ascii").splitlines() if ln.strip())
+        for name, count, props in elements:
+            data[name] = _read_ascii_element(lines, count, props)
+    else:
+        endian = "<" if fmt == "binary_little_endian" else ">"
+        buf, pos = memoryview(body), 0
+        for name, count, props in elements:
+            data[name], pos = _read_binary_element(buf, pos, count, props, endian)
+    if "vertex" not in data:
+        raise ValueError(f"{path}: no vertex element")
+    v = data["vertex"]
+    verts = np.stack([np.asarray(v[k], dtype=np.float32) for k in ("x", "y", "z")], axis=1)
+    vcolor = None
+    if all(k in v for k in ("red", "green", "blue")):
+        cols = [np.asarray(v[k]) for k in ("red", "green", "blue")]
+        vcolor = np.stack([c.astype(np.float32) / 255.0 if c.dtype == np.uint8 else c.astype(np.float32) for c in cols], axis=1)
+        vcolor = vcolor.astype(np.float32)
+    faces = np.zeros((0, 3), dtype=np.int32)
+    if "face" in data:
+        fd = data["face"]
+        key = "vertex_indices" if "vertex_indices" in fd else "vertex_index" if "vertex_index" in fd else None
+        if key is None:
+            raise ValueError(f"{path}: face element without vertex_indices / vertex_index")
+        faces = _triangulate(fd[key])
+    return verts, faces, vcolor
+
+
+def nocs_normalisation(verts) -> Tuple[np.ndarray, np.ndarray]:
+    """(centre, scale) per axis as SoftPhongNOCSShader computes them over all vertices (mvrenderer.py:702-708): the mean and the
+    largest |v - mean|; a vertex maps to ((v - centre) / scale + 1) / 2."""
+    v = torch.as_tensor(np.asarray(verts, dtype=np.float32))
+    ct = v.mean(dim=0)
+    return ct.numpy(), (v - ct).abs().max(dim=0).values.numpy()
+
+
+def calibrate_pose(pose: torch.Tensor, depth_scale: float) -> torch.Tensor:
+    """[B,3,4] pose in nerf.depth.scale units -> [R|t] in mm as compute_surfelinfo.py:107 and MVRenderer.calibrate_pose hand it to
+    PyTorch3D: t * 1000 / depth_scale, R re-orthonormalised like the 6D round trip (Gram-Schmidt of the first two columns, third =
+    their cross product; the rotation by pi about z the renderer applies before it commutes with this)."""
+    pose = pose.float()
+    a1, a2 = pose[:, :, 0], pose[:, :, 1]
+    b1 = torch.nn.functional.normalize(a1, dim=-1)
+    b2 = torch.nn.functional.normalize(a2 - (b1 * a2).sum(-1, keepdim=True) * b1, dim=-1)
+    b3 = torch.cross(b1, b2, dim=-1)
+    return torch.cat([torch.stack([b1, b2, b3], dim=-1), pose[:, :, 3:] * 1000.0 / depth_scale], dim=-1).contiguous()
+
+
+class SurfelRenderer:
+    """The colour + NOCS renders and normals of compute_surfelinfo for one CAD mesh at batches of poses (one tp_mesh_raster call)."""
+
+    def __init__(self, verts, faces, vcolor=None, H: int = 480, W: int = 640, device="cuda:0"):
+        self.device = torch.device(device)
+        self.H, self.W = int(H), int(W)
+        self.nocs_center, self.nocs_scale = nocs_normalisation(verts)
+        self.verts = torch.as_tensor(np.asarray(verts, dtype=np.float32)).to(self.device)
+        self.faces = torch.as_tensor(np.asarray(faces, dtype=np.int32)).to(self.device)
+        self.vcolor = None if vcolor is None else torch.as_tensor(np.asarray(vcolor, dtype=np.float32)).to(self.device)
+
+    def __call__(self, pose, intr, depth_scale: float) -> AttrDict:
+        """pose [B,3,4] (t in nerf.depth.scale units, like pose_init), intr [B,3,3] or [3,3] ->
+        rgb_syn [B,3,H,W] (zero without vertex colours), mask_syn [B,H,W], nocs [B,3,H,W], depth [B,H,W] (mm, -1 on background),
+        normal [B,3,H,W]."""
+        pose = torch.as_tensor(pose, dtype=torch.float32).to(self.device)
+        if pose.dim() == 2:
+            pose = pose[None]
+        intr = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
+        r = ops.mesh_raster(self.verts, self.faces, calibrate_pose(pose, depth_scale), intr, H=self.H, W=self.W, vcolor=self.vcolor,
+                            nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True)
+        chw = lambda t: t.permute(0, 3, 1, 2)
+        depth = r["zbuf"]
+        rgb = chw(r["rgb"]) if "rgb" in r else torch.zeros(depth.shape[0], 3, self.H, self.W, device=self.device)
+        return AttrDict(rgb_syn=rgb, mask_syn=(depth > 0).float(), nocs=chw(r["nocs"]), depth=depth, normal=chw(r["normal"]))
+
+
+def surfel_file_name(frame_index: int, obj_scene_id: Optional[int] = None) -> str:
+    """data/lm.py:201-204: `{frame:06d}` or, for the multi-object data, `{frame:06d}_{obj:06d}` (no extension)."""
+    return "{:06d}".format(int(frame_index)) if obj_scene_id is None else "{:06d}_{:06d}".format(int(frame_index), int(obj_scene_id))
+
+
+def write_surfel_frame(root: str, loop, frame_index: int, out: AttrDict, b: int, obj_scene_id: Optional[int] = None) -> None:
+    """Image ``b`` of a SurfelRenderer result as compute_surfelinfo.py:118-140 stores it under ``root``:
+    rgbsyn_<loop>/NAME.png (RGBA, (x * 255).astype(uint8), alpha 255 on covered pixels), nocs_<loop>/NAME.png (RGB = x, y, z),
+    normal_<loop>/NAME.npz (data = [H,W,3] float32).  cv2 wrote the BGR-flipped arrays, so the files hold R, G, B in order."""
+    from PIL import Image
+    name = surfel_file_name(frame_index, obj_scene_id)
+    hwc = lambda t: t[b].permute(1, 2, 0).detach().cpu().numpy().astype(np.float32)
+    alpha = (out.depth[b] > 0).cpu().numpy()[..., None]
+    rgba = np.concatenate([hwc(out.rgb_syn), alpha], axis=-1)
+    paths = {kind: os.path.join(root, "{}_{}".format(kind, loop)) for kind in ("rgbsyn", "nocs", "normal")}
+    for p in paths.values():
+        os.makedirs(p, exist_ok=True)
+    Image.fromarray((rgba * 255).astype(np.uint8), "RGBA").save(os.path.join(paths["rgbsyn"], name + ".png"))
+    Image.fromarray((hwc(out.nocs) * 255).astype(np.uint8), "RGB").save(os.path.join(paths["nocs"], name + ".png"))
+    np.savez_compressed(os.path.join(paths["normal"], name + ".npz"), data=hwc(out.normal))
