@@ -26,7 +26,7 @@ extern "C" {
 
 typedef void* tp_stream_t; /* hipStream_t */
 
-#define TP_ABI_VERSION 15
+#define TP_ABI_VERSION 16
 
 int tp_abi_version(void);
 const char* tp_last_error(void);
@@ -807,6 +807,37 @@ typedef struct tp_mesh_raster_args {
 } tp_mesh_raster_args;
 size_t tp_mesh_raster_workspace_bytes(int B, int H, int W, int F);
 int tp_mesh_raster(const tp_mesh_raster_args* args, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K20  the data layer's finish of the surfel maps: from tp_mesh_raster's outputs to the four tensors the reference's data
+ *      layer hands the trainer (image_syn, mask_syn, nocs_pred, normal_pred), without the files in between.
+ * ref: data/lm.py:196-253 (get_predicted_synthetic_image / get_predicted_nocs / get_predicted_normal),
+ *      data/lm.py:497-521 (get_edge, smooth_geo), compute_surfelinfo.py:118-140 (the 8-bit encode of the PNG files).
+ *      q(x) = float(uint8(trunc(x *_f32 255))) /_f32 255 (one fp32 product, truncation toward zero, the correctly rounded fp32
+ *      quotient).  The integer is clamped to [0, 255]: numpy's float -> uint8 cast is undefined outside that range, and the
+ *      rasteriser cannot produce such values (interpolated colours / NOCS lie in [0, 1] up to rounding); NaN gives 0.
+ *      image_syn = q(rgb) (zero when rgb is NULL), mask_syn = zbuf > 0 ? 1 : 0, nocs_pred = smooth_geo(q(nocs)),
+ *      normal_pred = smooth_geo(normal) (the .npz is float32: no quantisation).  smooth_geo: the mask is channel 0 != 0 of
+ *      the map being smoothed (after q for NOCS); an edge pixel is in the mask and has a 4-neighbour inside the image that
+ *      is not; its three channels become the medians of the 3x3 neighbourhood of the unsmoothed map with replicated
+ *      borders (cv2.medianBlur(x, 3)); every other pixel keeps its value.  quantize = 0 skips q for rgb and nocs (not what
+ *      the reference trains on; for callers who do not want the 8-bit loss).
+ *      One launch; inputs interleaved [B,H,W,3], outputs planar [B,3,H,W]; outputs must not overlap inputs (a pixel reads
+ *      its neighbours).  Every output may be NULL.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_surfel_finish_args {
+  const float* rgb;        /* [B,H,W,3] or NULL (mesh without vertex colours: image_syn = 0) */
+  const float* nocs;       /* [B,H,W,3]; may be NULL when nocs_pred is NULL */
+  const float* normal;     /* [B,H,W,3]; may be NULL when normal_pred is NULL */
+  const float* zbuf;       /* [B,H,W], <= 0 on background */
+  int B, H, W;
+  int quantize;            /* non-zero: the 8-bit round trip q on rgb and nocs (the reference's files) */
+  float* image_syn;        /* [B,3,H,W] out or NULL */
+  float* mask_syn;         /* [B,H,W] out or NULL */
+  float* nocs_pred;        /* [B,3,H,W] out or NULL */
+  float* normal_pred;      /* [B,3,H,W] out or NULL */
+} tp_surfel_finish_args;
+int tp_surfel_finish(const tp_surfel_finish_args* args, tp_stream_t stream);
 
 #ifdef __cplusplus
 }

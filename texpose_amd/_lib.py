@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TEXPOSE_AMD_LIB selects another build of the SAME library (e.g. the `make trace` diagnostic build); never a fallback
 LIB_PATH = os.environ.get("TEXPOSE_AMD_LIB") or os.path.join(_HERE, "libtexpose_amd.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 # Every symbol include/texpose_amd.h declares (checked by tests/test_capi_cpu.py).
 SYMBOLS = (
@@ -39,6 +39,7 @@ SYMBOLS = (
     "tp_disc_tail_workspace_bytes", "tp_disc_tail_fwd", "tp_disc_tail_bwd", "tp_disc_tail_bwd_bwd", "tp_disc_tail_fwd_pair", "tp_disc_tail_bwd_pair",
     "tp_feat_chain_workspace", "tp_feat_chain_packed_floats", "tp_feat_chain_pack", "tp_feat_chain",
     "tp_mesh_raster_workspace_bytes", "tp_mesh_raster",
+    "tp_surfel_finish",
 )
 
 vp = C.c_void_p
@@ -211,6 +212,11 @@ class MeshRasterArgs(C.Structure):
                 ("normals_from_zbuf", C.c_int), ("zbuf", vp), ("face", vp), ("rgb", vp), ("nocs", vp), ("normal", vp), ("workspace", vp)]
 
 
+class SurfelFinishArgs(C.Structure):
+    _fields_ = [("rgb", vp), ("nocs", vp), ("normal", vp), ("zbuf", vp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("quantize", C.c_int), ("image_syn", vp), ("mask_syn", vp), ("nocs_pred", vp), ("normal_pred", vp)]
+
+
 class TexposeLibraryError(RuntimeError):
     pass
 
@@ -328,6 +334,7 @@ def load() -> C.CDLL:
         sig(name, [C.POINTER(DiscTailArgs), vp])
     sig("tp_mesh_raster_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t)
     sig("tp_mesh_raster", [C.POINTER(MeshRasterArgs), vp])
+    sig("tp_surfel_finish", [C.POINTER(SurfelFinishArgs), vp])
     _lib = lib
     return lib
 

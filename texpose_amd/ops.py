@@ -1099,6 +1099,46 @@ def normals_from_depth(depth: Tensor, pose: Tensor, intr: Tensor) -> Tensor:
     return normal
 
 
+# ------------------------------------------------------------------------------------------ K20
+SURFEL_FINISH_KEYS = ("image_syn", "mask_syn", "nocs_pred", "normal_pred")
+
+
+@_on_tensor_device
+def surfel_finish(zbuf: Tensor, nocs: Tensor, normal: Tensor, rgb: Optional[Tensor] = None, *, quantize: bool = True,
+                  out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The data layer's decode of the surfel files, applied to mesh_raster's outputs (tp_surfel_finish): zbuf [B,H,W], nocs / normal /
+    rgb [B,H,W,3] (``rgb`` None: image_syn zero) -> image_syn [B,3,H,W] (8-bit round trip), mask_syn [B,H,W] (zbuf > 0), nocs_pred
+    (8-bit round trip + smooth_geo) and normal_pred (smooth_geo) [B,3,H,W].  ``quantize=False`` skips the 8-bit round trip.
+    ``out``: the four tensors to write into (float32, contiguous, of those shapes) instead of fresh ones."""
+    lib = _lib.load()
+    zbuf, nocs, normal = _f32(zbuf, "zbuf"), _f32(nocs, "nocs"), _f32(normal, "normal")
+    if zbuf.dim() != 3:
+        raise ValueError("surfel_finish: zbuf [B,H,W] expected")
+    B, H, W = zbuf.shape
+    if rgb is not None:
+        rgb = _f32(rgb, "rgb")
+    for name, t in (("nocs", nocs), ("normal", normal), ("rgb", rgb)):
+        if t is not None and t.shape != (B, H, W, 3):
+            raise ValueError(f"surfel_finish: {name} [B,H,W,3] expected")
+    shapes = {"image_syn": (B, 3, H, W), "mask_syn": (B, H, W), "nocs_pred": (B, 3, H, W), "normal_pred": (B, 3, H, W)}
+    res = {}
+    for k in SURFEL_FINISH_KEYS:
+        if out is None:
+            res[k] = torch.empty(shapes[k], device=zbuf.device)
+            continue
+        t = out[k]
+        if not t.is_cuda or t.device != zbuf.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shapes[k]:
+            raise ValueError(f"surfel_finish: out[{k!r}] must be a contiguous float32 tensor of shape {shapes[k]} on {zbuf.device}")
+        res[k] = t
+    a = _lib.SurfelFinishArgs()
+    a.rgb, a.nocs, a.normal, a.zbuf = _ptr(rgb), nocs.data_ptr(), normal.data_ptr(), zbuf.data_ptr()
+    a.B, a.H, a.W, a.quantize = B, H, W, int(bool(quantize))
+    a.image_syn, a.mask_syn = res["image_syn"].data_ptr(), res["mask_syn"].data_ptr()
+    a.nocs_pred, a.normal_pred = res["nocs_pred"].data_ptr(), res["normal_pred"].data_ptr()
+    check(lib.tp_surfel_finish(C.byref(a), _stream()), "tp_surfel_finish")
+    return res
+
+
 # ------------------------------------------------------------------------------------------ K11
 _conv_counters = {}          # (device index, stream) -> zero-filled int32 tensor (the kernels leave it zero)
 _conv_counters_retired = []  # outgrown counter tensors: a captured hipGraph may still hold their address -- never freed

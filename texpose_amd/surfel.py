@@ -1,7 +1,8 @@
 """Surfel maps of the adaptation loops: the synthetic RGB / mask, NOCS and normal maps that the reference renders with PyTorch3D
 (compute_surfelinfo.py:60-140) and its data layer reads back (data/lm.py:196-253), rendered by the HIP rasteriser (tp_mesh_raster).
 
-load_ply (numpy only), SurfelRenderer (one mesh, batches of predicted poses), write_surfel_frame (the reference's files).
+load_ply (numpy only), SurfelRenderer (one mesh, batches of predicted poses; data_layer_maps = the tensors the data layer would load,
+tp_surfel_finish), SurfelMapStore (those tensors for a whole sequence, resident), write_surfel_frame / read_surfel_frame (the reference's files).
 Conventions and what differs from PyTorch3D: DESIGN.md section 11."""
 from __future__ import annotations
 
@@ -187,20 +188,74 @@ class SurfelRenderer:
         self.faces = torch.as_tensor(np.asarray(faces, dtype=np.int32)).to(self.device)
         self.vcolor = None if vcolor is None else torch.as_tensor(np.asarray(vcolor, dtype=np.float32)).to(self.device)
 
-    def __call__(self, pose, intr, depth_scale: float) -> AttrDict:
-        """pose [B,3,4] (t in nerf.depth.scale units, like pose_init), intr [B,3,3] or [3,3] ->
-        rgb_syn [B,3,H,W] (zero without vertex colours), mask_syn [B,H,W], nocs [B,3,H,W], depth [B,H,W] (mm, -1 on background),
-        normal [B,3,H,W]."""
+    def _raster(self, pose, intr, depth_scale: float):
         pose = torch.as_tensor(pose, dtype=torch.float32).to(self.device)
         if pose.dim() == 2:
             pose = pose[None]
         intr = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
-        r = ops.mesh_raster(self.verts, self.faces, calibrate_pose(pose, depth_scale), intr, H=self.H, W=self.W, vcolor=self.vcolor,
-                            nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True)
+        return ops.mesh_raster(self.verts, self.faces, calibrate_pose(pose, depth_scale), intr, H=self.H, W=self.W, vcolor=self.vcolor,
+                               nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True)
+
+    def __call__(self, pose, intr, depth_scale: float) -> AttrDict:
+        """pose [B,3,4] (t in nerf.depth.scale units, like pose_init), intr [B,3,3] or [3,3] ->
+        rgb_syn [B,3,H,W] (zero without vertex colours), mask_syn [B,H,W], nocs [B,3,H,W], depth [B,H,W] (mm, -1 on background),
+        normal [B,3,H,W].  These are the raw renders (what the files are written from), not what the trainer is fed: data_layer_maps."""
+        r = self._raster(pose, intr, depth_scale)
         chw = lambda t: t.permute(0, 3, 1, 2)
         depth = r["zbuf"]
         rgb = chw(r["rgb"]) if "rgb" in r else torch.zeros(depth.shape[0], 3, self.H, self.W, device=self.device)
         return AttrDict(rgb_syn=rgb, mask_syn=(depth > 0).float(), nocs=chw(r["nocs"]), depth=depth, normal=chw(r["normal"]))
+
+    def data_layer_maps(self, pose, intr, depth_scale: float, quantize: bool = True, out=None) -> AttrDict:
+        """The four tensors the reference's data layer would load from the files write_surfel_frame writes for these poses
+        (data/lm.py:196-253), bit for bit, without the files: image_syn [B,3,H,W] (8-bit round trip), mask_syn [B,H,W],
+        nocs_pred [B,3,H,W] (8-bit round trip, then smooth_geo), normal_pred [B,3,H,W] (smooth_geo); plus depth [B,H,W] (mm).
+        Two C calls (tp_mesh_raster, tp_surfel_finish), nothing on the host.  ``quantize=False`` keeps the fp32 colour and NOCS
+        (not what the reference trains on).  ``out``: a dict of the four tensors to write into.  With ground-truth poses this is
+        the `_GT` variant of the maps."""
+        r = self._raster(pose, intr, depth_scale)
+        m = ops.surfel_finish(r["zbuf"], r["nocs"], r["normal"], r.get("rgb"), quantize=quantize, out=out)
+        return AttrDict(depth=r["zbuf"], **m)
+
+
+MAP_KEYS = ops.SURFEL_FINISH_KEYS
+
+
+class SurfelMapStore:
+    """The surfel maps of all N training frames of a sequence, resident on the device: what the reference's data layer reads from
+    rgbsyn_<loop> / nocs_<loop> / normal_<loop> for one pose loop.  Ten fp32 planes per frame (640 KB at 128x128).
+    ``batch(idx)`` gathers the four keys of a training batch (``var.update(store.batch(var.idx))``); ``refresh(pose_init)``
+    re-renders into the same storage for the next pose loop."""
+
+    def __init__(self, renderer: SurfelRenderer, pose_init, intr, depth_scale: float, batch: int = 16, quantize: bool = True):
+        self.renderer, self.depth_scale, self.chunk, self.quantize = renderer, float(depth_scale), max(1, int(batch)), bool(quantize)
+        pose_init = torch.as_tensor(pose_init, dtype=torch.float32)
+        if pose_init.dim() != 3 or pose_init.shape[1:] != (3, 4):
+            raise ValueError("SurfelMapStore: pose_init [N,3,4] expected")
+        N, H, W, dev = pose_init.shape[0], renderer.H, renderer.W, renderer.device
+        intr = torch.as_tensor(intr, dtype=torch.float32).to(dev)
+        if intr.shape not in ((3, 3), (N, 3, 3)):
+            raise ValueError("SurfelMapStore: intr [N,3,3] or [3,3] expected")
+        self.N, self.intr = N, intr
+        self.maps = AttrDict(image_syn=torch.empty(N, 3, H, W, device=dev), mask_syn=torch.empty(N, H, W, device=dev),
+                             nocs_pred=torch.empty(N, 3, H, W, device=dev), normal_pred=torch.empty(N, 3, H, W, device=dev))
+        self.refresh(pose_init)
+
+    def refresh(self, pose_init) -> None:
+        """Render all N frames at ``pose_init`` [N,3,4] into the tensors the store already holds (their addresses do not change)."""
+        pose_init = torch.as_tensor(pose_init, dtype=torch.float32).to(self.renderer.device)
+        if pose_init.shape != (self.N, 3, 4):
+            raise ValueError(f"SurfelMapStore.refresh: pose_init [{self.N},3,4] expected")
+        for n0 in range(0, self.N, self.chunk):
+            n1 = min(n0 + self.chunk, self.N)
+            intr = self.intr if self.intr.dim() == 2 else self.intr[n0:n1]
+            self.renderer.data_layer_maps(pose_init[n0:n1], intr, self.depth_scale, quantize=self.quantize,
+                                          out={k: self.maps[k][n0:n1] for k in MAP_KEYS})
+
+    def batch(self, idx) -> AttrDict:
+        """image_syn, mask_syn, nocs_pred, normal_pred of the frames ``idx`` [B] (int64; ``var.idx``), gathered on the device."""
+        idx = torch.as_tensor(idx, dtype=torch.int64).to(self.renderer.device)
+        return AttrDict({k: self.maps[k].index_select(0, idx) for k in MAP_KEYS})
 
 
 def surfel_file_name(frame_index: int, obj_scene_id: Optional[int] = None) -> str:
@@ -223,3 +278,35 @@ def write_surfel_frame(root: str, loop, frame_index: int, out: AttrDict, b: int,
     Image.fromarray((rgba * 255).astype(np.uint8), "RGBA").save(os.path.join(paths["rgbsyn"], name + ".png"))
     Image.fromarray((hwc(out.nocs) * 255).astype(np.uint8), "RGB").save(os.path.join(paths["nocs"], name + ".png"))
     np.savez_compressed(os.path.join(paths["normal"], name + ".npz"), data=hwc(out.normal))
+
+
+def _smooth_geo(x: np.ndarray) -> np.ndarray:
+    """data/lm.py:497-521 on a [H,W,3] float32 map (numpy only): pixels in the mask (channel 0 != 0) with a 4-neighbour inside the
+    image outside it take the per-channel 3x3 median of the unsmoothed map, borders replicated (cv2.medianBlur(x, 3))."""
+    x = np.array(x, dtype=np.float32, copy=True)
+    m = x[:, :, 0] != 0
+    out = np.zeros_like(m)
+    out[:-1] |= ~m[1:]
+    out[1:] |= ~m[:-1]
+    out[:, :-1] |= ~m[:, 1:]
+    out[:, 1:] |= ~m[:, :-1]
+    edge = m & out
+    pad = np.pad(x, ((1, 1), (1, 1), (0, 0)), mode="edge")
+    i, j = np.nonzero(edge)                                   # the median of nine is needed on the silhouette only
+    x[i, j] = np.median(np.stack([pad[i + di, j + dj] for di in range(3) for dj in range(3)]), axis=0).astype(np.float32)
+    return x
+
+
+def read_surfel_frame(root: str, loop, frame_index: int, obj_scene_id: Optional[int] = None) -> AttrDict:
+    """One frame of write_surfel_frame's files as the reference's data layer loads it (data/lm.py:196-253), on the host:
+    image_syn [3,H,W] (uint8 / 255), mask_syn [H,W] (alpha > 0), nocs_pred [3,H,W] (uint8 / 255, smoothed at the silhouette),
+    normal_pred [3,H,W] (smoothed at the silhouette), float32 CPU tensors.  SurfelRenderer.data_layer_maps gives the same tensors
+    without the files; this reader exists to check that (tools/surfel_maps.py --verify-online) and to time the file route."""
+    from PIL import Image
+    name = surfel_file_name(frame_index, obj_scene_id)
+    rgba = np.asarray(Image.open(os.path.join(root, "rgbsyn_{}".format(loop), name + ".png")))
+    nocs = np.asarray(Image.open(os.path.join(root, "nocs_{}".format(loop), name + ".png"))).astype(np.float32) / 255
+    normal = np.load(os.path.join(root, "normal_{}".format(loop), name + ".npz"))["data"]
+    chw = lambda a: torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))
+    return AttrDict(image_syn=chw(rgba[..., :3].astype(np.float32) / 255), mask_syn=torch.from_numpy((rgba[..., 3] > 0).astype(np.float32)),
+                    nocs_pred=chw(_smooth_geo(nocs)), normal_pred=chw(_smooth_geo(normal)))
