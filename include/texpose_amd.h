@@ -839,6 +839,49 @@ typedef struct tp_surfel_finish_args {
 } tp_surfel_finish_args;
 int tp_surfel_finish(const tp_surfel_finish_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K21  scene depth bounds, object labels and blended mesh depth for novel views: the z-buffer blend of K objects at B poses.
+ * ref: model/nerf_pretrain.py:307-416 (nerf_pretrain_env.py carries the same code): per object a slab test of its box against
+ *      every pixel ray (camera.py:292-314,415-433) and a depth render of its mesh; torch.where / min / gather / where over the
+ *      stack; data/lm.py:352-356 (range_source 'render': 0.8 x and 1.2 x the depth).
+ *      Per pixel, with z_k = zbuf_k > 0 ? zbuf_k : 100000 (mm; NaN counts as background):
+ *        winner  = the lowest k with the smallest z_k;  covered = zbuf_winner > 0
+ *        depth   = covered ? (z_winner /_f32 1000) *_f32 depth_scale : 0
+ *        label   = covered ? ids[winner] : 0
+ *        TP_SCENE_BOX    : label > 0 ? (t_near, t_far) of the winner's box on the pixel ray where the slab test is valid
+ *                          (t_far > 0 && t_far > t_near), (0, 0) where it is not : (bg_near, bg_far).  The ray is tp_raygen's
+ *                          TP_PIX_INDEX ray of the pixel (centre (j + 0.5, i + 0.5)), the slab test is tp_aabb's: the same device
+ *                          functions.  Unlike TP_BOUNDS_AABB, a non-positive t_near (camera inside the box) is kept.
+ *        TP_SCENE_RENDER : covered ? (depth *_f32 0.8f, depth *_f32 1.2f) : (bg_near, bg_far)
+ *        TP_SCENE_NONE   : (bg_near, bg_far); label and depth are still written.
+ *      Every operation is one rounded fp32 step (correctly rounded division, no fused multiply-add).
+ *      One launch, no workspace; outputs must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_SCENE_MAX_OBJECTS 32
+enum tp_scene_source {   /* options nerf.depth.range_source */
+  TP_SCENE_BOX = 0,
+  TP_SCENE_RENDER = 1,
+  TP_SCENE_NONE = 2
+};
+typedef struct tp_scene_bounds_args {
+  const float* pose;       /* [B,3,4] [R|t] object -> camera, t in NeRF units (depth_scale per metre); TP_SCENE_BOX only, else may be NULL */
+  const float* intr;       /* [B,3,3]; TP_SCENE_BOX only, else may be NULL */
+  const float* zbuf;       /* [K,B,H,W] tp_mesh_raster's zbuf of every object: view-space z in mm, <= 0 on background */
+  const float* boxes;      /* [K,2,3] device: (min, max) of every object's box in NeRF units (bb_mm * depth_scale / 1000);
+                            * TP_SCENE_BOX only, else may be NULL */
+  const int32_t* ids;      /* [K] device: the label of every object (> 0) */
+  int B, H, W;
+  int K;                   /* 1 .. TP_SCENE_MAX_OBJECTS */
+  int source;              /* tp_scene_source */
+  float depth_scale;       /* NeRF units per metre (options nerf.depth.scale) */
+  float bg_near, bg_far;   /* the background range, NeRF units (nerf.depth.range * nerf.depth.scale) */
+  float* z_near;           /* [B,H*W] out */
+  float* z_far;            /* [B,H*W] out */
+  int32_t* label;          /* [B,H*W] out */
+  float* depth;            /* [B,H*W] out: NeRF units, 0 where uncovered */
+} tp_scene_bounds_args;
+int tp_scene_bounds(const tp_scene_bounds_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ SYMBOLS = (
     "tp_feat_chain_workspace", "tp_feat_chain_packed_floats", "tp_feat_chain_pack", "tp_feat_chain",
     "tp_mesh_raster_workspace_bytes", "tp_mesh_raster",
     "tp_surfel_finish",
+    "tp_scene_bounds",
 )
 
 vp = C.c_void_p
@@ -217,6 +218,15 @@ class SurfelFinishArgs(C.Structure):
                 ("quantize", C.c_int), ("image_syn", vp), ("mask_syn", vp), ("nocs_pred", vp), ("normal_pred", vp)]
 
 
+SCENE_MAX_OBJECTS = 32
+
+
+class SceneBoundsArgs(C.Structure):
+    _fields_ = [("pose", vp), ("intr", vp), ("zbuf", vp), ("boxes", vp), ("ids", vp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("K", C.c_int), ("source", C.c_int), ("depth_scale", C.c_float), ("bg_near", C.c_float), ("bg_far", C.c_float),
+                ("z_near", vp), ("z_far", vp), ("label", vp), ("depth", vp)]
+
+
 class TexposeLibraryError(RuntimeError):
     pass
 
@@ -335,6 +345,7 @@ def load() -> C.CDLL:
     sig("tp_mesh_raster_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t)
     sig("tp_mesh_raster", [C.POINTER(MeshRasterArgs), vp])
     sig("tp_surfel_finish", [C.POINTER(SurfelFinishArgs), vp])
+    sig("tp_scene_bounds", [C.POINTER(SceneBoundsArgs), vp])
     _lib = lib
     return lib
 

@@ -15,41 +15,17 @@
 // workgroup write the 256*N depth samples of the tile as contiguous 16-byte stores, with the
 // per-ray (near, far-near) pair staged in LDS.
 #include "tp_common.h"
+#include "ray_geometry.h"
 #include "step_prologue.h"
 
 namespace {
 
 constexpr int kTile = 256;
 
-struct Cam {
-  float kinv[9];
-  float rt[9];    // R^T
-  float tinv[3];  // -R^T t
-};
-
-__device__ __forceinline__ void load_cam(const float* __restrict__ intr, const float* __restrict__ pose, int b, Cam& c) {
-  const float* K = intr + 9 * b;
-  const float a = K[0], bb = K[1], cc = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
-  const float A = e * i - f * h, Bc = -(d * i - f * g), C = d * h - e * g;
-  const float det = a * A + bb * Bc + cc * C;
-  const float r = 1.0f / det;
-  c.kinv[0] = A * r;  c.kinv[1] = -(bb * i - cc * h) * r;  c.kinv[2] = (bb * f - cc * e) * r;
-  c.kinv[3] = Bc * r; c.kinv[4] = (a * i - cc * g) * r;    c.kinv[5] = -(a * f - cc * d) * r;
-  c.kinv[6] = C * r;  c.kinv[7] = -(a * h - bb * g) * r;   c.kinv[8] = (a * e - bb * d) * r;
-  const float* P = pose + 12 * b;
-#pragma unroll
-  for (int r_ = 0; r_ < 3; ++r_)
-#pragma unroll
-    for (int c_ = 0; c_ < 3; ++c_) c.rt[r_ * 3 + c_] = P[c_ * 4 + r_];
-  const float t0 = P[3], t1 = P[7], t2 = P[11];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    float acc = tp::mul_rn(-c.rt[j * 3 + 0], t0);
-    acc = tp::fma_rn(-c.rt[j * 3 + 1], t1, acc);
-    acc = tp::fma_rn(-c.rt[j * 3 + 2], t2, acc);
-    c.tinv[j] = acc;
-  }
-}
+using tp_ray::Cam;          // (ray_geometry.h: shared with the scene bounds, K21)
+using tp_ray::load_cam;
+using tp_ray::pixel_ray;
+using tp_ray::slab;
 
 // grid_sample(bilinear, align_corners=True, zeros) of one channel, accumulated the way torch's
 // CPU kernel does (one multiply, three fused multiply-adds in nw,ne,sw,se order).
@@ -137,23 +113,6 @@ struct Args {
   int sampler_on, ray_blocks;
 };
 
-__device__ __forceinline__ void slab(const float* amin, const float* amax, const float* o, const float* d,
-                                     float& tn, float& tf, bool& valid) {
-  tn = -INFINITY; tf = INFINITY;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float inv = tp::div_rn(1.0f, d[a]);
-    const float ta = tp::mul_rn(tp::sub_rn(amin[a], o[a]), inv);
-    const float tb = tp::mul_rn(tp::sub_rn(amax[a], o[a]), inv);
-    // torch.minimum/maximum propagate NaN (0*inf when the origin sits on a slab plane of a parallel ray)
-    const float lo = (ta != ta || tb != tb) ? NAN : fminf(ta, tb);
-    const float hi = (ta != ta || tb != tb) ? NAN : fmaxf(ta, tb);
-    tn = (tn != tn || lo != lo) ? NAN : fmaxf(tn, lo);
-    tf = (tf != tf || hi != hi) ? NAN : fminf(tf, hi);
-  }
-  valid = (tf > 0.0f) && (tf > tn);
-}
-
 // TILE rays per workgroup of kTile threads: 256 for image-sized launches (one ray per thread, then 256 N depths written by the
 // workgroup), 32 for patch-sized ones (a training step has 1,024 rays: 4 workgroups would each walk 16 K depths -- and, with the
 // in-kernel Philox draw, 16 x 10 rounds per thread -- on the step's critical path; 32 workgroups take an eighth of that).
@@ -190,22 +149,8 @@ __global__ __launch_bounds__(kTile) void raygen_kernel(Args a) {
       v = (float)row + 0.5f;
     }
     // g = K^-1 [u,v,1];  world = R^T g + tinv;  ray = world - tinv  (camera.py:266-277,308-314)
-    float g[3], o[3], d[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float acc = tp::mul_rn(u, cam.kinv[j * 3 + 0]);
-      acc = tp::fma_rn(v, cam.kinv[j * 3 + 1], acc);
-      g[j] = tp::add_rn(acc, cam.kinv[j * 3 + 2]);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float acc = tp::mul_rn(g[0], cam.rt[j * 3 + 0]);
-      acc = tp::fma_rn(g[1], cam.rt[j * 3 + 1], acc);
-      acc = tp::fma_rn(g[2], cam.rt[j * 3 + 2], acc);
-      const float world = tp::add_rn(acc, cam.tinv[j]);
-      o[j] = cam.tinv[j];
-      d[j] = tp::sub_rn(world, cam.tinv[j]);
-    }
+    float o[3], d[3];
+    pixel_ray(cam, u, v, o, d);
     if (!a.ndc) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) {

@@ -1038,10 +1038,11 @@ def render_eval(packed: Tensor, intr: Tensor, pose: Tensor, ray_idx: Tensor, z_n
 @_on_tensor_device
 def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: int, W: int, vcolor: Optional[Tensor] = None,
                 nocs_norm: Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]] = None,
-                face_ids: bool = True, normals: bool = True) -> Dict[str, Tensor]:
+                face_ids: bool = True, normals: bool = True, zbuf_out: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Hard rasterisation of one mesh at B poses (tp_mesh_raster).  verts [V,3] and pose [B,3,4] ([R|t], t) in the same units (mm),
     faces [F,3] int, intr [B,3,3] or [3,3].  Returns zbuf [B,H,W] (-1 on background) and, as asked, face [B,H,W] int32, rgb
-    (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3]."""
+    (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3].
+    ``zbuf_out``: a contiguous float32 [B,H,W] tensor (e.g. one plane of a [K,B,H,W] stack) to write zbuf into."""
     lib = _lib.load()
     verts, pose = _f32(verts, "verts"), _f32(pose, "pose")
     if pose.dim() == 2:
@@ -1060,7 +1061,10 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     a = _lib.MeshRasterArgs()
     a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
-    out = {"zbuf": torch.empty(B, H, W, device=dev)}
+    if zbuf_out is not None and (zbuf_out.device != dev or zbuf_out.dtype != torch.float32 or not zbuf_out.is_contiguous()
+                                 or tuple(zbuf_out.shape) != (B, H, W)):
+        raise ValueError(f"mesh_raster: zbuf_out must be a contiguous float32 tensor of shape {(B, H, W)} on {dev}")
+    out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else zbuf_out}
     if face_ids:
         out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
     if vcolor is not None:
@@ -1136,6 +1140,53 @@ def surfel_finish(zbuf: Tensor, nocs: Tensor, normal: Tensor, rgb: Optional[Tens
     a.image_syn, a.mask_syn = res["image_syn"].data_ptr(), res["mask_syn"].data_ptr()
     a.nocs_pred, a.normal_pred = res["nocs_pred"].data_ptr(), res["normal_pred"].data_ptr()
     check(lib.tp_surfel_finish(C.byref(a), _stream()), "tp_surfel_finish")
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K21
+SCENE_SOURCES = {"box": 0, "render": 1, "none": 2}          # options nerf.depth.range_source -> TP_SCENE_*
+SCENE_BOUNDS_KEYS = ("z_near", "z_far", "label", "depth")
+
+
+@_on_tensor_device
+def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float, bg_range: Tuple[float, float], source: str = "box",
+                 pose: Optional[Tensor] = None, intr: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The z-buffer blend of K objects at B poses (tp_scene_bounds): zbuf [K,B,H,W] (mesh_raster's planes: mm, <= 0 on background),
+    boxes [K,2,3] (min, max in NeRF units: bb_mm * depth_scale / 1000), ids [K] int32 (> 0), pose [B,3,4] (t in NeRF units) and intr
+    [B,3,3] (needed by ``source`` 'box' only) -> z_near, z_far [B,H*W] float32, label [B,H*W] int32 (the nearest object's id, 0 where
+    nothing is covered), depth [B,H*W] (the nearest mesh depth in NeRF units, 0 where uncovered).  ``source`` 'box': the winner's slab
+    bounds on the pixel ray (0 where the slab test fails), 'render': 0.8 x / 1.2 x depth, 'none': ``bg_range`` everywhere; uncovered
+    pixels always get ``bg_range``.  Inputs are taken as they are (float32 / int32, contiguous, on one GPU) -- nothing is converted or
+    copied; ``out``: the four tensors to write into.  One launch, no allocation beyond fresh outputs, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    if source not in SCENE_SOURCES:
+        raise ValueError(f"scene_bounds: source must be one of {sorted(SCENE_SOURCES)}, not {source!r}")
+
+    def want(t, name, dtype, shape):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"scene_bounds: {name} must be a contiguous {dtype} GPU tensor" + ("" if shape is None else f" of shape {shape}"))
+        return t
+
+    want(zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 4:
+        raise ValueError("scene_bounds: zbuf [K,B,H,W] expected")
+    K, B, H, W = zbuf.shape
+    want(ids, "ids", torch.int32, (K,))
+    a = _lib.SceneBoundsArgs()
+    if source == "box":
+        want(boxes, "boxes", torch.float32, (K, 2, 3))
+        want(pose, "pose", torch.float32, (B, 3, 4))
+        want(intr, "intr", torch.float32, (B, 3, 3))
+        a.boxes, a.pose, a.intr = boxes.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    dtypes = {"z_near": torch.float32, "z_far": torch.float32, "label": torch.int32, "depth": torch.float32}
+    res = {}
+    for k in SCENE_BOUNDS_KEYS:
+        res[k] = torch.empty(B, H * W, device=zbuf.device, dtype=dtypes[k]) if out is None else want(out[k], f"out[{k!r}]", dtypes[k], (B, H * W))
+    a.zbuf, a.ids = zbuf.data_ptr(), ids.data_ptr()
+    a.B, a.H, a.W, a.K, a.source = B, H, W, K, SCENE_SOURCES[source]
+    a.depth_scale, a.bg_near, a.bg_far = float(depth_scale), float(bg_range[0]), float(bg_range[1])
+    a.z_near, a.z_far, a.label, a.depth = (res[k].data_ptr() for k in SCENE_BOUNDS_KEYS)
+    check(lib.tp_scene_bounds(C.byref(a), _stream()), "tp_scene_bounds")
     return res
 
 
