@@ -882,6 +882,49 @@ typedef struct tp_scene_bounds_args {
 } tp_scene_bounds_args;
 int tp_scene_bounds(const tp_scene_bounds_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K22  the per-object annotations a BOP scene folder stores for a frame (scene_gt_info.json, mask/, mask_visib/), for K objects
+ *      at B poses, from K21's inputs and output; and the 8-bit / 16-bit images of a rendered view (rgb/, depth/).
+ * ref: data/lm.py:161-180,255-300 (what the reference's data layer reads of such a folder); the rules themselves are the BOP
+ *      format's, restated in tests/scene_annotate_ref.py.
+ *      tp_scene_annotate, per object k, pose b, pixel p (x = column, y = row):
+ *        all_k(p)   = zbuf[k,b,p] > 0                      (NaN counts as background)
+ *        visib_k(p) = all_k(p) && label[b,p] == ids[k]     (ids must be distinct)
+ *        info[b,k]  = { px_count_all, px_count_visib, xmin, ymin, xmax, ymax of all_k, xmin, ymin, xmax, ymax of visib_k }:
+ *                     inclusive pixel indices; an empty set gives -1 in its four extents
+ *        mask[b,k,p] = all_k(p) ? 255 : 0,  mask_visib[b,k,p] = visib_k(p) ? 255 : 0
+ *      The call initialises info itself (a first launch writes 0 / -1, the second accumulates with integer atomics: add, signed
+ *      max, unsigned min): no memset by the caller, no workspace, no allocation, no host synchronisation; integer reductions, so
+ *      the result is exactly reproducible.  Outputs must not overlap inputs.  Safe to capture.
+ *      tp_view_images, one rounded fp32 operation per step, NaN -> 0:
+ *        rgb8    = uint8(trunc(clamp(rgb, 0, 1) *_f32 255))
+ *        depth16 = uint16(trunc(clamp((depth /_f32 depth_scale) *_f32 png_per_metre, 0, 65535)))
+ *      One launch.  Either pair (rgb, rgb8) / (depth, depth16) may be NULL as a whole.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_SCENE_INFO_FIELDS 10
+typedef struct tp_scene_annotate_args {
+  const float* zbuf;       /* [K,B,H,W] tp_mesh_raster's zbuf of every object: view-space z in mm, <= 0 or NaN on background */
+  const int32_t* label;    /* [B,H*W] tp_scene_bounds' label: the id of the nearest object, 0 where nothing is covered */
+  const int32_t* ids;      /* [K] device: the label of every object, distinct */
+  int B, H, W;
+  int K;                   /* 1 .. TP_SCENE_MAX_OBJECTS */
+  int32_t* info;           /* [B,K,TP_SCENE_INFO_FIELDS] out */
+  uint8_t* mask;           /* [B,K,H,W] out or NULL: 0 / 255 */
+  uint8_t* mask_visib;     /* [B,K,H,W] out or NULL: 0 / 255 */
+} tp_scene_annotate_args;
+int tp_scene_annotate(const tp_scene_annotate_args* args, tp_stream_t stream);
+
+typedef struct tp_view_images_args {
+  const float* rgb;        /* [B,H*W,3] or NULL */
+  const float* depth;      /* [B,H*W] in NeRF units (depth_scale per metre), or NULL */
+  int B, H, W;
+  float depth_scale;       /* NeRF units per metre (options nerf.depth.scale) */
+  float png_per_metre;     /* depth16 units per metre (2000: the file stores half millimetres) */
+  uint8_t* rgb8;           /* [B,H,W,3] out (NULL with rgb) */
+  uint16_t* depth16;       /* [B,H,W] out (NULL with depth) */
+} tp_view_images_args;
+int tp_view_images(const tp_view_images_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ SYMBOLS = (
     "tp_mesh_raster_workspace_bytes", "tp_mesh_raster",
     "tp_surfel_finish",
     "tp_scene_bounds",
+    "tp_scene_annotate", "tp_view_images",
 )
 
 vp = C.c_void_p
@@ -227,6 +228,19 @@ class SceneBoundsArgs(C.Structure):
                 ("z_near", vp), ("z_far", vp), ("label", vp), ("depth", vp)]
 
 
+SCENE_INFO_FIELDS = 10
+
+
+class SceneAnnotateArgs(C.Structure):
+    _fields_ = [("zbuf", vp), ("label", vp), ("ids", vp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("K", C.c_int),
+                ("info", vp), ("mask", vp), ("mask_visib", vp)]
+
+
+class ViewImagesArgs(C.Structure):
+    _fields_ = [("rgb", vp), ("depth", vp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("depth_scale", C.c_float),
+                ("png_per_metre", C.c_float), ("rgb8", vp), ("depth16", vp)]
+
+
 class TexposeLibraryError(RuntimeError):
     pass
 
@@ -346,6 +360,8 @@ def load() -> C.CDLL:
     sig("tp_mesh_raster", [C.POINTER(MeshRasterArgs), vp])
     sig("tp_surfel_finish", [C.POINTER(SurfelFinishArgs), vp])
     sig("tp_scene_bounds", [C.POINTER(SceneBoundsArgs), vp])
+    sig("tp_scene_annotate", [C.POINTER(SceneAnnotateArgs), vp])
+    sig("tp_view_images", [C.POINTER(ViewImagesArgs), vp])
     _lib = lib
     return lib
 

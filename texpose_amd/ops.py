@@ -1190,6 +1190,81 @@ def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float
     return res
 
 
+# ------------------------------------------------------------------------------------------ K22
+SCENE_INFO_KEYS = ("px_count_all", "px_count_visib", "obj_xmin", "obj_ymin", "obj_xmax", "obj_ymax", "visib_xmin", "visib_ymin",
+                   "visib_xmax", "visib_ymax")                      # the ten columns of info, in order
+
+
+def _want_gpu(op: str, t, name: str, dtype, shape):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError(f"{op}: {name} must be a contiguous {dtype} GPU tensor" + ("" if shape is None else f" of shape {shape}"))
+    return t
+
+
+@_on_tensor_device
+def scene_annotate(zbuf: Tensor, label: Tensor, ids: Tensor, *, masks: bool = True, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The per-object annotations of K objects at B poses (tp_scene_annotate): zbuf [K,B,H,W] (mesh_raster's planes: mm, <= 0 or NaN on
+    background), label [B,H*W] int32 (scene_bounds' label), ids [K] int32 -> info [B,K,10] int32 (columns: SCENE_INFO_KEYS; extents
+    are inclusive pixel indices, -1 for an empty set) and, with ``masks``, mask and mask_visib [B,K,H,W] uint8 (0 / 255: the full
+    silhouette inside the image and the part that ``label`` gives to the object).  The ids must be distinct: a wrapper that builds
+    them (SceneBounds) checks that on the host; here they are taken as they are, like every input -- nothing is converted, copied or
+    read back.  ``out``: the tensors to write into ('info', and 'mask' / 'mask_visib' when ``masks``); info needs no clearing.
+    No allocation beyond fresh outputs, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    _want_gpu("scene_annotate", zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 4:
+        raise ValueError("scene_annotate: zbuf [K,B,H,W] expected")
+    K, B, H, W = zbuf.shape
+    _want_gpu("scene_annotate", label, "label", torch.int32, (B, H * W))
+    _want_gpu("scene_annotate", ids, "ids", torch.int32, (K,))
+    spec = {"info": (torch.int32, (B, K, _lib.SCENE_INFO_FIELDS))}
+    if masks:
+        spec.update(mask=(torch.uint8, (B, K, H, W)), mask_visib=(torch.uint8, (B, K, H, W)))
+    res = {}
+    for k, (dtype, shape) in spec.items():
+        res[k] = torch.empty(shape, device=zbuf.device, dtype=dtype) if out is None else _want_gpu("scene_annotate", out[k], f"out[{k!r}]", dtype, shape)
+    a = _lib.SceneAnnotateArgs()
+    a.zbuf, a.label, a.ids = zbuf.data_ptr(), label.data_ptr(), ids.data_ptr()
+    a.B, a.H, a.W, a.K = B, H, W, K
+    a.info = res["info"].data_ptr()
+    if masks:
+        a.mask, a.mask_visib = res["mask"].data_ptr(), res["mask_visib"].data_ptr()
+    check(lib.tp_scene_annotate(C.byref(a), _stream()), "tp_scene_annotate")
+    return res
+
+
+@_on_tensor_device
+def view_images(rgb: Optional[Tensor], depth: Optional[Tensor], *, H: int, W: int, depth_scale: float = 1.0, png_per_metre: float = 2000.0,
+                out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The files' pixels of rendered views (tp_view_images): rgb [B,H*W,3] -> rgb8 [B,H,W,3] uint8 = trunc(clamp(rgb, 0, 1) * 255);
+    depth [B,H*W] or [B,H*W,1] in NeRF units -> depth16 [B,H,W] uint16 = trunc(clamp((depth / depth_scale) * png_per_metre, 0, 65535));
+    NaN gives 0.  Either input may be None (its output is then absent).  ``out``: 'rgb8' / 'depth16' tensors to write into."""
+    lib = _lib.load()
+    if rgb is None and depth is None:
+        raise ValueError("view_images: rgb or depth expected")
+    first = rgb if rgb is not None else depth
+    _want_gpu("view_images", first, "rgb" if rgb is not None else "depth", torch.float32, None)
+    B, HW = int(first.shape[0]), int(H) * int(W)
+    a = _lib.ViewImagesArgs()
+    a.B, a.H, a.W, a.depth_scale, a.png_per_metre = B, int(H), int(W), float(depth_scale), float(png_per_metre)
+    res = {}
+
+    def output(key, dtype, shape):
+        res[key] = torch.empty(shape, device=first.device, dtype=dtype) if out is None else _want_gpu("view_images", out[key], f"out[{key!r}]", dtype, shape)
+        return res[key].data_ptr()
+
+    if rgb is not None:
+        _want_gpu("view_images", rgb, "rgb", torch.float32, (B, HW, 3))
+        a.rgb, a.rgb8 = rgb.data_ptr(), output("rgb8", torch.uint8, (B, H, W, 3))
+    if depth is not None:
+        if depth.dim() == 3 and depth.shape[-1] == 1:
+            depth = depth[..., 0]
+        _want_gpu("view_images", depth, "depth", torch.float32, (B, HW))
+        a.depth, a.depth16 = depth.data_ptr(), output("depth16", torch.uint16, (B, H, W))
+    check(lib.tp_view_images(C.byref(a), _stream()), "tp_view_images")
+    return res
+
+
 # ------------------------------------------------------------------------------------------ K11
 _conv_counters = {}          # (device index, stream) -> zero-filled int32 tensor (the kernels leave it zero)
 _conv_counters_retired = []  # outgrown counter tensors: a captured hipGraph may still hold their address -- never freed

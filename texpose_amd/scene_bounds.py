@@ -27,6 +27,17 @@ def novel_view_poses_obj(pose_anchor: torch.Tensor, N: int = 10) -> torch.Tensor
     return compose_poses(make_pose(R=R_z), pose_anchor.detach().cpu().float()[None])
 
 
+def distinct_object_ids(ids) -> list:
+    """The ids as a list of ints, after checking what the scene kernels take for granted: every id positive (0 labels the background)
+    and no id twice (tp_scene_annotate tells the objects apart by their label)."""
+    ids = [int(k) for k in ids]
+    if not ids or min(ids) <= 0:
+        raise ValueError("SceneBounds: object ids must be positive (0 labels the background)")
+    if len(set(ids)) != len(ids):
+        raise ValueError("SceneBounds: duplicate object ids %s" % sorted(k for k in set(ids) if ids.count(k) > 1))
+    return ids
+
+
 class SceneBounds:
     """``objects``: {object id (> 0): (SurfelRenderer, bb_min_mm, bb_max_mm)} in blend order (ties go to the earlier object; they only
     occur between backgrounds); every renderer renders H x W on one device.  ``depth_scale_opt``: options nerf.depth.scale (NeRF
@@ -44,9 +55,7 @@ class SceneBounds:
             raise ValueError(f"SceneBounds: 1 .. {_lib.SCENE_MAX_OBJECTS} objects expected, not {len(objects)}")
         self.H, self.W, self.depth_scale = int(H), int(W), float(depth_scale_opt)
         self.bg_range = (float(bg_range[0]), float(bg_range[1]))
-        self.object_ids = [int(k) for k in objects]
-        if min(self.object_ids) <= 0:
-            raise ValueError("SceneBounds: object ids must be positive (0 labels the background)")
+        self.object_ids = distinct_object_ids(objects)
         self.renderers = [objects[k][0] for k in objects]
         for r in self.renderers:
             if (r.H, r.W) != (self.H, self.W) or r.device != self.renderers[0].device:
@@ -57,6 +66,7 @@ class SceneBounds:
         self.boxes = ((bb * self.depth_scale) / 1000).contiguous().to(self.device)
         self.ids = torch.tensor(self.object_ids, dtype=torch.int32, device=self.device)
         self._buffers: Dict[int, dict] = {}
+        self._annotations: Dict[int, dict] = {}
 
     def _buffers_for(self, B: int) -> dict:
         buf = self._buffers.get(B)
@@ -95,3 +105,19 @@ class SceneBounds:
         torch.gt(out["label"], 0, out=buf["mask"])
         return AttrDict(depth_range=(out["z_near"][..., None], out["z_far"][..., None]), label=out["label"], object_mask=buf["mask"],
                         depth=out["depth"], zbuf=zbuf)
+
+    def annotate(self, sb: AttrDict, masks: bool = True) -> AttrDict:
+        """The per-object annotations of the views a call returned (tp_scene_annotate, K22): ``info`` [B,K,10] int32 (columns
+        ``ops.SCENE_INFO_KEYS``: pixel counts and inclusive extents of the full and of the visible silhouette, -1 where empty) and, with
+        ``masks``, ``mask`` / ``mask_visib`` [B,K,H,W] uint8 (0 / 255), objects in blend order.  Needs ``sb.zbuf`` and ``sb.label`` as the
+        call left them; the results live in buffers kept per (B, K) like the call's own."""
+        K, B = sb.zbuf.shape[:2]
+        buf = self._annotations.get(B)
+        if buf is None:
+            buf = dict(info=torch.empty(B, K, _lib.SCENE_INFO_FIELDS, device=self.device, dtype=torch.int32))
+            self._annotations[B] = buf
+        if masks and "mask" not in buf:
+            for k in ("mask", "mask_visib"):
+                buf[k] = torch.empty(B, K, self.H, self.W, device=self.device, dtype=torch.uint8)
+        out = ops.scene_annotate(sb.zbuf, sb.label, self.ids, masks=masks, out=buf)
+        return AttrDict(info=out["info"], mask=out.get("mask"), mask_visib=out.get("mask_visib"))
