@@ -75,6 +75,146 @@ def test_ops_refuse_cpu_tensors():
                           torch.zeros(1, 2, 4, 1), torch.zeros(1, 2, 4, 1))
 
 
+# ------------------------------------------------------------------ the binding is derived from the header
+def _header_text():
+    text = open(os.path.join(REPO, "include", "texpose_amd.h")).read()
+    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+
+
+def _header_struct_fields():
+    """{struct: [field, ...]} by this test's own regex, independent of the binding's parser."""
+    out = {}
+    for body, name in re.findall(r"typedef struct tp_\w+ \{(.*?)\}\s*(tp_\w+);", _header_text(), flags=re.S):
+        decls = [re.sub(r"^(?:const\s+)?(?:unsigned\s+)?\w+", "", d.strip(), count=1) for d in body.split(";") if d.strip()]
+        out[name] = [re.sub(r"\[\w+\]|\bconst\b|[*\s]", "", n) for d in decls for n in d.split(",")]
+    return out
+
+
+def _host_cc():
+    import shutil
+    return shutil.which("cc") or shutil.which("/opt/rocm/lib/llvm/bin/clang")
+
+
+def test_struct_layout_matches_host_compiler(tmp_path):
+    # sizeof of every struct, offsetof and size of every field, as a C compiler lays the header out
+    import subprocess
+    cc = _host_cc()
+    if cc is None:
+        pytest.skip("no host C compiler (cc, ROCm clang)")
+    structs = _lib.HEADER.structs
+    assert len(structs) == len(_header_struct_fields()) >= 29
+    lines = ['#include <stdio.h>', '#include "texpose_amd.h"', "int main(void) {"]
+    for cname, cls in structs.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'  printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f, _ in cls._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]))
+    subprocess.run([cc, "-I", os.path.join(REPO, "include"), "-o", str(tmp_path / "layout"), str(src)], check=True)
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines()
+    want = []
+    for cname, cls in structs.items():
+        want.append(f"{cname} {C.sizeof(cls)}")
+        want += [f"{cname}.{f} {getattr(cls, f).offset} {getattr(cls, f).size}" for f, _ in cls._fields_]
+    assert got == want
+    assert len(want) > 29 + 300          # every field of every struct took part
+
+
+def test_struct_fields_match_header_and_refuse_unknown_names():
+    fields = _header_struct_fields()
+    assert list(fields) == list(_lib.HEADER.structs)
+    for cname, cls in _lib.HEADER.structs.items():
+        assert [f for f, _ in cls._fields_] == fields[cname], cname
+        assert getattr(_lib, cls.__name__) is cls
+        with pytest.raises(AttributeError):
+            cls().no_such_field = 1
+    assert "inp" in fields["tp_conv3s1_args"] and len(fields["tp_disc_tail_args"]) == 36
+    a = _lib.MeshRasterArgs()
+    with pytest.raises(AttributeError):
+        a.zbuff = 1          # (the field is zbuf)
+
+
+def test_constants_come_from_header():
+    from texpose_amd import bop_scene, ops
+    defines = {k: int(v) for k, v in re.findall(r"^#define (TP_\w+) (\d+)\s*$", _header_text(), flags=re.M)}
+    assert len(defines) >= 17 and defines["TP_ABI_VERSION"] == _lib.ABI_VERSION
+    for k, v in defines.items():
+        assert getattr(_lib, k) == getattr(_lib, k[3:]) == v, k
+    assert (_lib.TP_PIX_INDEX, _lib.TP_BOUNDS_NONE, _lib.TP_JITTER_PHILOX, _lib.TP_DEPTH_INVERSE, _lib.TP_SCENE_NONE) == (1, 2, 2, 1, 2)
+    assert (ops.PACK_TRUNK, ops.PACK_HEADS, ops.PACK_ALL, ops.PACK_F16X3, ops.PACK_RAYBIAS, ops.PACK_F16) == (1, 2, 3, 4, 8, 16)
+    assert ops.PRECISIONS == {"fp32": 0, "f16x3": 1, "f16": 2} and ops.SCENE_SOURCES == {"box": 0, "render": 1, "none": 2}
+    assert ops.DEPTH_PARAMS == {"metric": 0, "inverse": 1}
+    assert bop_scene.INFO_FIELDS == _lib.SCENE_INFO_FIELDS == len(ops.SCENE_INFO_KEYS)
+
+
+def test_prototypes_match_header():
+    lib = _lib.load()
+    width = {"int": 4, "int64_t": 8, "size_t": 8, "const char*": 8}
+    protos = re.findall(r"^(int|int64_t|size_t|const char\*)\s+(tp_\w+)\s*\(([^)]*)\)\s*;", _header_text(), flags=re.M)
+    assert [name for _, name, _ in protos] == list(_lib.SYMBOLS)
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+        assert C.sizeof(fn.restype) == width[ret], name
+    vp, i = C.c_void_p, C.c_int
+    assert lib.tp_sample_depth.argtypes == [vp, vp, vp, i, C.c_uint64, C.c_uint64, C.c_int64, i, i, vp, vp]
+    assert lib.tp_adam_step.argtypes == [C.POINTER(_lib.AdamTensor), i, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, i, vp, vp]
+    assert lib.tp_mlp_packed_bytes.argtypes == [] and lib.tp_mlp_packed_bytes.restype is C.c_size_t
+    assert lib.tp_last_error.restype is C.c_char_p
+    # a pointer to a tp_* struct is typed: byref of another struct is refused before the call
+    with pytest.raises(C.ArgumentError):
+        lib.tp_raygen(C.byref(_lib.CompositeArgs()), None)
+
+
+_EDGES = """
+#define TP_N 3
+enum { TP_A = 1, TP_B = 2,
+       TP_C = 8 /* OR-ed in */ };
+enum tp_mode { TP_M0, TP_M1 };
+typedef void* tp_stream_t;
+typedef struct tp_inner { const float* w[2]; int64_t n; } tp_inner;
+typedef struct tp_outer {
+  int B, R; float lo, hi;
+  void* param[TP_N];
+  tp_inner inner;
+  int64_t* idx_copy /* or NULL */;
+  uint8_t flag; double d; size_t s;
+} tp_outer;
+int64_t tp_f(const tp_outer* args,
+             const float* const* terms, uint64_t seed,
+             tp_stream_t stream);
+size_t tp_g(void);
+"""
+
+
+def test_parser_edges():
+    h = _lib.parse_header(_EDGES)
+    assert h.constants == {"TP_N": 3, "TP_A": 1, "TP_B": 2, "TP_C": 8, "TP_M0": 0, "TP_M1": 1}
+    inner, outer = h.structs["tp_inner"], h.structs["tp_outer"]
+    assert (inner.__name__, outer.__name__) == ("Inner", "Outer")
+    vp = C.c_void_p
+    assert outer._fields_ == [("B", C.c_int), ("R", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("param", vp * 3), ("inner", inner),
+                              ("idx_copy", vp), ("flag", C.c_uint8), ("d", C.c_double), ("s", C.c_size_t)]
+    assert inner._fields_ == [("w", vp * 2), ("n", C.c_int64)] and outer.inner.offset == 40 and C.sizeof(outer) == 96
+    assert h.prototypes == {"tp_f": (C.c_int64, [C.POINTER(outer), vp, C.c_uint64, vp]), "tp_g": (C.c_size_t, [])}
+
+
+@pytest.mark.parametrize("text, shown", [
+    ("static inline int tp_f(void) { return 0; }", "static inline int tp_f"),
+    ("struct tp_x;", "struct tp_x;"),
+    ("int tp_counter;", "int tp_counter;"),
+    ("typedef struct tp_x { union { int a; float b; } u; } tp_x;", "typedef struct tp_x { union"),
+    ("typedef struct tp_x { long double a; } tp_x;", "long double a"),
+    ("typedef struct tp_x { int a[TP_UNKNOWN]; } tp_x;", "a[TP_UNKNOWN]"),
+    ("int tp_f(tp_unknown_args* a);", "tp_unknown_args"),
+    ("int tp_f(int);", "tp_f(int)"),
+    ("#define TP_F(x) (x)", "#define TP_F(x)"),
+    ("#if 0\n#endif", "#if 0"),
+])
+def test_parser_raises_on_what_it_does_not_know(text, shown):
+    with pytest.raises(_lib.TexposeLibraryError, match=re.escape(shown)):          # the message shows the offending text
+        _lib.parse_header("#define TP_OK 1\n" + text + "\nint tp_after(void);")
+
+
 # ------------------------------------------------------------------ packed-stream emulation
 def _feat_of(t, r, h):
     return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h

@@ -23,7 +23,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-INFO_FIELDS = 10          # ops.SCENE_INFO_KEYS
+from ._lib import SCENE_INFO_FIELDS as INFO_FIELDS          # the columns ops.SCENE_INFO_KEYS names
 
 
 def _host(x) -> np.ndarray:

@@ -639,8 +639,8 @@ static int conv3_launch(const tp_conv3s1_args* a, int transposed, tp_stream_t st
   Plan q; Conv3P p;
   const int rc = conv3_plan(a, transposed, &q, &p);
   if (rc != 0) return rc;
-  TP_REQUIRE(a->in && a->w && a->out && a->counters && (!q.ws_floats || a->workspace), "operand / counters / workspace missing");
-  p.in = a->in; p.w = a->w; p.bias = transposed ? nullptr : a->bias; p.mask = transposed ? a->mask : nullptr; p.out = a->out;
+  TP_REQUIRE(a->inp && a->w && a->out && a->counters && (!q.ws_floats || a->workspace), "operand / counters / workspace missing");
+  p.in = a->inp; p.w = a->w; p.bias = transposed ? nullptr : a->bias; p.mask = transposed ? a->mask : nullptr; p.out = a->out;
   p.ws = a->workspace; p.cnt = (unsigned*)a->counters;
   const dim3 grid((unsigned)(q.tiles_m * q.tiles_n * q.S)), block(256);
   hipStream_t st = (hipStream_t)stream;

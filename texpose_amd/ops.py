@@ -17,15 +17,13 @@ import torch
 from . import _lib, knobs
 from ._lib import (CompositeArgs, CompositeBwdArgs, MlpBwdArgs, MlpFwdArgs, MlpWeights, PatchGatherArgs, RaygenArgs,
                    check)
+# the header's enumerators (TP_PIX_COORDS, ...) under their short names: tests and tools import them from here
+from ._lib import (BOUNDS_AABB, BOUNDS_MAP, BOUNDS_NONE, JITTER_GIVEN, JITTER_MID, JITTER_PHILOX, MLP_F16, MLP_F16X3,  # noqa: F401
+                   MLP_FP32, PACK_ALL, PACK_F16, PACK_F16X3, PACK_HEADS, PACK_RAYBIAS, PACK_TRUNK, PIX_COORDS, PIX_INDEX)
 
 Tensor = torch.Tensor
 
-PIX_COORDS, PIX_INDEX = 0, 1
-BOUNDS_MAP, BOUNDS_AABB, BOUNDS_NONE = 0, 1, 2
-JITTER_MID, JITTER_GIVEN, JITTER_PHILOX = 0, 1, 2
-DEPTH_PARAMS = {"metric": 0, "inverse": 1}          # options nerf.depth.param -> TP_DEPTH_*
-PACK_TRUNK, PACK_HEADS, PACK_ALL, PACK_F16X3, PACK_RAYBIAS, PACK_F16 = 1, 2, 3, 4, 8, 16
-MLP_FP32, MLP_F16X3, MLP_F16 = 0, 1, 2
+DEPTH_PARAMS = {"metric": _lib.DEPTH_METRIC, "inverse": _lib.DEPTH_INVERSE}          # options nerf.depth.param -> TP_DEPTH_*
 # "f16": single fp16 products with fp32 accumulation, inference only (include/texpose_amd.h, TP_MLP_F16)
 PRECISIONS = {"fp32": MLP_FP32, "f16x3": MLP_F16X3, "f16": MLP_F16}
 # the arithmetics whose forward raises the fp16 range flag (mlp_status) and whose training forms do not exist
@@ -675,10 +673,11 @@ def _pair_slot() -> int:
     return 1 if _pair_state["active"] and _pair_state["pending"] is not None else 0
 
 
-def _launch(name: str, args, extra=()):
+def _launch(name: str, args, extra=(), keep=()):
     """Launch ``lib.<name>(byref(args), *extra, stream)`` -- or, inside ops.paired(), hold it back / launch it with its partner through
     ``lib.<name>_pair``.  ``extra``: per-problem trailing arguments (pointers), interleaved per problem in the pair entry points as the
-    header declares them; scalars shared by both problems are taken from the second call."""
+    header declares them; scalars shared by both problems are taken from the second call.  ``keep``: the tensors ``args`` points into (a
+    held-back first problem of a pair keeps them alive until its partner launches both)."""
     lib = _lib.load()
     if not _pair_state["active"]:
         if name == "tp_inorm_lrelu_bwd":
@@ -690,9 +689,9 @@ def _launch(name: str, args, extra=()):
         return
     pending = _pair_state["pending"]
     if pending is None:
-        _pair_state["pending"] = (name, args, extra, torch.cuda.current_stream().cuda_stream)
+        _pair_state["pending"] = (name, args, extra, torch.cuda.current_stream().cuda_stream, keep)
         return
-    p_name, p_args, p_extra, p_stream = pending
+    p_name, p_args, p_extra, p_stream, _ = pending
     _pair_state["pending"] = None
     if p_name != name or p_stream != torch.cuda.current_stream().cuda_stream:
         raise RuntimeError("ops.paired(): %s cannot be paired with %s (same op, same stream)" % (name, p_name))
@@ -753,7 +752,7 @@ def spectral_norm_fwd(weights, us, vs, training: bool, keep_uv: bool = False, ou
     return (outs, sigmas, u_copies, v_copies) if keep_uv else (outs, sigmas)
 
 
-SN_MAX_SETS = 3
+SN_MAX_SETS = _lib.SN_MAX_SETS
 
 
 @_on_tensor_device
@@ -951,8 +950,7 @@ def inorm_lrelu_bwd(xhat: Tensor, rstd: Tensor, gy: Tensor, slope: float, addend
     a = _lib.InormBwdArgs()
     a.xhat, a.rstd, a.gy, a.n_inst, a.hw, a.slope = xhat.data_ptr(), rstd.data_ptr(), gy.data_ptr(), rstd.numel(), xhat.numel() // rstd.numel(), float(slope)
     a.addend, a.gx = _ptr(addend), gx.data_ptr()
-    a._keep = (xhat, rstd, gy, addend, gx)
-    _launch("tp_inorm_lrelu_bwd", a)
+    _launch("tp_inorm_lrelu_bwd", a, keep=(xhat, rstd, gy, addend, gx))
     return gx
 
 
@@ -1144,7 +1142,7 @@ def surfel_finish(zbuf: Tensor, nocs: Tensor, normal: Tensor, rgb: Optional[Tens
 
 
 # ------------------------------------------------------------------------------------------ K21
-SCENE_SOURCES = {"box": 0, "render": 1, "none": 2}          # options nerf.depth.range_source -> TP_SCENE_*
+SCENE_SOURCES = {"box": _lib.SCENE_BOX, "render": _lib.SCENE_RENDER, "none": _lib.SCENE_NONE}          # options nerf.depth.range_source -> TP_SCENE_*
 SCENE_BOUNDS_KEYS = ("z_near", "z_far", "label", "depth")
 
 
@@ -1193,6 +1191,7 @@ def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float
 # ------------------------------------------------------------------------------------------ K22
 SCENE_INFO_KEYS = ("px_count_all", "px_count_visib", "obj_xmin", "obj_ymin", "obj_xmax", "obj_ymax", "visib_xmin", "visib_ymin",
                    "visib_xmax", "visib_ymax")                      # the ten columns of info, in order
+assert len(SCENE_INFO_KEYS) == _lib.SCENE_INFO_FIELDS
 
 
 def _want_gpu(op: str, t, name: str, dtype, shape):
@@ -1298,13 +1297,13 @@ def _conv4s2(op: int, name: str, x, w, gy, out, N, C_in, H, W, Co, inorm=None):
     ws, cnt = _conv_scratch(lib, lib.tp_conv4s2_workspace, a, op, out.device)
     a.x, a.w, a.gy = _ptr(x), _ptr(w), _ptr(gy)
     a.out, a.counters, a.workspace = out.data_ptr(), cnt.data_ptr(), _ptr(ws)
-    a._keep = (x, w, gy, out, ws, cnt)                # (a held-back first problem of a pair keeps its tensors alive)
+    keep = (x, w, gy, out, ws, cnt)
     if inorm is not None:                             # (xhat, rstd, addend or None, gx, slope, skip_out)
         a.in_xhat, a.in_rstd, a.in_addend, a.in_gx = inorm[0].data_ptr(), inorm[1].data_ptr(), _ptr(inorm[2]), inorm[3].data_ptr()
         a.in_slope, a.skip_out = float(inorm[4]), int(bool(inorm[5]))
-        a._keep = a._keep + tuple(inorm[:4])
+        keep += tuple(inorm[:4])
     if name in PAIRABLE:
-        _launch(name, a)
+        _launch(name, a, keep=keep)
     else:
         check(getattr(lib, name)(C.byref(a), _stream()), name)
     return out
@@ -1341,12 +1340,11 @@ def conv4s2_fwd_inorm(x: Tensor, w: Tensor, eps: float, slope: float, y_out: Opt
     ws, cnt = _conv_scratch(lib, lambda args, _op, n: lib.tp_conv4s2_fwd_inorm_workspace(args, n), a, 0, x.device)
     a.x, a.w = x.data_ptr(), w.data_ptr()
     a.out, a.counters, a.workspace = y.data_ptr(), cnt.data_ptr(), _ptr(ws)
-    a._keep = (x, w, y, xhat, rstd, ws, cnt, copy_to)
     if copy_to is not None:
         if copy_to.shape != x.shape or copy_to.dtype != torch.float32 or not copy_to.is_contiguous() or copy_to.device != x.device:
             raise ValueError("conv4s2_fwd_inorm: copy_to must be a contiguous float32 tensor shaped like x")
         a.x_copy = copy_to.data_ptr()
-    _launch("tp_conv4s2_fwd_inorm", a, (xhat.data_ptr(), rstd.data_ptr(), float(eps), float(slope)))
+    _launch("tp_conv4s2_fwd_inorm", a, (xhat.data_ptr(), rstd.data_ptr(), float(eps), float(slope)), keep=(x, w, y, xhat, rstd, ws, cnt, copy_to))
     return y, xhat, rstd
 
 
@@ -1541,7 +1539,7 @@ def feat_chain_pack(weights, out: Optional[Tensor] = None) -> Tensor:
         if torch.cuda.is_current_stream_capturing():
             raise _lib.TexposeLibraryError("tp_feat_chain_pack: pack before the hipGraph capture (run one eager step first)")
         out = torch.empty(n, device=dev)
-    ptrs = (C.c_void_p * 7)(*[w.data_ptr() for w in weights])
+    ptrs = (C.c_void_p * _lib.FEAT_CHAIN_LAYERS)(*[w.data_ptr() for w in weights])
     with torch.cuda.device(dev):
         check(lib.tp_feat_chain_pack(ptrs, out.data_ptr(), _stream()), "tp_feat_chain_pack")
     return out
@@ -1556,7 +1554,7 @@ def feat_chain(rgb: Tensor, gathered: Tensor, packed: Tensor, biases, mean, std,
     lib = _lib.load()
     rgb, gathered = _f32(rgb.detach(), "rgb"), _f32(gathered, "gathered")
     B, dev = rgb.shape[0], rgb.device
-    if len(biases) != 7 or packed.numel() != int(lib.tp_feat_chain_packed_floats()) or packed.dtype != torch.float32:
+    if len(biases) != _lib.FEAT_CHAIN_LAYERS or packed.numel() != int(lib.tp_feat_chain_packed_floats()) or packed.dtype != torch.float32:
         raise ValueError("feat_chain: packed weights (feat_chain_pack) and the seven biases of VGG19 features[:15] expected")
     for b, co in zip(biases, (64, 64, 128, 128, 256, 256, 256)):
         if tuple(b.shape) != (co,) or b.dtype != torch.float32:
@@ -1579,7 +1577,7 @@ def feat_chain(rgb: Tensor, gathered: Tensor, packed: Tensor, biases, mean, std,
     for c in range(3):
         a.mean[c], a.std[c] = f.mean[c], f.std[c]
     a.packed = packed.data_ptr()
-    for l in range(7):
+    for l in range(_lib.FEAT_CHAIN_LAYERS):
         a.bias[l] = biases[l].data_ptr()
     a.w2, a.scale = float(w2), float(scale)
     loss3, g_rgb = torch.empty(3, device=dev), torch.empty_like(rgb)
@@ -2013,8 +2011,7 @@ def disc_tail_fwd(a: Tensor, W0: Tensor, scale: Tensor, W1: Tensor, W2: Tensor, 
     ws = _tail_workspace(dev, q.N)
     q.a, q.scale, q.out, q.t0, q.t1, q.t2 = a.data_ptr(), scale.data_ptr(), out.data_ptr(), t0.data_ptr(), t1.data_ptr(), t2.data_ptr()
     q.workspace, q.ticket = ws.data_ptr(), _ticket(dev, "disc_tail%d" % _pair_slot())
-    q._keep = (a, W0, scale, W1, W2, W3, out, t0, t1, t2, ws)
-    _launch("tp_disc_tail_fwd", q)
+    _launch("tp_disc_tail_fwd", q, keep=(a, W0, scale, W1, W2, W3, out, t0, t1, t2, ws))
     return out, t0, t1, t2
 
 
@@ -2070,8 +2067,7 @@ def disc_tail_bwd(g_out: Tensor, t0: Tensor, t1: Tensor, t2: Tensor, W0: Tensor,
     q.g_out, q.t0, q.t1, q.t2 = g_out.data_ptr(), t0.data_ptr(), t1.data_ptr(), t2.data_ptr()
     q.c_a, q.gW0, q.gW1, q.gW2, q.gW3 = (_ptr(res[k]) for k in ("c_a", "gW0", "gW1", "gW2", "gW3"))
     q.gz, q.e1, q.e2 = _ptr(res["gz"]), _ptr(res["e1"]), _ptr(res["e2"])
-    q._keep = (g_out, t0, t1, t2, W0, W1, W2, W3, a, keep, dict(res))
-    _launch("tp_disc_tail_bwd", q)
+    _launch("tp_disc_tail_bwd", q, keep=(g_out, t0, t1, t2, W0, W1, W2, W3, a, keep, dict(res)))
     return res
 
 
