@@ -925,6 +925,40 @@ typedef struct tp_view_images_args {
 } tp_view_images_args;
 int tp_view_images(const tp_view_images_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K23  Lab chroma loss of the generator step (loss_weight.lab) and its gradient wrt the rendered colours, one launch each way.
+ * ref: model/nerf_adapt_st_gan.py:772-773, layers/lab_loss.py:13-48; the colour conversion is kornia.color.rgb_to_lab as
+ *      published, restated in tests/lab_ref.py, not pinned to a kornia call.
+ *      Per pixel, fake = rgb, real = the three planes at `real`:  lab(c) = normalize_lab(rgb_to_lab(c)),
+ *        l = SmoothL1(lab(fake)[1] - lab(real)[1]) + SmoothL1(lab(fake)[2] - lab(real)[2])      (beta = 1, the two chroma channels)
+ *        mask given:  sums = { sum l * mask, sum mask },   loss = sums[0] / sums[1]      (no epsilon: an empty mask gives NaN)
+ *        mask NULL:   sums = { sum l, 2 * B * P },         loss = sums[0] / sums[1]      (the mean over both channels)
+ *        fake_lab = lab(fake) with its L plane replaced by lab(real)'s, real_lab = lab(real)
+ *      fp32 in and out; each value is the rule evaluated in fp64 registers and rounded once.  The sums are reduced per wavefront,
+ *      per block and by the last block to arrive over the blocks in ascending order, all in double: no float atomics, the result
+ *      does not depend on the order the blocks ran in.  The backward recomputes the Lab values from the inputs and reads sums[1];
+ *      it writes every element of g_rgb.  No allocation, no host synchronisation; outputs must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_LAB_LOSS_MAX_BLOCKS 256
+typedef struct tp_lab_loss_args {
+  const float* rgb;             /* [B,P,3]  the rendered colours (composite output) */
+  const float* real;            /* channel c of image b, pixel p: real[b * real_batch_stride + c * real_channel_stride + p] --
+                                   channels 3..5 of tp_patch_gather's [B,14,P] (strides 14 P, P) or a dense [B,3,P] (3 P, P) */
+  const float* mask;            /* pixel p of image b: mask[b * mask_batch_stride + p], or NULL */
+  int64_t real_batch_stride, real_channel_stride, mask_batch_stride;      /* in floats */
+  int B, P;
+  float* fake_lab;              /* fwd, optional [B,3,P] */
+  float* real_lab;              /* fwd, optional [B,3,P] */
+  void* workspace;              /* fwd: 2 * TP_LAB_LOSS_MAX_BLOCKS doubles */
+  double* sums;                 /* [2]  (fwd: out, bwd: in) */
+  float* loss;                  /* fwd: [1] */
+  uint32_t* ticket;             /* fwd: ONE zero-filled device word owned by the calling stream (tp_nerf_losses_args.ticket's rules); the
+                                   launch leaves it zero.  Unused by the backward. */
+} tp_lab_loss_args;
+int tp_lab_loss_fwd(const tp_lab_loss_args* args, tp_stream_t stream);
+/* g: the upstream gradient of the loss, one device scalar; g_rgb [B,P,3] = g[0] * d loss / d rgb */
+int tp_lab_loss_bwd(const tp_lab_loss_args* args, const float* g, float* g_rgb, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

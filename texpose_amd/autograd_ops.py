@@ -138,6 +138,35 @@ def nerf_losses(rgb, uncert, density, gathered):
     return _NerfLosses.apply(rgb, uncert, density, gathered)
 
 
+class _LabLoss(torch.autograd.Function):
+    """The Lab chroma loss of the rendered colours against the real image (reference layers/lab_loss.py) and the two maps it
+    returns for logging: one forward and one backward launch (K23) instead of ~40 element-wise / reduction kernels each way.
+    The gradient flows to rgb only: the real image is data."""
+
+    @staticmethod
+    def forward(ctx, rgb, real, mask, real_channel, mask_channel):
+        sums, loss, fake_lab, real_lab = ops.lab_loss_fwd(rgb, real, mask, real_channel=real_channel, mask_channel=mask_channel)
+        ctx.save_for_backward(rgb, real, mask, sums)
+        ctx.channels = (real_channel, mask_channel)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(fake_lab, real_lab)
+        return loss, fake_lab, real_lab
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_fake_lab, _g_real_lab):
+        rgb, real, mask, sums = ctx.saved_tensors
+        if g_loss is None:
+            return None, None, None, None, None
+        return ops.lab_loss_bwd(rgb, real, mask, sums, g_loss, real_channel=ctx.channels[0], mask_channel=ctx.channels[1]), None, None, None, None
+
+
+def lab_loss(rgb, real, mask=None, real_channel=0, mask_channel=0):
+    """rgb [B,P,3]; ``real`` / ``mask``: dense [B,3,...] / [B,1,...] tensors, or the patch gather's [B,14,p,p] for both with
+    real_channel = 3 (image_syn) and mask_channel = 13 (mask_syn), as `nerf_losses` reads it.  -> (loss, fake_lab [B,3,P], real_lab)."""
+    return _LabLoss.apply(rgb, real, mask, int(real_channel), int(mask_channel))
+
+
 class _InormLreluBackward(torch.autograd.Function):
     """gx of the fused InstanceNorm + LeakyReLU, itself differentiable (the R1 penalty back-propagates through the
     gradient wrt the discriminator input, reference model/nerf_adapt_st_gan.py:794-807).  ``x`` is only the handle

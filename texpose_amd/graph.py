@@ -10,8 +10,9 @@ What differs by design (documented in DESIGN.md):
   * the NaN-retry host syncs (:554,569) are gone (the kernels produce NaN only from NaN inputs);
   * stratified jitter comes from an in-kernel Philox stream seeded from torch's seed (the reference's
     own CPU and CUDA torch.rand streams already differ); ``rand=`` injects a tensor for parity tests.
-The discriminator / perceptual / Lab modules are the reference's stock PyTorch modules and are
-injected, not re-implemented.
+The discriminator / perceptual modules are the reference's stock PyTorch modules and are injected, not
+re-implemented; an injected Lab module is called like the reference's, without one the Lab
+term is the project's own (K23 on the GPU, texpose_amd/lab.py on CPU tensors).
 """
 from __future__ import annotations
 
@@ -423,6 +424,13 @@ class Graph(torch.nn.Module):
             seen.add(message)
             warnings.warn("texpose_amd: " + message)
 
+    def _lab_loss_torch(self):
+        """The Lab chroma loss as torch ops (texpose_amd/lab.py): CPU tensors only -- on the GPU the term is K23."""
+        if "_lab_module" not in self.__dict__:
+            from .lab import LabLoss
+            self.__dict__["_lab_module"] = LabLoss()           # (no parameters, no buffers: kept out of the module tree / state dict)
+        return self.__dict__["_lab_module"]
+
     @staticmethod
     def MSE_loss(pred, label, mask=None):
         loss = (pred.contiguous() - label) ** 2
@@ -432,7 +440,8 @@ class Graph(torch.nn.Module):
         """Photometric / uncertainty / transient-regulariser / feature / GAN terms (reference :712-776)."""
         loss = edict()
         B = len(var.idx)
-        if opt.nerf.rand_rays and mode in ["train", "test-optim"]:
+        patch_mode = bool(opt.nerf.rand_rays and mode in ["train", "test-optim"])
+        if patch_mode:
             _, h, w, _ = var.ray_idx.shape
             var = self.gather_patches(opt, var)
             image, obj_mask = var.image_sample, var.mask_sample
@@ -501,7 +510,19 @@ class Graph(torch.nn.Module):
                 if l1 is not None:
                     loss.feat = l1 + 5 * l2
             if lw.lab is not None:
-                loss.lab, var.rgb_lab, var.img_syn_lab = self.lab_loss(rgb, image_syn, mask=mask_syn)
+                if self.lab_loss is not None:                          # an injected module, called like the reference's (:772-773)
+                    loss.lab, var.rgb_lab, var.img_syn_lab = self.lab_loss(rgb, image_syn, mask=mask_syn)
+                elif var.rgb.is_cuda:
+                    # K23: one launch each way; the real image and its mask are read where they lie -- channels 3..5 / 13 of the patch
+                    # gather in patch mode, the dense tensors otherwise
+                    if patch_mode and "gathered" in var:
+                        out = autograd_ops.lab_loss(var.rgb, var.gathered, var.gathered, real_channel=3, mask_channel=13)
+                    else:
+                        out = autograd_ops.lab_loss(var.rgb, image_syn, mask_syn)
+                    loss.lab = out[0]
+                    var.rgb_lab, var.img_syn_lab = (t.view(B, 3, *image_syn.shape[-2:]) for t in out[1:])
+                else:
+                    loss.lab, var.rgb_lab, var.img_syn_lab = self._lab_loss_torch()(rgb, image_syn, mask=mask_syn)
             if opt.gan is not None and lw.gan_nerf is not None and mode == "train":
                 loss.gan_nerf = (var.gan_nerf_precomputed if "gan_nerf_precomputed" in var
                                  else self.compute_gan_loss(opt, d_outs=var.d_fake_nerf, target=1))

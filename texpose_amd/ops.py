@@ -921,6 +921,62 @@ def nerf_losses_bwd(rgb: Tensor, uncert: Tensor, density: Tensor, gathered: Tens
     return g_rgb, g_unc, g_den
 
 
+# ------------------------------------------------------------------------------------------ K23
+def _lab_loss_args(rgb, real, mask, real_channel, mask_channel):
+    """``real`` [B,C,...] holds the real image as channels real_channel .. real_channel + 2 and ``mask`` [B,C',...] (or None) the mask
+    as channel mask_channel, P elements per channel: dense tensors (channel 0) or the patch gather's [B,14,p,p] (channels 3 and 13)."""
+    lib = _lib.load()
+    rgb, real = _f32(rgb, "rgb"), _f32(real, "real")
+    mask = None if mask is None else _f32(mask, "mask")
+    if rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.numel() == 0:
+        raise ValueError("lab_loss: rgb [B,P,3] expected, got %s" % (tuple(rgb.shape),))
+    B, P = rgb.shape[0], rgb.shape[1]
+    for name, t, c0, n in (("real", real, int(real_channel), 3), ("mask", mask, int(mask_channel), 1)):
+        if t is not None and (t.dim() < 2 or t.shape[0] != B or t.numel() != B * t.shape[1] * P or not 0 <= c0 <= t.shape[1] - n):
+            raise ValueError("lab_loss: %s [B=%d,C,...] with %d elements per channel and channels %d..%d expected, got %s"
+                             % (name, B, P, c0, c0 + n - 1, tuple(t.shape)))
+    a = _lib.LabLossArgs()
+    a.rgb, a.B, a.P = rgb.data_ptr(), B, P
+    a.real, a.real_batch_stride, a.real_channel_stride = real.data_ptr() + 4 * int(real_channel) * P, real.shape[1] * P, P
+    if mask is not None:
+        a.mask, a.mask_batch_stride = mask.data_ptr() + 4 * int(mask_channel) * P, mask.shape[1] * P
+    return lib, a, (rgb, real, mask)
+
+
+@_on_tensor_device
+def lab_loss_fwd(rgb: Tensor, real: Tensor, mask: Optional[Tensor] = None, *, real_channel: int = 0, mask_channel: int = 0,
+                 want_maps: bool = True):
+    """The Lab chroma loss of rgb [B,P,3] against the real image (reference layers/lab_loss.py): one launch.
+    -> (sums [2] fp64 = [sum l * mask, sum mask] (no mask: [sum l, 2 B P]), loss (0-dim) = sums[0] / sums[1], fake_lab, real_lab);
+    the maps are [B,3,P] (None unless ``want_maps``): normalised Lab of the real image, and of rgb with its L plane replaced by that."""
+    lib, a, keep = _lab_loss_args(rgb, real, mask, real_channel, mask_channel)
+    dev = keep[0].device
+    ws = torch.empty(2 * _lib.LAB_LOSS_MAX_BLOCKS, dtype=torch.float64, device=dev)
+    sums, loss = torch.empty(2, dtype=torch.float64, device=dev), torch.empty(1, device=dev)
+    fake_lab = real_lab = None
+    a.workspace, a.sums, a.loss = ws.data_ptr(), sums.data_ptr(), loss.data_ptr()
+    if want_maps:
+        fake_lab, real_lab = torch.empty(a.B, 3, a.P, device=dev), torch.empty(a.B, 3, a.P, device=dev)
+        a.fake_lab, a.real_lab = fake_lab.data_ptr(), real_lab.data_ptr()
+    a.ticket = _ticket(dev, "lab_loss")
+    check(lib.tp_lab_loss_fwd(C.byref(a), _stream()), "tp_lab_loss_fwd")
+    return sums, loss[0], fake_lab, real_lab
+
+
+@_on_tensor_device
+def lab_loss_bwd(rgb: Tensor, real: Tensor, mask: Optional[Tensor], sums: Tensor, g_loss: Tensor, *, real_channel: int = 0,
+                 mask_channel: int = 0):
+    """g_rgb [B,P,3] = g_loss * d loss / d rgb, recomputed from the forward's inputs and its ``sums``: one launch, every element written."""
+    lib, a, keep = _lab_loss_args(rgb, real, mask, real_channel, mask_channel)
+    g_loss = _f32(g_loss, "g_loss")
+    if sums.dtype != torch.float64 or sums.numel() != 2 or not sums.is_cuda or not sums.is_contiguous() or g_loss.numel() != 1:
+        raise ValueError("lab_loss_bwd: sums [2] float64 on the GPU (lab_loss_fwd's) and a one-element g_loss expected")
+    a.sums = sums.data_ptr()
+    g_rgb = torch.empty_like(keep[0])
+    check(lib.tp_lab_loss_bwd(C.byref(a), g_loss.data_ptr(), g_rgb.data_ptr(), _stream()), "tp_lab_loss_bwd")
+    return g_rgb
+
+
 # ------------------------------------------------------------------------------------------ K9
 @_on_tensor_device
 def inorm_lrelu_fwd(x: Tensor, eps: float, slope: float, y_out: Optional[Tensor] = None):
