@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Build-container check of the drop-in claim in INTEGRATION.md (needs /root/reference, so it cannot run on the GPU box):
-construct the shim `model/nerf_adapt_st_gan_amd.py` would define -- the reference's Graph with the ray-marching path
-swapped for texpose_amd's -- and compare its state dict, method table and option handling with the reference Graph.
+"""Build-container check of the drop-in claim in INTEGRATION.md (needs the reference code base, so it cannot run on the GPU box;
+tests/test_shim_cpu.py runs it as a child process wherever the reference is present): construct the shim
+`model/nerf_adapt_st_gan_amd.py` defines -- texpose_amd.graph.RenderMixin mixed into the reference's Graph -- compare its state
+dict, method table and option handling with the reference Graph, then drive both with the reference's own engine (two training
+iterations) and its own nerf_forward (validation / evaluation renders, camera.ndc, inverse depths) on the CPU oracle.
 
     python tests/golden/check_shim_here.py
 """
@@ -11,34 +13,22 @@ import sys
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden as MG                                            # noqa: E402
+sys.path[:0] = [HERE, os.path.dirname(HERE)]
+import make_golden as MG                                            # noqa: E402  (puts the repository root on sys.path)
+from cpu_backend import oracle_backend                              # noqa: E402
 
 
 def main():
     opt, camera, M, NeRF, RaySampler, FlexPatchSampler = MG._load_reference()
     opt.patch_size = 16
-    from texpose_amd.graph import Graph as AmdGraph
+    from texpose_amd.graph import Graph as AmdGraph, RenderMixin
     from texpose_amd.nerf import NeRF as AmdNeRF
     from texpose_amd.gan_modules import Discriminator as AmdDisc
 
-    class Graph(M.Graph):
+    class Graph(RenderMixin, M.Graph):                              # INTEGRATION.md section 1, as documented
         def __init__(self, opt):
             super().__init__(opt)
             self.nerf = AmdNeRF(opt)
-        render = AmdGraph.render
-        render_by_slices = AmdGraph.render_by_slices
-        _slice_rays = staticmethod(AmdGraph._slice_rays)
-        _jitter = staticmethod(AmdGraph._jitter)
-        _render_by_slices = AmdGraph._render_by_slices
-        _range_guarded = AmdGraph._range_guarded
-        sample_depth = staticmethod(AmdGraph.sample_depth)
-        ray_batch_sample = staticmethod(AmdGraph.ray_batch_sample)
-        gather_patches = AmdGraph.gather_patches
-        sample_geometry = AmdGraph.sample_geometry
-        compute_loss = AmdGraph.compute_loss
-        _warn_once = AmdGraph._warn_once                 # (compute_loss says once when it leaves its fused launches)
-        evaluate_metrics = AmdGraph.evaluate_metrics
 
     torch.manual_seed(0)
     ref = M.Graph(opt)
@@ -83,7 +73,10 @@ def main():
         assert a == b[:len(a)], (name, a, b)
         print("signature ok:", name, a)
     print("shim signatures ok")
-    run_training_steps(opt, M, Graph)
+    with oracle_backend():
+        run_evaluation(*run_training_steps(opt, M, Graph))
+    from texpose_amd import ops
+    assert ops.raygen.__module__ == "texpose_amd.ops" and AmdNeRF.forward_samples.__module__ == "texpose_amd.nerf"     # restored
     print("shim check passed")
 
 
@@ -91,14 +84,13 @@ def run_training_steps(opt, M, ShimGraph):
     """The reference's OWN engine (Model.train_iteration -> nerf_trainstep / disc_trainstep, model/nerf_adapt_st_gan.py:
     108-202) drives the shim Graph for two iterations, next to the pure reference Graph on the same weights, batch and
     random draws.  There is no GPU here, so the four C-ABI entry points the shim's methods reach (tp_raygen, tp_mlp_fwd
-    /bwd, tp_composite, tp_patch_gather) are bound to the CPU oracle for THIS CHECK ONLY: what is exercised is the wiring
-    through the reference's method-resolution order (nerf_forward -> render -> compute_loss -> sample_geometry ...)."""
+    /bwd, tp_composite, tp_patch_gather) are bound to the CPU oracle by the caller (tests/cpu_backend.py): what is exercised is
+    the wiring through the reference's method-resolution order (nerf_forward -> render -> compute_loss -> sample_geometry ...)."""
     import copy
     import types
     import numpy as np
     from oracle import texpose_oracle as O
-    from texpose_amd import autograd_ops, ops
-    from texpose_amd.nerf import NeRF as AmdNeRF
+    from texpose_amd.graph import RenderMixin
 
     B, H, W, N = 2, 32, 32, 4
     opt = copy.deepcopy(opt)
@@ -108,31 +100,6 @@ def run_training_steps(opt, M, ShimGraph):
     opt.max_epoch, opt.max_iter = 10, 1000
     for k in ("scalar", "vis", "val", "ckpt"):
         opt.freq[k] = 10 ** 9
-
-    # oracle-backed stand-ins for the HIP entry points (CPU tensors)
-    def raygen(intr, pose, *, H, W, n_samples=0, coords=None, ray_idx=None, z_near=None, z_far=None, rand=None, **kw):
-        c, r = O.rays_train(intr, coords, pose, H, W)
-        zn, zf = O.bounds_train(coords, z_near.view(len(pose), -1, 1), z_far.view(len(pose), -1, 1), H, W)
-        Bn = len(pose)
-        c, r, zn, zf = c.reshape(Bn, -1, 3), r.reshape(Bn, -1, 3), zn.reshape(Bn, -1), zf.reshape(Bn, -1)
-        if rand is None and kw.get("jitter") == ops.JITTER_PHILOX:          # the kernel's in-kernel stream; here: the draw the
-            rand = torch.rand(Bn, c.shape[1], n_samples, 1)                  # reference makes at this point (:690-692)
-        return c, r, zn, zf, O.stratified_depths(zn, zf, n_samples, rand)[..., 0]
-
-    def forward_samples(self, opt_, center, ray, depth_samples, latent_variable_trans=None, latent_variable_light=None, mode=None):
-        p = {k: v for k, v in self.named_parameters() if k.startswith("mlp_")}
-        return O.forward_samples(p, center, ray, depth_samples, latent_variable_trans, latent_variable_light)
-
-    def composite(opt_, ray, rgb_samples, density_samples, depth_samples, uncert_samples=None, per_sample=True, want_prob=True,
-                  fan_out=None):                      # (the oracle stand-in hands out no aliases: every consumer reads rgb / density)
-        return O.composite(ray, rgb_samples, density_samples, depth_samples, uncert_samples, opt_.nerf.min_uncert)
-
-    def patch_gather(coords, image, image_syn, nocs, normal, obj_mask, mask_syn):
-        g = O.patch_gather(coords, image, image_syn, nocs, normal, obj_mask, mask_syn)
-        return torch.cat([g["image"], g["image_syn"], g["nocs_sample"], g["normal_sample"], g["mask"], g["mask_syn"]], dim=1)
-
-    ops.raygen, ops.patch_gather = raygen, patch_gather
-    AmdNeRF.forward_samples, AmdNeRF.composite = forward_samples, staticmethod(composite)
 
     def model(graph_cls, seed):
         torch.manual_seed(seed)
@@ -148,6 +115,11 @@ def run_training_steps(opt, M, ShimGraph):
         return m
 
     ref, shim = model(M.Graph, 5), model(ShimGraph, 6)
+    # what the mixin asks of its host, the reference's Graph (with the engine's latent tables) provides
+    for name in RenderMixin.HOST_REQUIRED:
+        assert hasattr(shim.graph, name), name
+    assert [n for n in RenderMixin.HOST_OPTIONAL if hasattr(ref.graph, n)] == ["perceptual_loss"]
+    assert shim.graph.perceptual_loss is not None
     state = O.seeded_state(ref.graph.state_dict(), salt=3)
     ref.graph.load_state_dict(state)
     shim.graph.load_state_dict(state)                              # same keys: the reference state dict loads into the shim
@@ -183,6 +155,59 @@ def run_training_steps(opt, M, ShimGraph):
     assert moved > 20 and shim.it == 2 and shim.graph.patch_sampler.iterations == 1
     print("two reference-engine training iterations through the shim == through the reference Graph:",
           {k: round(v, 5) for k, v in losses["shim"][1].items()})
+    return opt, ref.graph, shim.graph
+
+
+def run_evaluation(opt, ref, shim):
+    """What evaluate.py / validate reach, through the reference's OWN nerf_forward (model/nerf_adapt_st_gan.py:464-503) on both
+    sides: the shim's render_by_slices -> render against the reference Graph's, same weights, same seeds, B = 1 on a disc mask."""
+    import copy
+    import numpy as np
+    from oracle import texpose_oracle as O
+    from texpose_amd.graph import RENDER_KEYS
+
+    H, W = opt.H, opt.W
+    shim.load_state_dict(ref.state_dict())                          # (the two training iterations left them a rounding apart)
+    sc = O.synthetic_scene(H, W, B=1, seed=2)
+    K = sc["intr"].clone()
+    K[:, 0, 0] = K[:, 1, 1] = 700.0 * H / 128.0
+    K[:, 0, 2], K[:, 1, 2] = W / 2.0, H / 2.0
+    yy, xx = np.mgrid[0:H, 0:W]
+    disk = torch.from_numpy((((yy - H / 2) ** 2 + (xx - W / 2) ** 2) < (0.4 * H) ** 2).astype(np.float32))
+    rs = np.random.RandomState(11)
+    u = lambda lo, hi: torch.from_numpy(rs.uniform(lo, hi, size=(1, H * W)).astype(np.float32))
+    ndc_near = u(0.76, 0.8)                 # fractions of the NDC depth axis (the object sits at metric z ~ 6: t = 1 - 1 / z ~ 0.83)
+    ranges = dict(metric=(sc["z_near"], sc["z_far"]), ndc=(ndc_near, ndc_near + u(0.06, 0.12)),
+                  inverse=(1 / sc["z_far"], 1 / sc["z_near"]))
+    anchors = O.synthetic_scene(H, W, B=5, seed=7)["pose"]
+    EasyDict = sys.modules["easydict"].EasyDict
+    off = disk.reshape(-1) == 0
+    assert 0 < int(off.sum()) < H * W
+    for label, mode, rng, flags in (("val", "val", "metric", {}), ("evaluation branch", "eval_noalign", "metric", {}),
+                                    ("val, camera.ndc", "val", "ndc", dict(ndc=True)),
+                                    ("val, nerf.depth.param = inverse", "val", "inverse", dict(param="inverse"))):
+        o = copy.deepcopy(opt)
+        o.camera.ndc, o.nerf.depth.param = flags.get("ndc", False), flags.get("param", "metric")
+        o.arch.mlp_range_check = "off"                              # (the oracle is exact fp32 and keeps no device flag to read)
+        out = []
+        for graph in (ref, shim):
+            var = EasyDict(idx=torch.tensor([0]), obj_mask=disk[None].clone(), intr=K.clone(), pose=sc["pose"].clone(),
+                           pose_init=sc["pose"].clone(), pose_anchor=anchors.clone(), z_near=ranges[rng][0].clone(), z_far=ranges[rng][1].clone())
+            torch.manual_seed(91)                                   # the light row's randperm, then the stratified draw
+            with torch.no_grad():
+                out.append(graph.nerf_forward(o, var, mode=mode))
+        keys = [k for k in RENDER_KEYS if k in out[0] and k in out[1]]
+        assert len(keys) == len(RENDER_KEYS), keys
+        for k in keys:
+            a, b = out[0][k], out[1][k]
+            assert a.shape == b.shape and bool(torch.isfinite(b).all()), (label, k, a.shape, b.shape)
+            # the bars tests/test_oracle_golden.py holds the oracle to for the G9 render slices (per-ray and per-sample maps alike)
+            torch.testing.assert_close(b, a, rtol=2e-5, atol=2e-6, msg=lambda m: "%s, %s: %s" % (label, k, m))
+            if mode != "val":                                       # pixels off the mask: the default fills, bit for bit
+                assert torch.equal(a[0, off], b[0, off]), (label, k)
+                assert not torch.equal(a[0, ~off], torch.broadcast_to(a[0, off][:1], a[0, ~off].shape)), (label, k)
+        print("evaluation render through the shim == through the reference Graph:", label,
+              " max |diff| rgb %.2e depth %.2e" % (float((out[0].rgb - out[1].rgb).abs().max()), float((out[0].depth - out[1].depth).abs().max())))
 
 
 if __name__ == "__main__":

@@ -42,41 +42,21 @@ def _ones_like_cached(t):
     return _ones_cache[key]
 
 
-class Graph(torch.nn.Module):
+class RenderMixin:
+    """What a reference-side ``Graph`` takes from this package (``class Graph(RenderMixin, ref.Graph)``): the
+    ray-marching path and its consumers.  A plain class -- no ``__init__``, not a Module; closed under its own ``self.`` references
+    except for the names below, which the class it is mixed into provides (tests/test_shim_cpu.py holds it to that)."""
 
-    def __init__(self, opt, discriminator=None, perceptual_loss=None, lab_loss=None):
-        super().__init__()
-        self.nerf = NeRF(opt)
-        if discriminator is not None:
-            self.discriminator = discriminator
-        if perceptual_loss is not None:
-            self.perceptual_loss = perceptual_loss
-        self.lab_loss = lab_loss
-        self.ray_sampler = RaySampler(opt)
-        # the reference passes `opt` into the random_shift slot (:424); truthy => default behaviour
-        self.patch_sampler = FlexPatchSampler(True, scale_anneal=0.0002)
-
-    def attach_latents(self, n_train, opt):
-        """Per-image appearance embeddings (Model.build_networks, reference :56-59)."""
-        self.latent_vars_trans = torch.nn.Embedding(n_train, opt.nerf.N_latent_trans).to(opt.device)
-        self.latent_vars_light = torch.nn.Embedding(n_train, opt.nerf.N_latent_light).to(opt.device)
-        torch.nn.init.normal_(self.latent_vars_trans.weight)
-        torch.nn.init.normal_(self.latent_vars_light.weight)
-
-    # ------------------------------------------------------------------ ray / sample selection
-    def get_ray_idx(self, opt, var):
-        # var.patch_u (optional, [3,B,1,1,1] uniforms) pins the scale / shift draw for parity tests
-        # (`fuse_prologue`, set by the captured training step around its render: the coordinates are drawn by the ray-generation launch)
-        defer = dict(defer=True) if getattr(self, "fuse_prologue", False) and var.get("patch_u") is None else {}
-        var.ray_idx, var.ray_scales = self.patch_sampler(nbatch=opt.batch_size, patch_size=opt.patch_size,
-                                                         device=opt.device, u=var.get("patch_u"), **defer)
-        return var
-
-    @staticmethod
-    def get_pose(opt, var, mode=None):
-        if mode == "train":
-            return dict(gt=var.pose, predicted=var.pose_init)[opt.data.pose_source]
-        return var.pose
+    # read as bare ``self.x``
+    HOST_REQUIRED = ("nerf", "lab_loss", "latent_vars_trans", "latent_vars_light", "MSE_loss", "compute_gan_loss")
+    # read through getattr / hasattr, or only on a path that only this package's Graph sets up
+    HOST_OPTIONAL = (
+        "fuse_prologue",        # graphed_trainer.GraphedGanTrainer, around the render of its captured step
+        "step_counter",         # graphed_trainer.GraphedGanTrainer: the device word its replays advance
+        "range_fallbacks",      # _range_guarded itself, on the first image it renders twice
+        "perceptual_loss",      # the host's __init__ (an injected module; the reference builds its own)
+        "feat_stream",          # graphed_trainer.GraphedGanTrainer; read only behind var.feat_early_for, which Graph.nerf_forward sets
+    )
 
     @staticmethod
     def _jitter(opt, rand, step_counter=None):
@@ -95,7 +75,7 @@ class Graph(torch.nn.Module):
     def sample_depth(opt, batch_size, depth_range, num_rays=None, rand=None):
         """(near, far) [B,R] -> stratified depths [B,R,N,1] (reference :683-700)."""
         near, far = depth_range
-        return ops.sample_depth(near, far, opt.nerf.sample_intvs, depth_param=Graph._depth_param(opt), **Graph._jitter(opt, rand))[..., None]
+        return ops.sample_depth(near, far, opt.nerf.sample_intvs, depth_param=RenderMixin._depth_param(opt), **RenderMixin._jitter(opt, rand))[..., None]
 
     @staticmethod
     def _depth_param(opt):
@@ -283,6 +263,180 @@ class Graph(torch.nn.Module):
         var.nocs_sample, var.normal_sample = var.nocs_pred * ms, var.normal_pred * ms
         return var
 
+    def evaluate_metrics(self, opt, var, lpips_module=None):
+        """PSNR / SSIM of ``Model.evaluate_full`` (reference :340-362) for a rendered ``var`` (mode 'eval_*'): static
+        render vs masked image, resized to 480x640 when the data is not the 128x128 crop.  Returns 0-dim device tensors.
+
+        ``lpips_module``: the STOCK perceptual metric, injected (the reference builds ``lpips.LPIPS(net='alex')`` in
+        ``Model.__init__`` (:31) and calls ``self.lpips_loss(rgb_map * 2 - 1, image_masked * 2 - 1).item()`` (:363-364);
+        SURVEY 8 f4: "VGG / LPIPS stay stock").  When given, it is called exactly like that on the same two images
+        PSNR / SSIM see -- [B,3,h,w], the static render and ``image * obj_mask``, after the reference's optional resize
+        (bilinear ``align_corners=False`` for the images, nearest for the mask) -- and ``lpips`` is added to the result.  The
+        AlexNet weights are not available offline, so the value itself is unpinned (SURVEY 8c); the call contract is tested."""
+        out_hw = None if list(opt.data.image_size) == [128, 128] else (480, 640)
+        psnr, ssim, _ = ops.eval_metrics(var.rgb_static, var.image, var.obj_mask, opt.H, opt.W, out_hw=out_hw)
+        out = edict(psnr=psnr, ssim=ssim)
+        if lpips_module is not None:
+            B = var.image.shape[0]
+            rgb_map = var.rgb_static.view(B, opt.H, opt.W, 3).permute(0, 3, 1, 2)
+            image, mask = var.image.view(B, 3, opt.H, opt.W), var.obj_mask.view(B, 1, opt.H, opt.W).float()
+            if out_hw is not None:                  # reference :344-349
+                rgb_map = torch_F.interpolate(rgb_map, size=list(out_hw), mode="bilinear", align_corners=False)
+                image = torch_F.interpolate(image, size=list(out_hw), mode="bilinear", align_corners=False)
+                mask = torch_F.interpolate(mask, size=list(out_hw), mode="nearest")
+            with torch.no_grad():
+                out.lpips = lpips_module(rgb_map * 2 - 1, (image * mask) * 2 - 1).reshape(-1).mean()
+        return out
+
+    def _warn_once(self, message):
+        seen = self.__dict__.setdefault("_warned", set())
+        if message not in seen:
+            seen.add(message)
+            warnings.warn("texpose_amd: " + message)
+
+    def _lab_loss_torch(self):
+        """The Lab chroma loss as torch ops (texpose_amd/lab.py): CPU tensors only -- on the GPU the term is K23."""
+        if "_lab_module" not in self.__dict__:
+            from .lab import LabLoss
+            self.__dict__["_lab_module"] = LabLoss()           # (no parameters, no buffers: kept out of the module tree / state dict)
+        return self.__dict__["_lab_module"]
+
+    def compute_loss(self, opt, var, mode=None, train_step="nerf"):
+        """Photometric / uncertainty / transient-regulariser / feature / GAN terms (reference :712-776)."""
+        loss = edict()
+        B = len(var.idx)
+        patch_mode = bool(opt.nerf.rand_rays and mode in ["train", "test-optim"])
+        if patch_mode:
+            _, h, w, _ = var.ray_idx.shape
+            var = self.gather_patches(opt, var)
+            image, obj_mask = var.image_sample, var.mask_sample
+            image_syn, mask_syn = var.image_syn_sample, var.mask_syn_sample
+            rgb = var.rgb.view(B, h, w, 3).permute(0, 3, 1, 2)
+            uncert = var.uncert.view(B, h, w, 1).permute(0, 3, 1, 2)
+        else:
+            image = var.image.view(B, 3, opt.H, opt.W)
+            obj_mask = (var.obj_mask > 0).float().view(B, 1, opt.H, opt.W)
+            image_syn = var.get("image_syn", var.image).view(B, 3, opt.H, opt.W)
+            mask_syn = (var.get("mask_syn", var.obj_mask) > 0).float().view(B, 1, opt.H, opt.W)
+            rgb = var.rgb.view(B, opt.H, opt.W, 3).permute(0, 3, 1, 2)
+            uncert = var.uncert.view(B, opt.H, opt.W, 1).permute(0, 3, 1, 2)
+            var.image_syn_sample, var.image_sample, var.mask_sample, var.mask_syn_sample = (image_syn, image, obj_mask,
+                                                                                            mask_syn)
+        lw = opt.loss_weight
+        if train_step == "nerf":
+            # default configuration: the three render-consuming terms and their gradients in one launch each way (K8)
+            fused = ("gathered" in var and opt.nerf.mask_obj and lw.render is not None and lw.uncert is not None
+                     and lw.trans_reg is not None and lw.mask is None and var.rgb.is_cuda)
+            if fused:
+                loss.render, loss.uncert, loss.trans_reg = autograd_ops.nerf_losses(var.rgb, var.uncert,
+                                                                                     var.get("density_losses", var.density), var.gathered)
+            elif var.rgb.is_cuda:
+                # non-reference option combinations (a term switched off, mask_obj = False, full-image losses): the terms are
+                # formed with torch element-wise ops on the render outputs -- same values, many small launches.  Said once.
+                self._warn_once("compute_loss: loss options differ from the reference configuration (render / uncert / "
+                                "trans_reg on, mask off, mask_obj, patch mode): the render-consuming terms run as torch ops "
+                                "instead of the fused K8 launch")
+            if not fused and lw.render is not None:
+                if opt.nerf.mask_obj:
+                    loss.render = (obj_mask * ((image - rgb) ** 2 / uncert ** 2)).sum() / (obj_mask.sum() + 1e-5)
+                else:
+                    loss.render = self.MSE_loss(rgb, image)
+            if lw.mask is not None:
+                loss.mask = self.MSE_loss(obj_mask, var.opacity[..., None])
+            if not fused and lw.uncert is not None:
+                loss.uncert = 5 + torch.log(var.uncert ** 2).mean() / 2
+            if not fused and lw.trans_reg is not None:
+                loss.trans_reg = var.density[..., -1].mean()
+            if lw.feat is not None:
+                if not hasattr(self, "perceptual_loss"):
+                    raise RuntimeError("loss_weight.feat is set but no perceptual_loss module was injected")
+                fused_feat = ("gathered" in var and var.rgb.is_cuda and hasattr(self.perceptual_loss, "pairs_from_patches")
+                              and opt.nerf.rand_rays and mode in ["train", "test-optim"])
+                if fused_feat and var.get("feat_early_for") is var.ray_idx:
+                    if not var.get("feat_early_joined"):
+                        torch.cuda.current_stream(var.rgb.device).wait_stream(self.feat_stream)      # (enqueued by nerf_forward)
+                    loss.feat, l1 = var.feat_early, None
+                elif fused_feat and hasattr(self.perceptual_loss, "loss_from_patches"):
+                    # K13 + K12: inputs of the four batches in one launch, one pass through the network, l1 + 5 l2 in one launch
+                    loss.feat = self.perceptual_loss.loss_from_patches(var.get("rgb_feat", var.rgb), var.gathered, (h, w), 5.0)
+                    l1 = None
+                elif fused_feat:
+                    l1, l2 = self.perceptual_loss.pairs_from_patches(var.rgb, var.gathered, (h, w))
+                else:
+                    mask_pad = torch.logical_and(mask_syn == 1, obj_mask == 0).float()
+                    pair1 = (rgb, image * obj_mask + image_syn * mask_pad)
+                    pair2 = (rgb * obj_mask + image * (1 - obj_mask), image)
+                    if hasattr(self.perceptual_loss, "pairs"):        # both terms through one pass of the feature network
+                        l1, l2 = self.perceptual_loss.pairs(pair1, pair2)
+                    else:                                              # any injected module with the reference's call signature
+                        self._warn_once("compute_loss: the injected perceptual_loss has no fused entry points; calling it "
+                                        "twice like the reference (:762-764)")
+                        l1, l2 = self.perceptual_loss(*pair1), self.perceptual_loss(*pair2)
+                if l1 is not None:
+                    loss.feat = l1 + 5 * l2
+            if lw.lab is not None:
+                if self.lab_loss is not None:                          # an injected module, called like the reference's (:772-773)
+                    loss.lab, var.rgb_lab, var.img_syn_lab = self.lab_loss(rgb, image_syn, mask=mask_syn)
+                elif var.rgb.is_cuda:
+                    # K23: one launch each way; the real image and its mask are read where they lie -- channels 3..5 / 13 of the patch
+                    # gather in patch mode, the dense tensors otherwise
+                    if patch_mode and "gathered" in var:
+                        out = autograd_ops.lab_loss(var.rgb, var.gathered, var.gathered, real_channel=3, mask_channel=13)
+                    else:
+                        out = autograd_ops.lab_loss(var.rgb, image_syn, mask_syn)
+                    loss.lab = out[0]
+                    var.rgb_lab, var.img_syn_lab = (t.view(B, 3, *image_syn.shape[-2:]) for t in out[1:])
+                else:
+                    loss.lab, var.rgb_lab, var.img_syn_lab = self._lab_loss_torch()(rgb, image_syn, mask=mask_syn)
+            if opt.gan is not None and lw.gan_nerf is not None and mode == "train":
+                loss.gan_nerf = (var.gan_nerf_precomputed if "gan_nerf_precomputed" in var
+                                 else self.compute_gan_loss(opt, d_outs=var.d_fake_nerf, target=1))
+        elif train_step == "disc":
+            if lw.gan_disc_real is not None:
+                loss.gan_disc_real = self.compute_gan_loss(opt, d_outs=var.d_real_disc, target=1)
+            if lw.gan_disc_fake is not None:
+                loss.gan_disc_fake = self.compute_gan_loss(opt, d_outs=var.d_fake_disc, target=0)
+        else:
+            raise NotImplementedError
+        return loss
+
+
+class Graph(RenderMixin, torch.nn.Module):
+
+    def __init__(self, opt, discriminator=None, perceptual_loss=None, lab_loss=None):
+        super().__init__()
+        self.nerf = NeRF(opt)
+        if discriminator is not None:
+            self.discriminator = discriminator
+        if perceptual_loss is not None:
+            self.perceptual_loss = perceptual_loss
+        self.lab_loss = lab_loss
+        self.ray_sampler = RaySampler(opt)
+        # the reference passes `opt` into the random_shift slot (:424); truthy => default behaviour
+        self.patch_sampler = FlexPatchSampler(True, scale_anneal=0.0002)
+
+    def attach_latents(self, n_train, opt):
+        """Per-image appearance embeddings (Model.build_networks, reference :56-59)."""
+        self.latent_vars_trans = torch.nn.Embedding(n_train, opt.nerf.N_latent_trans).to(opt.device)
+        self.latent_vars_light = torch.nn.Embedding(n_train, opt.nerf.N_latent_light).to(opt.device)
+        torch.nn.init.normal_(self.latent_vars_trans.weight)
+        torch.nn.init.normal_(self.latent_vars_light.weight)
+
+    # ------------------------------------------------------------------ ray / sample selection
+    def get_ray_idx(self, opt, var):
+        # var.patch_u (optional, [3,B,1,1,1] uniforms) pins the scale / shift draw for parity tests
+        # (`fuse_prologue`, set by the captured training step around its render: the coordinates are drawn by the ray-generation launch)
+        defer = dict(defer=True) if getattr(self, "fuse_prologue", False) and var.get("patch_u") is None else {}
+        var.ray_idx, var.ray_scales = self.patch_sampler(nbatch=opt.batch_size, patch_size=opt.patch_size,
+                                                         device=opt.device, u=var.get("patch_u"), **defer)
+        return var
+
+    @staticmethod
+    def get_pose(opt, var, mode=None):
+        if mode == "train":
+            return dict(gt=var.pose, predicted=var.pose_init)[opt.data.pose_source]
+        return var.pose
+
     @staticmethod
     def eval_light_index(opt, var):
         """Row of ``latent_vars_light`` an evaluation render uses (reference model/nerf_adapt_st_gan.py:487-494): one of the
@@ -393,147 +547,10 @@ class Graph(torch.nn.Module):
         var.d_fake_disc = self.discriminator(opt, var.patch_fake, var.ray_scales)
         return var
 
-    def evaluate_metrics(self, opt, var, lpips_module=None):
-        """PSNR / SSIM of ``Model.evaluate_full`` (reference :340-362) for a rendered ``var`` (mode 'eval_*'): static
-        render vs masked image, resized to 480x640 when the data is not the 128x128 crop.  Returns 0-dim device tensors.
-
-        ``lpips_module``: the STOCK perceptual metric, injected (the reference builds ``lpips.LPIPS(net='alex')`` in
-        ``Model.__init__`` (:31) and calls ``self.lpips_loss(rgb_map * 2 - 1, image_masked * 2 - 1).item()`` (:363-364);
-        SURVEY 8 f4: "VGG / LPIPS stay stock").  When given, it is called exactly like that on the same two images
-        PSNR / SSIM see -- [B,3,h,w], the static render and ``image * obj_mask``, after the reference's optional resize
-        (bilinear ``align_corners=False`` for the images, nearest for the mask) -- and ``lpips`` is added to the result.  The
-        AlexNet weights are not available offline, so the value itself is unpinned (SURVEY 8c); the call contract is tested."""
-        out_hw = None if list(opt.data.image_size) == [128, 128] else (480, 640)
-        psnr, ssim, _ = ops.eval_metrics(var.rgb_static, var.image, var.obj_mask, opt.H, opt.W, out_hw=out_hw)
-        out = edict(psnr=psnr, ssim=ssim)
-        if lpips_module is not None:
-            B = var.image.shape[0]
-            rgb_map = var.rgb_static.view(B, opt.H, opt.W, 3).permute(0, 3, 1, 2)
-            image, mask = var.image.view(B, 3, opt.H, opt.W), var.obj_mask.view(B, 1, opt.H, opt.W).float()
-            if out_hw is not None:                  # reference :344-349
-                rgb_map = torch_F.interpolate(rgb_map, size=list(out_hw), mode="bilinear", align_corners=False)
-                image = torch_F.interpolate(image, size=list(out_hw), mode="bilinear", align_corners=False)
-                mask = torch_F.interpolate(mask, size=list(out_hw), mode="nearest")
-            with torch.no_grad():
-                out.lpips = lpips_module(rgb_map * 2 - 1, (image * mask) * 2 - 1).reshape(-1).mean()
-        return out
-
-    def _warn_once(self, message):
-        seen = self.__dict__.setdefault("_warned", set())
-        if message not in seen:
-            seen.add(message)
-            warnings.warn("texpose_amd: " + message)
-
-    def _lab_loss_torch(self):
-        """The Lab chroma loss as torch ops (texpose_amd/lab.py): CPU tensors only -- on the GPU the term is K23."""
-        if "_lab_module" not in self.__dict__:
-            from .lab import LabLoss
-            self.__dict__["_lab_module"] = LabLoss()           # (no parameters, no buffers: kept out of the module tree / state dict)
-        return self.__dict__["_lab_module"]
-
     @staticmethod
     def MSE_loss(pred, label, mask=None):
         loss = (pred.contiguous() - label) ** 2
         return loss.mean() if mask is None else (loss * mask).sum() / (mask.sum() + 1e-5)
-
-    def compute_loss(self, opt, var, mode=None, train_step="nerf"):
-        """Photometric / uncertainty / transient-regulariser / feature / GAN terms (reference :712-776)."""
-        loss = edict()
-        B = len(var.idx)
-        patch_mode = bool(opt.nerf.rand_rays and mode in ["train", "test-optim"])
-        if patch_mode:
-            _, h, w, _ = var.ray_idx.shape
-            var = self.gather_patches(opt, var)
-            image, obj_mask = var.image_sample, var.mask_sample
-            image_syn, mask_syn = var.image_syn_sample, var.mask_syn_sample
-            rgb = var.rgb.view(B, h, w, 3).permute(0, 3, 1, 2)
-            uncert = var.uncert.view(B, h, w, 1).permute(0, 3, 1, 2)
-        else:
-            image = var.image.view(B, 3, opt.H, opt.W)
-            obj_mask = (var.obj_mask > 0).float().view(B, 1, opt.H, opt.W)
-            image_syn = var.get("image_syn", var.image).view(B, 3, opt.H, opt.W)
-            mask_syn = (var.get("mask_syn", var.obj_mask) > 0).float().view(B, 1, opt.H, opt.W)
-            rgb = var.rgb.view(B, opt.H, opt.W, 3).permute(0, 3, 1, 2)
-            uncert = var.uncert.view(B, opt.H, opt.W, 1).permute(0, 3, 1, 2)
-            var.image_syn_sample, var.image_sample, var.mask_sample, var.mask_syn_sample = (image_syn, image, obj_mask,
-                                                                                            mask_syn)
-        lw = opt.loss_weight
-        if train_step == "nerf":
-            # default configuration: the three render-consuming terms and their gradients in one launch each way (K8)
-            fused = ("gathered" in var and opt.nerf.mask_obj and lw.render is not None and lw.uncert is not None
-                     and lw.trans_reg is not None and lw.mask is None and var.rgb.is_cuda)
-            if fused:
-                loss.render, loss.uncert, loss.trans_reg = autograd_ops.nerf_losses(var.rgb, var.uncert,
-                                                                                     var.get("density_losses", var.density), var.gathered)
-            elif var.rgb.is_cuda:
-                # non-reference option combinations (a term switched off, mask_obj = False, full-image losses): the terms are
-                # formed with torch element-wise ops on the render outputs -- same values, many small launches.  Said once.
-                self._warn_once("compute_loss: loss options differ from the reference configuration (render / uncert / "
-                                "trans_reg on, mask off, mask_obj, patch mode): the render-consuming terms run as torch ops "
-                                "instead of the fused K8 launch")
-            if not fused and lw.render is not None:
-                if opt.nerf.mask_obj:
-                    loss.render = (obj_mask * ((image - rgb) ** 2 / uncert ** 2)).sum() / (obj_mask.sum() + 1e-5)
-                else:
-                    loss.render = self.MSE_loss(rgb, image)
-            if lw.mask is not None:
-                loss.mask = self.MSE_loss(obj_mask, var.opacity[..., None])
-            if not fused and lw.uncert is not None:
-                loss.uncert = 5 + torch.log(var.uncert ** 2).mean() / 2
-            if not fused and lw.trans_reg is not None:
-                loss.trans_reg = var.density[..., -1].mean()
-            if lw.feat is not None:
-                if not hasattr(self, "perceptual_loss"):
-                    raise RuntimeError("loss_weight.feat is set but no perceptual_loss module was injected")
-                fused_feat = ("gathered" in var and var.rgb.is_cuda and hasattr(self.perceptual_loss, "pairs_from_patches")
-                              and opt.nerf.rand_rays and mode in ["train", "test-optim"])
-                if fused_feat and var.get("feat_early_for") is var.ray_idx:
-                    if not var.get("feat_early_joined"):
-                        torch.cuda.current_stream(var.rgb.device).wait_stream(self.feat_stream)      # (enqueued by nerf_forward)
-                    loss.feat, l1 = var.feat_early, None
-                elif fused_feat and hasattr(self.perceptual_loss, "loss_from_patches"):
-                    # K13 + K12: inputs of the four batches in one launch, one pass through the network, l1 + 5 l2 in one launch
-                    loss.feat = self.perceptual_loss.loss_from_patches(var.get("rgb_feat", var.rgb), var.gathered, (h, w), 5.0)
-                    l1 = None
-                elif fused_feat:
-                    l1, l2 = self.perceptual_loss.pairs_from_patches(var.rgb, var.gathered, (h, w))
-                else:
-                    mask_pad = torch.logical_and(mask_syn == 1, obj_mask == 0).float()
-                    pair1 = (rgb, image * obj_mask + image_syn * mask_pad)
-                    pair2 = (rgb * obj_mask + image * (1 - obj_mask), image)
-                    if hasattr(self.perceptual_loss, "pairs"):        # both terms through one pass of the feature network
-                        l1, l2 = self.perceptual_loss.pairs(pair1, pair2)
-                    else:                                              # any injected module with the reference's call signature
-                        self._warn_once("compute_loss: the injected perceptual_loss has no fused entry points; calling it "
-                                        "twice like the reference (:762-764)")
-                        l1, l2 = self.perceptual_loss(*pair1), self.perceptual_loss(*pair2)
-                if l1 is not None:
-                    loss.feat = l1 + 5 * l2
-            if lw.lab is not None:
-                if self.lab_loss is not None:                          # an injected module, called like the reference's (:772-773)
-                    loss.lab, var.rgb_lab, var.img_syn_lab = self.lab_loss(rgb, image_syn, mask=mask_syn)
-                elif var.rgb.is_cuda:
-                    # K23: one launch each way; the real image and its mask are read where they lie -- channels 3..5 / 13 of the patch
-                    # gather in patch mode, the dense tensors otherwise
-                    if patch_mode and "gathered" in var:
-                        out = autograd_ops.lab_loss(var.rgb, var.gathered, var.gathered, real_channel=3, mask_channel=13)
-                    else:
-                        out = autograd_ops.lab_loss(var.rgb, image_syn, mask_syn)
-                    loss.lab = out[0]
-                    var.rgb_lab, var.img_syn_lab = (t.view(B, 3, *image_syn.shape[-2:]) for t in out[1:])
-                else:
-                    loss.lab, var.rgb_lab, var.img_syn_lab = self._lab_loss_torch()(rgb, image_syn, mask=mask_syn)
-            if opt.gan is not None and lw.gan_nerf is not None and mode == "train":
-                loss.gan_nerf = (var.gan_nerf_precomputed if "gan_nerf_precomputed" in var
-                                 else self.compute_gan_loss(opt, d_outs=var.d_fake_nerf, target=1))
-        elif train_step == "disc":
-            if lw.gan_disc_real is not None:
-                loss.gan_disc_real = self.compute_gan_loss(opt, d_outs=var.d_real_disc, target=1)
-            if lw.gan_disc_fake is not None:
-                loss.gan_disc_fake = self.compute_gan_loss(opt, d_outs=var.d_fake_disc, target=0)
-        else:
-            raise NotImplementedError
-        return loss
 
     @staticmethod
     def compute_grad2(opt, d_outs, x_in):
