@@ -959,6 +959,78 @@ int tp_lab_loss_fwd(const tp_lab_loss_args* args, tp_stream_t stream);
 /* g: the upstream gradient of the loss, one device scalar; g_rgb [B,P,3] = g[0] * d loss / d rgb */
 int tp_lab_loss_bwd(const tp_lab_loss_args* args, const float* g, float* g_rgb, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K24  brute-force 1-nearest / 1-farthest neighbour in 3-D: the search under ADD-S, the model diameter and the one-directional
+ *      chamfer distance (texpose_amd/pose_error.py; the definitions are restated in tests/pose_error_ref.py).
+ * ref: camera.py:469-586 (p2p_distance: PyTorch3D's knn_points with K = 1).
+ *      Per batch element b and query i < x_len[b], with bx = (Bx == 1 ? 0 : b), bt = (Bt == 1 ? 0 : b), the distance is taken
+ *      between q = x[bx,i] and the targets y' = y[bt,j], j < y_len[bt]; or, with A, between A[b][:, :3] x[bx,i] + A[b][:, 3] and
+ *      y[bt,j], evaluated in the frame before A's translation t = A[b][:, 3]: q = A[b][:, :3] x[bx,i] (in fp64, rounded once to
+ *      fp32) and y' = y[bt,j] -_f32 t.  Both sides are then of the model's size rather than of the camera distance, where fp32
+ *      roundings are ~1e-5 mm instead of ~1e-4 mm.  The mapped cloud is never stored; with Bx = 1 one model is searched under B maps.
+ *        d2(j) = dx*dx + dy*dy + dz*dz of the fp32 differences q - y'   (the direct form; dx*dx rounded, then two fused
+ *                multiply-adds -- one fixed evaluation order)
+ *        TP_NN1_NEAREST : the smallest d2(j), TP_NN1_FARTHEST : the largest; on equal d2 the LOWEST j wins
+ *        a target with a NaN coordinate never wins (nor any j whose d2 is NaN)
+ *        no winner (NaN query, i >= x_len[b], no target left): d2 = +inf (-inf in TP_NN1_FARTHEST), idx = -1
+ *      The result is a function of the inputs alone: where the targets are split over workgroups (target_slices), the slices meet
+ *      through a 64-bit integer key (bits of d2, then index) and integer atomic min / max -- no float atomics; the call writes the
+ *      keys' initial value itself.  One launch without slices, three with.  No allocation, no host synchronisation; outputs and
+ *      workspace must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_NN1_TILE 1024                /* targets staged in LDS at a time */
+#define TP_NN1_QUERIES_PER_BLOCK 1024   /* queries one workgroup owns (256 threads x 4) */
+enum tp_nn1_mode {
+  TP_NN1_NEAREST = 0,
+  TP_NN1_FARTHEST = 1
+};
+typedef struct tp_nn1_args {
+  const float* x;          /* [Bx,P1,3] queries */
+  const float* y;          /* [Bt,P2,3] targets */
+  const int32_t* x_len;    /* [B] or NULL (= P1 everywhere); clamped to 0 .. P1 */
+  const int32_t* y_len;    /* [Bt] or NULL (= P2 everywhere); clamped to 0 .. P2 */
+  const float* A;          /* [B,3,4] or NULL: the affine map applied to the queries of b */
+  int B;                   /* batch elements: rows of A, of x_len and of the outputs */
+  int Bx, Bt;              /* 1 (one query set / one target set shared by every b) or B */
+  int P1, P2;
+  int mode;                /* tp_nn1_mode */
+  int target_slices;       /* 0: chosen from the shapes; n > 0: min(n, number of target tiles) slices.  The result does not depend on it */
+  float* d2;               /* [B,P1] out */
+  int32_t* idx;            /* [B,P1] out */
+  void* workspace;         /* tp_nn1_workspace_bytes(args) bytes (0: may be NULL); needs no clearing */
+} tp_nn1_args;
+/* B * P1 * 8 where the call splits the targets into more than one slice, else 0 (and 0 for arguments tp_nn1 refuses) */
+size_t tp_nn1_workspace_bytes(const tp_nn1_args* args);
+int tp_nn1(const tp_nn1_args* args, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K25  the per-pose errors of the BOP evaluation that need no search: ADD, MSSD, MSPD and the mean projection error, for B pose
+ *      pairs over one model and its S symmetry transforms.  The BOP definitions are restated (tests/pose_error_ref.py), not pinned
+ *      to a bop_toolkit call.  With e = P_e x, g_s = P_g S_s x and pi(X) = (fx X / Z + cx, fy Y / Z + cy):
+ *        out[b] = { add  = mean_x |e - g_0|,              mssd = min_s max_x |e - g_s|,
+ *                   mspd = min_s max_x |pi(e) - pi(g_s)|,  proj = mean_x |pi(e) - pi(g_0)| }
+ *        s_mssd[b], s_mspd[b]: the winning s, the lowest on ties
+ *      sym[0] must be the identity (add and proj are taken at s = 0).  mspd, proj and s_mspd are written only when intr is given.
+ *      A point with Z <= 0 (or NaN) under P_e or any P_g S_s makes mspd = proj = NaN and s_mspd = -1 for that b; add and mssd are
+ *      unaffected.  fp32 in and out, fp64 in between, reduced by a fixed tree (one workgroup per (b, s), then the minimum over s in
+ *      a second launch): bit-identical from run to run.  S > TP_POSE_ERRORS_MAX_SYM is refused (-1, tp_last_error).
+ *      Two launches.  No allocation, no host synchronisation; outputs must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_POSE_ERRORS_MAX_SYM 64
+typedef struct tp_pose_errors_args {
+  const float* pts;        /* [M,3] model points */
+  const float* pose_est;   /* [B,3,4] */
+  const float* pose_gt;    /* [B,3,4] */
+  const float* sym;        /* [S,3,4], row 0 the identity */
+  const float* intr;       /* [B,3,3] or NULL */
+  int M, B, S;
+  float* out;              /* [B,4]: add, mssd, mspd, proj (columns 2, 3 untouched without intr) */
+  int32_t* s_mssd;         /* [B] */
+  int32_t* s_mspd;         /* [B]; may be NULL without intr */
+  void* workspace;         /* B * S * 4 doubles; needs no clearing */
+} tp_pose_errors_args;
+int tp_pose_errors(const tp_pose_errors_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

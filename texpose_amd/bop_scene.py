@@ -121,18 +121,34 @@ def read_bop_frame(root: str, frame: int) -> dict:
     from PIL import Image
     load = lambda name: json.load(open(os.path.join(root, name + ".json")))
     key = str(int(frame))
-    cam, gt, info = load("scene_camera")[key], load("scene_gt")[key], load("scene_gt_info")[key]
+    cam, info = load("scene_camera")[key], load("scene_gt_info")[key]
+    poses = read_bop_poses(root)[int(frame)]                # the one reader of the pose fields (float64 there, float32 here)
     png = lambda sub, name: np.asarray(Image.open(os.path.join(root, sub, name)))
-    K = len(gt)
-    out = dict(cam_K=np.array(cam["cam_K"], dtype=np.float32).reshape(3, 3), depth_scale=float(cam["depth_scale"]),
-               obj_id=np.array([g["obj_id"] for g in gt], dtype=np.int64),
-               cam_R_m2c=np.array([g["cam_R_m2c"] for g in gt], dtype=np.float32).reshape(K, 3, 3),
-               cam_t_m2c=np.array([g["cam_t_m2c"] for g in gt], dtype=np.float32).reshape(K, 3), info=info,
+    K = len(poses["obj_id"])
+    out = dict(cam_K=poses["cam_K"].astype(np.float32), depth_scale=float(cam["depth_scale"]), obj_id=poses["obj_id"],
+               cam_R_m2c=poses["cam_R_m2c"].astype(np.float32), cam_t_m2c=poses["cam_t_m2c"].astype(np.float32), info=info,
                rgb=png("rgb", "%06d.png" % frame), depth=png("depth", "%06d.png" % frame),
                mask=np.stack([png("mask", "%06d_%06d.png" % (frame, k)) for k in range(K)]),
                mask_visib=np.stack([png("mask_visib", "%06d_%06d.png" % (frame, k)) for k in range(K)]), objects=None)
     if os.path.exists(os.path.join(root, "scene_object.json")):
         out["objects"] = load("scene_object")[key]
+    return out
+
+
+def read_bop_poses(root: str, camera: bool = True) -> Dict[int, dict]:
+    """The poses of a scene folder from its json files alone (no image is opened): frame -> obj_id [K] int64, cam_R_m2c [K,3,3],
+    cam_t_m2c [K,3] float64 (mm) in the order of scene_gt.json and, with ``camera``, cam_K [3,3] float64 from scene_camera.json."""
+    load = lambda name: json.load(open(os.path.join(root, name + ".json")))
+    gt = load("scene_gt")
+    cam = load("scene_camera") if camera else None
+    out = {}
+    for key, entries in gt.items():
+        K = len(entries)
+        out[int(key)] = dict(obj_id=np.array([g["obj_id"] for g in entries], dtype=np.int64),
+                             cam_R_m2c=np.array([g["cam_R_m2c"] for g in entries], dtype=np.float64).reshape(K, 3, 3),
+                             cam_t_m2c=np.array([g["cam_t_m2c"] for g in entries], dtype=np.float64).reshape(K, 3))
+        if camera:
+            out[int(key)]["cam_K"] = np.array(cam[key]["cam_K"], dtype=np.float64).reshape(3, 3)
     return out
 
 

@@ -977,6 +977,94 @@ def lab_loss_bwd(rgb: Tensor, real: Tensor, mask: Optional[Tensor], sums: Tensor
     return g_rgb
 
 
+# ------------------------------------------------------------------------------------------ K24, K25
+NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
+
+
+def _lengths(op: str, t: Optional[Tensor], name: str, n: int, like: Tensor) -> Optional[Tensor]:
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != like.device:
+        raise ValueError(f"{op}: {name} must be an int32 GPU tensor of shape ({n},)")
+    return t.contiguous()
+
+
+@_on_tensor_device
+def nn1(x: Tensor, y: Tensor, *, x_len: Optional[Tensor] = None, y_len: Optional[Tensor] = None, A: Optional[Tensor] = None,
+        mode: str = "nearest", target_slices: int = 0):
+    """Brute-force 1-nearest (``mode`` 'farthest': 1-farthest) neighbour in 3-D (tp_nn1): queries x [Bx,P1,3], targets y [Bt,P2,3] with
+    Bx, Bt 1 (shared by every b) or B (B: A's batch size, else x's), optional int32 lengths x_len [B] / y_len [Bt] for ragged sets, optional A [B,3,4] applied to the
+    queries in registers (q = A[:, :3] x + A[:, 3]; evaluated before A's translation, which is taken off the targets) -> (d2 [B,P1] float32, idx [B,P1] int32): the squared distance in the direct form
+    and the winner's index, the lowest on equal d2; +inf (-inf for 'farthest') and -1 where there is no winner (a NaN query, a query
+    past x_len, no target).  ``target_slices``: 0 lets the library split the targets over workgroups from the shapes; the result does
+    not depend on it.  Not differentiable.  No allocation beyond the outputs and the split's key buffer, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    if mode not in NN1_MODES:
+        raise ValueError(f"nn1: mode must be one of {sorted(NN1_MODES)}, not {mode!r}")
+    x, y = _f32(x.detach(), "x"), _f32(y.detach(), "y")
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != 3 or y.shape[2] != 3 or x.shape[1] == 0 or y.shape[1] == 0 or x.shape[0] == 0:
+        raise ValueError("nn1: x [Bx,P1,3] and y [Bt,P2,3] expected, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    Bx, P1, Bt, P2 = x.shape[0], x.shape[1], y.shape[0], y.shape[1]
+    B = Bx if A is None else A.shape[0]
+    if Bx not in (1, B) or Bt not in (1, B):
+        raise ValueError("nn1: x and y must hold 1 or B = %d sets, got %d and %d" % (B, Bx, Bt))
+    x_len, y_len = _lengths("nn1", x_len, "x_len", B, x), _lengths("nn1", y_len, "y_len", Bt, x)
+    a = _lib.Nn1Args()
+    if A is not None:
+        A = _f32(A.detach(), "A")
+        if tuple(A.shape) != (B, 3, 4):
+            raise ValueError("nn1: A [B=%d,3,4] expected, got %s" % (B, tuple(A.shape)))
+        a.A = A.data_ptr()
+    d2 = torch.empty(B, P1, device=x.device)
+    idx = torch.empty(B, P1, device=x.device, dtype=torch.int32)
+    a.x, a.y, a.x_len, a.y_len = x.data_ptr(), y.data_ptr(), _ptr(x_len), _ptr(y_len)
+    a.B, a.Bx, a.Bt, a.P1, a.P2, a.mode, a.target_slices = B, Bx, Bt, P1, P2, NN1_MODES[mode], int(target_slices)
+    a.d2, a.idx = d2.data_ptr(), idx.data_ptr()
+    n_ws = lib.tp_nn1_workspace_bytes(C.byref(a))
+    ws = torch.empty(n_ws // 8, device=x.device, dtype=torch.int64) if n_ws else None
+    a.workspace = _ptr(ws)
+    check(lib.tp_nn1(C.byref(a), _stream()), "tp_nn1")
+    return d2, idx
+
+
+@_on_tensor_device
+def pose_errors(pts: Tensor, pose_est: Tensor, pose_gt: Tensor, sym: Optional[Tensor] = None, intr: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """ADD, MSSD, MSPD and the mean projection error of B pose pairs over one model (tp_pose_errors): pts [M,3], pose_est / pose_gt
+    [B,3,4], sym [S,3,4] (row 0 the identity; None: the identity alone; at most 64), intr [B,3,3] or None -> 'add', 'mssd' [B] float32
+    and 's_mssd' [B] int32 (the winning symmetry, the lowest on ties) and, with ``intr``, 'mspd', 'proj' and 's_mspd' (pixels; NaN /
+    -1 for a b with a point at Z <= 0 under either pose).  Not differentiable.  Two launches, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    pts, pose_est, pose_gt = _f32(pts.detach(), "pts"), _f32(pose_est.detach(), "pose_est"), _f32(pose_gt.detach(), "pose_gt")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+        raise ValueError("pose_errors: pts [M,3] expected, got %s" % (tuple(pts.shape),))
+    if pose_est.dim() != 3 or tuple(pose_est.shape[1:]) != (3, 4) or pose_est.shape[0] == 0 or pose_gt.shape != pose_est.shape:
+        raise ValueError("pose_errors: pose_est and pose_gt [B,3,4] expected, got %s and %s" % (tuple(pose_est.shape), tuple(pose_gt.shape)))
+    M, B = pts.shape[0], pose_est.shape[0]
+    if sym is None:
+        sym = torch.eye(3, 4, device=pts.device)[None]
+    sym = _f32(sym.detach(), "sym")
+    if sym.dim() != 3 or tuple(sym.shape[1:]) != (3, 4) or sym.shape[0] == 0:
+        raise ValueError("pose_errors: sym [S,3,4] expected, got %s" % (tuple(sym.shape),))
+    S = sym.shape[0]
+    a = _lib.PoseErrorsArgs()
+    if intr is not None:
+        intr = _f32(intr.detach(), "intr")
+        if tuple(intr.shape) != (B, 3, 3):
+            raise ValueError("pose_errors: intr [B=%d,3,3] expected, got %s" % (B, tuple(intr.shape)))
+        a.intr = intr.data_ptr()
+    out = torch.empty(B, 4, device=pts.device)
+    s_out = torch.empty(2, B, device=pts.device, dtype=torch.int32)
+    ws = torch.empty(B * min(S, _lib.POSE_ERRORS_MAX_SYM) * 4, device=pts.device, dtype=torch.float64)
+    a.pts, a.pose_est, a.pose_gt, a.sym = pts.data_ptr(), pose_est.data_ptr(), pose_gt.data_ptr(), sym.data_ptr()
+    a.M, a.B, a.S = M, B, S
+    a.out, a.s_mssd, a.s_mspd, a.workspace = out.data_ptr(), s_out[0].data_ptr(), s_out[1].data_ptr(), ws.data_ptr()
+    check(lib.tp_pose_errors(C.byref(a), _stream()), "tp_pose_errors")          # (S > 64: the library's error)
+    res = dict(add=out[:, 0], mssd=out[:, 1], s_mssd=s_out[0])
+    if intr is not None:
+        res.update(mspd=out[:, 2], proj=out[:, 3], s_mspd=s_out[1])
+    return res
+
+
 # ------------------------------------------------------------------------------------------ K9
 @_on_tensor_device
 def inorm_lrelu_fwd(x: Tensor, eps: float, slope: float, y_out: Optional[Tensor] = None):
