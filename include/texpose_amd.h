@@ -1031,6 +1031,42 @@ typedef struct tp_pose_errors_args {
 } tp_pose_errors_args;
 int tp_pose_errors(const tp_pose_errors_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K26  the per-pixel part of BOP's Visible Surface Discrepancy (VSD, cost 'step', visibility 'bop19') for B pose pairs and T
+ *      misalignment tolerances (texpose_amd/pose_error.py; restated in tests/vsd_ref.py, not pinned to a bop_toolkit call; DESIGN
+ *      section 16).  Per pose pair b, with K = intr[b], the test plane d = depth_test[frame ? frame[b] : (Ft == 1 ? 0 : b)] and, at
+ *      the pixel in row i and column j,
+ *        f        = sqrt(((j + 0.5 - cx) / fx)^2 + ((i + 0.5 - cy) / fy)^2 + 1)      (the project's pixel centres, not the toolkit's (j, i))
+ *        D_x      = z_x * f for x in {est, gt, test}: the distance from the camera centre
+ *        ok(z)    = z > 0                              (a NaN is not ok)
+ *        missing  = !(d > 0)                           (0, negative, NaN; the toolkit tests == 0)
+ *        vis(z)   = ok(z) && (missing || D_z - D_test <= delta_mm)
+ *        V_gt     = vis(z_gt),   V_est = vis(z_est) || (V_gt && ok(z_est))
+ *        I = V_gt && V_est,      U = V_gt || V_est
+ *        n_U = |U|, n_I = |I|, c_t = |{p in I : |D_gt - D_est| >= tau_mm[b,t]}|
+ *        err[b,t] = (c_t + n_U - n_I) / n_U, and 1 where n_U = 0
+ *      Everything between the fp32 inputs and the integer counts is fp64, evaluated as written (left to right, no contraction); err
+ *      is the fp64 quotient rounded once.  The counts meet through integer atomic adds only, so the outputs are a function of the
+ *      inputs alone: bit-identical from run to run and under graph replay.  The call clears counts itself.  A frame[b] outside
+ *      [0, Ft) is the caller's error; it is CLAMPED into the range, nothing is read out of bounds.  T outside 1 .. TP_VSD_MAX_TAUS,
+ *      non-positive sizes, H * W >= 2^31 and, without frame, an Ft that is neither 1 nor B are refused (-1, tp_last_error).
+ *      Three launches.  No allocation, no host synchronisation; outputs must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_VSD_MAX_TAUS 16
+typedef struct tp_vsd_args {
+  const float* z_est;        /* [B,H,W] mm, <= 0 or NaN: background */
+  const float* z_gt;         /* [B,H,W] */
+  const float* depth_test;   /* [Ft,H,W] mm, 0: no measurement */
+  const int32_t* frame;      /* [B] index into depth_test, or NULL: b when Ft == B, 0 when Ft == 1 */
+  const float* intr;         /* [B,3,3] */
+  const float* tau_mm;       /* [B,T] */
+  float delta_mm;
+  int B, Ft, H, W, T;        /* 1 <= T <= TP_VSD_MAX_TAUS (16) */
+  int32_t* counts;           /* [B, 2+T] out: n_U, n_I, c_0 .. c_{T-1}; the caller clears nothing */
+  float* err;                /* [B,T] out */
+} tp_vsd_args;
+int tp_vsd(const tp_vsd_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1065,6 +1065,49 @@ def pose_errors(pts: Tensor, pose_est: Tensor, pose_gt: Tensor, sym: Optional[Te
     return res
 
 
+# ------------------------------------------------------------------------------------------ K26
+@_on_tensor_device
+def vsd(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, tau_mm: Tensor, *, delta_mm: float = 15.0,
+        frame: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The per-pixel part of BOP's Visible Surface Discrepancy for B pose pairs and T tolerances (tp_vsd; the rules are in the header):
+    z_est, z_gt [B,H,W] (mesh_raster's zbuf: mm, <= 0 or NaN on background), depth_test [Ft,H,W] (the measured depth in mm, 0: no
+    value; Ft 1 or B, or any Ft with ``frame`` [B] int32, the plane of each b), intr [B,3,3] or one [3,3], tau_mm [B,T] (or [T] for
+    every b), T <= 16 -> 'err' [B,T] float32 and 'counts' [B,2+T] int32 (n_U, n_I, c_0 .. c_{T-1}).  ``out``: the two tensors to write
+    into (neither needs clearing).  Not differentiable.  Three launches, no allocation beyond fresh outputs, safe under
+    torch.cuda.graph."""
+    lib = _lib.load()
+    z_est, z_gt, depth_test = _f32(z_est.detach(), "z_est"), _f32(z_gt.detach(), "z_gt"), _f32(depth_test.detach(), "depth_test")
+    if z_est.dim() != 3 or z_est.numel() == 0 or z_gt.shape != z_est.shape:
+        raise ValueError("vsd: z_est and z_gt [B,H,W] expected, got %s and %s" % (tuple(z_est.shape), tuple(z_gt.shape)))
+    B, H, W = z_est.shape
+    if depth_test.dim() != 3 or tuple(depth_test.shape[1:]) != (H, W) or depth_test.shape[0] == 0:
+        raise ValueError("vsd: depth_test [Ft,H=%d,W=%d] expected, got %s" % (H, W, tuple(depth_test.shape)))
+    Ft = depth_test.shape[0]
+    frame = _lengths("vsd", frame, "frame", B, z_est)
+    if frame is None and Ft not in (1, B):
+        raise ValueError("vsd: depth_test must hold 1 or B = %d planes without frame=, got %d" % (B, Ft))
+    intr, tau_mm = _f32(intr.detach(), "intr"), _f32(tau_mm.detach(), "tau_mm")
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3).contiguous()
+    if tuple(intr.shape) != (B, 3, 3):
+        raise ValueError("vsd: intr [B=%d,3,3] or [3,3] expected, got %s" % (B, tuple(intr.shape)))
+    if tau_mm.dim() == 1:
+        tau_mm = tau_mm[None].expand(B, -1).contiguous()
+    if tau_mm.dim() != 2 or tau_mm.shape[0] != B:
+        raise ValueError("vsd: tau_mm [B=%d,T] or [T] expected, got %s" % (B, tuple(tau_mm.shape)))
+    T = tau_mm.shape[1]
+    spec = {"err": (torch.float32, (B, T)), "counts": (torch.int32, (B, 2 + T))}
+    res = {k: torch.empty(shape, device=z_est.device, dtype=dtype) if out is None else _want_gpu("vsd", out[k], f"out[{k!r}]", dtype, shape)
+           for k, (dtype, shape) in spec.items()}
+    a = _lib.VsdArgs()
+    a.z_est, a.z_gt, a.depth_test, a.frame = z_est.data_ptr(), z_gt.data_ptr(), depth_test.data_ptr(), _ptr(frame)
+    a.intr, a.tau_mm, a.delta_mm = intr.data_ptr(), tau_mm.data_ptr(), float(delta_mm)
+    a.B, a.Ft, a.H, a.W, a.T = B, Ft, H, W, T
+    a.counts, a.err = res["counts"].data_ptr(), res["err"].data_ptr()
+    check(lib.tp_vsd(C.byref(a), _stream()), "tp_vsd")                          # (T outside 1 .. 16: the library's error)
+    return res
+
+
 # ------------------------------------------------------------------------------------------ K9
 @_on_tensor_device
 def inorm_lrelu_fwd(x: Tensor, eps: float, slope: float, y_out: Optional[Tensor] = None):

@@ -9,6 +9,10 @@ chunked so that no block above ~64 MB is formed -- that route is also the yardst
 The BOP definitions and `p2p_distance` are RESTATED (tests/pose_error_ref.py says them again in numpy fp64): neither bop_toolkit nor
 PyTorch3D is a dependency, and nothing is pinned to a call of either.  Rules and what is pinned to what: DESIGN.md section 15.
 
+The third BOP error, the Visible Surface Discrepancy, and the BOP average recall are at the end of this file: `vsd` renders the model
+at both poses (K19 `tp_mesh_raster`) and `vsd_from_depth` turns the two renders and the measured depth into errors (K26 `tp_vsd` on
+CUDA tensors, `vsd_torch` on CPU tensors; restated in tests/vsd_ref.py).  Rules and what is pinned to what: DESIGN.md section 16.
+
 Poses are [B,3,4] = [R|t], model -> camera, t in the model's unit (mm for BOP models); a single [3,4] pose is taken as B = 1."""
 from __future__ import annotations
 
@@ -23,6 +27,9 @@ from . import geometry
 Tensor = torch.Tensor
 CHUNK_BYTES = 64 << 20          # the largest intermediate block of the torch route
 MAX_SYM = 64                    # tp_pose_errors takes at most this many symmetry transforms (TP_POSE_ERRORS_MAX_SYM)
+BOP19_TAUS = tuple(round(0.05 * i, 2) for i in range(1, 11))               # VSD's misalignment tolerances, fractions of the diameter
+BOP19_THRESHOLDS = tuple(round(0.05 * i, 2) for i in range(1, 11))         # the thresholds of correctness of VSD and (x diameter) MSSD
+BOP19_MSPD_PX = tuple(range(5, 51, 5))                                     # MSPD's thresholds in pixels of a 640-pixel-wide image
 
 
 def _poses(p: Tensor, name: str) -> Tensor:
@@ -287,3 +294,118 @@ def auc(errors, max_threshold: float) -> float:
     e = _host_list(errors)
     T = float(max_threshold)
     return sum(max(0.0, 1.0 - v / T) for v in e if v == v) / len(e) if e else math.nan
+
+
+# ----------------------------------------------------------------------------- VSD and the BOP average recall
+def depth_from_png(depth16: Tensor, depth_scale: float) -> Tensor:
+    """A scene folder's 16-bit depth image(s) -> float32 mm on the input's device: png * depth_scale (bop_scene.read_bop_frame's
+    'depth' and 'depth_scale'; a numpy uint16 array is accepted); 0 stays 0, "no measurement"."""
+    if not torch.is_tensor(depth16):
+        import numpy as np
+        depth16 = torch.from_numpy(np.ascontiguousarray(depth16).astype(np.int32))
+    return depth16.detach().to(torch.float32) * float(depth_scale)
+
+
+def vsd_torch(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, tau_mm: Tensor, delta_mm: float = 15.0,
+              frame: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """ops.vsd's rules (include/texpose_amd.h, K26) in plain torch ops in fp64 on the tensors' device: z_est, z_gt [B,H,W],
+    depth_test [Ft,H,W] (Ft 1 or B, or indexed by ``frame`` [B], clamped into range), intr [B,3,3], tau_mm [B,T]
+    -> {'err' [B,T] float32, 'counts' [B,2+T] int32}."""
+    B, H, W = z_est.shape
+    dev = z_est.device
+    if frame is not None:
+        depth_test = depth_test[frame.to(device=dev, dtype=torch.int64).clamp(0, depth_test.shape[0] - 1)]
+    elif depth_test.shape[0] not in (1, B):
+        raise ValueError("vsd: depth_test must hold 1 or B = %d planes without frame=, got %d" % (B, depth_test.shape[0]))
+    K = intr.double()
+    j = torch.arange(W, device=dev, dtype=torch.float64)[None, None, :]
+    i = torch.arange(H, device=dev, dtype=torch.float64)[None, :, None]
+    k = lambda r, c: K[:, r, c].view(B, 1, 1)
+    u, v = ((j + 0.5) - k(0, 2)) / k(0, 0), ((i + 0.5) - k(1, 2)) / k(1, 1)
+    f = ((u * u + v * v) + 1.0).sqrt()
+    ok_e, ok_g, missing = z_est > 0, z_gt > 0, ~(depth_test > 0)
+    D_e, D_g, D_t = z_est.double() * f, z_gt.double() * f, depth_test.double() * f
+    delta = float(torch.tensor(delta_mm, dtype=torch.float32))              # (the kernel takes it as fp32)
+    vis_g = ok_g & (missing | (D_g - D_t <= delta))
+    vis_e = ok_e & (missing | (D_e - D_t <= delta) | vis_g)
+    inter = vis_g & vis_e
+    diff = (D_g - D_e).abs()
+    n_u, n_i = (vis_g | vis_e).sum((1, 2)), inter.sum((1, 2))
+    c = torch.stack([(inter & (diff >= tau_mm[:, t].double().view(B, 1, 1))).sum((1, 2)) for t in range(tau_mm.shape[1])], 1)      # [B,T]
+    err = torch.where(n_u[:, None] > 0, (c + (n_u - n_i)[:, None]).double() / n_u.clamp(min=1)[:, None].double(),
+                      torch.ones((), dtype=torch.float64, device=dev))
+    return dict(err=err.float(), counts=torch.cat([n_u[:, None], n_i[:, None], c], 1).to(torch.int32))
+
+
+def vsd_from_depth(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, diameter, *, taus: Sequence[float] = BOP19_TAUS,
+                   delta: float = 15.0, frame: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """BOP's Visible Surface Discrepancy (cost 'step', visibility 'bop19') from depth planes: z_est, z_gt [B,H,W] the model's
+    view-space depth in mm at the estimated and the true pose (<= 0 or NaN on background: ops.mesh_raster's zbuf), depth_test
+    [Ft,H,W] the measured depth in mm (0: no value; Ft 1 or B, or indexed by ``frame`` [B]), intr [B,3,3] or [3,3], ``diameter``
+    a float or a [B] tensor, ``taus`` at most 16 fractions of it, ``delta`` the visibility tolerance in mm
+    -> 'err' [B,T] float32 in [0, 1] and 'counts' [B,2+T] int32 (n_U, n_I, c_t).  tau_mm = taus x diameter is formed on the tensors'
+    device; nothing is read back.  CUDA tensors: K26 (ops.vsd); CPU tensors: `vsd_torch`."""
+    z_est, z_gt, depth_test, intr = z_est.detach(), z_gt.detach(), depth_test.detach(), intr.detach()
+    if z_est.dim() != 3 or z_gt.shape != z_est.shape or depth_test.dim() != 3 or depth_test.shape[1:] != z_est.shape[1:]:
+        raise ValueError("vsd: z_est, z_gt [B,H,W] and depth_test [Ft,H,W] expected, got %s, %s and %s"
+                         % (tuple(z_est.shape), tuple(z_gt.shape), tuple(depth_test.shape)))
+    B, dev = z_est.shape[0], z_est.device
+    if not 1 <= len(taus) <= 16:
+        raise ValueError("vsd: 1 .. 16 taus expected, got %d" % len(taus))
+    d = diameter.detach().to(device=dev, dtype=torch.float32).reshape(-1) if torch.is_tensor(diameter) else \
+        torch.full((1,), float(diameter), dtype=torch.float32, device=dev)
+    if d.numel() not in (1, B):
+        raise ValueError("vsd: diameter must be a number or a [B] tensor")
+    tau_mm = (torch.tensor([float(t) for t in taus], dtype=torch.float32, device=dev)[None] * d[:, None]).expand(B, -1).contiguous()
+    intr = intr[None].expand(B, -1, -1) if intr.dim() == 2 else intr
+    if z_est.is_cuda:
+        from . import ops
+        return ops.vsd(z_est, z_gt, depth_test.to(dev), intr.to(dev).contiguous(), tau_mm, delta_mm=delta,
+                       frame=None if frame is None else frame.to(device=dev, dtype=torch.int32))
+    return vsd_torch(z_est, z_gt, depth_test, intr, tau_mm, delta, frame)
+
+
+def vsd(verts: Tensor, faces: Tensor, pose_est: Tensor, pose_gt: Tensor, intr: Tensor, depth_test: Tensor, diameter, *, H: int, W: int,
+        taus: Sequence[float] = BOP19_TAUS, delta: float = 15.0, frame: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """VSD of B pose pairs of one mesh: ONE ops.mesh_raster call renders the 2 B stacked poses (depth only), `vsd_from_depth` does the
+    rest.  verts [V,3] (mm), faces [F,3], pose_est / pose_gt [B,3,4] (t in mm), intr [B,3,3] or [3,3]; the other arguments are
+    `vsd_from_depth`'s.  GPU only: the rasteriser has no CPU route."""
+    pose_est, pose_gt = _poses(pose_est, "pose_est"), _poses(pose_gt, "pose_gt")
+    if pose_est.shape != pose_gt.shape:
+        raise ValueError("pose_est and pose_gt: the same number of poses expected")
+    if not verts.is_cuda:
+        raise ValueError("vsd: the mesh is rendered by the HIP rasteriser, which has no CPU route; pass CUDA tensors "
+                         "(depth planes rendered elsewhere can be scored on the CPU with vsd_from_depth)")
+    from . import ops
+    B = pose_est.shape[0]
+    intr = intr.detach()
+    intr = intr[None].expand(B, -1, -1) if intr.dim() == 2 else intr
+    z = ops.mesh_raster(verts.detach(), faces, torch.cat([pose_est, pose_gt]).to(verts.device), torch.cat([intr, intr]).to(verts.device),
+                        H=H, W=W, face_ids=False, normals=False)["zbuf"]
+    return vsd_from_depth(z[:B], z[B:], depth_test, intr, diameter, taus=taus, delta=delta, frame=frame)
+
+
+def average_recall(vsd_err, mssd, mspd, diameter, width: int, valid=None) -> Dict[str, float]:
+    """The BOP average recall over G ground-truth instances: vsd_err [G,T] (`vsd`'s 'err'), mssd [G], mspd [G], diameter [G] (or one
+    number), ``width`` the image width in pixels, valid [G] (False: the instance has no estimate) ->
+      ar_vsd  = mean over T x BOP19_THRESHOLDS of the share of instances with err < theta,
+      ar_mssd = mean over BOP19_THRESHOLDS of the share with mssd < theta x diameter,
+      ar_mspd = mean over r in 5, 10 .. 50 of the share with mspd < r x width / 640,
+      ar      = their mean.
+    An instance without an estimate, or with a NaN error, is a miss.  Host-side, like `recall`."""
+    rows = vsd_err.detach().double().cpu().tolist() if torch.is_tensor(vsd_err) else [[float(x) for x in r] for r in vsd_err]
+    ms, mp = _host_list(mssd), _host_list(mspd)
+    G = len(rows)
+    d = _host_list(diameter)
+    d = d * G if len(d) == 1 else d
+    ok = [True] * G if valid is None else [bool(x) for x in (valid.detach().reshape(-1).tolist() if torch.is_tensor(valid) else valid)]
+    if not (len(ms) == len(mp) == len(d) == len(ok) == G):
+        raise ValueError("average_recall: vsd_err [G,T], mssd, mspd, diameter and valid [G] expected")
+    if G == 0:
+        return dict(ar_vsd=math.nan, ar_mssd=math.nan, ar_mspd=math.nan, ar=math.nan)
+    T = len(rows[0])
+    hits = sum(1 for g in range(G) if ok[g] for e in rows[g] for th in BOP19_THRESHOLDS if e < th)
+    ar_vsd = hits / (G * T * len(BOP19_THRESHOLDS))
+    ar_mssd = sum(1 for g in range(G) if ok[g] for th in BOP19_THRESHOLDS if ms[g] < th * d[g]) / (G * len(BOP19_THRESHOLDS))
+    ar_mspd = sum(1 for g in range(G) if ok[g] for r in BOP19_MSPD_PX if mp[g] < r * width / 640.0) / (G * len(BOP19_MSPD_PX))
+    return dict(ar_vsd=ar_vsd, ar_mssd=ar_mssd, ar_mspd=ar_mspd, ar=(ar_vsd + ar_mssd + ar_mspd) / 3.0)
