@@ -1067,6 +1067,54 @@ typedef struct tp_vsd_args {
 } tp_vsd_args;
 int tp_vsd(const tp_vsd_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K27  bake B posed images onto the V vertices of a mesh as weighted colour sums (texpose_amd/texture_bake.py; restated in
+ *      tests/texture_bake_ref.py; the project's own step, no reference code).  Per vertex i and view b, in
+ *      ascending b, with [R|t] = pose[b], K = intr[b], v = verts[i], n = normals[i]:
+ *        x      = R v + t,  z = x_z;                      the pair is skipped unless z > 0
+ *        c      = -(((R n) . x) / |x|);                    skipped unless c >= cos_min          (no image memory is touched so far)
+ *        q      = K x,  (u, v) = (q_0, q_1) / q_2;        pixel (row r, column j) has its centre at (j + 0.5, r + 0.5)
+ *        su = u - 0.5, sv = v - 0.5, j0 = floor(su), r0 = floor(sv), a = su - j0, be = sv - r0
+ *        taps (r0 + dr, j0 + dj), dr, dj in {0, 1}, with weights w = (dj ? a : 1 - a) * (dr ? be : 1 - be)
+ *        tol    = z_tol_mm + slope * (z / min(K_00, K_11)) * sqrt(max(0, 1 - c * c)) / c
+ *                 (the depth a plane of that obliquity gains over the <= sqrt(2) px to a tap: a shadow-map bias from the normal)
+ *        a tap is valid iff it lies inside the image, zbuf_tap > 0, |zbuf_tap - z| <= tol, and its three colour channels (and
+ *                 its weight sample, if weight is given) are finite
+ *        cover  = sum of w over the valid taps (in the order (0,0), (0,1), (1,0), (1,1) of (dr, dj));  skipped unless cover >= cover_min
+ *        colour = (sum of w * rgb_tap over the valid taps) / cover
+ *        wb     = c * cover, times (sum of w * weight_tap over the valid taps) / cover if weight is given
+ *        acc[i] += wb * (colour_r, colour_g, colour_b, 1),  count[i] += 1
+ *      A pair whose (su, sv) is not inside [-1, W) x [-1, H) (a NaN included) has no tap inside the image and is skipped before
+ *      anything is read.  Everything between the fp32 inputs and a pair's four products is fp64, evaluated as written (left to
+ *      right, no contraction).  The views are cut into S = ceil(B / L) slices of L = max(4, ceil(B / ceil(65536 / V))) consecutive
+ *      views (at most B): S depends on V and B alone, never on the device.  One thread per (vertex, slice) adds its pairs in
+ *      ascending b in fp64 and stores the partial sums into the workspace; a second launch adds a vertex's S partial sums in
+ *      ascending order in fp64 and writes acc = fl32(sum) where clear is non-zero, acc = fl32(fp64(acc) + sum) otherwise, and the
+ *      same for count.  No atomics: the outputs are a function of the inputs alone, bit-identical from run to run, from device
+ *      to device and under graph replay.  Non-positive sizes, B > 65535, H * W >= 2^31, V > 2^30, cos_min or cover_min
+ *      outside (0, 1] and a negative or NaN z_tol_mm or slope are refused (-1, tp_last_error).  Nothing is read out of
+ *      bounds for any pose.  Two launches.  No allocation, no host synchronisation; outputs and workspace must not overlap inputs.
+ *      Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_texture_bake_args {
+  const float* verts;        /* [V,3] model frame, mm */
+  const float* normals;      /* [V,3] unit, model frame */
+  const float* pose;         /* [B,3,4] [R|t] model -> camera, t in mm (K19's convention) */
+  const float* intr;         /* [B,3,3] */
+  const float* rgb;          /* [B,H,W,3] */
+  const float* zbuf;         /* [B,H,W] K19's plane: mm, <= 0 or NaN: background */
+  const float* weight;       /* [B,H,W] or NULL */
+  int V, B, H, W;
+  int clear;                 /* non-zero: acc and count are overwritten; zero: added to */
+  float cos_min, cover_min, z_tol_mm, slope;
+  float* acc;                /* [V,4] in/out: sum of wb * r, wb * g, wb * b, wb */
+  int32_t* count;            /* [V] in/out: contributing views */
+  void* workspace;           /* tp_texture_bake_workspace_bytes(V, B) bytes, 16-byte aligned; needs no clearing */
+} tp_texture_bake_args;
+int tp_texture_bake_slices(int V, int B);                 /* S of the rule above; 0 for non-positive sizes */
+size_t tp_texture_bake_workspace_bytes(int V, int B);
+int tp_texture_bake(const tp_texture_bake_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1108,6 +1108,62 @@ def vsd(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, tau_mm: T
     return res
 
 
+# ------------------------------------------------------------------------------------------ K27
+def texture_bake_workspace(V: int, B: int, device) -> Tensor:
+    """A workspace for texture_bake at V vertices and B views (tp_texture_bake_workspace_bytes); needs no clearing."""
+    return torch.empty(max(2, (int(_lib.load().tp_texture_bake_workspace_bytes(V, B)) + 7) // 8), device=device, dtype=torch.float64)
+
+
+@_on_tensor_device
+def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb: Tensor, zbuf: Tensor, weight: Optional[Tensor] = None, *,
+                 acc: Optional[Tensor] = None, count: Optional[Tensor] = None, clear: bool = True, cos_min: float = 0.3,
+                 cover_min: float = 0.5, z_tol_mm: float = 0.5, slope: float = 2.0, workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Project B posed images onto the V vertices of a mesh (tp_texture_bake; the rules are in the header): verts, normals [V,3]
+    (model frame, mm; unit normals), pose [B,3,4] (model -> camera, mm), intr [B,3,3] or one [3,3], rgb [B,H,W,3], zbuf [B,H,W]
+    (mesh_raster's plane), weight [B,H,W] or None -> 'acc' [V,4] float32 (sums of w r, w g, w b, w) and 'count' [V] int32.  ``acc`` /
+    ``count``: the tensors to write into; with ``clear=False`` the call adds to what they hold, so views can be streamed in chunks.
+    ``workspace``: texture_bake_workspace(V, B) (a fresh one otherwise).  Not differentiable.  Two launches, no atomics, safe under
+    torch.cuda.graph."""
+    lib = _lib.load()
+    verts, normals, pose = _f32(verts.detach(), "verts"), _f32(normals.detach(), "normals"), _f32(pose.detach(), "pose")
+    rgb, zbuf = _f32(rgb.detach(), "rgb"), _f32(zbuf.detach(), "zbuf")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0 or normals.shape != verts.shape:
+        raise ValueError("texture_bake: verts and normals [V,3] expected, got %s and %s" % (tuple(verts.shape), tuple(normals.shape)))
+    if pose.dim() != 3 or tuple(pose.shape[1:]) != (3, 4) or pose.shape[0] == 0:
+        raise ValueError("texture_bake: pose [B,3,4] expected, got %s" % (tuple(pose.shape),))
+    V, B = verts.shape[0], pose.shape[0]
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0 or tuple(rgb.shape) != tuple(zbuf.shape) + (3,):
+        raise ValueError("texture_bake: zbuf [B=%d,H,W] and rgb [B,H,W,3] expected, got %s and %s" % (B, tuple(zbuf.shape), tuple(rgb.shape)))
+    H, W = zbuf.shape[1:]
+    intr = _f32(intr.detach(), "intr")
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3).contiguous()
+    if tuple(intr.shape) != (B, 3, 3):
+        raise ValueError("texture_bake: intr [B=%d,3,3] or [3,3] expected, got %s" % (B, tuple(intr.shape)))
+    if weight is not None:
+        weight = _f32(weight.detach(), "weight")
+        if weight.numel() != B * H * W:
+            raise ValueError("texture_bake: weight [B=%d,H=%d,W=%d] expected, got %s" % (B, H, W, tuple(weight.shape)))
+    if (acc is None) != (count is None) or (acc is None and not clear):
+        raise ValueError("texture_bake: acc and count come together, and clear=False needs both")
+    dev = verts.device
+    acc = torch.empty(V, 4, device=dev) if acc is None else _want_gpu("texture_bake", acc, "acc", torch.float32, (V, 4))
+    count = torch.empty(V, device=dev, dtype=torch.int32) if count is None else _want_gpu("texture_bake", count, "count", torch.int32, (V,))
+    need = int(lib.tp_texture_bake_workspace_bytes(V, B))
+    if workspace is None:
+        workspace = texture_bake_workspace(V, B, dev)
+    elif not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("texture_bake: workspace must be a contiguous GPU tensor of >= %d bytes" % need)
+    a = _lib.TextureBakeArgs()
+    a.verts, a.normals, a.pose, a.intr = verts.data_ptr(), normals.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.rgb, a.zbuf, a.weight = rgb.data_ptr(), zbuf.data_ptr(), _ptr(weight)
+    a.V, a.B, a.H, a.W, a.clear = V, B, H, W, int(bool(clear))
+    a.cos_min, a.cover_min, a.z_tol_mm, a.slope = float(cos_min), float(cover_min), float(z_tol_mm), float(slope)
+    a.acc, a.count, a.workspace = acc.data_ptr(), count.data_ptr(), workspace.data_ptr()
+    check(lib.tp_texture_bake(C.byref(a), _stream()), "tp_texture_bake")        # (thresholds out of range: the library's error)
+    return {"acc": acc, "count": count}
+
+
 # ------------------------------------------------------------------------------------------ K9
 @_on_tensor_device
 def inorm_lrelu_fwd(x: Tensor, eps: float, slope: float, y_out: Optional[Tensor] = None):

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Bake the texture a checkpoint has learned onto the object's CAD mesh as vertex colours: a coloured .ply that SurfelRenderer,
+SceneBounds, the BOP writer and any BOP tool render at rasteriser speed (texpose_amd.texture_bake, K27 tp_texture_bake).
+
+    python tools/bake_texture.py --checkpoint model.ckpt --ply 5=obj_000005.ply --scene scene.npz --out textured.ply --report bake.json
+
+--scene: an .npz with pose [N,3,4] (the training poses, t in nerf.depth.scale units) and intr [3,3] or [N,3,3]; the default source of
+views -- a field trained on an upper hemisphere should not be baked from below.  --sphere N --distance-mm D instead: N Fibonacci
+look-at views around the model origin with a pinhole of --focal pixels (default 1.5 x the longer image side) centred in the image.
+Per chunk of --chunk views: depth bounds, mask and the mesh's depth planes from SceneBounds, Graph.render_by_slices(mode="eval"), and
+rgb_static is baked with opacity_static as the weight against those depth planes.  One --light-index per bake.
+--report JSON: vertices, views, coverage (share of vertices some view reached), coloured (share with a positive weight), mean views per
+vertex, filled and unseen counts, thresholds, seconds.  --verify re-renders the baked mesh with ops.mesh_raster at the bake poses and
+prints (and stores) the PSNR against the NeRF views inside the mask; nothing is asserted on it.
+Out of scope: texture atlases, view-dependent textures, photographs."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--ply", required=True, metavar="ID=PATH", help="the one object of the bake")
+    ap.add_argument("--scene", default=None, help=".npz with pose [N,3,4] (NeRF units) and intr")
+    ap.add_argument("--sphere", type=int, default=None, metavar="N", help="N Fibonacci views instead of --scene")
+    ap.add_argument("--distance-mm", type=float, default=None, help="camera distance of the --sphere views")
+    ap.add_argument("--focal", type=float, default=None, help="focal length in pixels of the --sphere views")
+    ap.add_argument("--out", required=True, help="the coloured .ply")
+    ap.add_argument("--report", default=None, metavar="JSON")
+    ap.add_argument("--verify", action="store_true", help="re-render the baked mesh and print the PSNR against the NeRF views")
+    ap.add_argument("--H", type=int, default=480)
+    ap.add_argument("--W", type=int, default=640)
+    ap.add_argument("--samples", type=int, default=None, help="nerf.sample_intvs")
+    ap.add_argument("--source", choices=["box", "render", "none"], default=None, help="nerf.depth.range_source of the renders")
+    ap.add_argument("--precision", choices=["fp32", "f16x3", "f16"], default=None)
+    ap.add_argument("--light-index", type=int, default=0, help="row of latent_vars_light the views are lit with")
+    ap.add_argument("--chunk", type=int, default=8, help="views per SceneBounds / bake call")
+    ap.add_argument("--cos-min", type=float, default=None)
+    ap.add_argument("--cover-min", type=float, default=None)
+    ap.add_argument("--z-tol-mm", type=float, default=None)
+    ap.add_argument("--slope", type=float, default=None)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if (a.scene is None) == (a.sphere is None):
+        ap.error("either --scene or --sphere N --distance-mm D expected")
+    if a.sphere is not None and not (a.sphere >= 1 and a.distance_mm and a.distance_mm > 0):
+        ap.error("--sphere N needs N >= 1 and --distance-mm D > 0")
+    import torch
+    from texpose_amd import checkpoint as ck, ops
+    from texpose_amd import texture_bake as tb
+    from texpose_amd.graph import Graph
+    from texpose_amd.options import default_options
+    from texpose_amd.scene_bounds import SceneBounds
+    from texpose_amd.surfel import SurfelRenderer, load_ply
+    dev = torch.device(a.device)
+    opt = default_options(H=a.H, W=a.W, device=a.device)
+    if a.samples:
+        opt.nerf.sample_intvs = a.samples
+    opt.nerf.sample_stratified = False
+    if a.precision:
+        opt.arch.mlp_precision = a.precision
+    source = a.source or opt.nerf.depth.range_source
+    blob = torch.load(a.checkpoint, map_location=dev, weights_only=False)
+    graph = Graph(opt).to(dev)
+    graph.attach_latents(blob["graph"]["latent_vars_light.weight"].shape[0], opt)
+    ck.restore_checkpoint(graph, blob, resume=False)
+    oid, path = a.ply.split("=", 1)
+    verts, faces, _ = load_ply(path)
+    scale = float(opt.nerf.depth.scale)
+    if a.scene is not None:
+        scene = np.load(a.scene)
+        pose = torch.from_numpy(np.asarray(scene["pose"], dtype=np.float32).reshape(-1, 3, 4))
+        intr = torch.from_numpy(np.asarray(scene["intr"], dtype=np.float32))
+    else:
+        pose = tb.poses_to_nerf_units(torch.from_numpy(tb.sphere_view_poses(a.sphere, a.distance_mm)), scale).float()
+        f = a.focal or 1.5 * max(a.H, a.W)
+        intr = torch.tensor([[f, 0.0, a.W / 2.0], [0.0, f, a.H / 2.0], [0.0, 0.0, 1.0]])
+    N = pose.shape[0]
+    intr = (intr[None].expand(N, 3, 3) if intr.dim() == 2 else intr).contiguous().to(dev)
+    pose = pose.contiguous().to(dev)
+    bg = tuple(float(v) * scale for v in opt.nerf.depth.range)
+    bounds = SceneBounds({int(oid): (SurfelRenderer(verts, faces, None, a.H, a.W, a.device), verts.min(axis=0), verts.max(axis=0))},
+                         a.H, a.W, scale, bg)
+    thresholds = {k: v for k, v in dict(cos_min=a.cos_min, cover_min=a.cover_min, z_tol_mm=a.z_tol_mm, slope=a.slope).items() if v is not None}
+    baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds)
+    light = torch.tensor(a.light_index, device=dev)
+    kept = []                                                         # (rgb, mask) of every view, for --verify
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        for c in range(0, N, a.chunk):
+            p, k = pose[c:c + a.chunk], intr[c:c + a.chunk]
+            n = p.shape[0]
+            sb = bounds(p, k, source)
+            rgb = torch.empty(n, a.H, a.W, 3, device=dev)
+            weight = torch.empty(n, a.H, a.W, device=dev)
+            for i in range(n):
+                dr = (sb.depth_range[0][i:i + 1], sb.depth_range[1][i:i + 1])
+                ret = graph.render_by_slices(opt, p[i:i + 1], intr=k[i:i + 1], depth_range=dr, object_mask=sb.object_mask[i:i + 1],
+                                             sample_idx=light, mode="eval")
+                rgb[i] = ret.rgb_static.view(a.H, a.W, 3)
+                weight[i] = ret.opacity_static.view(a.H, a.W)
+            baker.add_views(rgb, tb.poses_to_mm(p, scale), k, zbuf=sb.zbuf[0], weight=weight)
+            if a.verify:
+                kept.append((rgb, sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)))
+    res = baker.result(fill=True)
+    torch.cuda.synchronize(dev)
+    seconds = time.perf_counter() - t0
+    ops.check_mlp_status(dev)
+    tb.write_ply(a.out, verts, faces, res.vcolor.cpu().numpy())
+    V = len(verts)
+    report = dict(vertices=V, faces=int(len(faces)), views=N, H=a.H, W=a.W, coverage=float((res.count > 0).sum()) / V,
+                  coloured=float(res.seen.sum()) / V, mean_views_per_vertex=float(res.count.double().mean()), filled=res.filled,
+                  unseen=res.unseen, thresholds=baker.thresholds, seconds_render_and_bake=seconds, mlp=graph.nerf.precision, out=a.out)
+    if a.verify:
+        se, px = 0.0, 0
+        with torch.no_grad():
+            for c, (rgb, mask) in zip(range(0, N, a.chunk), kept):
+                r = ops.mesh_raster(baker.verts, baker.faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
+                                    H=a.H, W=a.W, vcolor=res.vcolor, face_ids=False, normals=False)
+                m = mask & (r["zbuf"] > 0)
+                se += float((((r["rgb"] - rgb.clamp(0, 1)) ** 2).sum(-1) * m).double().sum())
+                px += int(m.sum())
+        mse = se / max(1, 3 * px)
+        report["verify"] = dict(pixels=px, mse=mse, psnr_db=(float("inf") if mse == 0 else -10.0 * float(np.log10(mse))) if px else None)
+        print("bake_texture: re-rendered mesh against the NeRF views inside the mask: PSNR %s dB over %d pixels"
+              % ("%.2f" % report["verify"]["psnr_db"] if px else "n/a", px))
+    if a.report:
+        with open(a.report, "w") as fh:
+            json.dump(report, fh, indent=1)
+    print("bake_texture: %d views %dx%d -> %s: %d vertices, coverage %.4f, %.2f views per vertex, %d filled, %d unseen, %.2f s"
+          % (N, a.H, a.W, a.out, V, report["coverage"], report["mean_views_per_vertex"], res.filled, res.unseen, seconds))
+
+
+if __name__ == "__main__":
+    main()
