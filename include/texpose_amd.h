@@ -1115,6 +1115,122 @@ int tp_texture_bake_slices(int V, int B);                 /* S of the rule above
 size_t tp_texture_bake_workspace_bytes(int V, int B);
 int tp_texture_bake(const tp_texture_bake_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K28  batched PnP-RANSAC: poses from dense 2D-3D correspondence (NOCS) maps (texpose_amd/pnp.py; restated in tests/pnp_ref.py; the
+ *      project's own step, no reference code).  Common inputs: xy [B,N,2] pixel coordinates (pixel (row r,
+ *      column j) has its centre at (j + 0.5, r + 0.5)), xyz [B,N,3] model points in mm, count [B] (image b uses the entries
+ *      0 .. n-1 with n = count[b] CLAMPED into [0, N]), intr [B,3,3] (fx = K_00, fy = K_11, cx = K_02, cy = K_12; no skew), poses
+ *      [R|t] model -> camera in mm, row-major 12 floats.  Every call launches on the caller's stream, allocates nothing and never
+ *      synchronises; all of them are safe to capture.  No input value (NaN, Inf, huge poses, a count outside [0, N]) causes an access
+ *      out of bounds.  Non-positive B, N, T or stride, T > TP_PNP_MAX_HYP, a tau_px that is not finite and positive, iters outside
+ *      0 .. TP_PNP_MAX_ITERS, H * W >= 2^31 and null pointers are refused (-1, tp_last_error) before anything is launched.
+ *
+ *      tp_corr_from_nocs: the strided pixels k = 0 .. N-1, N = ceil(H / stride) * ceil(W / stride), (r, j) = (k / Ws * stride,
+ *      k % Ws * stride) with Ws = ceil(W / stride), are visited in ascending k (= ascending r * W + j).  A pixel is kept iff its
+ *      mask is non-zero (uint8, or float with mask_is_float; a NaN is non-zero) and its three NOCS values q are finite; the kept
+ *      ones are written densely in that order as xy = (j + 0.5, r + 0.5), xyz_c = (2 q_c - 1) * scale_c + centre_c in fp32 as
+ *      written (no contraction), and count[b] is their number.  Entries from count[b] on are not written.  Ranks come from wave
+ *      ballots, per-tile counts (256 pixels) and their prefix sums: no atomic cursor, the order is a function of the inputs alone.
+ *      Two launches.
+ *
+ *      tp_pnp_hypotheses: hypothesis h of image b draws w = philox4x32_10(counter (b, h, 0x706E7034 'pnp4', 0), key (seed low,
+ *      seed high)) and from it four distinct indices: i0 = mulhi(w0, n), i1 = mulhi(w1, n-1), i2 = mulhi(w2, n-2), i3 = mulhi(w3,
+ *      n-3), each of i1, i2, i3 moved past the earlier ones (visited in ascending order: i += 1 for every earlier index <= i);
+ *      sample_idx = (i0, i1, i2, i3), or four -1 where n < 4.  In fp64: the bearings f_k = normalise((u - cx) / fx, (v - cy) / fy,
+ *      1) of the first three, the P3P quartic in v = s3 / s1 (Grunert's elimination: s2 = u s1, 2 u (cos g - v cos a) =
+ *      (k-1) v^2 - 2 k cos b v + 1 + k with k = (a^2 - c^2) / b^2), its real roots in closed form (Ferrari) with two Newton steps
+ *      each, per root with v > 0, u > 0 the depths, polished by two Newton steps on the three distance equations themselves (the
+ *      quartic's coefficients cancel where two roots are close), and [R|t] as the rigid motion between the two triangles from their
+ *      orthonormal frames.  The kept solution has the smallest squared reprojection error on the fourth point (infinite where its depth is not
+ *      positive; ties go to the smaller v).  hyp_valid = 0, and hyp is 12 zeros, when n < 4, a sampled value is not finite, the
+ *      three image points are collinear (twice the triangle's area <= 1e-9 x the sum of two squared edges), there is no real root,
+ *      no root has three positive depths, or the pose is not finite.  One thread per hypothesis.
+ *
+ *      tp_pnp_score: inliers[b,h] = the number of entries i < n with, in fp32 as written (no contraction),
+ *        x = ((R_k0 X + R_k1 Y) + R_k2 Z) + t_k,  x_z > 0 and finite,
+ *        du = ((fx * x_x) / x_z + cx) - u,  dv = ((fy * x_y) / x_z + cy) - v,  du * du + dv * dv <= tau_px * tau_px
+ *      (a NaN anywhere fails the comparison).  valid (or NULL: all valid): a hypothesis with valid = 0 counts 0.  A workgroup holds
+ *      1024 points of one image in registers and walks all T poses (the pose index is uniform: the 12 floats come through scalar
+ *      loads, the valid bytes of 64 poses as one ballot); per pose a wave ballot and popcount, LDS integer sums across the waves,
+ *      one integer atomic add per (workgroup, pose) to inliers, which the call clears itself: integer sums do not depend on the
+ *      order of arrival.  With inlier_mask [B,N] given, a further launch writes inlier_mask[b,i] = 1 where entry i is an inlier of
+ *      pose sel[b], 0 elsewhere (i >= n, an invalid pose, a sel outside [0, T) and a NULL sel included); it is a launch of its own
+ *      because a byte store inside the pose loop would take the pose loads off the scalar unit.  Two launches, three with the mask.
+ *
+ *      tp_pnp_refine: the winner of image b is the valid hypothesis with the largest hyp_inliers, the lowest h among equals.  Then
+ *      iters Gauss-Newton steps in fp64 throughout (the fp32 inputs widened; the inlier test as above but in fp64).  Each step is a
+ *      reduce launch (ceil(N / 1024) workgroups per image, a function of N alone: the inliers of the current pose at tau, for them
+ *      the 21 + 6 entries of J^T J and J^T r, sum |r|^2 and the count, for x' = x + w x x + v in the camera frame, parameters (w, v);
+ *      butterfly sums inside a wave, the four waves in ascending order) and a solve launch per image (the partials in ascending
+ *      order; keep-best: the pose just evaluated replaces the stored best iff its count is higher, or equal at a lower sum |r|^2;
+ *      then J^T J is factored by Cholesky: a pivot that is not finite or <= 1e-10 x its diagonal entry means NOT POSITIVE DEFINITE:
+ *      status 3, the best pose so far is kept and nothing more changes; otherwise (J^T J + 1e-3 diag(J^T J)) d = -J^T r is solved
+ *      by Cholesky, R <- exp(w) R, t <- exp(w) t + v with Rodrigues' formula, and R is re-orthonormalised (Gram-Schmidt on its first
+ *      two columns, the third their cross product)).  One more reduce and compare evaluates the last iterate.  pose [B,3,4] = the
+ *      best pose rounded to fp32, inliers its count, rms = sqrt(sum |r|^2 / count) in px (NaN at count 0), status 0 = ok, 1 = n < 4,
+ *      2 = no valid hypothesis, 3 as above; with status 1 or 2 pose and rms are NaN and inliers is 0.  The returned count is never
+ *      below the winner's own count under the same fp64 test.  3 + 2 iters launches.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_PNP_MAX_HYP 4096
+#define TP_PNP_MAX_ITERS 32
+typedef struct tp_corr_from_nocs_args {
+  const float* nocs;         /* [B,H,W,3] */
+  const void* mask;          /* [B,H,W] uint8, or float where mask_is_float is non-zero */
+  int mask_is_float;
+  float centre[3], scale[3]; /* surfel.nocs_normalisation: a vertex v maps to ((v - centre) / scale + 1) / 2 */
+  int B, H, W, stride;
+  float* xy;                 /* [B,N,2] out, N = ceil(H / stride) * ceil(W / stride) */
+  float* xyz;                /* [B,N,3] out */
+  int32_t* count;            /* [B] out */
+  void* workspace;           /* tp_pnp_workspace_bytes(B, N, 1) bytes; needs no clearing */
+} tp_corr_from_nocs_args;
+typedef struct tp_pnp_hypotheses_args {
+  const float* xy;           /* [B,N,2] */
+  const float* xyz;          /* [B,N,3] */
+  const int32_t* count;      /* [B] */
+  const float* intr;         /* [B,3,3] */
+  int B, N, T;
+  uint64_t seed;
+  int32_t* sample_idx;       /* [B,T,4] out */
+  float* hyp;                /* [B,T,12] out */
+  uint8_t* hyp_valid;        /* [B,T] out */
+} tp_pnp_hypotheses_args;
+typedef struct tp_pnp_score_args {
+  const float* xy;
+  const float* xyz;
+  const int32_t* count;
+  const float* intr;
+  const float* poses;        /* [B,T,12] */
+  const uint8_t* valid;      /* [B,T] or NULL */
+  int B, N, T;
+  float tau_px;
+  int32_t* inliers;          /* [B,T] out; the caller clears nothing */
+  const int32_t* sel;        /* [B] or NULL: the pose whose inliers inlier_mask marks */
+  uint8_t* inlier_mask;      /* [B,N] out, or NULL */
+} tp_pnp_score_args;
+typedef struct tp_pnp_refine_args {
+  const float* xy;
+  const float* xyz;
+  const int32_t* count;
+  const float* intr;
+  const float* hyp;          /* [B,T,12] */
+  const uint8_t* hyp_valid;  /* [B,T] or NULL */
+  const int32_t* hyp_inliers;/* [B,T] */
+  int B, N, T;
+  float tau_px;
+  int iters;                 /* 0 .. TP_PNP_MAX_ITERS */
+  float* pose;               /* [B,3,4] out */
+  int32_t* inliers;          /* [B] out */
+  float* rms;                /* [B] out */
+  int32_t* status;           /* [B] out */
+  void* workspace;           /* tp_pnp_workspace_bytes(B, N, T) bytes, 16-byte aligned; needs no clearing */
+} tp_pnp_refine_args;
+size_t tp_pnp_workspace_bytes(int B, int N, int T);       /* 0 for non-positive sizes */
+int tp_corr_from_nocs(const tp_corr_from_nocs_args* args, tp_stream_t stream);
+int tp_pnp_hypotheses(const tp_pnp_hypotheses_args* args, tp_stream_t stream);
+int tp_pnp_score(const tp_pnp_score_args* args, tp_stream_t stream);
+int tp_pnp_refine(const tp_pnp_refine_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1164,6 +1164,193 @@ def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb
     return {"acc": acc, "count": count}
 
 
+# ------------------------------------------------------------------------------------------ K28
+PNP_MAX_HYP, PNP_MAX_ITERS = _lib.PNP_MAX_HYP, _lib.PNP_MAX_ITERS
+
+
+def pnp_workspace(B: int, N: int, T: int, device) -> Tensor:
+    """A workspace for corr_from_nocs / pnp_refine / pnp_ransac at B images, N entries and T hypotheses (tp_pnp_workspace_bytes);
+    needs no clearing."""
+    return torch.empty(max(2, (int(_lib.load().tp_pnp_workspace_bytes(B, N, T)) + 7) // 8), device=device, dtype=torch.float64)
+
+
+def _pnp_workspace(op: str, workspace: Optional[Tensor], B: int, N: int, T: int, dev) -> Tensor:
+    need = int(_lib.load().tp_pnp_workspace_bytes(B, N, T))
+    if workspace is None:
+        return pnp_workspace(B, N, T, dev)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16:
+        raise ValueError("%s: workspace must be a contiguous, 16-byte aligned GPU tensor of >= %d bytes" % (op, need))
+    return workspace
+
+
+def _pnp_outputs(op: str, out: Optional[Dict[str, Tensor]], spec, dev) -> Dict[str, Tensor]:
+    return {k: torch.empty(shape, device=dev, dtype=dtype) if out is None or k not in out else _want_gpu(op, out[k], f"out[{k!r}]", dtype, shape)
+            for k, (dtype, shape) in spec.items()}
+
+
+def _pnp_common(op: str, xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor):
+    xy, xyz = _f32(xy.detach(), "xy"), _f32(xyz.detach(), "xyz")
+    if xy.dim() != 3 or xy.shape[2] != 2 or xy.shape[0] == 0 or xy.shape[1] == 0 or tuple(xyz.shape) != tuple(xy.shape[:2]) + (3,):
+        raise ValueError("%s: xy [B,N,2] and xyz [B,N,3] expected, got %s and %s" % (op, tuple(xy.shape), tuple(xyz.shape)))
+    B, N = xy.shape[:2]
+    count = _lengths(op, count, "count", B, xy)
+    if count is None:
+        raise ValueError(f"{op}: count must be an int32 GPU tensor of shape ({B},)")
+    intr = _f32(intr.detach(), "intr")
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3).contiguous()
+    if tuple(intr.shape) != (B, 3, 3):
+        raise ValueError("%s: intr [B=%d,3,3] or [3,3] expected, got %s" % (op, B, tuple(intr.shape)))
+    return xy, xyz, count, intr, B, N
+
+
+@_on_tensor_device
+def corr_from_nocs(nocs: Tensor, mask: Tensor, centre, scale, *, stride: int = 1, workspace: Optional[Tensor] = None,
+                   out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """A NOCS map as a dense 2D-3D correspondence list (tp_corr_from_nocs; the rules are in the header): nocs [B,H,W,3], mask [B,H,W]
+    (uint8, bool or float; non-zero: use the pixel), ``centre`` / ``scale`` [3] as surfel.nocs_normalisation returns them -> 'xy'
+    [B,N,2] (pixel centres), 'xyz' [B,N,3] (mm) and 'count' [B] int32 with N = ceil(H / stride) * ceil(W / stride), the kept pixels in
+    scan order; entries from count[b] on are not written.  ``workspace``: pnp_workspace(B, N, 1).  Two launches, no atomics, safe
+    under torch.cuda.graph."""
+    lib = _lib.load()
+    nocs = _f32(nocs.detach(), "nocs")
+    if nocs.dim() != 4 or nocs.shape[3] != 3 or nocs.numel() == 0:
+        raise ValueError("corr_from_nocs: nocs [B,H,W,3] expected, got %s" % (tuple(nocs.shape),))
+    B, H, W = nocs.shape[:3]
+    if not torch.is_tensor(mask) or not mask.is_cuda or tuple(mask.shape) != (B, H, W):
+        raise ValueError("corr_from_nocs: mask must be a GPU tensor of shape %s" % ((B, H, W),))
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    elif mask.dtype not in (torch.uint8, torch.float32):
+        mask = mask.float()
+    mask = mask.contiguous()
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("corr_from_nocs: stride >= 1 expected, got %d" % stride)
+    N = -(-H // stride) * -(-W // stride)
+    dev = nocs.device
+    res = _pnp_outputs("corr_from_nocs", out, {"xy": (torch.float32, (B, N, 2)), "xyz": (torch.float32, (B, N, 3)), "count": (torch.int32, (B,))}, dev)
+    workspace = _pnp_workspace("corr_from_nocs", workspace, B, N, 1, dev)
+    a = _lib.CorrFromNocsArgs()
+    a.nocs, a.mask, a.mask_is_float = nocs.data_ptr(), mask.data_ptr(), int(mask.dtype == torch.float32)
+    a.centre = (C.c_float * 3)(*[float(x) for x in centre])
+    a.scale = (C.c_float * 3)(*[float(x) for x in scale])
+    a.B, a.H, a.W, a.stride = B, H, W, stride
+    a.xy, a.xyz, a.count, a.workspace = res["xy"].data_ptr(), res["xyz"].data_ptr(), res["count"].data_ptr(), workspace.data_ptr()
+    check(lib.tp_corr_from_nocs(C.byref(a), _stream()), "tp_corr_from_nocs")
+    return res
+
+
+@_on_tensor_device
+def pnp_hypotheses(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, *, T: int = 256, seed: int = 0,
+                   out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """T minimal-sample pose hypotheses per image (tp_pnp_hypotheses; the rules are in the header): xy [B,N,2], xyz [B,N,3], count [B]
+    int32, intr [B,3,3] or one [3,3] -> 'sample_idx' [B,T,4] int32 (four distinct Philox draws, a function of seed, b, h and the
+    count alone), 'hyp' [B,T,12] ([R|t] row-major, P3P in fp64) and 'hyp_valid' [B,T] uint8.  One launch, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    xy, xyz, count, intr, B, N = _pnp_common("pnp_hypotheses", xy, xyz, count, intr)
+    T = int(T)
+    dev = xy.device
+    res = _pnp_outputs("pnp_hypotheses", out, {"sample_idx": (torch.int32, (B, max(T, 0), 4)), "hyp": (torch.float32, (B, max(T, 0), 12)),
+                                               "hyp_valid": (torch.uint8, (B, max(T, 0)))}, dev)
+    a = _lib.PnpHypothesesArgs()
+    a.xy, a.xyz, a.count, a.intr = xy.data_ptr(), xyz.data_ptr(), count.data_ptr(), intr.data_ptr()
+    a.B, a.N, a.T, a.seed = B, N, T, int(seed) & (2 ** 64 - 1)
+    a.sample_idx, a.hyp, a.hyp_valid = res["sample_idx"].data_ptr(), res["hyp"].data_ptr(), res["hyp_valid"].data_ptr()
+    check(lib.tp_pnp_hypotheses(C.byref(a), _stream()), "tp_pnp_hypotheses")     # (T outside 1 .. 4096: the library's error)
+    return res
+
+
+@_on_tensor_device
+def pnp_score(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, poses: Tensor, *, tau_px: float = 2.0, valid: Optional[Tensor] = None,
+              sel: Optional[Tensor] = None, inliers: Optional[Tensor] = None, inlier_mask: Optional[Tensor] = None):
+    """Inlier counts of T poses per image (tp_pnp_score; the rules are in the header): poses [B,T,12] or [B,T,3,4] -> inliers [B,T]
+    int32 (the entries reprojected within tau_px, in fp32).  ``valid`` [B,T] uint8: poses with 0 count 0.  ``sel`` [B] int32: also
+    return inlier_mask [B,N] uint8 of pose sel[b] (then the result is the pair).  ``inliers`` / ``inlier_mask``: the tensors to
+    write into (neither needs clearing).  Integer atomics only: bit-identical from run to run.  Two launches, three with the mask;
+    safe under torch.cuda.graph."""
+    lib = _lib.load()
+    xy, xyz, count, intr, B, N = _pnp_common("pnp_score", xy, xyz, count, intr)
+    poses = _f32(poses.detach(), "poses")
+    if poses.dim() == 4 and tuple(poses.shape[2:]) == (3, 4):
+        poses = poses.reshape(B, -1, 12)
+    if poses.dim() != 3 or poses.shape[0] != B or poses.shape[2] != 12:
+        raise ValueError("pnp_score: poses [B=%d,T,12] or [B,T,3,4] expected, got %s" % (B, tuple(poses.shape)))
+    T = poses.shape[1]
+    dev = xy.device
+    if valid is not None:
+        valid = _want_gpu("pnp_score", valid, "valid", torch.uint8, (B, T))
+    sel = _lengths("pnp_score", sel, "sel", B, xy)
+    inliers = torch.empty(B, T, device=dev, dtype=torch.int32) if inliers is None else _want_gpu("pnp_score", inliers, "inliers", torch.int32, (B, T))
+    if sel is not None:
+        inlier_mask = torch.empty(B, N, device=dev, dtype=torch.uint8) if inlier_mask is None else _want_gpu("pnp_score", inlier_mask, "inlier_mask", torch.uint8, (B, N))
+    elif inlier_mask is not None:
+        raise ValueError("pnp_score: inlier_mask needs sel")
+    a = _lib.PnpScoreArgs()
+    a.xy, a.xyz, a.count, a.intr, a.poses, a.valid = xy.data_ptr(), xyz.data_ptr(), count.data_ptr(), intr.data_ptr(), poses.data_ptr(), _ptr(valid)
+    a.B, a.N, a.T, a.tau_px = B, N, T, float(tau_px)
+    a.inliers, a.sel, a.inlier_mask = inliers.data_ptr(), _ptr(sel), _ptr(inlier_mask)
+    check(lib.tp_pnp_score(C.byref(a), _stream()), "tp_pnp_score")               # (T, tau_px out of range: the library's error)
+    return inliers if sel is None else (inliers, inlier_mask)
+
+
+@_on_tensor_device
+def pnp_refine(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, hyp: Tensor, hyp_inliers: Optional[Tensor] = None,
+               hyp_valid: Optional[Tensor] = None, *, tau_px: float = 2.0, iters: int = 5, workspace: Optional[Tensor] = None,
+               out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """Pick each image's winner among hyp [B,T,12] by hyp_inliers [B,T] int32 (ties: the lowest h; hyp_valid [B,T] uint8 = 0 is never
+    picked) and refine it by ``iters`` keep-best Gauss-Newton steps in fp64 on its inliers at tau_px (tp_pnp_refine; the rules are in
+    the header).  One start pose per image: hyp [B,3,4] (or [B,12]) alone.  -> 'pose' [B,3,4], 'inliers' [B] int32, 'rms' [B] (px),
+    'status' [B] int32 (0 ok, 1 fewer than 4 entries, 2 no valid hypothesis, 3 a system was not positive definite: the best pose so
+    far).  ``workspace``: pnp_workspace(B, N, T).  3 + 2 iters launches, no atomics, safe under torch.cuda.graph."""
+    lib = _lib.load()
+    xy, xyz, count, intr, B, N = _pnp_common("pnp_refine", xy, xyz, count, intr)
+    hyp = _f32(hyp.detach(), "hyp")
+    if hyp.dim() == 4 and tuple(hyp.shape[2:]) == (3, 4):
+        hyp = hyp.reshape(B, -1, 12)
+    elif tuple(hyp.shape) in ((B, 3, 4), (B, 12)) and hyp_inliers is None:
+        hyp = hyp.reshape(B, 1, 12)
+    if hyp.dim() != 3 or hyp.shape[0] != B or hyp.shape[2] != 12:
+        raise ValueError("pnp_refine: hyp [B=%d,T,12], or one start pose [B,3,4] per image, expected, got %s" % (B, tuple(hyp.shape)))
+    T = hyp.shape[1]
+    dev = xy.device
+    if hyp_inliers is None:
+        if T != 1:
+            raise ValueError("pnp_refine: hyp_inliers [B,T] is needed to pick among T = %d hypotheses" % T)
+        hyp_inliers = torch.zeros(B, 1, device=dev, dtype=torch.int32)
+    hyp_inliers = _want_gpu("pnp_refine", hyp_inliers, "hyp_inliers", torch.int32, (B, T))
+    if hyp_valid is not None:
+        hyp_valid = _want_gpu("pnp_refine", hyp_valid, "hyp_valid", torch.uint8, (B, T))
+    res = _pnp_outputs("pnp_refine", out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+                                           "status": (torch.int32, (B,))}, dev)
+    workspace = _pnp_workspace("pnp_refine", workspace, B, N, T, dev)
+    a = _lib.PnpRefineArgs()
+    a.xy, a.xyz, a.count, a.intr = xy.data_ptr(), xyz.data_ptr(), count.data_ptr(), intr.data_ptr()
+    a.hyp, a.hyp_valid, a.hyp_inliers = hyp.data_ptr(), _ptr(hyp_valid), hyp_inliers.data_ptr()
+    a.B, a.N, a.T, a.tau_px, a.iters = B, N, T, float(tau_px), int(iters)
+    a.pose, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
+                                                       res["status"].data_ptr(), workspace.data_ptr())
+    check(lib.tp_pnp_refine(C.byref(a), _stream()), "tp_pnp_refine")             # (tau_px, iters out of range: the library's error)
+    return res
+
+
+PNP_RANSAC_KEYS = ("pose", "inliers", "rms", "status", "sample_idx", "hyp", "hyp_valid", "hyp_inliers")
+
+
+@_on_tensor_device
+def pnp_ransac(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, *, T: int = 256, tau_px: float = 2.0, iters: int = 5, seed: int = 0,
+               workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """PnP with RANSAC for B images at once: pnp_hypotheses, pnp_score and pnp_refine in a row (the rules are in the header).
+    -> pnp_refine's 'pose', 'inliers', 'rms', 'status' and the intermediate 'sample_idx', 'hyp', 'hyp_valid', 'hyp_inliers'.
+    ``out``: any of these tensors to write into; ``workspace``: pnp_workspace(B, N, T).  With both given nothing is allocated.
+    6 + 2 iters launches, bit-identical from run to run, safe under torch.cuda.graph."""
+    hy = pnp_hypotheses(xy, xyz, count, intr, T=T, seed=seed, out=out)
+    inl = pnp_score(xy, xyz, count, intr, hy["hyp"], tau_px=tau_px, valid=hy["hyp_valid"], inliers=None if out is None else out.get("hyp_inliers"))
+    res = pnp_refine(xy, xyz, count, intr, hy["hyp"], inl, hy["hyp_valid"], tau_px=tau_px, iters=iters, workspace=workspace, out=out)
+    res.update(hy, hyp_inliers=inl)
+    return res
+
+
 # ------------------------------------------------------------------------------------------ K9
 @_on_tensor_device
 def inorm_lrelu_fwd(x: Tensor, eps: float, slope: float, y_out: Optional[Tensor] = None):
