@@ -1,7 +1,6 @@
 """GPU: the hard mesh rasteriser behind the surfel maps (tp_mesh_raster, texpose_amd.surfel) against the fp64 brute force of
 tests/mesh_raster_ref.py on every pixel, against golden G21 (the reference's normals), against the NeRF's own rays, and end to
 end through tools/surfel_maps.py and the decoding rules of the reference's data layer."""
-import math
 import os
 import struct
 import subprocess
@@ -12,36 +11,13 @@ import pytest
 import torch
 
 import mesh_raster_ref as REF
+from texture_bake_ref import torus, uv_sphere  # noqa: F401  (other test modules import them from here)
 from oracle.texpose_oracle import LINEMOD_K, rotation_from_axis_angle
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
-
-
-def uv_sphere(n_lat, n_lon, radius=50.0, ripple=0.0):
-    th = np.linspace(0, math.pi, n_lat + 1)
-    ph = np.linspace(0, 2 * math.pi, n_lon, endpoint=False)
-    T, P = np.meshgrid(th, ph, indexing="ij")
-    r = radius * (1 + ripple * np.sin(5 * T) * np.cos(3 * P))
-    v = np.stack([r * np.sin(T) * np.cos(P), r * np.sin(T) * np.sin(P), r * np.cos(T)], -1).reshape(-1, 3)
-    idx = np.arange((n_lat + 1) * n_lon).reshape(n_lat + 1, n_lon)
-    a, b, c, d = idx[:-1], np.roll(idx[:-1], -1, axis=1), idx[1:], np.roll(idx[1:], -1, axis=1)
-    f = np.concatenate([np.stack([a, c, d], -1)[:-1], np.stack([a, d, b], -1)[1:]]).reshape(-1, 3)
-    return v.astype(np.float32), f.astype(np.int32)
-
-
-def torus(n_major, n_minor, R=45.0, r=16.0):
-    u = np.linspace(0, 2 * math.pi, n_major, endpoint=False)
-    w = np.linspace(0, 2 * math.pi, n_minor, endpoint=False)
-    U, Wm = np.meshgrid(u, w, indexing="ij")
-    v = np.stack([(R + r * np.cos(Wm)) * np.cos(U), (R + r * np.cos(Wm)) * np.sin(U), r * np.sin(Wm)], -1).reshape(-1, 3)
-    idx = np.arange(n_major * n_minor).reshape(n_major, n_minor)
-    a, b = idx, np.roll(idx, -1, axis=0)
-    c, d = np.roll(idx, -1, axis=1), np.roll(np.roll(idx, -1, axis=0), -1, axis=1)
-    f = np.concatenate([np.stack([a, b, d], -1), np.stack([a, d, c], -1)]).reshape(-1, 3)
-    return v.astype(np.float32), f.astype(np.int32)
 
 
 def soup(n, rs, extent=60.0):

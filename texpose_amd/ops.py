@@ -93,6 +93,69 @@ def _ptr(t: Optional[Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _float3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+# The argument rules of the scene / pose entry points (K19 on).  Inputs go through _f32 (converted if need be) and a shape helper;
+# tensors that are written into, or that the docstring says are "taken as they are", go through _want_gpu: nothing is converted.
+def _want_gpu(op: str, t, name: str, dtype, shape):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError(f"{op}: {name} must be a contiguous {dtype} GPU tensor" + ("" if shape is None else f" of shape {shape}"))
+    return t
+
+
+def _outputs(op: str, out: Optional[Dict[str, Tensor]], spec, dev, partial: bool = False) -> Dict[str, Tensor]:
+    """``spec``: key -> (dtype, shape).  Every key's ``out[key]``, taken as it is, or a fresh tensor on ``dev`` where ``out`` is None
+    or, with ``partial``, lacks the key (without it a missing key is the KeyError)."""
+    return {k: torch.empty(shape, device=dev, dtype=dtype) if out is None or (partial and k not in out)
+            else _want_gpu(op, out[k], f"out[{k!r}]", dtype, shape) for k, (dtype, shape) in spec.items()}
+
+
+def _workspace_arg(op: str, workspace: Optional[Tensor], need_bytes: int, dev, align: int = 1) -> Tensor:
+    """The caller's workspace of at least ``need_bytes`` bytes at an address that is a multiple of ``align``, else a fresh one."""
+    if workspace is None:
+        return torch.empty(max(2, (need_bytes + 7) // 8), device=dev, dtype=torch.float64)
+    if (not torch.is_tensor(workspace) or not workspace.is_cuda or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < need_bytes or workspace.data_ptr() % align):
+        raise ValueError("%s: workspace must be a contiguous%s GPU tensor of >= %d bytes" % (op, ", %d-byte aligned" % align if align > 1 else "", need_bytes))
+    return workspace
+
+
+def _lengths(op: str, t: Optional[Tensor], name: str, n: int, like: Tensor, required: bool = False) -> Optional[Tensor]:
+    if t is None and not required:
+        return None
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != like.device:
+        raise ValueError(f"{op}: {name} must be an int32 GPU tensor of shape ({n},)")
+    return t.contiguous()
+
+
+def _intr_per_view(op: str, intr: Tensor, B: int, allow_single: bool = True) -> Tensor:
+    """``intr`` as float32 [B,3,3]; with ``allow_single`` one [3,3] stands for every view."""
+    intr = _f32(intr.detach(), "intr")
+    if allow_single and intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3).contiguous()
+    if tuple(intr.shape) != (B, 3, 3):
+        raise ValueError("%s: intr [B=%d,3,3]%s expected, got %s" % (op, B, " or [3,3]" if allow_single else "", tuple(intr.shape)))
+    return intr
+
+
+def _poses(op: str, t: Tensor, name: str, B: Optional[int] = None) -> Tensor:
+    """``t`` as float32 [B,3,4]: of the given ``B``, or of any B >= 1."""
+    t = _f32(t.detach(), name)
+    if t.dim() != 3 or tuple(t.shape[1:]) != (3, 4) or (t.shape[0] == 0 if B is None else t.shape[0] != B):
+        raise ValueError("%s: %s [%s,3,4] expected, got %s" % (op, name, "B" if B is None else "B=%d" % B, tuple(t.shape)))
+    return t
+
+
+def _points(op: str, t: Tensor, name: str, n: Optional[int] = None) -> Tensor:
+    """``t`` as float32 [n,3]: of the given ``n``, or of any n >= 1."""
+    t = _f32(t.detach(), name)
+    if t.dim() != 2 or t.shape[1] != 3 or (t.shape[0] == 0 if n is None else t.shape[0] != n):
+        raise ValueError("%s: %s [%s,3] expected, got %s" % (op, name, "n" if n is None else "n=%d" % n, tuple(t.shape)))
+    return t
+
+
 # ------------------------------------------------------------------------------------------ K1
 @_on_tensor_device
 def raygen(intr: Tensor, pose: Tensor, *, H: int, W: int, n_samples: int = 0, coords: Optional[Tensor] = None,
@@ -128,8 +191,7 @@ def raygen(intr: Tensor, pose: Tensor, *, H: int, W: int, n_samples: int = 0, co
     near = far = depth = None
     if aabb is not None:
         a.bounds_mode = BOUNDS_AABB
-        a.aabb_min = (C.c_float * 3)(*[float(v) for v in aabb[0]])
-        a.aabb_max = (C.c_float * 3)(*[float(v) for v in aabb[1]])
+        a.aabb_min, a.aabb_max = _float3(aabb[0]), _float3(aabb[1])
         a.bg_near, a.bg_far = float(bg_range[0]), float(bg_range[1])
         if valid_rect is not None:                      # [B,4] (x0,y0,x1,y1): pixels outside get the fallback range
             valid_rect = _f32(valid_rect, "valid_rect")
@@ -195,8 +257,7 @@ def aabb_intersect(aabb_min, aabb_max, o: Tensor, d: Tensor):
     tn = torch.empty(o.shape[:-1], device=o.device)
     tf = torch.empty_like(tn)
     ok = torch.empty(o.shape[:-1], device=o.device, dtype=torch.uint8)
-    lo = (C.c_float * 3)(*[float(v) for v in torch.as_tensor(aabb_min).flatten().tolist()])
-    hi = (C.c_float * 3)(*[float(v) for v in torch.as_tensor(aabb_max).flatten().tolist()])
+    lo, hi = _float3(torch.as_tensor(aabb_min).flatten().tolist()), _float3(torch.as_tensor(aabb_max).flatten().tolist())
     check(lib.tp_aabb(lo, hi, o.data_ptr(), d.data_ptr(), n, tn.data_ptr(), tf.data_ptr(), ok.data_ptr(), _stream()),
           "tp_aabb")
     return tn, tf, ok.bool()
@@ -981,14 +1042,6 @@ def lab_loss_bwd(rgb: Tensor, real: Tensor, mask: Optional[Tensor], sums: Tensor
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
 
 
-def _lengths(op: str, t: Optional[Tensor], name: str, n: int, like: Tensor) -> Optional[Tensor]:
-    if t is None:
-        return None
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != like.device:
-        raise ValueError(f"{op}: {name} must be an int32 GPU tensor of shape ({n},)")
-    return t.contiguous()
-
-
 @_on_tensor_device
 def nn1(x: Tensor, y: Tensor, *, x_len: Optional[Tensor] = None, y_len: Optional[Tensor] = None, A: Optional[Tensor] = None,
         mode: str = "nearest", target_slices: int = 0):
@@ -1011,9 +1064,7 @@ def nn1(x: Tensor, y: Tensor, *, x_len: Optional[Tensor] = None, y_len: Optional
     x_len, y_len = _lengths("nn1", x_len, "x_len", B, x), _lengths("nn1", y_len, "y_len", Bt, x)
     a = _lib.Nn1Args()
     if A is not None:
-        A = _f32(A.detach(), "A")
-        if tuple(A.shape) != (B, 3, 4):
-            raise ValueError("nn1: A [B=%d,3,4] expected, got %s" % (B, tuple(A.shape)))
+        A = _poses("nn1", A, "A", B)
         a.A = A.data_ptr()
     d2 = torch.empty(B, P1, device=x.device)
     idx = torch.empty(B, P1, device=x.device, dtype=torch.int32)
@@ -1034,12 +1085,9 @@ def pose_errors(pts: Tensor, pose_est: Tensor, pose_gt: Tensor, sym: Optional[Te
     and 's_mssd' [B] int32 (the winning symmetry, the lowest on ties) and, with ``intr``, 'mspd', 'proj' and 's_mspd' (pixels; NaN /
     -1 for a b with a point at Z <= 0 under either pose).  Not differentiable.  Two launches, safe under torch.cuda.graph."""
     lib = _lib.load()
-    pts, pose_est, pose_gt = _f32(pts.detach(), "pts"), _f32(pose_est.detach(), "pose_est"), _f32(pose_gt.detach(), "pose_gt")
-    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
-        raise ValueError("pose_errors: pts [M,3] expected, got %s" % (tuple(pts.shape),))
-    if pose_est.dim() != 3 or tuple(pose_est.shape[1:]) != (3, 4) or pose_est.shape[0] == 0 or pose_gt.shape != pose_est.shape:
-        raise ValueError("pose_errors: pose_est and pose_gt [B,3,4] expected, got %s and %s" % (tuple(pose_est.shape), tuple(pose_gt.shape)))
+    pts, pose_est = _points("pose_errors", pts, "pts"), _poses("pose_errors", pose_est, "pose_est")
     M, B = pts.shape[0], pose_est.shape[0]
+    pose_gt = _poses("pose_errors", pose_gt, "pose_gt", B)
     if sym is None:
         sym = torch.eye(3, 4, device=pts.device)[None]
     sym = _f32(sym.detach(), "sym")
@@ -1048,9 +1096,7 @@ def pose_errors(pts: Tensor, pose_est: Tensor, pose_gt: Tensor, sym: Optional[Te
     S = sym.shape[0]
     a = _lib.PoseErrorsArgs()
     if intr is not None:
-        intr = _f32(intr.detach(), "intr")
-        if tuple(intr.shape) != (B, 3, 3):
-            raise ValueError("pose_errors: intr [B=%d,3,3] expected, got %s" % (B, tuple(intr.shape)))
+        intr = _intr_per_view("pose_errors", intr, B, allow_single=False)
         a.intr = intr.data_ptr()
     out = torch.empty(B, 4, device=pts.device)
     s_out = torch.empty(2, B, device=pts.device, dtype=torch.int32)
@@ -1086,19 +1132,13 @@ def vsd(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, tau_mm: T
     frame = _lengths("vsd", frame, "frame", B, z_est)
     if frame is None and Ft not in (1, B):
         raise ValueError("vsd: depth_test must hold 1 or B = %d planes without frame=, got %d" % (B, Ft))
-    intr, tau_mm = _f32(intr.detach(), "intr"), _f32(tau_mm.detach(), "tau_mm")
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3).contiguous()
-    if tuple(intr.shape) != (B, 3, 3):
-        raise ValueError("vsd: intr [B=%d,3,3] or [3,3] expected, got %s" % (B, tuple(intr.shape)))
+    intr, tau_mm = _intr_per_view("vsd", intr, B), _f32(tau_mm.detach(), "tau_mm")
     if tau_mm.dim() == 1:
         tau_mm = tau_mm[None].expand(B, -1).contiguous()
     if tau_mm.dim() != 2 or tau_mm.shape[0] != B:
         raise ValueError("vsd: tau_mm [B=%d,T] or [T] expected, got %s" % (B, tuple(tau_mm.shape)))
     T = tau_mm.shape[1]
-    spec = {"err": (torch.float32, (B, T)), "counts": (torch.int32, (B, 2 + T))}
-    res = {k: torch.empty(shape, device=z_est.device, dtype=dtype) if out is None else _want_gpu("vsd", out[k], f"out[{k!r}]", dtype, shape)
-           for k, (dtype, shape) in spec.items()}
+    res = _outputs("vsd", out, {"err": (torch.float32, (B, T)), "counts": (torch.int32, (B, 2 + T))}, z_est.device)
     a = _lib.VsdArgs()
     a.z_est, a.z_gt, a.depth_test, a.frame = z_est.data_ptr(), z_gt.data_ptr(), depth_test.data_ptr(), _ptr(frame)
     a.intr, a.tau_mm, a.delta_mm = intr.data_ptr(), tau_mm.data_ptr(), float(delta_mm)
@@ -1111,7 +1151,7 @@ def vsd(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor, tau_mm: T
 # ------------------------------------------------------------------------------------------ K27
 def texture_bake_workspace(V: int, B: int, device) -> Tensor:
     """A workspace for texture_bake at V vertices and B views (tp_texture_bake_workspace_bytes); needs no clearing."""
-    return torch.empty(max(2, (int(_lib.load().tp_texture_bake_workspace_bytes(V, B)) + 7) // 8), device=device, dtype=torch.float64)
+    return _workspace_arg("texture_bake", None, int(_lib.load().tp_texture_bake_workspace_bytes(V, B)), device)
 
 
 @_on_tensor_device
@@ -1125,21 +1165,14 @@ def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb
     ``workspace``: texture_bake_workspace(V, B) (a fresh one otherwise).  Not differentiable.  Two launches, no atomics, safe under
     torch.cuda.graph."""
     lib = _lib.load()
-    verts, normals, pose = _f32(verts.detach(), "verts"), _f32(normals.detach(), "normals"), _f32(pose.detach(), "pose")
-    rgb, zbuf = _f32(rgb.detach(), "rgb"), _f32(zbuf.detach(), "zbuf")
-    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0 or normals.shape != verts.shape:
-        raise ValueError("texture_bake: verts and normals [V,3] expected, got %s and %s" % (tuple(verts.shape), tuple(normals.shape)))
-    if pose.dim() != 3 or tuple(pose.shape[1:]) != (3, 4) or pose.shape[0] == 0:
-        raise ValueError("texture_bake: pose [B,3,4] expected, got %s" % (tuple(pose.shape),))
+    verts, pose = _points("texture_bake", verts, "verts"), _poses("texture_bake", pose, "pose")
     V, B = verts.shape[0], pose.shape[0]
+    normals = _points("texture_bake", normals, "normals", V)
+    rgb, zbuf = _f32(rgb.detach(), "rgb"), _f32(zbuf.detach(), "zbuf")
     if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0 or tuple(rgb.shape) != tuple(zbuf.shape) + (3,):
         raise ValueError("texture_bake: zbuf [B=%d,H,W] and rgb [B,H,W,3] expected, got %s and %s" % (B, tuple(zbuf.shape), tuple(rgb.shape)))
     H, W = zbuf.shape[1:]
-    intr = _f32(intr.detach(), "intr")
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3).contiguous()
-    if tuple(intr.shape) != (B, 3, 3):
-        raise ValueError("texture_bake: intr [B=%d,3,3] or [3,3] expected, got %s" % (B, tuple(intr.shape)))
+    intr = _intr_per_view("texture_bake", intr, B)
     if weight is not None:
         weight = _f32(weight.detach(), "weight")
         if weight.numel() != B * H * W:
@@ -1149,11 +1182,7 @@ def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb
     dev = verts.device
     acc = torch.empty(V, 4, device=dev) if acc is None else _want_gpu("texture_bake", acc, "acc", torch.float32, (V, 4))
     count = torch.empty(V, device=dev, dtype=torch.int32) if count is None else _want_gpu("texture_bake", count, "count", torch.int32, (V,))
-    need = int(lib.tp_texture_bake_workspace_bytes(V, B))
-    if workspace is None:
-        workspace = texture_bake_workspace(V, B, dev)
-    elif not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError("texture_bake: workspace must be a contiguous GPU tensor of >= %d bytes" % need)
+    workspace = _workspace_arg("texture_bake", workspace, int(lib.tp_texture_bake_workspace_bytes(V, B)), dev)
     a = _lib.TextureBakeArgs()
     a.verts, a.normals, a.pose, a.intr = verts.data_ptr(), normals.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.rgb, a.zbuf, a.weight = rgb.data_ptr(), zbuf.data_ptr(), _ptr(weight)
@@ -1171,21 +1200,7 @@ PNP_MAX_HYP, PNP_MAX_ITERS = _lib.PNP_MAX_HYP, _lib.PNP_MAX_ITERS
 def pnp_workspace(B: int, N: int, T: int, device) -> Tensor:
     """A workspace for corr_from_nocs / pnp_refine / pnp_ransac at B images, N entries and T hypotheses (tp_pnp_workspace_bytes);
     needs no clearing."""
-    return torch.empty(max(2, (int(_lib.load().tp_pnp_workspace_bytes(B, N, T)) + 7) // 8), device=device, dtype=torch.float64)
-
-
-def _pnp_workspace(op: str, workspace: Optional[Tensor], B: int, N: int, T: int, dev) -> Tensor:
-    need = int(_lib.load().tp_pnp_workspace_bytes(B, N, T))
-    if workspace is None:
-        return pnp_workspace(B, N, T, dev)
-    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16:
-        raise ValueError("%s: workspace must be a contiguous, 16-byte aligned GPU tensor of >= %d bytes" % (op, need))
-    return workspace
-
-
-def _pnp_outputs(op: str, out: Optional[Dict[str, Tensor]], spec, dev) -> Dict[str, Tensor]:
-    return {k: torch.empty(shape, device=dev, dtype=dtype) if out is None or k not in out else _want_gpu(op, out[k], f"out[{k!r}]", dtype, shape)
-            for k, (dtype, shape) in spec.items()}
+    return _workspace_arg("pnp", None, int(_lib.load().tp_pnp_workspace_bytes(B, N, T)), device)
 
 
 def _pnp_common(op: str, xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor):
@@ -1193,15 +1208,7 @@ def _pnp_common(op: str, xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor):
     if xy.dim() != 3 or xy.shape[2] != 2 or xy.shape[0] == 0 or xy.shape[1] == 0 or tuple(xyz.shape) != tuple(xy.shape[:2]) + (3,):
         raise ValueError("%s: xy [B,N,2] and xyz [B,N,3] expected, got %s and %s" % (op, tuple(xy.shape), tuple(xyz.shape)))
     B, N = xy.shape[:2]
-    count = _lengths(op, count, "count", B, xy)
-    if count is None:
-        raise ValueError(f"{op}: count must be an int32 GPU tensor of shape ({B},)")
-    intr = _f32(intr.detach(), "intr")
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3).contiguous()
-    if tuple(intr.shape) != (B, 3, 3):
-        raise ValueError("%s: intr [B=%d,3,3] or [3,3] expected, got %s" % (op, B, tuple(intr.shape)))
-    return xy, xyz, count, intr, B, N
+    return xy, xyz, _lengths(op, count, "count", B, xy, required=True), _intr_per_view(op, intr, B), B, N
 
 
 @_on_tensor_device
@@ -1229,12 +1236,11 @@ def corr_from_nocs(nocs: Tensor, mask: Tensor, centre, scale, *, stride: int = 1
         raise ValueError("corr_from_nocs: stride >= 1 expected, got %d" % stride)
     N = -(-H // stride) * -(-W // stride)
     dev = nocs.device
-    res = _pnp_outputs("corr_from_nocs", out, {"xy": (torch.float32, (B, N, 2)), "xyz": (torch.float32, (B, N, 3)), "count": (torch.int32, (B,))}, dev)
-    workspace = _pnp_workspace("corr_from_nocs", workspace, B, N, 1, dev)
+    res = _outputs("corr_from_nocs", out, {"xy": (torch.float32, (B, N, 2)), "xyz": (torch.float32, (B, N, 3)), "count": (torch.int32, (B,))}, dev, partial=True)
+    workspace = _workspace_arg("corr_from_nocs", workspace, int(lib.tp_pnp_workspace_bytes(B, N, 1)), dev, align=16)
     a = _lib.CorrFromNocsArgs()
     a.nocs, a.mask, a.mask_is_float = nocs.data_ptr(), mask.data_ptr(), int(mask.dtype == torch.float32)
-    a.centre = (C.c_float * 3)(*[float(x) for x in centre])
-    a.scale = (C.c_float * 3)(*[float(x) for x in scale])
+    a.centre, a.scale = _float3(centre), _float3(scale)
     a.B, a.H, a.W, a.stride = B, H, W, stride
     a.xy, a.xyz, a.count, a.workspace = res["xy"].data_ptr(), res["xyz"].data_ptr(), res["count"].data_ptr(), workspace.data_ptr()
     check(lib.tp_corr_from_nocs(C.byref(a), _stream()), "tp_corr_from_nocs")
@@ -1251,8 +1257,8 @@ def pnp_hypotheses(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, *, T: i
     xy, xyz, count, intr, B, N = _pnp_common("pnp_hypotheses", xy, xyz, count, intr)
     T = int(T)
     dev = xy.device
-    res = _pnp_outputs("pnp_hypotheses", out, {"sample_idx": (torch.int32, (B, max(T, 0), 4)), "hyp": (torch.float32, (B, max(T, 0), 12)),
-                                               "hyp_valid": (torch.uint8, (B, max(T, 0)))}, dev)
+    res = _outputs("pnp_hypotheses", out, {"sample_idx": (torch.int32, (B, max(T, 0), 4)), "hyp": (torch.float32, (B, max(T, 0), 12)),
+                                           "hyp_valid": (torch.uint8, (B, max(T, 0)))}, dev, partial=True)
     a = _lib.PnpHypothesesArgs()
     a.xy, a.xyz, a.count, a.intr = xy.data_ptr(), xyz.data_ptr(), count.data_ptr(), intr.data_ptr()
     a.B, a.N, a.T, a.seed = B, N, T, int(seed) & (2 ** 64 - 1)
@@ -1321,9 +1327,9 @@ def pnp_refine(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, hyp: Tensor
     hyp_inliers = _want_gpu("pnp_refine", hyp_inliers, "hyp_inliers", torch.int32, (B, T))
     if hyp_valid is not None:
         hyp_valid = _want_gpu("pnp_refine", hyp_valid, "hyp_valid", torch.uint8, (B, T))
-    res = _pnp_outputs("pnp_refine", out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
-                                           "status": (torch.int32, (B,))}, dev)
-    workspace = _pnp_workspace("pnp_refine", workspace, B, N, T, dev)
+    res = _outputs("pnp_refine", out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+                                       "status": (torch.int32, (B,))}, dev, partial=True)
+    workspace = _workspace_arg("pnp_refine", workspace, int(lib.tp_pnp_workspace_bytes(B, N, T)), dev, align=16)
     a = _lib.PnpRefineArgs()
     a.xy, a.xyz, a.count, a.intr = xy.data_ptr(), xyz.data_ptr(), count.data_ptr(), intr.data_ptr()
     a.hyp, a.hyp_valid, a.hyp_inliers = hyp.data_ptr(), _ptr(hyp_valid), hyp_inliers.data_ptr()
@@ -1476,12 +1482,10 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     if pose.dim() == 2:
         pose = pose[None]
     B = pose.shape[0]
-    intr = _f32(intr, "intr")
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3).contiguous()
+    intr = _intr_per_view("mesh_raster", intr, B)
     faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
     V, F = verts.shape[0], faces.shape[0]
-    if verts.shape != (V, 3) or faces.shape != (F, 3) or pose.shape != (B, 3, 4) or intr.shape != (B, 3, 3):
+    if verts.shape != (V, 3) or faces.shape != (F, 3) or pose.shape != (B, 3, 4):
         raise ValueError("mesh_raster: verts [V,3], faces [F,3], pose [B,3,4], intr [B,3,3] expected")
     if F == 0 or V == 0:
         raise ValueError("mesh_raster: empty mesh")
@@ -1489,10 +1493,7 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     a = _lib.MeshRasterArgs()
     a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
-    if zbuf_out is not None and (zbuf_out.device != dev or zbuf_out.dtype != torch.float32 or not zbuf_out.is_contiguous()
-                                 or tuple(zbuf_out.shape) != (B, H, W)):
-        raise ValueError(f"mesh_raster: zbuf_out must be a contiguous float32 tensor of shape {(B, H, W)} on {dev}")
-    out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else zbuf_out}
+    out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else _want_gpu("mesh_raster", zbuf_out, "zbuf_out", torch.float32, (B, H, W))}
     if face_ids:
         out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
     if vcolor is not None:
@@ -1502,8 +1503,7 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
         a.vcolor = vcolor.data_ptr()
         out["rgb"] = torch.empty(B, H, W, 3, device=dev)
     if nocs_norm is not None:
-        a.nocs_center = (C.c_float * 3)(*[float(x) for x in nocs_norm[0]])
-        a.nocs_scale = (C.c_float * 3)(*[float(x) for x in nocs_norm[1]])
+        a.nocs_center, a.nocs_scale = _float3(nocs_norm[0]), _float3(nocs_norm[1])
         out["nocs"] = torch.empty(B, H, W, 3, device=dev)
     if normals:
         out["normal"] = torch.empty(B, H, W, 3, device=dev)
@@ -1519,10 +1519,9 @@ def normals_from_depth(depth: Tensor, pose: Tensor, intr: Tensor) -> Tensor:
     """The normal stage of tp_mesh_raster alone (compute_surfelinfo.normal_from_depth) on a given depth [B,H,W] (mm, <= 0 background),
     pose [B,3,4] (t in mm), intr [B,3,3] -> normal [B,H,W,3]."""
     lib = _lib.load()
-    depth, pose, intr = _f32(depth, "depth"), _f32(pose, "pose"), _f32(intr, "intr")
+    depth = _f32(depth, "depth")
     B, H, W = depth.shape
-    if pose.shape != (B, 3, 4) or intr.shape != (B, 3, 3):
-        raise ValueError("normals_from_depth: depth [B,H,W], pose [B,3,4], intr [B,3,3] expected")
+    pose, intr = _poses("normals_from_depth", pose, "pose", B), _intr_per_view("normals_from_depth", intr, B, allow_single=False)
     normal = torch.empty(B, H, W, 3, device=depth.device)
     a = _lib.MeshRasterArgs()
     a.pose, a.intr, a.zbuf, a.normal = pose.data_ptr(), intr.data_ptr(), depth.data_ptr(), normal.data_ptr()
@@ -1552,16 +1551,7 @@ def surfel_finish(zbuf: Tensor, nocs: Tensor, normal: Tensor, rgb: Optional[Tens
     for name, t in (("nocs", nocs), ("normal", normal), ("rgb", rgb)):
         if t is not None and t.shape != (B, H, W, 3):
             raise ValueError(f"surfel_finish: {name} [B,H,W,3] expected")
-    shapes = {"image_syn": (B, 3, H, W), "mask_syn": (B, H, W), "nocs_pred": (B, 3, H, W), "normal_pred": (B, 3, H, W)}
-    res = {}
-    for k in SURFEL_FINISH_KEYS:
-        if out is None:
-            res[k] = torch.empty(shapes[k], device=zbuf.device)
-            continue
-        t = out[k]
-        if not t.is_cuda or t.device != zbuf.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shapes[k]:
-            raise ValueError(f"surfel_finish: out[{k!r}] must be a contiguous float32 tensor of shape {shapes[k]} on {zbuf.device}")
-        res[k] = t
+    res = _outputs("surfel_finish", out, {k: (torch.float32, (B, H, W) if k == "mask_syn" else (B, 3, H, W)) for k in SURFEL_FINISH_KEYS}, zbuf.device)
     a = _lib.SurfelFinishArgs()
     a.rgb, a.nocs, a.normal, a.zbuf = _ptr(rgb), nocs.data_ptr(), normal.data_ptr(), zbuf.data_ptr()
     a.B, a.H, a.W, a.quantize = B, H, W, int(bool(quantize))
@@ -1589,27 +1579,18 @@ def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float
     lib = _lib.load()
     if source not in SCENE_SOURCES:
         raise ValueError(f"scene_bounds: source must be one of {sorted(SCENE_SOURCES)}, not {source!r}")
-
-    def want(t, name, dtype, shape):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"scene_bounds: {name} must be a contiguous {dtype} GPU tensor" + ("" if shape is None else f" of shape {shape}"))
-        return t
-
-    want(zbuf, "zbuf", torch.float32, None)
+    _want_gpu("scene_bounds", zbuf, "zbuf", torch.float32, None)
     if zbuf.dim() != 4:
         raise ValueError("scene_bounds: zbuf [K,B,H,W] expected")
     K, B, H, W = zbuf.shape
-    want(ids, "ids", torch.int32, (K,))
+    _want_gpu("scene_bounds", ids, "ids", torch.int32, (K,))
     a = _lib.SceneBoundsArgs()
     if source == "box":
-        want(boxes, "boxes", torch.float32, (K, 2, 3))
-        want(pose, "pose", torch.float32, (B, 3, 4))
-        want(intr, "intr", torch.float32, (B, 3, 3))
+        _want_gpu("scene_bounds", boxes, "boxes", torch.float32, (K, 2, 3))
+        _want_gpu("scene_bounds", pose, "pose", torch.float32, (B, 3, 4))
+        _want_gpu("scene_bounds", intr, "intr", torch.float32, (B, 3, 3))
         a.boxes, a.pose, a.intr = boxes.data_ptr(), pose.data_ptr(), intr.data_ptr()
-    dtypes = {"z_near": torch.float32, "z_far": torch.float32, "label": torch.int32, "depth": torch.float32}
-    res = {}
-    for k in SCENE_BOUNDS_KEYS:
-        res[k] = torch.empty(B, H * W, device=zbuf.device, dtype=dtypes[k]) if out is None else want(out[k], f"out[{k!r}]", dtypes[k], (B, H * W))
+    res = _outputs("scene_bounds", out, {k: (torch.int32 if k == "label" else torch.float32, (B, H * W)) for k in SCENE_BOUNDS_KEYS}, zbuf.device)
     a.zbuf, a.ids = zbuf.data_ptr(), ids.data_ptr()
     a.B, a.H, a.W, a.K, a.source = B, H, W, K, SCENE_SOURCES[source]
     a.depth_scale, a.bg_near, a.bg_far = float(depth_scale), float(bg_range[0]), float(bg_range[1])
@@ -1622,12 +1603,6 @@ def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float
 SCENE_INFO_KEYS = ("px_count_all", "px_count_visib", "obj_xmin", "obj_ymin", "obj_xmax", "obj_ymax", "visib_xmin", "visib_ymin",
                    "visib_xmax", "visib_ymax")                      # the ten columns of info, in order
 assert len(SCENE_INFO_KEYS) == _lib.SCENE_INFO_FIELDS
-
-
-def _want_gpu(op: str, t, name: str, dtype, shape):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
-        raise ValueError(f"{op}: {name} must be a contiguous {dtype} GPU tensor" + ("" if shape is None else f" of shape {shape}"))
-    return t
 
 
 @_on_tensor_device
@@ -1649,9 +1624,7 @@ def scene_annotate(zbuf: Tensor, label: Tensor, ids: Tensor, *, masks: bool = Tr
     spec = {"info": (torch.int32, (B, K, _lib.SCENE_INFO_FIELDS))}
     if masks:
         spec.update(mask=(torch.uint8, (B, K, H, W)), mask_visib=(torch.uint8, (B, K, H, W)))
-    res = {}
-    for k, (dtype, shape) in spec.items():
-        res[k] = torch.empty(shape, device=zbuf.device, dtype=dtype) if out is None else _want_gpu("scene_annotate", out[k], f"out[{k!r}]", dtype, shape)
+    res = _outputs("scene_annotate", out, spec, zbuf.device)
     a = _lib.SceneAnnotateArgs()
     a.zbuf, a.label, a.ids = zbuf.data_ptr(), label.data_ptr(), ids.data_ptr()
     a.B, a.H, a.W, a.K = B, H, W, K
@@ -1676,20 +1649,17 @@ def view_images(rgb: Optional[Tensor], depth: Optional[Tensor], *, H: int, W: in
     B, HW = int(first.shape[0]), int(H) * int(W)
     a = _lib.ViewImagesArgs()
     a.B, a.H, a.W, a.depth_scale, a.png_per_metre = B, int(H), int(W), float(depth_scale), float(png_per_metre)
-    res = {}
-
-    def output(key, dtype, shape):
-        res[key] = torch.empty(shape, device=first.device, dtype=dtype) if out is None else _want_gpu("view_images", out[key], f"out[{key!r}]", dtype, shape)
-        return res[key].data_ptr()
-
+    spec = {}
     if rgb is not None:
         _want_gpu("view_images", rgb, "rgb", torch.float32, (B, HW, 3))
-        a.rgb, a.rgb8 = rgb.data_ptr(), output("rgb8", torch.uint8, (B, H, W, 3))
+        spec["rgb8"] = (torch.uint8, (B, H, W, 3))
     if depth is not None:
         if depth.dim() == 3 and depth.shape[-1] == 1:
             depth = depth[..., 0]
         _want_gpu("view_images", depth, "depth", torch.float32, (B, HW))
-        a.depth, a.depth16 = depth.data_ptr(), output("depth16", torch.uint16, (B, H, W))
+        spec["depth16"] = (torch.uint16, (B, H, W))
+    res = _outputs("view_images", out, spec, first.device)
+    a.rgb, a.rgb8, a.depth, a.depth16 = _ptr(rgb), _ptr(res.get("rgb8")), _ptr(depth), _ptr(res.get("depth16"))
     check(lib.tp_view_images(C.byref(a), _stream()), "tp_view_images")
     return res
 

@@ -357,12 +357,11 @@ def vsd_from_depth(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor
     if d.numel() not in (1, B):
         raise ValueError("vsd: diameter must be a number or a [B] tensor")
     tau_mm = (torch.tensor([float(t) for t in taus], dtype=torch.float32, device=dev)[None] * d[:, None]).expand(B, -1).contiguous()
-    intr = intr[None].expand(B, -1, -1) if intr.dim() == 2 else intr
     if z_est.is_cuda:
         from . import ops
-        return ops.vsd(z_est, z_gt, depth_test.to(dev), intr.to(dev).contiguous(), tau_mm, delta_mm=delta,
+        return ops.vsd(z_est, z_gt, depth_test.to(dev), intr.to(dev), tau_mm, delta_mm=delta,
                        frame=None if frame is None else frame.to(device=dev, dtype=torch.int32))
-    return vsd_torch(z_est, z_gt, depth_test, intr, tau_mm, delta, frame)
+    return vsd_torch(z_est, z_gt, depth_test, intr[None].expand(B, -1, -1) if intr.dim() == 2 else intr, tau_mm, delta, frame)
 
 
 def vsd(verts: Tensor, faces: Tensor, pose_est: Tensor, pose_gt: Tensor, intr: Tensor, depth_test: Tensor, diameter, *, H: int, W: int,
@@ -379,9 +378,8 @@ def vsd(verts: Tensor, faces: Tensor, pose_est: Tensor, pose_gt: Tensor, intr: T
     from . import ops
     B = pose_est.shape[0]
     intr = intr.detach()
-    intr = intr[None].expand(B, -1, -1) if intr.dim() == 2 else intr
-    z = ops.mesh_raster(verts.detach(), faces, torch.cat([pose_est, pose_gt]).to(verts.device), torch.cat([intr, intr]).to(verts.device),
-                        H=H, W=W, face_ids=False, normals=False)["zbuf"]
+    z = ops.mesh_raster(verts.detach(), faces, torch.cat([pose_est, pose_gt]).to(verts.device),
+                        (intr if intr.dim() == 2 else torch.cat([intr, intr])).to(verts.device), H=H, W=W, face_ids=False, normals=False)["zbuf"]
     return vsd_from_depth(z[:B], z[B:], depth_test, intr, diameter, taus=taus, delta=delta, frame=frame)
 
 

@@ -19,28 +19,18 @@ records the pose error against the truth of the kernels and of the numpy restate
 repository's tests/ folder; nothing is timed there)."""
 import argparse
 import json
-import math
 import os
-import statistics
 import sys
 import time
 
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+import kernel_bench as KB  # noqa: E402
+from texture_bake_ref import torus  # noqa: E402  (numpy only: the tests' mesh generators; needs the repository's tests/ folder)
 
 LINEMOD_K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]], np.float32)
-
-
-def torus(n_major, n_minor, R=45.0, r=16.0):
-    u, w = np.linspace(0, 2 * math.pi, n_major, endpoint=False), np.linspace(0, 2 * math.pi, n_minor, endpoint=False)
-    U, Wm = np.meshgrid(u, w, indexing="ij")
-    v = np.stack([(R + r * np.cos(Wm)) * np.cos(U), (R + r * np.cos(Wm)) * np.sin(U), r * np.sin(Wm)], -1).reshape(-1, 3)
-    idx = np.arange(n_major * n_minor).reshape(n_major, n_minor)
-    a, b = idx, np.roll(idx, -1, axis=0)
-    c, d = np.roll(idx, -1, axis=1), np.roll(np.roll(idx, -1, axis=0), -1, axis=1)
-    return v.astype(np.float32), np.concatenate([np.stack([a, b, d], -1), np.stack([a, d, c], -1)]).reshape(-1, 3).astype(np.int32)
 
 
 def rotation(rs):
@@ -58,7 +48,6 @@ def pose_error(pose, truth):
 
 def end_to_end(torch, ops, dev):
     """The case of tests/pnp_ref.py::end_to_end_inputs (what the GPU test solves), both routes' errors against the truth."""
-    sys.path.insert(0, os.path.join(REPO, "tests"))
     import pnp_ref as REF                                       # (numpy only: the restatement and the case's inputs)
     from texpose_amd.surfel import nocs_normalisation
     t = lambda x, dtype=torch.float32: torch.from_numpy(np.ascontiguousarray(x)).to(dev, dtype)
@@ -88,10 +77,7 @@ def end_to_end(torch, ops, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3)
+    KB.add_timing_args(ap, iters=20, warmup=3, repeats=3)
     ap.add_argument("--end-to-end", action="store_true")
     a = ap.parse_args(argv)
     import torch
@@ -102,20 +88,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     rs = np.random.RandomState(0)
 
-    def timed(fn, iters):
-        for _ in range(a.warmup):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters                    # us per call
-
-    clock = lambda: ops.clock_ghz_from_probe(ops.clock_probe())
-    clock_before = clock()
+    clock_before = KB.shader_clock()
     t_start = time.time()
     B, T, H, W, tau = 64, 256, 480, 640, 2.0
     verts, faces = torus(160, 80)
@@ -145,13 +118,8 @@ def main(argv=None):
     if largest > 1e-3 * n_max:                                      # (a count off by one: a decision that two fp32 divisions round apart)
         raise SystemExit("pnp_bench: the two scoring routes disagree on %d of %d counts (largest difference %d); nothing was timed"
                          % (differ, B * T, largest))
-    times = {"tp_pnp_score": [], "torch": [], "pnp_ransac": [], "corr_from_nocs": []}
-    for _ in range(a.repeats):                                      # alternating: drift of the box hits every route alike
-        times["tp_pnp_score"].append(timed(kernel, a.iters))
-        times["torch"].append(timed(plain, max(2, a.iters // 10)))
-        times["pnp_ransac"].append(timed(ransac, a.iters))
-        times["corr_from_nocs"].append(timed(corr_call, a.iters))
-    med = {k: statistics.median(v) for k, v in times.items()}
+    med, times = KB.race({"tp_pnp_score": kernel, "torch": plain, "pnp_ransac": ransac, "corr_from_nocs": corr_call},
+                         {"tp_pnp_score": a.iters, "torch": max(2, a.iters // 10), "pnp_ransac": a.iters, "corr_from_nocs": a.iters}, a.warmup, a.repeats)
     n_sum = int(count.sum())
     errs = [pose_error(first["pose"][b].double().cpu().numpy(), P[b].astype(np.float64)) for b in range(B)]
     row = dict(B=B, T=T, H=H, W=W, tau_px=tau, iters=5, n_mean=n_sum / B, n_max=n_max, us=med, us_all_repeats=times,
@@ -162,14 +130,10 @@ def main(argv=None):
                max_rot_err_deg=max(e[0] for e in errs), max_trans_err_mm=max(e[1] for e in errs))
     print(json.dumps(row), flush=True)
     res = dict(bench="pnp", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
-               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=clock(), seconds=time.time() - t_start, rows=[row])
+               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start, rows=[row])
     if a.end_to_end:
         res["end_to_end_64x80"] = end_to_end(torch, ops, dev)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+    KB.finish(res, a.out)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ without (a share of peak of the CALL: both launches and the gap between them are
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
 import time
@@ -22,6 +21,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import kernel_bench as KB  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -37,10 +37,7 @@ def sclk():
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--iters", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3)
+    KB.add_timing_args(ap, iters=100, warmup=10, repeats=3)
     ap.add_argument("--B", type=int, default=10)
     a = ap.parse_args(argv)
     import torch
@@ -51,28 +48,9 @@ def main(argv=None):
     B = a.B
     rs = np.random.RandomState(0)
 
-    def timed(fn, iters):
-        for _ in range(a.warmup):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters                    # us per call
-
-    def race(routes, iters):
-        times = {name: [] for name in routes}
-        for _ in range(a.repeats):                                  # alternating: drift of the box hits every route alike
-            for name, fn in routes.items():
-                times[name].append(timed(fn, iters))
-        return {name: statistics.median(v) for name, v in times.items()}, times
-
     # ms_per_step of the box: a fixed torch workload, so that records from different boxes can be told apart
     x = torch.randn(4096, 4096, device=dev)
-    box_ms = timed(lambda: x @ x, 20) / 1e3
+    box_ms = KB.timed(lambda: x @ x, 20, a.warmup) / 1e3
     rows, image_rows = [], []
     clock_before = sclk()
     t_start = time.time()
@@ -117,7 +95,7 @@ def main(argv=None):
             same = {k: bool(torch.equal(r_new[k], r_old[k])) for k in r_new}
             same["info_without_masks"] = bool(torch.equal(k22_lean()["info"], r_old["info"]))
             iters = a.iters if H * W * K < 3e6 else max(10, a.iters // 4)
-            med, raw = race(dict(k22_masks=k22_masks, k22_no_masks=k22_lean, torch=torch_route), iters)
+            med, raw = KB.race(dict(k22_masks=k22_masks, k22_no_masks=k22_lean, torch=torch_route), iters, a.warmup, a.repeats)
             px = B * H * W
             bytes_masks, bytes_lean = (4 * K + 4 + 2 * K) * px, (4 * K + 4) * px
             rows.append(dict(K=K, B=B, H=H, W=W, us=med, us_all_repeats=raw, torch_over_k22_masks=med["torch"] / med["k22_masks"],
@@ -139,7 +117,7 @@ def main(argv=None):
                 res.append(((rgb[i].view(H, W, 3).clamp(0, 1) * 255).byte(), ((depth[i].view(H, W) / 10.0) * 2000).clamp(0, 65535).to(torch.int32)))
             return res
 
-        med, raw = race(dict(view_images=images_new, torch=images_torch), a.iters)
+        med, raw = KB.race(dict(view_images=images_new, torch=images_torch), a.iters, a.warmup, a.repeats)
         old = images_torch()
         got = images_new()
         same = dict(rgb8=bool(all(torch.equal(got["rgb8"][i], old[i][0]) for i in range(B))),
@@ -151,11 +129,7 @@ def main(argv=None):
     res = dict(bench="scene_annotate", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
                ms_per_step_of_the_box_4096_matmul=box_ms, seconds=time.time() - t_start, sclk_before=clock_before, sclk_after=sclk(),
                rows=rows, view_images=image_rows)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+    KB.finish(res, a.out)
 
 
 if __name__ == "__main__":

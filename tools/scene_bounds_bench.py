@@ -17,6 +17,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import kernel_bench as KB  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -87,16 +88,7 @@ def main(argv=None):
         same = {k: bool(torch.equal(r_new[k], r_old[k].to(r_new[k].dtype))) for k in ops.SCENE_BOUNDS_KEYS}
         times = {}
         for name, fn in (("new", new_route), ("old", old_route), ("new_again", new_route), ("old_again", old_route)):
-            for _ in range(a.warmup):
-                fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            times[name] = e0.elapsed_time(e1) * 1e3 / a.iters       # us per call
+            times[name] = KB.timed(fn, a.iters, a.warmup)
         nbytes = (4 * K + 16) * B * H * W
         t_new = min(times["new"], times["new_again"])
         t_old = min(times["old"], times["old_again"])
@@ -106,11 +98,7 @@ def main(argv=None):
         print(json.dumps(rows[-1]))
     res = dict(bench="scene_bounds", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, source="box",
                sclk_before=clock_before, sclk_after=sclk(), rows=rows)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+    KB.finish(res, a.out)
 
 
 if __name__ == "__main__":

@@ -21,26 +21,15 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def rippled_sphere(n_lat, n_lon, radius=50.0, ripple=0.15):
-    th, ph = np.linspace(0, np.pi, n_lat + 1), np.linspace(0, 2 * np.pi, n_lon, endpoint=False)
-    T, P = np.meshgrid(th, ph, indexing="ij")
-    r = radius * (1 + ripple * np.sin(5 * T) * np.cos(3 * P))
-    v = np.stack([r * np.sin(T) * np.cos(P), r * np.sin(T) * np.sin(P), r * np.cos(T)], -1).reshape(-1, 3)
-    idx = np.arange((n_lat + 1) * n_lon).reshape(n_lat + 1, n_lon)
-    a, b, c, d = idx[:-1], np.roll(idx[:-1], -1, axis=1), idx[1:], np.roll(idx[1:], -1, axis=1)
-    f = np.concatenate([np.stack([a, c, d], -1)[:-1], np.stack([a, d, b], -1)[1:]]).reshape(-1, 3)
-    return v.astype(np.float32), f.astype(np.int32)
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+import kernel_bench as KB  # noqa: E402
+from texture_bake_ref import uv_sphere  # noqa: E402  (numpy only: the tests' mesh generators; needs the repository's tests/ folder)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3)
+    KB.add_timing_args(ap, iters=50, warmup=5, repeats=3)
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import ops, texture_bake as TB
@@ -49,20 +38,7 @@ def main(argv=None):
         raise SystemExit("texture_bake_bench: needs a GPU (a CPU run cannot give a time)")
     dev = torch.device("cuda:0")
 
-    def timed(fn, iters):
-        for _ in range(a.warmup):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters                    # us per call
-
-    clock = lambda: ops.clock_ghz_from_probe(ops.clock_probe())
-    clock_before = clock()
+    clock_before = KB.shader_clock()
     t_start = time.time()
     H, W, B, focal, dist = 480, 640, 64, 1000.0, 400.0
     pose = torch.from_numpy(TB.sphere_view_poses(B, dist).astype(np.float32)).to(dev)
@@ -70,7 +46,7 @@ def main(argv=None):
     weight = torch.from_numpy(np.random.RandomState(0).uniform(0.2, 1.0, (B, H, W)).astype(np.float32)).to(dev)
     rows, end_to_end = [], []
     for n_lat, n_lon in ((99, 200), (399, 500)):
-        v_np, f_np = rippled_sphere(n_lat, n_lon)
+        v_np, f_np = uv_sphere(n_lat, n_lon, ripple=0.15)
         V = len(v_np)
         verts, faces = torch.from_numpy(v_np).to(dev), torch.from_numpy(f_np).to(dev)
         normals = torch.from_numpy(TB.vertex_normals(v_np, f_np)).to(dev)
@@ -89,11 +65,7 @@ def main(argv=None):
             raise SystemExit("texture_bake_bench: the two routes disagree at V = %d (%d counts differ, colours by %.3g); nothing was timed"
                              % (V, differ, dcol))
         reached = int(want["reached"])
-        times = {"tp_texture_bake": [], "torch": []}
-        for _ in range(a.repeats):                                  # alternating: drift of the box hits both routes alike
-            times["tp_texture_bake"].append(timed(kernel, a.iters))
-            times["torch"].append(timed(plain, max(3, a.iters // 10)))
-        med = {k: statistics.median(v) for k, v in times.items()}
+        med, times = KB.race({"tp_texture_bake": kernel, "torch": plain}, {"tp_texture_bake": a.iters, "torch": max(3, a.iters // 10)}, a.warmup, a.repeats)
         gather = reached * 64
         rows.append(dict(V=V, F=len(f_np), B=B, H=H, W=W, slices=int(ops._lib.load().tp_texture_bake_slices(V, B)), us=med, us_all_repeats=times,
                          torch_over_tp_texture_bake=med["torch"] / med["tp_texture_bake"], pairs=V * B, pairs_reaching_taps=reached,
@@ -115,19 +87,15 @@ def main(argv=None):
             bake_s.append(time.perf_counter() - t0)
         renderer = SurfelRenderer(v_np, f_np, res.vcolor.cpu().numpy(), H, W, dev)
         pose_nerf = TB.poses_to_nerf_units(pose, 10.0).contiguous()
-        frame_us = statistics.median(timed(lambda: renderer(pose_nerf, K, 10.0), max(3, a.iters // 5)) for _ in range(a.repeats))
+        frame_us = statistics.median(KB.timed(lambda: renderer(pose_nerf, K, 10.0), max(3, a.iters // 5), a.warmup) for _ in range(a.repeats))
         err = float((res.vcolor - vcol).abs()[res.seen].max())
         end_to_end.append(dict(V=V, views=B, H=H, W=W, bake_seconds=statistics.median(bake_s), bake_seconds_all=bake_s, filled=res.filled, unseen=res.unseen,
                                max_error_against_the_source_colours=err, surfel_renderer_us_per_64_frames=frame_us,
                                surfel_renderer_frames_per_second=B / (frame_us * 1e-6)))
         print(json.dumps(end_to_end[-1]), flush=True)
     res = dict(bench="texture_bake", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
-               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=clock(), seconds=time.time() - t_start, rows=rows, end_to_end=end_to_end)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start, rows=rows, end_to_end=end_to_end)
+    KB.finish(res, a.out)
 
 
 if __name__ == "__main__":

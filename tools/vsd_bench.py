@@ -12,23 +12,20 @@ bytes, 3 x 4 x H x W per pose pair (a share of peak of the CALL: the three launc
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import kernel_bench as KB  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3)
+    KB.add_timing_args(ap, iters=50, warmup=5, repeats=3)
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import ops, pose_error as PE
@@ -37,20 +34,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     rs = np.random.RandomState(0)
 
-    def timed(fn, iters):
-        for _ in range(a.warmup):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters                    # us per call
-
-    clock = lambda: ops.clock_ghz_from_probe(ops.clock_probe())
-    clock_before = clock()
+    clock_before = KB.shader_clock()
     t_start = time.time()
     H, W, T = 480, 640, 10
     rows = []
@@ -69,11 +53,7 @@ def main(argv=None):
         got, want = kernel(), plain()
         if not (torch.equal(got["counts"], want["counts"]) and torch.equal(got["err"], want["err"])):
             raise SystemExit("vsd_bench: the two routes disagree at B = %d; nothing was timed" % B)
-        times = {"tp_vsd": [], "torch": []}
-        for _ in range(a.repeats):                                  # alternating: drift of the box hits both routes alike
-            times["tp_vsd"].append(timed(kernel, a.iters))
-            times["torch"].append(timed(plain, max(3, a.iters // 10)))
-        med = {k: statistics.median(v) for k, v in times.items()}
+        med, times = KB.race({"tp_vsd": kernel, "torch": plain}, {"tp_vsd": a.iters, "torch": max(3, a.iters // 10)}, a.warmup, a.repeats)
         nbytes = 3 * 4 * H * W * B
         rows.append(dict(B=B, Ft=B, H=H, W=W, T=T, us=med, us_all_repeats=times, torch_over_tp_vsd=med["torch"] / med["tp_vsd"],
                          algorithmic_bytes=nbytes, bytes_per_second=nbytes / (med["tp_vsd"] * 1e-6),
@@ -81,12 +61,8 @@ def main(argv=None):
                          n_U=int(want["counts"][:, 0].sum()), n_I=int(want["counts"][:, 1].sum())))
         print(json.dumps(rows[-1]), flush=True)
     res = dict(bench="vsd", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
-               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=clock(), seconds=time.time() - t_start, rows=rows)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+               shader_clock_ghz_before=clock_before, shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start, rows=rows)
+    KB.finish(res, a.out)
 
 
 if __name__ == "__main__":
