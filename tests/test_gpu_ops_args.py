@@ -1,8 +1,9 @@
-"""GPU: the argument helpers of texpose_amd/ops.py through the scene / pose entry points that use them, at the smallest shapes that reach
+"""GPU: the argument helpers of texpose_amd/ops/_base.py through the scene / pose entry points that use them, at the smallest shapes that reach
 every branch: B = 2 views of 8 x 8, K = 2 objects, a tetrahedron, N = 64 correspondences, T = 4 hypotheses.  A caller's ``out`` tensors
 come back as the same objects with the bits of a call that allocated its own; partial ``out`` dicts; workspaces that are too short or
 badly aligned; one [3,3] intr against its [B,3,3] expansion; no allocation with ``out`` and ``workspace`` given.  Every refused call is
-refused on the host, before any launch."""
+refused on the host, before any launch.  And the launch helper `_call` behind every wrapper: it launches on the current stream, and a
+refusal of the library's own surfaces as TexposeLibraryError with the entry point's name, the ``_pair`` one for a paired launch."""
 import numpy as np
 import pytest
 import torch
@@ -215,3 +216,38 @@ def test_nothing_is_allocated_with_out_and_workspace_given(scene):
         assert torch.cuda.max_memory_allocated() == before, name    # not for a moment either
         assert all(res[k] is out[k] for k in out)
         del res, out                                                # (freed here, not inside the next route's measurement)
+
+
+BCE_CAPTURE_NODES = 1       # measured on the commit before ops became a package: one captured ops.bce_logits_fwd call adds one kernel node
+
+
+def test_launches_go_to_the_current_stream():
+    x = torch.linspace(-3, 3, 64, device=DEV)
+    eager = ops.bce_logits_fwd(x, 1.0)                              # (warm: nothing is loaded or made inside the capture)
+    torch.cuda.synchronize()
+    side, graph = torch.cuda.Stream(device=DEV), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        before = ops.capture_node_count()                           # counts the nodes of the stream that is current: the side stream
+        out = ops.bce_logits_fwd(x, 1.0)
+        rise = ops.capture_node_count() - before
+    assert before is not None and rise == BCE_CAPTURE_NODES and ops.capture_node_count() is None
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same(out, eager)
+
+
+def test_the_librarys_refusal_names_its_entry_point():
+    z = torch.full((1, 4, 4), 500.0, device=DEV)
+    with pytest.raises(_lib.TexposeLibraryError, match=r"^tp_vsd failed \(rc=-1\): tp_vsd: T = 17 tolerances, 1 \.\. 16 expected$"):
+        ops.vsd(z, z, z, torch.eye(3, device=DEV), torch.ones(1, _lib.VSD_MAX_TAUS + 1, device=DEV))
+    # a pair of the fused tail with one row more than it takes: refused by the library's size check, in front of the launch
+    M, Kt, Nt, L, Ht = ops.DISC_TAIL_MAX_ROWS + 1, 8, 4, 1, 4
+    zeros = lambda *shape: torch.zeros(*shape, device=DEV)
+    tail = lambda: ops.disc_tail_fwd(zeros(M, Kt), zeros(Nt, Kt), zeros(M), zeros(Ht, Nt + 2 * L + 1), zeros(Ht, Ht), zeros(1, Ht), L, 0.2)
+    with pytest.raises(_lib.TexposeLibraryError, match=r"^tp_disc_tail_fwd_pair failed \(rc=-1\): tp_disc_tail_fwd_pair: bad sizes \(at most 16 rows"):
+        with ops.paired():
+            tail()                                                  # held back: the second call launches both
+            tail()
+    assert not ops._pair_state["active"] and ops._pair_state["pending"] is None
+    with pytest.raises(_lib.TexposeLibraryError, match=r"^tp_disc_tail_fwd failed \(rc=-1\): tp_disc_tail_fwd: bad sizes"):
+        tail()

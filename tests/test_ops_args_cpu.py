@@ -1,4 +1,4 @@
-"""The argument helpers at the top of texpose_amd/ops.py, on the paths that need no device: what they refuse, with which exception,
+"""The argument helpers of texpose_amd/ops/_base.py, on the paths that need no device: what they refuse, with which exception,
 and that the message names the entry point and the argument.  Every tensor here lives on the CPU, so a refusal of a wrong dtype, shape
 or stride is also a refusal of a CPU tensor; tests/test_gpu_ops_args.py repeats those cases with GPU tensors, where only the named
 property is wrong."""

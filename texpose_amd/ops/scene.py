@@ -1,0 +1,244 @@
+"""K19-K22, K27: the mesh rasteriser, the surfel maps, the BOP scene writers and the texture bake."""
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from .. import _lib
+from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg)
+
+__all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
+           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake"]
+
+
+# ------------------------------------------------------------------------------------------ K19
+@_on_tensor_device
+def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: int, W: int, vcolor: Optional[Tensor] = None,
+                nocs_norm: Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]] = None,
+                face_ids: bool = True, normals: bool = True, zbuf_out: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Hard rasterisation of one mesh at B poses (tp_mesh_raster).  verts [V,3] and pose [B,3,4] ([R|t], t) in the same units (mm),
+    faces [F,3] int, intr [B,3,3] or [3,3].  Returns zbuf [B,H,W] (-1 on background) and, as asked, face [B,H,W] int32, rgb
+    (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3].
+    ``zbuf_out``: a contiguous float32 [B,H,W] tensor (e.g. one plane of a [K,B,H,W] stack) to write zbuf into."""
+    verts, pose = _f32(verts, "verts"), _f32(pose, "pose")
+    if pose.dim() == 2:
+        pose = pose[None]
+    B = pose.shape[0]
+    intr = _intr_per_view("mesh_raster", intr, B)
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    V, F = verts.shape[0], faces.shape[0]
+    if verts.shape != (V, 3) or faces.shape != (F, 3) or pose.shape != (B, 3, 4):
+        raise ValueError("mesh_raster: verts [V,3], faces [F,3], pose [B,3,4], intr [B,3,3] expected")
+    if F == 0 or V == 0:
+        raise ValueError("mesh_raster: empty mesh")
+    dev = verts.device
+    a = _lib.MeshRasterArgs()
+    a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
+    out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else _want_gpu("mesh_raster", zbuf_out, "zbuf_out", torch.float32, (B, H, W))}
+    if face_ids:
+        out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
+    if vcolor is not None:
+        vcolor = _f32(vcolor, "vcolor")
+        if vcolor.shape != (V, 3):
+            raise ValueError("mesh_raster: vcolor [V,3] expected")
+        a.vcolor = vcolor.data_ptr()
+        out["rgb"] = torch.empty(B, H, W, 3, device=dev)
+    if nocs_norm is not None:
+        a.nocs_center, a.nocs_scale = _float3(nocs_norm[0]), _float3(nocs_norm[1])
+        out["nocs"] = torch.empty(B, H, W, 3, device=dev)
+    if normals:
+        out["normal"] = torch.empty(B, H, W, 3, device=dev)
+    ws = torch.empty(max(1, int(_lib.load().tp_mesh_raster_workspace_bytes(B, H, W, F)) // 4), device=dev)
+    a.zbuf, a.face, a.rgb = out["zbuf"].data_ptr(), _ptr(out.get("face")), _ptr(out.get("rgb"))
+    a.nocs, a.normal, a.workspace = _ptr(out.get("nocs")), _ptr(out.get("normal")), ws.data_ptr()
+    _call("tp_mesh_raster", a)
+    return out
+
+
+@_on_tensor_device
+def normals_from_depth(depth: Tensor, pose: Tensor, intr: Tensor) -> Tensor:
+    """The normal stage of tp_mesh_raster alone (compute_surfelinfo.normal_from_depth) on a given depth [B,H,W] (mm, <= 0 background),
+    pose [B,3,4] (t in mm), intr [B,3,3] -> normal [B,H,W,3]."""
+    depth = _f32(depth, "depth")
+    B, H, W = depth.shape
+    pose, intr = _poses("normals_from_depth", pose, "pose", B), _intr_per_view("normals_from_depth", intr, B, allow_single=False)
+    normal = torch.empty(B, H, W, 3, device=depth.device)
+    a = _lib.MeshRasterArgs()
+    a.pose, a.intr, a.zbuf, a.normal = pose.data_ptr(), intr.data_ptr(), depth.data_ptr(), normal.data_ptr()
+    a.B, a.H, a.W, a.normals_from_zbuf = B, H, W, 1
+    _call("tp_mesh_raster", a)
+    return normal
+
+
+# ------------------------------------------------------------------------------------------ K20
+SURFEL_FINISH_KEYS = ("image_syn", "mask_syn", "nocs_pred", "normal_pred")
+
+
+@_on_tensor_device
+def surfel_finish(zbuf: Tensor, nocs: Tensor, normal: Tensor, rgb: Optional[Tensor] = None, *, quantize: bool = True,
+                  out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The data layer's decode of the surfel files, applied to mesh_raster's outputs (tp_surfel_finish): zbuf [B,H,W], nocs / normal /
+    rgb [B,H,W,3] (``rgb`` None: image_syn zero) -> image_syn [B,3,H,W] (8-bit round trip), mask_syn [B,H,W] (zbuf > 0), nocs_pred
+    (8-bit round trip + smooth_geo) and normal_pred (smooth_geo) [B,3,H,W].  ``quantize=False`` skips the 8-bit round trip.
+    ``out``: the four tensors to write into (float32, contiguous, of those shapes) instead of fresh ones."""
+    zbuf, nocs, normal = _f32(zbuf, "zbuf"), _f32(nocs, "nocs"), _f32(normal, "normal")
+    if zbuf.dim() != 3:
+        raise ValueError("surfel_finish: zbuf [B,H,W] expected")
+    B, H, W = zbuf.shape
+    if rgb is not None:
+        rgb = _f32(rgb, "rgb")
+    for name, t in (("nocs", nocs), ("normal", normal), ("rgb", rgb)):
+        if t is not None and t.shape != (B, H, W, 3):
+            raise ValueError(f"surfel_finish: {name} [B,H,W,3] expected")
+    res = _outputs("surfel_finish", out, {k: (torch.float32, (B, H, W) if k == "mask_syn" else (B, 3, H, W)) for k in SURFEL_FINISH_KEYS}, zbuf.device)
+    a = _lib.SurfelFinishArgs()
+    a.rgb, a.nocs, a.normal, a.zbuf = _ptr(rgb), nocs.data_ptr(), normal.data_ptr(), zbuf.data_ptr()
+    a.B, a.H, a.W, a.quantize = B, H, W, int(bool(quantize))
+    a.image_syn, a.mask_syn = res["image_syn"].data_ptr(), res["mask_syn"].data_ptr()
+    a.nocs_pred, a.normal_pred = res["nocs_pred"].data_ptr(), res["normal_pred"].data_ptr()
+    _call("tp_surfel_finish", a)
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K21
+SCENE_SOURCES = {"box": _lib.SCENE_BOX, "render": _lib.SCENE_RENDER, "none": _lib.SCENE_NONE}          # options nerf.depth.range_source -> TP_SCENE_*
+SCENE_BOUNDS_KEYS = ("z_near", "z_far", "label", "depth")
+
+
+@_on_tensor_device
+def scene_bounds(zbuf: Tensor, boxes: Tensor, ids: Tensor, *, depth_scale: float, bg_range: Tuple[float, float], source: str = "box",
+                 pose: Optional[Tensor] = None, intr: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The z-buffer blend of K objects at B poses (tp_scene_bounds): zbuf [K,B,H,W] (mesh_raster's planes: mm, <= 0 on background),
+    boxes [K,2,3] (min, max in NeRF units: bb_mm * depth_scale / 1000), ids [K] int32 (> 0), pose [B,3,4] (t in NeRF units) and intr
+    [B,3,3] (needed by ``source`` 'box' only) -> z_near, z_far [B,H*W] float32, label [B,H*W] int32 (the nearest object's id, 0 where
+    nothing is covered), depth [B,H*W] (the nearest mesh depth in NeRF units, 0 where uncovered).  ``source`` 'box': the winner's slab
+    bounds on the pixel ray (0 where the slab test fails), 'render': 0.8 x / 1.2 x depth, 'none': ``bg_range`` everywhere; uncovered
+    pixels always get ``bg_range``.  Inputs are taken as they are (float32 / int32, contiguous, on one GPU) -- nothing is converted or
+    copied; ``out``: the four tensors to write into.  One launch, no allocation beyond fresh outputs, safe under torch.cuda.graph."""
+    if source not in SCENE_SOURCES:
+        raise ValueError(f"scene_bounds: source must be one of {sorted(SCENE_SOURCES)}, not {source!r}")
+    _want_gpu("scene_bounds", zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 4:
+        raise ValueError("scene_bounds: zbuf [K,B,H,W] expected")
+    K, B, H, W = zbuf.shape
+    _want_gpu("scene_bounds", ids, "ids", torch.int32, (K,))
+    a = _lib.SceneBoundsArgs()
+    if source == "box":
+        _want_gpu("scene_bounds", boxes, "boxes", torch.float32, (K, 2, 3))
+        _want_gpu("scene_bounds", pose, "pose", torch.float32, (B, 3, 4))
+        _want_gpu("scene_bounds", intr, "intr", torch.float32, (B, 3, 3))
+        a.boxes, a.pose, a.intr = boxes.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    res = _outputs("scene_bounds", out, {k: (torch.int32 if k == "label" else torch.float32, (B, H * W)) for k in SCENE_BOUNDS_KEYS}, zbuf.device)
+    a.zbuf, a.ids = zbuf.data_ptr(), ids.data_ptr()
+    a.B, a.H, a.W, a.K, a.source = B, H, W, K, SCENE_SOURCES[source]
+    a.depth_scale, a.bg_near, a.bg_far = float(depth_scale), float(bg_range[0]), float(bg_range[1])
+    a.z_near, a.z_far, a.label, a.depth = (res[k].data_ptr() for k in SCENE_BOUNDS_KEYS)
+    _call("tp_scene_bounds", a)
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K22
+SCENE_INFO_KEYS = ("px_count_all", "px_count_visib", "obj_xmin", "obj_ymin", "obj_xmax", "obj_ymax", "visib_xmin", "visib_ymin",
+                   "visib_xmax", "visib_ymax")                      # the ten columns of info, in order
+assert len(SCENE_INFO_KEYS) == _lib.SCENE_INFO_FIELDS
+
+
+@_on_tensor_device
+def scene_annotate(zbuf: Tensor, label: Tensor, ids: Tensor, *, masks: bool = True, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The per-object annotations of K objects at B poses (tp_scene_annotate): zbuf [K,B,H,W] (mesh_raster's planes: mm, <= 0 or NaN on
+    background), label [B,H*W] int32 (scene_bounds' label), ids [K] int32 -> info [B,K,10] int32 (columns: SCENE_INFO_KEYS; extents
+    are inclusive pixel indices, -1 for an empty set) and, with ``masks``, mask and mask_visib [B,K,H,W] uint8 (0 / 255: the full
+    silhouette inside the image and the part that ``label`` gives to the object).  The ids must be distinct: a wrapper that builds
+    them (SceneBounds) checks that on the host; here they are taken as they are, like every input -- nothing is converted, copied or
+    read back.  ``out``: the tensors to write into ('info', and 'mask' / 'mask_visib' when ``masks``); info needs no clearing.
+    No allocation beyond fresh outputs, safe under torch.cuda.graph."""
+    _want_gpu("scene_annotate", zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 4:
+        raise ValueError("scene_annotate: zbuf [K,B,H,W] expected")
+    K, B, H, W = zbuf.shape
+    _want_gpu("scene_annotate", label, "label", torch.int32, (B, H * W))
+    _want_gpu("scene_annotate", ids, "ids", torch.int32, (K,))
+    spec = {"info": (torch.int32, (B, K, _lib.SCENE_INFO_FIELDS))}
+    if masks:
+        spec.update(mask=(torch.uint8, (B, K, H, W)), mask_visib=(torch.uint8, (B, K, H, W)))
+    res = _outputs("scene_annotate", out, spec, zbuf.device)
+    a = _lib.SceneAnnotateArgs()
+    a.zbuf, a.label, a.ids = zbuf.data_ptr(), label.data_ptr(), ids.data_ptr()
+    a.B, a.H, a.W, a.K = B, H, W, K
+    a.info = res["info"].data_ptr()
+    if masks:
+        a.mask, a.mask_visib = res["mask"].data_ptr(), res["mask_visib"].data_ptr()
+    _call("tp_scene_annotate", a)
+    return res
+
+
+@_on_tensor_device
+def view_images(rgb: Optional[Tensor], depth: Optional[Tensor], *, H: int, W: int, depth_scale: float = 1.0, png_per_metre: float = 2000.0,
+                out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The files' pixels of rendered views (tp_view_images): rgb [B,H*W,3] -> rgb8 [B,H,W,3] uint8 = trunc(clamp(rgb, 0, 1) * 255);
+    depth [B,H*W] or [B,H*W,1] in NeRF units -> depth16 [B,H,W] uint16 = trunc(clamp((depth / depth_scale) * png_per_metre, 0, 65535));
+    NaN gives 0.  Either input may be None (its output is then absent).  ``out``: 'rgb8' / 'depth16' tensors to write into."""
+    if rgb is None and depth is None:
+        raise ValueError("view_images: rgb or depth expected")
+    first = rgb if rgb is not None else depth
+    _want_gpu("view_images", first, "rgb" if rgb is not None else "depth", torch.float32, None)
+    B, HW = int(first.shape[0]), int(H) * int(W)
+    a = _lib.ViewImagesArgs()
+    a.B, a.H, a.W, a.depth_scale, a.png_per_metre = B, int(H), int(W), float(depth_scale), float(png_per_metre)
+    spec = {}
+    if rgb is not None:
+        _want_gpu("view_images", rgb, "rgb", torch.float32, (B, HW, 3))
+        spec["rgb8"] = (torch.uint8, (B, H, W, 3))
+    if depth is not None:
+        if depth.dim() == 3 and depth.shape[-1] == 1:
+            depth = depth[..., 0]
+        _want_gpu("view_images", depth, "depth", torch.float32, (B, HW))
+        spec["depth16"] = (torch.uint16, (B, H, W))
+    res = _outputs("view_images", out, spec, first.device)
+    a.rgb, a.rgb8, a.depth, a.depth16 = _ptr(rgb), _ptr(res.get("rgb8")), _ptr(depth), _ptr(res.get("depth16"))
+    _call("tp_view_images", a)
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K27
+def texture_bake_workspace(V: int, B: int, device) -> Tensor:
+    """A workspace for texture_bake at V vertices and B views (tp_texture_bake_workspace_bytes); needs no clearing."""
+    return _workspace_arg("texture_bake", None, int(_lib.load().tp_texture_bake_workspace_bytes(V, B)), device)
+
+
+@_on_tensor_device
+def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb: Tensor, zbuf: Tensor, weight: Optional[Tensor] = None, *,
+                 acc: Optional[Tensor] = None, count: Optional[Tensor] = None, clear: bool = True, cos_min: float = 0.3,
+                 cover_min: float = 0.5, z_tol_mm: float = 0.5, slope: float = 2.0, workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Project B posed images onto the V vertices of a mesh (tp_texture_bake; the rules are in the header): verts, normals [V,3]
+    (model frame, mm; unit normals), pose [B,3,4] (model -> camera, mm), intr [B,3,3] or one [3,3], rgb [B,H,W,3], zbuf [B,H,W]
+    (mesh_raster's plane), weight [B,H,W] or None -> 'acc' [V,4] float32 (sums of w r, w g, w b, w) and 'count' [V] int32.  ``acc`` /
+    ``count``: the tensors to write into; with ``clear=False`` the call adds to what they hold, so views can be streamed in chunks.
+    ``workspace``: texture_bake_workspace(V, B) (a fresh one otherwise).  Not differentiable.  Two launches, no atomics, safe under
+    torch.cuda.graph."""
+    verts, pose = _points("texture_bake", verts, "verts"), _poses("texture_bake", pose, "pose")
+    V, B = verts.shape[0], pose.shape[0]
+    normals = _points("texture_bake", normals, "normals", V)
+    rgb, zbuf = _f32(rgb.detach(), "rgb"), _f32(zbuf.detach(), "zbuf")
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0 or tuple(rgb.shape) != tuple(zbuf.shape) + (3,):
+        raise ValueError("texture_bake: zbuf [B=%d,H,W] and rgb [B,H,W,3] expected, got %s and %s" % (B, tuple(zbuf.shape), tuple(rgb.shape)))
+    H, W = zbuf.shape[1:]
+    intr = _intr_per_view("texture_bake", intr, B)
+    if weight is not None:
+        weight = _f32(weight.detach(), "weight")
+        if weight.numel() != B * H * W:
+            raise ValueError("texture_bake: weight [B=%d,H=%d,W=%d] expected, got %s" % (B, H, W, tuple(weight.shape)))
+    if (acc is None) != (count is None) or (acc is None and not clear):
+        raise ValueError("texture_bake: acc and count come together, and clear=False needs both")
+    dev = verts.device
+    acc = torch.empty(V, 4, device=dev) if acc is None else _want_gpu("texture_bake", acc, "acc", torch.float32, (V, 4))
+    count = torch.empty(V, device=dev, dtype=torch.int32) if count is None else _want_gpu("texture_bake", count, "count", torch.int32, (V,))
+    workspace = _workspace_arg("texture_bake", workspace, int(_lib.load().tp_texture_bake_workspace_bytes(V, B)), dev)
+    a = _lib.TextureBakeArgs()
+    a.verts, a.normals, a.pose, a.intr = verts.data_ptr(), normals.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.rgb, a.zbuf, a.weight = rgb.data_ptr(), zbuf.data_ptr(), _ptr(weight)
+    a.V, a.B, a.H, a.W, a.clear = V, B, H, W, int(bool(clear))
+    a.cos_min, a.cover_min, a.z_tol_mm, a.slope = float(cos_min), float(cover_min), float(z_tol_mm), float(slope)
+    a.acc, a.count, a.workspace = acc.data_ptr(), count.data_ptr(), workspace.data_ptr()
+    _call("tp_texture_bake", a)        # (thresholds out of range: the library's error)
+    return {"acc": acc, "count": count}
