@@ -1231,6 +1231,62 @@ int tp_pnp_hypotheses(const tp_pnp_hypotheses_args* args, tp_stream_t stream);
 int tp_pnp_score(const tp_pnp_score_args* args, tp_stream_t stream);
 int tp_pnp_refine(const tp_pnp_refine_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K29  one step of batched projective point-to-plane ICP: B poses refined against measured depth (texpose_amd/icp.py; restated in
+ *      tests/icp_ref.py; the project's own step, no reference code).  zbuf / face are K19's planes of the mesh
+ *      rendered at pose; the call compares them with the measured depth and takes one damped Gauss-Newton step of the update
+ *      x' = x + w x x + v in the camera frame (parameters (w, v), as tp_pnp_refine).  Per pixel (row i, column j) of image b, with
+ *      K = intr[b] (fx = K_00, fy = K_11, cx = K_02, cy = K_12), [R|t] = pose[b] and the depth plane fr = frame ? frame[b] CLAMPED
+ *      into [0, Ft) : (Ft == 1 ? 0 : b), everything in fp64 from the fp32 inputs, evaluated as written (no contraction):
+ *        1. z = zbuf[b,i,j];           skipped unless z > 0 and finite
+ *        2. f = face[b,i,j];           skipped unless 0 <= f < F and the three vertex indices of faces[f] lie in [0, V)
+ *        3. d = depth[fr,i,j];         skipped unless d > 0 and finite, and where mask is given and mask[fr,i,j] == 0
+ *        4. ray = ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1),  q = (ray_x^2 + ray_y^2) + 1,  P = z ray,  Q = d ray;
+ *           kept iff ((d - z) * (d - z)) * q <= tau_mm * tau_mm          (a NaN fails)
+ *        5. m = R ((v1 - v0) x (v2 - v0)), each row ((R_k0 c_x + R_k1 c_y) + R_k2 c_z);  skipped unless |m|^2 is finite and > 0;
+ *           n = m * (1 / sqrt(|m|^2)), negated where n . ray > 0: the face's own flat normal, towards the camera
+ *        6. r = n . (P - Q),  J = [P x n, n]
+ *      and the 29 sums of tp_pnp_refine over the kept pixels: the 21 upper-triangle entries of J^T J (row-major), the 6 of J^T r,
+ *      sum r^2 and the count.  A thread owns four consecutive flat pixels (ascending), a workgroup 1024; butterfly sums inside a
+ *      wave, the four waves in ascending order, one record per workgroup, the records in ascending order: no atomics, the outputs
+ *      are a function of the inputs alone, bit-identical from run to run and under graph replay.  Per image:
+ *        inliers = count;  rms = sqrt(sum r^2 / count) in mm (NaN at count 0): both describe `pose`, the pose the planes show
+ *        status  = 1 where count < 6; else 3 where J^T J is NOT POSITIVE DEFINITE by tp_pnp_refine's pivot rule (a Cholesky pivot
+ *                  that is not finite or <= 1e-10 x its diagonal entry), or, without evaluate_only, where the damped matrix does
+ *                  not factor or the stepped pose is not finite in fp32; else 0
+ *        pose_out = (status == 0 and not evaluate_only): (J^T J + damping diag(J^T J)) delta = -J^T r solved by Cholesky,
+ *                  R <- exp(w) R, t <- exp(w) t + v with Rodrigues' formula, Gram-Schmidt on R's first two columns (the third
+ *                  their cross product), rounded to fp32;  otherwise pose, bit for bit (pose_out may be NULL with evaluate_only)
+ *      Status is an output only: a failed step passes its pose through, so a loop over steps needs no state.  Non-positive sizes,
+ *      B > 65535, H * W >= 2^31, without frame an Ft that is neither 1 nor B, a tau_mm that is not finite and positive, a damping
+ *      that is not finite and >= 0, null pointers, a workspace that is not 16-byte aligned and pose_out == pose are refused (-1,
+ *      tp_last_error) before anything is launched.  No input value (NaN, Inf, a face or vertex index out of range, huge poses)
+ *      causes an access out of bounds.  Two launches.  No allocation, no host synchronisation; outputs and workspace must not
+ *      overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_depth_icp_args {
+  const float* verts;        /* [V,3] model frame, mm */
+  const int32_t* faces;      /* [F,3] */
+  const float* zbuf;         /* [B,H,W] K19's depth of the mesh at pose: mm, <= 0 or NaN: background */
+  const int32_t* face;       /* [B,H,W] K19's face index, -1: background */
+  const float* pose;         /* [B,3,4] the pose zbuf and face were rendered at */
+  const float* intr;         /* [B,3,3] */
+  const float* depth;        /* [Ft,H,W] measured depth in mm; <= 0, NaN, Inf: no measurement */
+  const int32_t* frame;      /* [B] index into depth (and mask), or NULL: b when Ft == B, 0 when Ft == 1 */
+  const uint8_t* mask;       /* [Ft,H,W] or NULL; 0: the pixel is skipped */
+  int V, F, B, Ft, H, W;
+  float tau_mm;              /* finite, > 0: the largest distance along the ray between model and measurement of a kept pixel */
+  float damping;             /* finite, >= 0: relative Levenberg damping of the diagonal */
+  int evaluate_only;         /* non-zero: inliers, rms and status of pose; no step */
+  float* pose_out;           /* [B,3,4] out; may be NULL with evaluate_only; must not be pose */
+  int32_t* inliers;          /* [B] out */
+  float* rms;                /* [B] out, mm */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels, 3 not positive definite */
+  void* workspace;           /* tp_depth_icp_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_depth_icp_args;
+size_t tp_depth_icp_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
+int tp_depth_icp_step(const tp_depth_icp_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

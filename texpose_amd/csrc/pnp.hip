@@ -10,6 +10,7 @@
 //                       solve launch per step, keep-best, one final evaluation
 // Integer atomics only; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
+#include "pose_gn.h"
 #include <math.h>
 
 namespace {
@@ -20,7 +21,7 @@ constexpr int kSums = 29;                              // 21 (J^T J, upper trian
 constexpr int kPart = 32;                              // doubles per partial record
 constexpr int kState = 32;                             // doubles per image: cur [12], best [12], best cost, best count, status, n, frozen
 constexpr int S_CUR = 0, S_BEST = 12, S_COST = 24, S_COUNT = 25, S_STATUS = 26, S_N = 27, S_FROZEN = 28;
-constexpr double kLambda = 1e-3, kPivotTol = 1e-10;
+constexpr double kLambda = 1e-3;                      // the damping handed to pose_gn.h's step
 
 __host__ __device__ inline int64_t tiles_of(int64_t n, int tile) { return (n + tile - 1) / tile; }
 __device__ __forceinline__ int clamped_count(const int32_t* count, int b, int N) {
@@ -102,13 +103,6 @@ __global__ __launch_bounds__(kBlock) void corr_write_kernel(CorrP p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- hypotheses
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 scaled(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 unit(V3 a) { return scaled(a, 1.0 / sqrt(dot(a, a))); }
-
 // real roots of y^2 + B y + C (a discriminant that is negative by rounding alone counts as zero)
 __device__ __forceinline__ int quadratic_roots(double B, double C, double* y) {
   double disc = B * B - 4.0 * C;
@@ -420,11 +414,6 @@ __global__ __launch_bounds__(kBlock) void pnp_select_kernel(tp_pnp_refine_args a
   st[S_FROZEN] = 0.0;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {                           // butterfly: the same order, and the same sum, in every lane
-  for (int m = 1; m < tp::kWave; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // grid (ceil(N / 1024), B): the sums of the current pose over this workgroup's points -> part [b][tile][32]
 __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a, const double* state, double* part, int G) {
   __shared__ double wave_part[kWaves][kPart];
@@ -479,24 +468,6 @@ __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a
   }
 }
 
-// Cholesky of the 6x6 matrix A (full storage, lower triangle written); false where a pivot is not finite or <= tol x its diagonal
-__device__ bool cholesky6(double (&A)[6][6], double tol) {
-  for (int j = 0; j < 6; ++j) {
-    const double diag = A[j][j];
-    double d = diag;
-    for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-    if (!isfinite(d) || !(d > tol * diag) || !(d > 0.0)) return false;
-    const double l = sqrt(d);
-    A[j][j] = l;
-    for (int i = j + 1; i < 6; ++i) {
-      double v = A[i][j];
-      for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
-      A[i][j] = v / l;
-    }
-  }
-  return true;
-}
-
 // grid B, one wave: the partials in ascending order, keep-best, then (unless `last`) one damped Gauss-Newton step; `last` writes the outputs
 __global__ __launch_bounds__(tp::kWave) void pnp_solve_kernel(tp_pnp_refine_args a, double* state, const double* part, int G, int last) {
   __shared__ double sum[kPart];
@@ -518,50 +489,11 @@ __global__ __launch_bounds__(tp::kWave) void pnp_solve_kernel(tp_pnp_refine_args
       st[S_COUNT] = count; st[S_COST] = cost;
     }
     if (!last) {
-      double A[6][6], D[6][6];
-      int e = 0;
-      for (int r = 0; r < 6; ++r)
-        for (int c = r; c < 6; ++c) { A[r][c] = A[c][r] = sum[e]; D[r][c] = D[c][r] = sum[e]; ++e; }
-      for (int r = 0; r < 6; ++r) D[r][r] = A[r][r] + kLambda * A[r][r];
-      if (!cholesky6(A, kPivotTol) || !cholesky6(D, 0.0)) {
-        st[S_STATUS] = 3.0; st[S_FROZEN] = 1.0;
+      double Pn[12];
+      if (gn_step(sum, st + S_CUR, kLambda, Pn)) {
+        for (int k = 0; k < 12; ++k) st[S_CUR + k] = Pn[k];
       } else {
-        double d[6];
-        for (int i = 0; i < 6; ++i) {                                            // L y = -J^T r
-          double v = -sum[21 + i];
-          for (int k = 0; k < i; ++k) v -= D[i][k] * d[k];
-          d[i] = v / D[i][i];
-        }
-        for (int i = 5; i >= 0; --i) {                                           // L^T d = y
-          double v = d[i];
-          for (int k = i + 1; k < 6; ++k) v -= D[k][i] * d[k];
-          d[i] = v / D[i][i];
-        }
-        const double wx = d[0], wy = d[1], wz = d[2];
-        const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
-        const double sa = th > 1e-8 ? sin(th) / th : 1.0 - th2 / 6.0;
-        const double sb = th > 1e-8 ? (1.0 - cos(th)) / th2 : 0.5 - th2 / 24.0;
-        // exp(w) = I + sa [w]x + sb [w]x^2
-        const double E[9] = {1.0 - sb * (wy * wy + wz * wz), -sa * wz + sb * wx * wy, sa * wy + sb * wx * wz,
-                             sa * wz + sb * wx * wy, 1.0 - sb * (wx * wx + wz * wz), -sa * wx + sb * wy * wz,
-                             -sa * wy + sb * wx * wz, sa * wx + sb * wy * wz, 1.0 - sb * (wx * wx + wy * wy)};
-        double Pn[12];
-        for (int r = 0; r < 3; ++r) {
-          for (int c = 0; c < 4; ++c) Pn[4 * r + c] = (E[3 * r] * st[c] + E[3 * r + 1] * st[4 + c]) + E[3 * r + 2] * st[8 + c];
-          Pn[4 * r + 3] += d[3 + r];
-        }
-        V3 c1 = unit(V3{Pn[0], Pn[4], Pn[8]});
-        V3 c2 = {Pn[1], Pn[5], Pn[9]};
-        c2 = unit(c2 - scaled(c1, dot(c1, c2)));
-        const V3 c3 = cross(c1, c2);
-        Pn[0] = c1.x; Pn[4] = c1.y; Pn[8] = c1.z; Pn[1] = c2.x; Pn[5] = c2.y; Pn[9] = c2.z; Pn[2] = c3.x; Pn[6] = c3.y; Pn[10] = c3.z;
-        bool ok = true;
-        for (int k = 0; k < 12; ++k) ok = ok && isfinite(Pn[k]);
-        if (ok) {
-          for (int k = 0; k < 12; ++k) st[S_CUR + k] = Pn[k];
-        } else {
-          st[S_STATUS] = 3.0; st[S_FROZEN] = 1.0;
-        }
+        st[S_STATUS] = 3.0; st[S_FROZEN] = 1.0;
       }
     }
   }

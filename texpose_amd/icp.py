@@ -1,0 +1,164 @@
+"""Pose refinement against measured depth: batched projective point-to-plane ICP on the device (K29).
+
+The step between "PnP gave a pose" (texpose_amd.pnp) and "score it" (texpose_amd.pose_error): the mesh is rendered at the current
+poses by the HIP rasteriser, every covered pixel with a measurement within ``tau_mm`` along its ray gives one point-to-plane residual
+against the face's own normal, and one damped Gauss-Newton step in fp64 moves the pose (``ops.depth_icp_step``; ``ops.depth_icp`` is
+the loop).  ``DepthRefiner`` keeps the mesh and the workspace of a batch size.  ``step_torch`` says the step again in plain torch ops
+in fp64: the comparator of tools/icp_bench.py, and the one piece that also runs without a GPU.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import ops
+from .options import AttrDict
+
+Tensor = torch.Tensor
+PIVOT_TOL = 1e-10
+MIN_COUNT = 6
+
+
+def _cholesky6(A: Tensor, tol: float):
+    """Batched Cholesky of A [B,6,6] with the header's pivot rule -> (L [B,6,6], ok [B] bool); rows of a failed matrix hold garbage."""
+    B = A.shape[0]
+    L = torch.zeros_like(A)
+    ok = torch.ones(B, dtype=torch.bool, device=A.device)
+    for j in range(6):
+        diag = A[:, j, j]
+        d = diag - (L[:, j, :j] * L[:, j, :j]).sum(-1)
+        ok = ok & torch.isfinite(d) & (d > tol * diag) & (d > 0)
+        l = torch.sqrt(torch.where(ok, d, torch.ones_like(d)))
+        L[:, j, j] = l
+        for i in range(j + 1, 6):
+            L[:, i, j] = (A[:, i, j] - (L[:, i, :j] * L[:, j, :j]).sum(-1)) / l
+    return L, ok
+
+
+def _exp_so3(w: Tensor) -> Tensor:
+    th2 = (w * w).sum(-1)
+    th = torch.sqrt(th2)
+    big = th > 1e-8
+    safe, safe2 = torch.where(big, th, torch.ones_like(th)), torch.where(big, th2, torch.ones_like(th2))
+    sa = torch.where(big, torch.sin(safe) / safe, 1.0 - th2 / 6.0)[:, None, None]
+    sb = torch.where(big, (1.0 - torch.cos(safe)) / safe2, 0.5 - th2 / 24.0)[:, None, None]
+    Wx = torch.zeros(w.shape[0], 3, 3, dtype=w.dtype, device=w.device)
+    Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0], Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    return torch.eye(3, dtype=w.dtype, device=w.device)[None] + sa * Wx + sb * (Wx @ Wx)
+
+
+def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, tau_mm: float,
+               damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False) -> Dict[str, Tensor]:
+    """ops.depth_icp_step's rules (include/texpose_amd.h, K29) in plain torch ops in fp64 on the tensors' device: the same arguments ->
+    'pose' [B,3,4] float32, 'inliers' [B] int32, 'rms' [B] float32, 'status' [B] int32.  The sums run in torch's order, not the
+    kernel's: counts and statuses agree, the rest to rounding."""
+    f64 = torch.float64
+    dev = zbuf.device
+    B, H, W = zbuf.shape
+    V, F = verts.shape[0], faces.shape[0]
+    verts64, faces = verts.float().to(f64), faces.long()
+    pose32 = pose.float().reshape(B, 3, 4)
+    intr = intr.float()
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3)
+    depth = depth.float()
+    if depth.dim() == 2:
+        depth = depth[None]
+    Ft = depth.shape[0]
+    if frame is None:
+        if Ft not in (1, B):
+            raise ValueError("step_torch: depth must hold 1 or B = %d planes without frame=, got %d" % (B, Ft))
+        fr = torch.zeros(B, dtype=torch.long, device=dev) if Ft == 1 else torch.arange(B, device=dev)
+    else:
+        fr = frame.long().clamp(0, Ft - 1)
+    tau = float(torch.tensor(tau_mm, dtype=torch.float32))
+    lam = float(torch.tensor(damping, dtype=torch.float32))
+    d_all = depth[fr]                                                                       # [B,H,W]
+    zf = zbuf.float()
+    cand = (zf > 0) & torch.isfinite(zf) & (d_all > 0) & torch.isfinite(d_all) & (face >= 0) & (face < F)
+    if mask is not None:
+        m = mask if mask.dim() == 3 else mask[None]
+        cand = cand & (m[fr] != 0)
+    bi, ii, ji = torch.nonzero(cand, as_tuple=True)
+    tri = faces[face[bi, ii, ji].long()]                                                    # [n,3]
+    good = ((tri >= 0) & (tri < V)).all(-1)
+    bi, ii, ji, tri = bi[good], ii[good], ji[good], tri[good]
+    z, d = zf[bi, ii, ji].to(f64), d_all[bi, ii, ji].to(f64)
+    K = intr.to(f64)
+    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / K[bi, 0, 0]
+    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / K[bi, 1, 1]
+    q = (rx * rx + ry * ry) + 1.0
+    dz = d - z
+    v0, v1, v2 = verts64[tri[:, 0]], verts64[tri[:, 1]], verts64[tri[:, 2]]
+    c = torch.cross(v1 - v0, v2 - v0, dim=-1)
+    R = pose32[:, :, :3].to(f64)[bi]                                                        # [n,3,3]
+    mvec = (R[:, :, 0] * c[:, None, 0] + R[:, :, 1] * c[:, None, 1]) + R[:, :, 2] * c[:, None, 2]
+    mm = (mvec[:, 0] * mvec[:, 0] + mvec[:, 1] * mvec[:, 1]) + mvec[:, 2] * mvec[:, 2]
+    keep = ((dz * dz) * q <= tau * tau) & torch.isfinite(mm) & (mm > 0)
+    bi, rx, ry, z, d, mvec, mm = bi[keep], rx[keep], ry[keep], z[keep], d[keep], mvec[keep], mm[keep]
+    n = mvec * (1.0 / torch.sqrt(mm))[:, None]
+    flip = (n[:, 0] * rx + n[:, 1] * ry) + n[:, 2] > 0
+    n = torch.where(flip[:, None], -n, n)
+    ray = torch.stack([rx, ry, torch.ones_like(rx)], -1)
+    P, Q = ray * z[:, None], ray * d[:, None]
+    r = (n * (P - Q)).sum(-1)
+    J = torch.cat([torch.cross(P, n, dim=-1), n], -1)                                       # [n,6]
+    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, bi, J[:, :, None] * J[:, None, :])
+    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
+    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
+    count = torch.bincount(bi, minlength=B)
+    rms = torch.sqrt(cost / count.to(f64))                                                  # (0 / 0: NaN)
+    few = count < MIN_COUNT
+    _, pd = _cholesky6(JtJ, PIVOT_TOL)
+    status = torch.where(few, 1, torch.where(pd, 0, 3))
+    out_pose = pose32.clone()
+    if not evaluate_only:
+        Dm = JtJ + lam * torch.diag_embed(torch.diagonal(JtJ, dim1=1, dim2=2))
+        L, ok = _cholesky6(Dm, 0.0)
+        ok = ok & pd & ~few
+        eye = torch.eye(6, dtype=f64, device=dev)[None]
+        L = torch.where(ok[:, None, None], L, eye)
+        y = torch.linalg.solve_triangular(L, -Jtr[:, :, None], upper=False)
+        delta = torch.linalg.solve_triangular(L.transpose(1, 2), y, upper=True)[:, :, 0]
+        Pn = _exp_so3(delta[:, :3]) @ pose32.to(f64)
+        Pn[:, :, 3] = Pn[:, :, 3] + delta[:, 3:]
+        c1 = Pn[:, :, 0] / torch.linalg.norm(Pn[:, :, 0], dim=-1, keepdim=True)
+        c2 = Pn[:, :, 1] - c1 * (c1 * Pn[:, :, 1]).sum(-1, keepdim=True)
+        c2 = c2 / torch.linalg.norm(c2, dim=-1, keepdim=True)
+        Pn = torch.stack([c1, c2, torch.cross(c1, c2, dim=-1), Pn[:, :, 3]], -1)
+        new32 = Pn.float()
+        ok = ok & torch.isfinite(new32).reshape(B, -1).all(-1)
+        status = torch.where(few, 1, torch.where(ok, 0, 3))
+        out_pose = torch.where(ok[:, None, None], new32, pose32)
+    return dict(pose=out_pose, inliers=count.to(torch.int32), rms=rms.float(), status=status.to(torch.int32))
+
+
+class DepthRefiner:
+    """Depth ICP for batches of poses of one mesh at H x W with the mesh on the device and a workspace per batch size.
+
+    ``tau_mm`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 20.0), ``iters`` (Gauss-Newton steps, 5), ``damping``
+    (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (pixels within tau of the
+    measurement), rms [B] (mm, point-to-plane), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was not
+    positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+
+    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6):
+        self.H, self.W, self.device = int(H), int(W), torch.device(device)
+        if self.device.type != "cuda":
+            raise ops._lib.TexposeLibraryError("DepthRefiner runs the HIP kernels: a GPU device is needed (step_torch alone has a CPU route)")
+        self.verts = torch.as_tensor(verts).to(device=self.device, dtype=torch.float32).contiguous()
+        self.faces = torch.as_tensor(faces).to(device=self.device, dtype=torch.int32).contiguous()
+        self.tau_mm, self.iters, self.damping = tau_mm, int(iters), float(damping)
+        self._workspaces: Dict[int, Tensor] = {}
+
+    def refine(self, pose: Tensor, intr: Tensor, depth: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
+        """pose [B,3,4], intr [B,3,3] or [3,3], depth [Ft,H,W] (mm; 0: no measurement), frame [B] int32 (the plane of each pose; without
+        it Ft is 1 or B), mask [Ft,H,W] uint8 / bool (0: do not use the pixel)."""
+        depth = depth if depth.dim() == 3 else depth[None]
+        if tuple(depth.shape[1:]) != (self.H, self.W):
+            raise ValueError("DepthRefiner.refine: depth planes of %d x %d expected, got %s" % (self.H, self.W, tuple(depth.shape)))
+        B = pose.shape[0]
+        if B not in self._workspaces:
+            self._workspaces[B] = ops.depth_icp_workspace(B, self.H, self.W, self.device)
+        return AttrDict(ops.depth_icp(self.verts, self.faces, pose, intr, depth, tau_mm=self.tau_mm, iters=self.iters, damping=self.damping,
+                                      frame=frame, mask=mask, workspace=self._workspaces[B]))

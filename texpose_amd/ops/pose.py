@@ -1,4 +1,4 @@
-"""K24-K26, K28: nearest neighbours, the pose errors, VSD and PnP-RANSAC."""
+"""K24-K26, K28, K29: nearest neighbours, the pose errors, VSD, PnP-RANSAC and the depth ICP."""
 from typing import Dict, Optional
 
 import torch
@@ -8,7 +8,8 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _lengths, _on_
                     _workspace_arg)
 
 __all__ = ["NN1_MODES", "nn1", "pose_errors", "vsd", "PNP_MAX_HYP", "PNP_MAX_ITERS", "pnp_workspace", "_pnp_common", "corr_from_nocs",
-           "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac"]
+           "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac", "depth_icp_workspace", "depth_icp_step",
+           "DEPTH_ICP_KEYS", "depth_icp"]
 
 # ------------------------------------------------------------------------------------------ K24, K25
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
@@ -275,3 +276,111 @@ def pnp_ransac(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, *, T: int =
     res = pnp_refine(xy, xyz, count, intr, hy["hyp"], inl, hy["hyp_valid"], tau_px=tau_px, iters=iters, workspace=workspace, out=out)
     res.update(hy, hyp_inliers=inl)
     return res
+
+
+# ------------------------------------------------------------------------------------------ K29
+def depth_icp_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for depth_icp_step / depth_icp at B images of H x W (tp_depth_icp_workspace_bytes); needs no clearing."""
+    return _workspace_arg("depth_icp", None, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), device)
+
+
+def _depth_icp_planes(op: str, depth: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
+    depth = _f32(depth.detach(), "depth")
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3 or tuple(depth.shape[1:]) != (H, W) or depth.shape[0] == 0:
+        raise ValueError("%s: depth [Ft,H=%d,W=%d] expected, got %s" % (op, H, W, tuple(depth.shape)))
+    Ft = depth.shape[0]
+    frame = _lengths(op, frame, "frame", B, like)
+    if frame is None and Ft not in (1, B):
+        raise ValueError("%s: depth must hold 1 or B = %d planes without frame=, got %d" % (op, B, Ft))
+    if mask is not None:
+        if torch.is_tensor(mask) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+        if torch.is_tensor(mask) and mask.dim() == 2:
+            mask = mask[None]
+        mask = _want_gpu(op, mask, "mask", torch.uint8, (Ft, H, W))
+    return depth, frame, mask, Ft
+
+
+@_on_tensor_device
+def depth_icp_step(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, *, tau_mm: float,
+                   damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                   workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of projective point-to-plane ICP for B poses (tp_depth_icp_step; the rules are in the header): verts [V,3], faces [F,3]
+    int32, zbuf / face [B,H,W] (mesh_raster's planes of the mesh at ``pose``; taken as they are), pose [B,3,4], intr [B,3,3] or one
+    [3,3], depth [Ft,H,W] (the measured depth in mm; <= 0, NaN, Inf: no value; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask
+    [Ft,H,W] uint8 or bool (0: skip the pixel) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with
+    ``evaluate_only`` or a non-zero status), 'inliers' [B] int32 and 'rms' [B] (mm) of ``pose`` over the pixels within tau_mm along
+    the ray, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
+    depth_icp_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches, no
+    atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "depth_icp_step"
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = _want_gpu(op, faces, "faces", torch.int32, None)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise ValueError("%s: faces [F,3] expected, got %s" % (op, tuple(faces.shape)))
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B=%d,H,W] expected, got %s" % (op, B, tuple(zbuf.shape)))
+    H, W = zbuf.shape[1:]
+    face = _want_gpu(op, face, "face", torch.int32, (B, H, W))
+    intr = _intr_per_view(op, intr, B)
+    depth, frame, mask, Ft = _depth_icp_planes(op, depth, frame, mask, B, H, W, zbuf)
+    dev = zbuf.device
+    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+                             "status": (torch.int32, (B,))}, dev, partial=True)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), dev, align=16)
+    a = _lib.DepthIcpArgs()
+    a.verts, a.faces, a.zbuf, a.face, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), zbuf.data_ptr(), face.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.depth, a.frame, a.mask = depth.data_ptr(), _ptr(frame), _ptr(mask)
+    a.V, a.F, a.B, a.Ft, a.H, a.W = verts.shape[0], faces.shape[0], B, Ft, H, W
+    a.tau_mm, a.damping, a.evaluate_only = float(tau_mm), float(damping), int(bool(evaluate_only))
+    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
+                                                           res["status"].data_ptr(), workspace.data_ptr())
+    _call("tp_depth_icp_step", a)         # (tau_mm, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+DEPTH_ICP_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
+
+
+@_on_tensor_device
+def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6,
+              frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against measured depth (the rules are in the header, K29): ``iters`` + 1 passes of mesh_raster at the
+    current poses (depth and face index, H x W = depth's) followed by depth_icp_step, the last with evaluate_only.  ``tau_mm``: one
+    value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose' [B,3,4], its
+    'inliers' [B] int32 and 'rms' [B] (mm), 'status' [B] int32 of the last step taken (of the evaluation where iters = 0) and
+    'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the rasteriser's,
+    bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "depth_icp"
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
+    taus = [float(tau_mm)] * (iters + 1) if isinstance(tau_mm, (int, float)) else [float(t) for t in tau_mm]
+    if len(taus) != iters + 1:
+        raise ValueError("%s: tau_mm must be one value or iters + 1 = %d values, got %d" % (op, iters + 1, len(taus)))
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    depth = _f32(depth.detach(), "depth")
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError("%s: depth [Ft,H,W] expected, got %s" % (op, tuple(depth.shape)))
+    H, W = depth.shape[1:]
+    intr = _intr_per_view(op, intr, B)
+    depth, frame, mask, _ = _depth_icp_planes(op, depth, frame, mask, B, H, W, pose)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), pose.device, align=16)
+    from .scene import mesh_raster
+    res, first, status = None, None, None
+    for it, tau in enumerate(taus):
+        r = mesh_raster(verts, faces, pose, intr, H=H, W=W, face_ids=True, normals=False)
+        res = depth_icp_step(verts, faces, r["zbuf"], r["face"], pose, intr, depth, tau_mm=tau, damping=damping, frame=frame, mask=mask,
+                             evaluate_only=it == iters, workspace=workspace)
+        first = res if first is None else first
+        status = res["status"] if it < iters or status is None else status
+        pose = res["pose"]
+    return dict(pose=res["pose"], inliers=res["inliers"], rms=res["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"])

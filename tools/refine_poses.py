@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Refine the estimated poses of a BOP results CSV against the depth images of a scene folder by batched projective ICP on the GPU
+(texpose_amd.icp, K29), written as the same CSV format, so that tools/pose_errors.py --est scores it unchanged.
+
+    python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
+
+--scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
+measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
+scene where the file holds several.  --ply: the object's mesh; a bare PATH serves every object id of the CSV, ID=PATH that object alone;
+rows of an object without a mesh are copied unchanged.  Each kept row is refined by --iters Gauss-Newton steps (the mesh rendered at
+the current pose, the covered pixels within --tau-mm of the measurement along their ray against the faces' normals; several --tau-mm
+values: a coarse-to-fine schedule of iters + 1 entries) and written with its score unchanged and the per-pose time of its batch added
+to its time.  --use-mask-visib: only the pixels of mask_visib/{frame:06d}_{k:06d}.png are used, k the object's first instance of the
+frame in scene_gt.json.  A pose whose last step failed (fewer than six usable pixels, a rank-deficient system) is written as the loop
+left it; the tool prints how many."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def read_rows(path, scene_id=None):
+    """The CSV's rows in file order: [scene_id, im_id, obj_id, score, R [3,3], t [3], time]."""
+    rows = []
+    with open(path, newline="") as f:
+        for row in csv.reader(f):
+            if not row or not row[0].strip().lstrip("-").isdigit():          # (the header line, blank lines)
+                continue
+            sid = int(row[0])
+            if scene_id is not None and sid != scene_id:
+                continue
+            R, t = np.array(row[4].split(), dtype=np.float64), np.array(row[5].split(), dtype=np.float64)
+            if R.size != 9 or t.size != 3:
+                raise ValueError("%s: R must hold 9 and t 3 numbers (frame %s, object %s)" % (path, row[1], row[2]))
+            rows.append([sid, int(row[1]), int(row[2]), float(row[3]), R.reshape(3, 3), t, float(row[6]) if len(row) > 6 and row[6].strip() else 0.0])
+    return rows
+
+
+def write_rows(path, rows):
+    with open(path, "w") as f:
+        f.write("scene_id,im_id,obj_id,score,R,t,time\n")
+        for sid, frame, oid, score, R, t, dt in rows:
+            f.write("%d,%d,%d,%.6f,%s,%s,%.6f\n" % (sid, frame, oid, score, " ".join("%.9g" % v for v in np.reshape(R, -1)),
+                                                     " ".join("%.9g" % v for v in np.reshape(t, -1)), dt))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scene", required=True, metavar="SCENE_DIR")
+    ap.add_argument("--ply", action="append", required=True, metavar="[ID=]PATH")
+    ap.add_argument("--est", required=True, metavar="CSV")
+    ap.add_argument("--out", required=True, metavar="CSV")
+    ap.add_argument("--scene-id", type=int, default=None)
+    ap.add_argument("--tau-mm", type=float, nargs="+", default=[20.0])
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--damping", type=float, default=1e-6)
+    ap.add_argument("--use-mask-visib", action="store_true")
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if not a.device.startswith("cuda"):
+        sys.exit("refine_poses: the refinement runs the HIP kernels, which have no CPU route; use --device cuda:N")
+    if len(a.tau_mm) not in (1, a.iters + 1):
+        sys.exit("refine_poses: --tau-mm takes one value or iters + 1 = %d values" % (a.iters + 1))
+    import torch
+    from PIL import Image
+    from texpose_amd import icp
+    from texpose_amd.pose_error import depth_from_png
+    from texpose_amd.surfel import load_ply
+    if not torch.cuda.is_available():
+        sys.exit("refine_poses: needs a GPU")
+    meshes = {}
+    for item in a.ply:
+        oid, sep, path = item.partition("=")
+        if sep and oid.strip().isdigit():
+            meshes[int(oid)] = load_ply(path)[:2]
+        else:
+            meshes[None] = load_ply(item)[:2]
+    cam = json.load(open(os.path.join(a.scene, "scene_camera.json")))
+    gt = None
+    if a.use_mask_visib:
+        gt = json.load(open(os.path.join(a.scene, "scene_gt.json")))
+    rows = read_rows(a.est, a.scene_id)
+    jobs = {}                                                   # object id -> indices into rows
+    for i, row in enumerate(rows):
+        if row[2] in meshes or None in meshes:
+            if str(row[1]) not in cam:
+                sys.exit("refine_poses: frame %d is not in scene_camera.json" % row[1])
+            jobs.setdefault(row[2], []).append(i)
+    tau = a.tau_mm[0] if len(a.tau_mm) == 1 else a.tau_mm
+    refined = failed = 0
+    dev = a.device
+    for oid, idx in jobs.items():
+        verts, faces = meshes.get(oid, meshes.get(None))
+        refiner = None
+        for s in range(0, len(idx), a.batch):
+            part = idx[s:s + a.batch]
+            frames = sorted({rows[i][1] for i in part})
+            planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
+                      for f in frames]
+            depth = torch.stack(planes)
+            H, W = depth.shape[1:]
+            mask = None
+            if a.use_mask_visib:
+                ms = []
+                for f in frames:
+                    ks = [k for k, e in enumerate(gt[str(f)]) if int(e["obj_id"]) == oid]
+                    path = os.path.join(a.scene, "mask_visib", "%06d_%06d.png" % (f, ks[0])) if ks else None
+                    if path is None or not os.path.exists(path):
+                        sys.exit("refine_poses: --use-mask-visib: no mask_visib image of object %d in frame %d" % (oid, f))
+                    ms.append((np.asarray(Image.open(path)) != 0).astype(np.uint8))
+                mask = torch.from_numpy(np.stack(ms)).to(dev)
+            if refiner is None or (refiner.H, refiner.W) != (H, W):
+                refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping)
+            pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
+            K = np.stack([np.array(cam[str(rows[i][1])]["cam_K"], np.float32).reshape(3, 3) for i in part])
+            index = torch.tensor([frames.index(rows[i][1]) for i in part], dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            r = refiner.refine(torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev), depth.to(dev), frame=index, mask=mask)
+            out, status = r.pose.double().cpu().numpy(), r.status.cpu().numpy()
+            dt = (time.time() - t0) / len(part)
+            for k, i in enumerate(part):
+                rows[i][4], rows[i][5], rows[i][6] = out[k, :, :3], out[k, :, 3], rows[i][6] + dt
+                refined += 1
+                failed += int(status[k] != 0)
+    write_rows(a.out, rows)
+    print("refine_poses: %d rows, %d refined (%d with a failed last step) -> %s" % (len(rows), refined, failed, a.out))
+    return rows
+
+
+if __name__ == "__main__":
+    main()
