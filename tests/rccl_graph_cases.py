@@ -82,7 +82,7 @@ def run_linear(mode):
                 raised = extra
                 break
         assert raised is not None and (raised >= 1 or not forced), raised           # (several ranks: the word travels through a pack first)
-        assert "_poll_on_side" not in tr.__dict__
+        assert tr._poll_on_side is None
         res["raised_after"] = raised
         return res, (tr, graph)
     finally:

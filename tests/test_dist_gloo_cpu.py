@@ -436,12 +436,14 @@ def test_graphed_trainer_form_selection_for_several_ranks(monkeypatch):
     tr = GraphedGanTrainer(opt, g, n_train=4)
     batch = AttrDict(idx=torch.arange(2))
     assert not tr._split_around_collectives() and not tr._has_collective()          # one rank: one graph, no collective
+    assert tr.form is None
+    tr._graph = "captured"                                    # (`form` is None while no step is captured; graph B is made by the capture)
     tr._select_form(batch)
-    assert not (tr._linear or tr._dp)
+    assert not (tr._linear or tr._dp) and tr.form == "one_graph"
     monkeypatch.setattr(tdist.FlatGradAllReducer, "world_size", property(lambda self: 2))
     assert tr._has_collective() and tr._split_around_collectives()                   # several ranks: A | reduce | B
     tr._select_form(batch)
-    assert not (tr._linear or tr._dp)
+    assert not (tr._linear or tr._dp) and tr.form == "one_graph"
     # (b) the full GAN iteration, as the GPU sees it (the predicates that need the HIP kernels are answered "yes" here)
     opt = default_options(H=32, W=32, device="cpu")
     g = Graph(opt, discriminator=Discriminator(opt))
@@ -450,8 +452,9 @@ def test_graphed_trainer_form_selection_for_several_ranks(monkeypatch):
     monkeypatch.setattr(GraphedGanTrainer, "_use_linear_graphs", lambda self, var: True)
     tr.optim_nerf = FusedAdam([dict(params=tr.nerf_group, lr=tr.lr_nerf_used)], capturable=True)
     tr.optim_disc = FusedRMSprop([dict(params=tr.disc_group, lr=tr.lr_disc_used)], capturable=True)
+    tr._graph = "captured"
     tr._select_form(batch)
-    assert tr._linear and tr._dp
+    assert tr._linear and tr._dp and tr.form == "linear_dp"
     assert tr.optim_nerf.gate.data_ptr() == tr.red_nerf.gate_words.data_ptr() and tr.optim_nerf.gate.dtype == torch.int32
     assert tr.optim_disc.gate.data_ptr() == tr.red_disc.gate_words.data_ptr() and len(tr.optim_disc.gate) == 3
     assert tr._poll_words().data_ptr() == tr.red_nerf.gate_words.data_ptr()
@@ -459,14 +462,20 @@ def test_graphed_trainer_form_selection_for_several_ranks(monkeypatch):
     knobs.reload()
     tr._select_form(batch)
     assert not (tr._linear or tr._dp) and tr.optim_nerf.gate is tr._gate_nerf      # the generic two-graph form
+    assert tr.form == "one_graph"
+    tr._graph_b = "captured"
+    assert tr.form == "two_graphs_eager_collectives"
+    tr._graph_b = None
     monkeypatch.delenv("TP_NO_LINEAR_DP")
     knobs.reload()
     monkeypatch.setattr(tdist.FlatGradAllReducer, "world_size", property(lambda self: 1))
     tr._select_form(batch)
     assert tr._linear and not tr._dp and tr.optim_nerf.gate is tr._gate_nerf and tr.optim_disc.gate is tr._gate_disc
+    assert tr.form == "linear"
     assert tr._poll_words() is tr._bad
     # the job-wide gate state of the `_dp` form is read from the two tails
     tr._dp = True
+    assert tr.form == "linear_dp"
     tr.red_disc.flag_tail[2] = 2.0                   # (two ranks raised word 2)
     assert tr._read_bad(blocking=True) == [0, 0, 1]
 

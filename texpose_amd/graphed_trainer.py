@@ -3,6 +3,8 @@ model/nerf_adapt_st_gan.py:108-202): `GraphedGanTrainer`, the captured twin of `
 bounds the iteration and the several-rank form are described in DESIGN.md sections 5 and 6."""
 from __future__ import annotations
 
+import collections
+import contextlib
 import copy
 import warnings
 
@@ -17,6 +19,27 @@ from .trainer import FusedAdam, FusedRMSprop, GanTrainer
 
 class _FormUnavailable(Exception):
     """Raised inside a warm-up iteration when the selected multi-graph form does not cover this configuration after all."""
+
+
+# The linear graphs (`_capture_linear`, `_replay_linear`; the sketch above `_seg_feat`), one row each: the stream it is captured on, the
+# stream it replays on ("main" = the capture stream, "side" = the discriminator's, "third"), the graph whose memory pool it shares
+# (None: its own) and the names of the TP_STAMPS stamps in front of and behind its segment (None: no stamp).  F is captured on the
+# third stream although it replays on `main`, G2a the other way round: per-stream kernel state -- tile counters, workspaces -- is
+# keyed by the CAPTURING stream, and the two run beside each other.
+LinearGraph = collections.namedtuple("LinearGraph", "captured_on replays_on pool stamp_before stamp_after")
+LINEAR_GRAPHS = {
+    "D1":  LinearGraph("side",  "side",  None, "D1.0",  "D1.1"),
+    "D1b": LinearGraph("side",  "side",  "D1", None,    None),
+    "G1":  LinearGraph("main",  "main",  None, "G1.0",  "G1.1"),
+    "F":   LinearGraph("third", "main",  None, "F.0",   "F.1"),
+    "G2a": LinearGraph("main",  "third", "G1", "G2a.0", "G2a.1"),
+    "G2b": LinearGraph("main",  "main",  "G1", "G2b.0", "G2b.1"),
+    "G2c": LinearGraph("main",  "main",  "G1", None,    None),
+    "D2a": LinearGraph("side",  "side",  "D1", "D2.0",  "D2a.1"),
+    "D2b": LinearGraph("side",  "side",  "D1", None,    "D2.1"),
+    "D2":  LinearGraph("side",  "side",  "D1", "D2.0",  "D2.1"),
+    "D2c": LinearGraph("side",  "side",  "D1", None,    None),
+}
 
 
 class GraphedGanTrainer(GanTrainer):
@@ -52,11 +75,11 @@ class GraphedGanTrainer(GanTrainer):
 
     def __init__(self, opt, graph: Graph, n_train: int, max_iter: int = 6000 * 189 // 8, group=None):
         super().__init__(opt, graph, n_train, max_iter, group=group)
-        self._graph = None
-        self._graph_b = None
-        self._deferred = False
-        self._static_in = None
-        self._static_loss = None
+        self._graph = None                       # `capture`: the generic form's graph (or its first half); not None once ANY form is captured
+        self._graph_b = None                     # `capture`, generic form with collectives: the optimiser steps behind the eager all-reduces
+        self._static_in = None                   # `capture`: the static tensors every replay reads its inputs from
+        self._static_loss = None                 # `capture`: the static tensors every replay leaves its losses in
+        self._deferred = False                   # `_body_a`: the optimiser steps (and reductions) follow after it
         dev = self.lr_nerf.device
         # sticky device words of the step gate: [range flag, non-finite nerf loss, non-finite discriminator loss] seen; the
         # gates are 1 only while all are 0 (separate words: the two branches of the captured step never write the same one)
@@ -71,8 +94,11 @@ class GraphedGanTrainer(GanTrainer):
         # opt-in: `train_iteration` returns with the calling stream ordered behind the consumption of its inputs, not behind its results
         # (read losses / parameters behind `wait_all()`); the linear graphs only (`_replay_linear`)
         self.defer_results = knobs.K.defer_results
-        self._d2_pending = False
+        self._g2_pending = self._d2_pending = False      # `_replay_linear`: the calling stream has not waited for ev g2 / ev d2 yet (`wait_all`)
         self._graphs, self._events = None, None  # the captured linear graphs by name, the events that order them across streams
+        self._graphs_keep = None                 # `_capture_linear`: what the segments returned, referenced for the life of the graphs
+        self._first_replay = False               # `_capture_linear` sets it, the first `_replay_linear` clears it: no event recorded yet
+        self._capture_stream = None              # `capture`: the stream the warm-up and the captures run on (`main` of the linear graphs)
         self._linear = False                     # the step as LINEAR graphs on three streams (`_use_linear_graphs`)
         self._dp = False                         # ... with a gradient all-reduce between each gradient graph and its optimiser graph
         # what the optimiser launches read: the words as they stood when the step's own flags had been folded in
@@ -81,7 +107,17 @@ class GraphedGanTrainer(GanTrainer):
             self.optim_nerf.gate = self._gate_nerf
         if self.has_disc and isinstance(self.optim_disc, FusedRMSprop):
             self.optim_disc.gate = self._gate_disc
-        self._bad_poll = None
+        self._bad_poll = None                    # `train_iteration` / `_replay_linear`: (pinned words, event behind their copy), until read
+        self._bad_host = None                    # `_bad_poll_slot`: the pinned host words of that copy, made on first use
+        self._rng_counter = None                 # `capture`: the device step counter of the in-kernel random draws (stays None with TP_TORCH_RNG=1)
+        self._extra_slots = None                 # `_capture_linear`: the word the TP_EXTRA_LAUNCHES launches write
+        self._stamps, self._stamp_names = None, None     # `_capture_linear` with TP_STAMPS=1: the device clock words and their names
+        # hand-overs: `train_iteration` sets them for the `_replay_linear` it calls, which reads each one and resets it to None
+        self._caller_mark = None                 # the event on the caller's stream in front of the step-input launch
+        self._inputs_event = None                # `defer_results`: the event behind the step-input launch on the third stream
+        self._poll_on_side = None                # `defer_results`, several ranks: pinned words the discriminator stream copies the gate words to
+        self.collective_events = None            # a caller sets a list: (name, start, end) HIP events around every all-reduce (`_timed`)
+        # (`launch_counts`: nodes per captured graph, and `queue_probe`: what the stream probe found, are GanTrainer's: `capture` fills them)
 
     # the guards run INSIDE the captured step: no host read, the update is multiplied by the 0/1 gate
     def _gate(self, ok, grads, lr, lr_used):
@@ -92,13 +128,6 @@ class GraphedGanTrainer(GanTrainer):
         flat = torch.where(ok, flat, torch.zeros((), device=flat.device))
         torch._foreach_copy_(grads, [v.view_as(g) for v, g in zip(flat.split([g.numel() for g in grads]), grads)])
         lr_used.copy_(lr * ok.to(torch.float32))
-
-    def _flag_nerf(self, loss):
-        """Before the backward (and before the branches of the step fork): fold this forward's range flag and the finiteness
-        of its loss into the sticky words and snapshot them as the nerf gate (which so also sees a discriminator flag of
-        EARLIER steps, never a concurrent write of this one).  One launch (K13 tp_step_flags)."""
-        status = ops.mlp_status(loss.all.device) if self._uses_f16x3() else None
-        ops.step_flags(loss.all, self._bad, 1, self._gate_nerf, status=status, word_status=0)
 
     def _guard_nerf(self, var, loss):
         if getattr(self.optim_nerf, "gate", None) is None:       # a stock optimiser: zero the gradients and the rate instead
@@ -151,6 +180,28 @@ class GraphedGanTrainer(GanTrainer):
             self._body_b()
         return out
 
+    @contextlib.contextmanager
+    def _render_prologue(self, var):
+        """What precedes the render in every form: yields ``var`` with its patch coordinates (and, with TP_TORCH_RNG=1, the jitter)."""
+        # The step counter of the in-kernel random draws belongs to THIS step function (its loss-total launch advances it): the
+        # graph object and its patch sampler see it only while the step is being issued, so that an eager trainer driving the same
+        # Graph afterwards draws from torch's generator as before instead of repeating one jitter pattern.
+        opt, counter = self.opt, self._rng_counter
+        self.graph.step_counter = self.graph.patch_sampler.device_counter = counter
+        try:
+            var = self.graph.get_ray_idx(opt, var)
+            if opt.nerf.sample_stratified and "jitter_rand" not in var and counter is None:
+                B, R = opt.batch_size, opt.patch_size ** 2
+                var.jitter_rand = torch.rand(B, R, opt.nerf.sample_intvs, 1, device=var.ray_idx.device)   # (TP_TORCH_RNG=1)
+            yield var
+        finally:
+            self.graph.step_counter = self.graph.patch_sampler.device_counter = None
+
+    def _nerf_gate_flags(self, dev):
+        """`_weighted_total(flags=)` of the nerf step: range flag and finiteness into the sticky words, gate snapshot, counter advance."""
+        status = ops.mlp_status(dev) if self._uses_f16x3() else None
+        return dict(bad=self._bad, word_finite=1, snapshot=self._gate_nerf, status=status, word_status=0, step_counter=self._rng_counter)
+
     def _body_a(self, var):
         """After the render and its losses the step forks (reference order kept where it matters: the nerf
         step's discriminator forward -- its power iteration -- comes first): the generator branch (feature-network and
@@ -160,34 +211,20 @@ class GraphedGanTrainer(GanTrainer):
         launch gaps of one chain of small dependent kernels are filled by the other: 2.50 -> 2.30 ms at B=4.
         With a gradient all-reduce in the step (`_deferred`) the branches only produce gradients and flags; reductions and
         both optimiser steps follow after the join (`_reduce_all`, `_body_b`)."""
-        opt = self.opt
         dev = var.idx.device
         overlap = self.has_disc and not knobs.K.no_branch_overlap
         if overlap and self._side is None:
             self._side = torch.cuda.Stream(device=dev)
-        if overlap and getattr(self.graph, "feat_stream", None) is None and not knobs.K.no_feat_branch:
+        if overlap and self._third is None and not knobs.K.no_feat_branch:
             # third chain of the replayed step: the feature network's forward and backward (graph.Graph._feature_loss_early)
             self.graph.feat_stream = torch.cuda.Stream(device=dev)
         self._prefetch_spectral_weights(var)                         # (first: it runs beside everything up to the render)
-        B, R = opt.batch_size, opt.patch_size ** 2
-        # the step counter of the in-kernel random draws belongs to THIS step function (its loss-total launch advances it): the
-        # graph object and its patch sampler see it only while the step is being issued, so that an eager trainer driving the same
-        # Graph afterwards draws from torch's generator as before instead of repeating one jitter pattern
-        counter = getattr(self, "_rng_counter", None)
-        self.graph.step_counter = self.graph.patch_sampler.device_counter = counter
-        try:
-            var = self.graph.get_ray_idx(opt, var)
-            if opt.nerf.sample_stratified and "jitter_rand" not in var and counter is None:
-                var.jitter_rand = torch.rand(B, R, opt.nerf.sample_intvs, 1, device=var.ray_idx.device)   # (TP_TORCH_RNG=1)
+        with self._render_prologue(var) as var:
             var, loss = self.nerf_forward_loss(var)
-        finally:
-            self.graph.step_counter = self.graph.patch_sampler.device_counter = None
         # loss total + step gate in one launch: this forward's range flag and the finiteness of its loss go into the sticky words,
         # which are snapshot as the nerf gate BEFORE the backward and before the branches fork (so the gate also sees a
         # discriminator flag of earlier steps, never a concurrent write of this one)
-        status = ops.mlp_status(dev) if self._uses_f16x3() else None
-        terms, ws = self._weighted_total(loss, flags=dict(bad=self._bad, word_finite=1, snapshot=self._gate_nerf, status=status,
-                                                          word_status=0, step_counter=getattr(self, "_rng_counter", None)))
+        terms, ws = self._weighted_total(loss, flags=self._nerf_gate_flags(dev))
         dloss = None
         # optimiser steps (and reductions) after this function: whenever a collective is part of the step, or on request
         self._deferred = self._has_collective() or self._split_around_collectives()
@@ -266,28 +303,22 @@ class GraphedGanTrainer(GanTrainer):
         # (the consumers run in OTHER graphs / on the other stream: their ordering behind this segment is the ev_sn event of the
         # replay loop, not a wait recorded while one of them is being captured)
         disc._sn_queue = [(o, sg, u, v, None) for o, sg, u, v, _ in disc._sn_queue]
+        return list(disc._sn_queue)                  # (the normalised sets cross the streams: `_capture_linear` keeps them referenced)
 
     def _seg_render(self, var):
-        opt = self.opt
-        counter = getattr(self, "_rng_counter", None)
-        self.graph.step_counter = self.graph.patch_sampler.device_counter = counter
         # the patch coordinates and the latent rows ride in the ray-generation launch (Graph.render, tp_raygen_train)
         self.graph.fuse_prologue = not knobs.K.no_fused_prologue
         try:
-            var = self.graph.get_ray_idx(opt, var)
-            if opt.nerf.sample_stratified and "jitter_rand" not in var and counter is None:
-                B, R = opt.batch_size, opt.patch_size ** 2
-                var.jitter_rand = torch.rand(B, R, opt.nerf.sample_intvs, 1, device=var.ray_idx.device)
-            var, _ = self.nerf_forward_loss(var, stage="render")
+            with self._render_prologue(var) as var:
+                var, _ = self.nerf_forward_loss(var, stage="render")
         finally:
-            self.graph.step_counter = self.graph.patch_sampler.device_counter = None
             self.graph.fuse_prologue = False
         return var
 
     def _seg_disc(self, var):
         out = self.disc_step(var, apply=not self._dp)
-        if self._dp:
-            self._seg_disc_pack()
+        if self._dp:                        # several ranks: the gradient graph ends with the pack (see `_seg_gen_b`)
+            self.red_disc.pack(flags=self._bad)
         return out
 
     def disc_step_zero_grads(self):
@@ -320,8 +351,8 @@ class GraphedGanTrainer(GanTrainer):
         with torch.no_grad():
             res = ctx.sched.run_paired_b(ctx, 10 ** float(lw.gan_reg_real), step=self._disc_step_tail(ctx.sched))
         out = self._disc_step_scheduled_post(var, res, ctx.real, ctx.fake, not self._dp)
-        if self._dp:
-            self._seg_disc_pack()
+        if self._dp:                        # several ranks: the gradient graph ends with the pack (see `_seg_gen_b`)
+            self.red_disc.pack(flags=self._bad)
         return out
 
     def _disc_step_tail(self, sched):
@@ -380,6 +411,7 @@ class GraphedGanTrainer(GanTrainer):
             (var.g_rgb_feat,) = torch.autograd.grad(feat, var.rgb_feat, grad_outputs=self._weight(self.opt.loss_weight.feat, feat.device))
         # (compute_loss takes the value from here; `joined`: the replay loop orders the streams, no wait is recorded in a capture)
         var.feat_early, var.feat_early_for, var.feat_early_joined = feat.detach(), var.ray_idx, True
+        return var
 
     def _seg_gen_a(self, var):
         lw = self.opt.loss_weight
@@ -402,12 +434,9 @@ class GraphedGanTrainer(GanTrainer):
 
     def _seg_gen_b(self, var, loss, g_disc):
         dev, lw = var.idx.device, self.opt.loss_weight
-        status = ops.mlp_status(dev) if self._uses_f16x3() else None
         keys = [k for k in loss if k != "all" and lw[k] is not None]
         # (the total + gate ride in the first launch of the backward pass, K8's: nothing differentiates through them)
-        terms, ws = self._weighted_total(loss, flags=dict(bad=self._bad, word_finite=1, snapshot=self._gate_nerf, status=status,
-                                                          word_status=0, step_counter=getattr(self, "_rng_counter", None)),
-                                         defer=not knobs.K.no_total_in_bwd)
+        terms, ws = self._weighted_total(loss, flags=self._nerf_gate_flags(dev), defer=not knobs.K.no_total_in_bwd)
         roots = {"gan_nerf": (var.rgb_disc, g_disc)}
         if "g_rgb_feat" in var:                        # (the feature chain ran as a graph of its own, `_seg_feat`)
             roots["feat"] = (var.rgb_feat, var.g_rgb_feat)
@@ -429,26 +458,23 @@ class GraphedGanTrainer(GanTrainer):
         self.optim_nerf.step()
         self.graph.nerf.mark_heads_dirty()
 
-    def _seg_disc_pack(self):
-        """End of the discriminator step's gradient graph with several ranks (see `_seg_gen_b`)."""
-        self.red_disc.pack(flags=self._bad)
-
     def _seg_disc_c(self):
         self.red_disc.adopt()
         self.optim_disc.step()
 
     def _collective(self, name, red):
-        """One flat all-reduce on the current stream, between two graph replays; HIP events around it when `collective_events` is a
-        list (bench.py / tools/train_dp.py: the xGMI figure)."""
-        ev = getattr(self, "collective_events", None)
-        if ev is None:
-            red.all_reduce()
-            return
+        """One flat all-reduce on the current stream, between two graph replays."""
+        self._timed(name, red.all_reduce)
+
+    def _timed(self, name, reduce):
+        """``reduce()`` on the current stream; between two HIP events, kept under ``name``, when `collective_events` is a list."""
+        if self.collective_events is None:                       # (a list: bench.py / tools/train_dp.py, the xGMI figure)
+            return reduce()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        red.all_reduce()
+        reduce()
         e1.record()
-        ev.append((name, e0, e1))
+        self.collective_events.append((name, e0, e1))
 
     def _linear_eager(self, var):
         """The segments on their streams, eagerly (warm-up), with the same dependencies as the replays."""
@@ -493,10 +519,8 @@ class GraphedGanTrainer(GanTrainer):
 
     def _stamp(self, name):
         """TP_STAMPS=1 (tools/linear_timeline.py): a one-thread launch writing the device clock, captured at the segment boundaries."""
-        if not knobs.K.stamps:
+        if not knobs.K.stamps or name is None:
             return
-        if getattr(self, "_stamps", None) is None:
-            self._stamps, self._stamp_names = torch.zeros(32, dtype=torch.int64, device=self._bad.device), []
         if name not in self._stamp_names:
             self._stamp_names.append(name)
         ops.stamp(self._stamps, self._stamp_names.index(name))
@@ -506,99 +530,90 @@ class GraphedGanTrainer(GanTrainer):
     # (256 / 248 / 240 / 232 / 224 / 208 CUs: 956 / 958 / 950 / 956 / 977 / 969 it/s on one box, profiles/r6)
     WGRAD_CU_SHARE = 7 / 8
 
-    def _capture_linear(self, cap):
-        side = self._side
-        has_feat = self.opt.loss_weight.feat is not None
-        if knobs.K.stamps and getattr(self, "_stamps", None) is None:
+    def _stream(self, which):
+        """The stream a LINEAR_GRAPHS row names."""
+        return {"main": self._capture_stream, "side": self._side, "third": self._third}[which]
+
+    def _capture_graph(self, name, segment, *args):
+        """Capture one row of LINEAR_GRAPHS: a new graph, on the row's stream and pool, the row's stamps around ``segment(*args)``, the
+        TP_EXTRA_LAUNCHES launches, then the node count.  Returns what the segment returned and keeps it referenced (`_graphs_keep`)."""
+        row = LINEAR_GRAPHS[name]
+        graph = self._graphs[name] = torch.cuda.CUDAGraph()
+        pool = self._graphs[row.pool].pool() if row.pool else None
+        with torch.cuda.graph(graph, stream=self._stream(row.captured_on), pool=pool):
+            self._stamp(row.stamp_before)
+            out = segment(*args)
+            self._stamp(row.stamp_after)
+            self._extra(name)
+            self.launch_counts[name] = ops.capture_node_count()
+        # (with a shallow copy of every dictionary in it: later segments overwrite entries)
+        self._graphs_keep += [out] + [dict(x) for x in (out if isinstance(out, tuple) else (out,)) if isinstance(x, dict)]
+        return out
+
+    def _capture_linear(self):
+        dev = self._bad.device
+        if knobs.K.stamps and self._stamps is None:
             # (made OUTSIDE the captures: a zero-fill captured into the first graph would wipe the other streams' stamps on every replay)
-            self._stamps, self._stamp_names = torch.zeros(32, dtype=torch.int64, device=self._bad.device), []
-            torch.cuda.synchronize(self._bad.device)
-        self._graphs = g = {k: torch.cuda.CUDAGraph() for k in ["D1", "G1"] + (["F"] if has_feat else []) + ["G2a", "G2b"]}
+            self._stamps, self._stamp_names = torch.zeros(32, dtype=torch.int64, device=dev), []
+            torch.cuda.synchronize(dev)
+        previous = self._graphs_keep                 # (of an earlier capture: released when this one is through, not in between)
+        self._graphs, self._graphs_keep = {}, []
         self._events = {k: torch.cuda.Event() for k in ("sn", "patches", "g2a", "g2", "d2")}
-        self._extra_slots = torch.zeros(1, dtype=torch.int64, device=self._bad.device)
+        self._extra_slots = torch.zeros(1, dtype=torch.int64, device=dev)
         # Memory pools: graphs that share a pool must replay in capture order and never concurrently (a block freed while one is
         # captured is handed to the next), which holds for D1 -> D2a -> D2b and for G1 -> G2a -> G2b but not across the streams (F: its own).
         # Tensors that cross the streams (the spectral-norm sets, the render's patch stacks / scales) are kept referenced for the life of
         # the graphs, so that no capture re-uses their memory.
-        counts = self.launch_counts = {}                 # nodes per captured graph (kernel launches; TP_STAMPS adds two to each)
+        capture = self._capture_graph
         # The generator's pass through the frozen discriminator (G2a) needs the FIRST normalised weight set only, and D1 does not start
         # before the render's MLP kernel ends (it sits that kernel out: every CU is taken), so G2a is what the render's backward waits
         # for: that set as a graph of its own (3 launches), the other two behind it (D1b: 2 x 2 + 1), 8 launches instead of 7.
         # Measured +0.8 % (939-940 -> 945-948 it/s on one box, profiles/r6) now that the iteration boundary is short; in round 5, with
         # a 70-us boundary in which D1 ran unhindered, the extra launch cost more than the split gave (914-920 against 925-926).
         if not knobs.K.no_sn_split:
-            g["D1b"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g["D1"], stream=side):
-                self._stamp("D1.0"); self._seg_sn(0); self._stamp("D1.1"); self._extra("D1"); counts["D1"] = ops.capture_node_count()
-            with torch.cuda.graph(g["D1b"], stream=side, pool=g["D1"].pool()):
-                self._seg_sn(1); self._extra("D1b"); counts["D1b"] = ops.capture_node_count()
+            capture("D1", self._seg_sn, 0)
+            capture("D1b", self._seg_sn, 1)
         else:
-            with torch.cuda.graph(g["D1"], stream=side):
-                self._stamp("D1.0"); self._seg_sn(); self._stamp("D1.1"); self._extra("D1"); counts["D1"] = ops.capture_node_count()
-        keep = [list(self.graph.discriminator._sn_queue)]
-        with torch.cuda.graph(g["G1"], stream=cap):
-            self._stamp("G1.0"); var = self._seg_render(AttrDict(dict(self._static_in))); self._stamp("G1.1"); self._extra("G1"); counts["G1"] = ops.capture_node_count()
-        keep.append(dict(var))
-        if has_feat:
-            # (captured on the THIRD stream although it replays on `main`: per-stream kernel state -- tile counters, workspaces -- is keyed
-            # by the capturing stream, and F runs beside G2a, which is captured on `cap`; a pool of its own for the same reason)
-            with torch.cuda.graph(g["F"], stream=self._third):
-                self._stamp("F.0"); self._seg_feat(var); self._stamp("F.1"); self._extra("F"); counts["F"] = ops.capture_node_count()
-            keep.append(dict(var))
-        with torch.cuda.graph(g["G2a"], stream=cap, pool=g["G1"].pool()):
-            self._stamp("G2a.0"); var, loss, g_disc = self._seg_gen_a(var); self._stamp("G2a.1"); self._extra("G2a"); counts["G2a"] = ops.capture_node_count()
-        keep.append((dict(var), dict(loss), g_disc))
-        with torch.cuda.graph(g["G2b"], stream=cap, pool=g["G1"].pool()):
-            self._stamp("G2b.0"); var, loss = self._seg_gen_b(var, loss, g_disc); self._stamp("G2b.1"); self._extra("G2b"); counts["G2b"] = ops.capture_node_count()
-        keep.append(dict(var))
-        split_dp = self._dp
-        if split_dp:
+            capture("D1", self._seg_sn)
+        var = capture("G1", self._seg_render, AttrDict(dict(self._static_in)))
+        if self.opt.loss_weight.feat is not None:
+            capture("F", self._seg_feat, var)
+        var, loss, g_disc = capture("G2a", self._seg_gen_a, var)
+        var, loss = capture("G2b", self._seg_gen_b, var, loss, g_disc)
+        if self._dp:
             # several ranks: [G2b: ... gradients, pack] | flat all-reduce (stream-ordered call) | [G2c: Adam from the flat buffer]
-            g["G2c"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g["G2c"], stream=cap, pool=g["G1"].pool()):
-                self._seg_gen_c(); self._extra("G2c"); counts["G2c"] = ops.capture_node_count()
+            capture("G2c", self._seg_gen_c)
         # The discriminator step in TWO graphs when its paired schedule applies: D2a = private copies of the patch stacks, forward pairs,
         # BCE terms -- the last reads of anything the render wrote -- and D2b = the R1 passes, backward pairs, spectral-norm backward,
         # RMSprop.  With `pipeline_disc_tail` the next iteration's render starts behind D2a instead of behind D2b (`_replay_linear`).
-        ctx = self._seg_disc_a(var) if not knobs.K.no_disc_split else None
-        if ctx is not None:
-            g["D2a"], g["D2b"] = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        if not knobs.K.no_disc_split and self._seg_disc_a(var) is not None:
             self._events["d2a"] = torch.cuda.Event()
             self.disc_step_zero_grads()
-            with torch.cuda.graph(g["D2a"], stream=side, pool=g["D1"].pool()):
-                self._stamp("D2.0"); ctx = self._seg_disc_a(var, run=True); self._stamp("D2a.1"); self._extra("D2a"); counts["D2a"] = ops.capture_node_count()
-            keep.append(ctx)
-            with torch.cuda.graph(g["D2b"], stream=side, pool=g["D1"].pool()):
-                var, dloss = self._seg_disc_b(var, ctx); self._stamp("D2.1"); counts["D2b"] = ops.capture_node_count()
-                self._extra("D2b")
+            ctx = capture("D2a", self._seg_disc_a, var, True)
+            var, dloss = capture("D2b", self._seg_disc_b, var, ctx)
         else:
-            g["D2"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g["D2"], stream=side, pool=g["D1"].pool()):
-                self._stamp("D2.0"); var, dloss = self._seg_disc(var); self._stamp("D2.1"); counts["D2"] = ops.capture_node_count()
-        keep.append(dict(var))
-        if split_dp:
-            g["D2c"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g["D2c"], stream=side, pool=g["D1"].pool()):
-                self._seg_disc_c(); self._extra("D2c"); counts["D2c"] = ops.capture_node_count()
-        self._graphs_keep = keep
+            var, dloss = capture("D2", self._seg_disc, var)
+        if self._dp:
+            capture("D2c", self._seg_disc_c)
         loss.update({k: v for k, v in dloss.items() if k != "all"})
         self._static_loss = {k: v.detach() for k, v in loss.items() if torch.is_tensor(v)}
         self._first_replay = True
 
     def _replay_linear(self):
         g, ev = self._graphs, self._events
-        main, side, third = self._capture_stream, self._side, self._third
+        # the streams the chains REPLAY on (LINEAR_GRAPHS): G1, F, G2b, G2c | every D graph | G2a
+        main, side, third = (self._stream(LINEAR_GRAPHS[k].replays_on) for k in ("G1", "D1", "G2a"))
         cur = torch.cuda.current_stream(self._bad.device)
         # the caller's stream hands over the step's inputs (and, the first time, parameters restored / loaded since the capture); it
         # waited for the previous iteration's last launches below, so does everything here
-        inputs = self.__dict__.pop("_inputs_event", None)
+        inputs, self._inputs_event = self._inputs_event, None
         if inputs is not None:
             main.wait_event(inputs)                   # (`defer_results`: the inputs went in on the third stream, behind the caller's mark)
         else:
             main.wait_stream(cur)
-        if getattr(self, "_g2_pending", False) and not self._pipelined():
+        if self._g2_pending and not self._pipelined():
             main.wait_event(ev["d2"])                 # (nothing else orders the render behind the previous discriminator step)
-        if getattr(self, "_d2_pending", False) and self._pipelined():
+        if self._d2_pending and self._pipelined():
             # pipelined: this render may start while the previous discriminator step's second half still runs; it overwrites the patch
             # stacks / scales, whose last readers are in that step's FIRST half
             main.wait_event(ev["d2a"])
@@ -607,14 +622,14 @@ class GraphedGanTrainer(GanTrainer):
             # place: a load_state_dict, parameter broadcast or checkpoint copy the caller enqueued between two iterations comes first).
             # `train_iteration` marks the caller's stream BEFORE its own tp_step_inputs launch (which writes nothing D1 reads): D1 then
             # starts behind the caller's work without waiting for that launch; a bare `replay()` waits for the whole stream.
-            mark = self.__dict__.pop("_caller_mark", None)
+            mark, self._caller_mark = self._caller_mark, None
             if mark is not None:
                 side.wait_event(mark)
             else:
                 side.wait_stream(cur)
             if not self._first_replay:
                 side.wait_event(ev["g2"])            # set 1 is read by the generator's passes through the frozen discriminator
-            poll = self.__dict__.pop("_poll_on_side", None)
+            poll, self._poll_on_side = self._poll_on_side, None
             if poll is not None:
                 # (several ranks + `defer_results`: the gate words out to the host HERE -- behind both all-reduces of the previous
                 # iteration, in front of this iteration's packs, on every rank alike; D1 sits the render's forward out anyway)
@@ -681,8 +696,8 @@ class GraphedGanTrainer(GanTrainer):
     @property
     def _third(self):
         """Third stream of the linear graphs (the generator's pass through the frozen discriminator); the generic form forks the feature
-        chain onto it (graph.Graph._feature_loss_early)."""
-        return self.graph.feat_stream
+        chain onto it (graph.Graph._feature_loss_early).  None until one of the two has made it."""
+        return getattr(self.graph, "feat_stream", None)
 
     def _pipelined(self):
         return bool(self.pipeline_disc_tail) and self._linear and self._graphs is not None and "D2a" in self._graphs
@@ -694,10 +709,10 @@ class GraphedGanTrainer(GanTrainer):
         """Make the calling stream wait for everything the last `train_iteration` enqueued (with `pipeline_disc_tail`: the
         discriminator step's second half and its RMSprop step)."""
         cur = torch.cuda.current_stream(self._bad.device)
-        if getattr(self, "_g2_pending", False):
+        if self._g2_pending:
             cur.wait_event(self._events["g2"])
             self._g2_pending = False
-        if getattr(self, "_d2_pending", False):
+        if self._d2_pending:
             cur.wait_event(self._events["d2"])
             self._d2_pending = False
 
@@ -778,34 +793,31 @@ class GraphedGanTrainer(GanTrainer):
         record the step.  ``var`` fixes the shapes.  The warm-up iterations are real optimiser steps on ``var``; they
         are rolled back afterwards, so that a captured run starts from the same state as an eager one."""
         dev = var.image.device
-        for name, optim in (("lr_nerf", self.optim_nerf), ("lr_disc", getattr(self, "optim_disc", None))):
-            if optim is not None:
-                self._adopt_group_lr(name, optim)             # (a load_state_dict before the capture replaced the tensors)
+        for name, optim, _ in self._optims():
+            self._adopt_group_lr(name, optim)                 # (a load_state_dict before the capture replaced the tensors)
         self.graph.patch_sampler.device_lo = torch.zeros((), device=dev)
         if not knobs.K.torch_rng:
             # the step's random draws (patch scale / shifts, stratified jitter) come from Philox streams keyed by the seed and a
             # step counter on the device, read inside tp_patch_coords / tp_raygen and advanced by the loss-total launch: no
             # torch.rand launches in the step and no generator-state fills before every replay
-            if getattr(self, "_rng_counter", None) is None:
-                self._rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)       # (attached to the graph only inside `_body_a`)
+            if self._rng_counter is None:
+                self._rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)       # (attached to the graph only in `_render_prologue`)
         self._static_in = AttrDict({k: v.clone() for k, v in var.items() if torch.is_tensor(v)})
         self._select_form(var)
         # the step's streams are made here, one after the other (main / capture, discriminator, feature chain): consecutive hardware queues
-        if self._linear and (getattr(self, "_capture_stream", None) is None or self._side is None
-                             or getattr(self.graph, "feat_stream", None) is None) and not knobs.K.no_queue_probe:
-            self._capture_stream, self._side, self.graph.feat_stream = streams_after_collectives(dev, 3, self.red_nerf.group)
+        streams = [self._capture_stream, self._side, self._third]
+        if self._linear and any(st is None for st in streams) and not knobs.K.no_queue_probe:
+            streams = list(streams_after_collectives(dev, 3, self.red_nerf.group))
             self.queue_probe = dict(LAST_QUEUE_PROBE)                    # (bench lines report it: `train.queues`)
-        if getattr(self, "_capture_stream", None) is None:
-            self._capture_stream = torch.cuda.Stream(device=dev)
-        if self._linear and self._side is None:
-            self._side = torch.cuda.Stream(device=dev)
-        if self._linear and getattr(self.graph, "feat_stream", None) is None:
-            self.graph.feat_stream = torch.cuda.Stream(device=dev)
+        for i in range(3 if self._linear else 1):                        # (the generic form forks onto streams `_body_a` makes)
+            if streams[i] is None:
+                streams[i] = torch.cuda.Stream(device=dev)
+        self._capture_stream, self._side = streams[:2]
+        if self._linear:
+            self.graph.feat_stream = streams[2]
         snap = self._snapshot()
         # warm up on the stream the capture will use: per-stream state (the tile counters of the convolution kernels,
         # ops._conv_scratch) must exist before the capture and is keyed by the stream
-        if getattr(self, "_capture_stream", None) is None:
-            self._capture_stream = torch.cuda.Stream(device=dev)
         side = self._capture_stream
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -833,10 +845,10 @@ class GraphedGanTrainer(GanTrainer):
             self.optim_disc.zero_grad(set_to_none=True)
         self.graph.patch_sampler.update_device_bound()          # outside the capture
         self._graph_b = None
+        self.launch_counts = {}                                 # nodes per captured graph (kernel launches; TP_STAMPS adds two to each)
         if self._linear:
-            self._capture_linear(side)
+            self._capture_linear()
         elif self._split_around_collectives():
-            self.launch_counts = {}
             with torch.cuda.graph(self._graph, stream=side):
                 self._static_loss = self._body_a(AttrDict(dict(self._static_in)))
                 self.launch_counts["A"] = ops.capture_node_count()
@@ -845,21 +857,16 @@ class GraphedGanTrainer(GanTrainer):
                 self._body_b()
                 self.launch_counts["B"] = ops.capture_node_count()
         else:
-            self.launch_counts = {}
             with torch.cuda.graph(self._graph, stream=side):
                 self._static_loss = self._body(AttrDict(dict(self._static_in)))
                 self.launch_counts["step"] = ops.capture_node_count()
         self._restore(snap)
-        flagged = self._read_bad(blocking=True)
-        if flagged[0] and self._uses_f16x3():
-            return self._fall_back_to_fp32(var, warmup)
-        if flagged[1] or flagged[2]:
-            raise FloatingPointError("non-finite loss during the warm-up iterations of the captured step")
+        self._act_on_flags(self._read_bad(blocking=True), var, warmup, "during the warm-up iterations of the captured step")
         return self
 
     def _after_step(self, fill_progress=True):
-        """``fill_progress=False``: the replay loop writes the value with the NEXT iteration's tp_step_inputs launch (nothing reads
-        `progress` in between: the reference's discriminator never uses it in its forward)."""
+        """``fill_progress=False``: the replay loop writes `progress` with the NEXT iteration's tp_step_inputs launch, in FRONT of that
+        replay: Discriminator.geo_encoding reads it there when `gan.geo_c2f` is set (the reference's default never does)."""
         if self.has_disc and fill_progress:
             self.graph.discriminator.progress.data.fill_(self.it / self.max_iter)
         self.it += 1
@@ -900,14 +907,18 @@ class GraphedGanTrainer(GanTrainer):
         if self._graph is None:
             return [0, 0, 0]
         self.wait_all()
-        flagged = self._read_bad(blocking=True)
-        if flagged[0] and self._uses_f16x3():
-            self._fall_back_to_fp32(AttrDict(dict(self._static_in)))
-        elif flagged[1] or flagged[2]:
-            raise FloatingPointError("non-finite loss in a captured training step (the update was withheld on the device)")
-        return flagged
+        return self._act_on_flags(self._read_bad(blocking=True))
 
     finish = flush_flags
+
+    def _act_on_flags(self, flagged, var=None, warmup=3, where="in a captured training step (the update was withheld on the device)"):
+        """The host's rule for the gate words [range flag, non-finite nerf loss, non-finite discriminator loss]: a range flag of the
+        f16x3 recording forward re-captures the step in fp32 (from ``var``; default: the static inputs), a non-finite loss raises."""
+        if flagged[0] and self._uses_f16x3():
+            self._fall_back_to_fp32(AttrDict(dict(self._static_in)) if var is None else var, warmup)
+        elif flagged[1] or flagged[2]:
+            raise FloatingPointError("non-finite loss " + where)
+        return flagged
 
     def _bad_poll_slot(self):
         """Pinned host words for this iteration's copy of the gate words (written by the tp_step_inputs launch in front of the
@@ -915,7 +926,7 @@ class GraphedGanTrainer(GanTrainer):
         if self._bad_poll is not None:
             return None
         n = self._poll_words().numel()
-        if getattr(self, "_bad_host", None) is None or self._bad_host.numel() != n:
+        if self._bad_host is None or self._bad_host.numel() != n:
             self._bad_host = torch.zeros(n, dtype=torch.int32).pin_memory()
         return self._bad_host
 
@@ -940,15 +951,17 @@ class GraphedGanTrainer(GanTrainer):
             return self._replay_linear()
         self._graph.replay()
         if self._graph_b is not None:                            # collectives between the two replays, stream-ordered
-            ev = getattr(self, "collective_events", None)        # (a list: HIP-event pairs around the step's reductions, bench.py)
-            if ev is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            self._reduce_all()
-            if ev is not None:
-                e1.record()
-                ev.append(("both", e0, e1))
+            self._timed("both", self._reduce_all)
             self._graph_b.replay()
+
+    @property
+    def form(self):
+        """The captured form, as tools/train_dp.py and bench.py report it; None while no step is captured."""
+        if self._graph is None:
+            return None
+        if self._linear:
+            return "linear_dp" if self._dp else "linear"
+        return "one_graph" if self._graph_b is None else "two_graphs_eager_collectives"
 
     def train_iteration(self, var: AttrDict):
         if self._graph is None:
@@ -970,8 +983,8 @@ class GraphedGanTrainer(GanTrainer):
             # the tp_step_inputs launch, which writes nothing the discriminator stream's first graph reads.)
             self._caller_mark = torch.cuda.Event()
             self._caller_mark.record()
-        for name, optim in (("lr_nerf", self.optim_nerf), ("lr_disc", getattr(self, "optim_disc", None))):
-            if optim is not None and any(g["lr"] is not getattr(self, name + "_used") for g in optim.param_groups):
+        for name, optim, used in self._optims():
+            if any(g["lr"] is not used for g in optim.param_groups):
                 self._adopt_group_lr(name, optim)             # an Optimizer.load_state_dict since the last replay
         sampler = self.graph.patch_sampler
         scalars = [(sampler.device_lo, sampler._host_range()[0])]
@@ -1011,9 +1024,5 @@ class GraphedGanTrainer(GanTrainer):
             self._bad_poll = (poll, ev)
         self.replay()
         self._after_step(fill_progress=False)
-        flagged = self._read_bad()                              # outside the graph: event query of the pinned copy
-        if flagged[0] and self._uses_f16x3():
-            self._fall_back_to_fp32(AttrDict(dict(self._static_in)))
-        elif flagged[1] or flagged[2]:
-            raise FloatingPointError("non-finite loss in a captured training step (the update was withheld on the device)")
+        self._act_on_flags(self._read_bad())                    # outside the graph: event query of the pinned copy
         return self._static_in, AttrDict(self._static_loss)

@@ -136,6 +136,8 @@ class GanTrainer:
                                 dict(params=graph.latent_vars_trans.parameters(), lr=self.lr_nerf_used)],
                                capturable=self.capturable)
         self.has_disc = hasattr(graph, "discriminator") and opt.gan is not None
+        # the discriminator step's parameters, rates and optimiser: None without a discriminator
+        self.disc_group = self.lr_disc = self.lr_disc_used = self.optim_disc = None
         if self.has_disc:
             self.disc_group = [p for p in graph.discriminator.parameters()]
             self.lr_disc = mk(opt.optim_disc.lr)
@@ -145,6 +147,12 @@ class GanTrainer:
         self.red_nerf = tdist.FlatGradAllReducer(self.nerf_group, group=group)
         self.red_disc = tdist.FlatGradAllReducer(self.disc_group, group=group) if self.has_disc else None
         self.skipped_steps = 0                   # optimiser steps withheld because the forward was flagged
+        self._weights, self._weight_vectors = {}, {}     # `_weight` / `_weighted_total`: the 10^w tensors, filled on first use
+        self._disc_sched = None                  # `_disc_schedule`: the explicit schedule of this discriminator, made on first use
+        self._disc_total = None                  # `disc_step`: the step's loss total, for a `disc_apply` the caller issues itself
+        self._disc_flagged = False               # `_disc_step_scheduled_post`: the total's launch has carried the gate update
+        # what tools/train_dp.py reports of a captured step (GraphedGanTrainer.capture fills them; None in the eager loop)
+        self.launch_counts = self.queue_probe = None
 
     @staticmethod
     def _toggle(module, flag):
@@ -182,7 +190,7 @@ class GanTrainer:
 
     def _weight(self, exponent, dev):
         """10^exponent as a 0-dim tensor on ``dev``, made once (a captured step may not create tensors from host values)."""
-        cache = self.__dict__.setdefault("_weights", {})
+        cache = self._weights
         key = (float(exponent), str(dev))
         if key not in cache:
             cache[key] = torch.tensor(10 ** float(exponent), device=dev)
@@ -197,7 +205,7 @@ class GanTrainer:
             assert k == "all" or (k in opt.loss_weight and loss[k].shape == ()), k
         dev = loss[keys[0]].device
         ws = [self._weight(opt.loss_weight[k], dev) for k in keys]
-        cache = self.__dict__.setdefault("_weight_vectors", {})
+        cache = self._weight_vectors
         vec_key = (tuple(keys), str(dev))
         if vec_key not in cache:
             cache[vec_key] = torch.stack(ws)
@@ -264,7 +272,7 @@ class GanTrainer:
         discriminator and these tensors, else None (CPU tensors, other ladders / GAN losses: the autograd form below)."""
         if knobs.K.disc_autograd:
             return None
-        sched = self.__dict__.get("_disc_sched")
+        sched = self._disc_sched
         if sched is None or sched.disc is not self.graph.discriminator:
             from .disc_step import DiscStepSchedule
             sched = self._disc_sched = DiscStepSchedule(self.graph.discriminator)
@@ -346,24 +354,34 @@ class GanTrainer:
 
     def set_lr(self, nerf: float = None, disc: float = None):
         """Learning rates for the following iterations (eager: param groups; captured: the device scalars the graph reads)."""
-        for value, name, optim in ((nerf, "lr_nerf", self.optim_nerf), (disc, "lr_disc", getattr(self, "optim_disc", None))):
-            if value is None or optim is None:
+        for value, (name, optim, _) in zip((nerf, disc), self._optims()):
+            if value is None:
                 continue
-            if self.capturable:
-                getattr(self, name).fill_(float(value))
-                getattr(self, name + "_used").fill_(float(value))
-            else:
-                setattr(self, name, float(value))
-                setattr(self, name + "_used", float(value))
+            self._set_rate(name, float(value))
+            if not self.capturable:
                 for g in optim.param_groups:
                     g["lr"] = float(value)
+
+    def _optims(self):
+        """(name, optimiser, the rate its groups read) of each optimiser step this configuration has: "nerf", then "disc"."""
+        return [("nerf", self.optim_nerf, self.lr_nerf_used)] + ([("disc", self.optim_disc, self.lr_disc_used)] if self.has_disc else [])
+
+    def _set_rate(self, name, value):
+        """lr_<name> and lr_<name>_used <- value (captured: in place, they are the device scalars the graph reads)."""
+        if self.capturable:
+            for t in (self.lr_nerf, self.lr_nerf_used) if name == "nerf" else (self.lr_disc, self.lr_disc_used):
+                t.fill_(value)
+        elif name == "nerf":
+            self.lr_nerf = self.lr_nerf_used = value
+        else:
+            self.lr_disc = self.lr_disc_used = value
 
     def load_optim_state(self, optim_nerf=None, optim_disc=None):
         """Resume: optimiser state dicts of a checkpoint (texpose_amd.checkpoint.restore_checkpoint passes them on).
         ``Optimizer.load_state_dict`` replaces each group's ``lr`` by the saved value; a captured step reads the rate
         from ``lr_*_used``, so the loaded value is copied there and the groups are pointed back at it."""
-        for sd, name, optim in ((optim_nerf, "lr_nerf", self.optim_nerf), (optim_disc, "lr_disc", getattr(self, "optim_disc", None))):
-            if sd is None or optim is None:
+        for sd, (name, optim, _) in zip((optim_nerf, optim_disc), self._optims()):
+            if sd is None:
                 continue
             optim.load_state_dict(sd)
             self._adopt_group_lr(name, optim)
@@ -388,23 +406,23 @@ class GanTrainer:
                     st["step"] = torch.tensor(value, dtype=torch.float32)
 
     def _adopt_group_lr(self, name, optim):
-        used = getattr(self, name + "_used")
+        used = self.lr_nerf_used if name == "nerf" else self.lr_disc_used
         for g in optim.param_groups:
             if g["lr"] is not used:
-                value = float(g["lr"])
+                self._set_rate(name, float(g["lr"]))
                 if self.capturable:
-                    getattr(self, name).fill_(value)
-                    used.fill_(value)
                     g["lr"] = used
-                else:
-                    setattr(self, name, value)
-                    setattr(self, name + "_used", value)
 
     def flush_flags(self):
         """The eager trainer reads its guards before every optimiser step: nothing is pending (see GraphedGanTrainer.flush_flags)."""
         return [0, 0, 0]
 
     finish = flush_flags
+
+    @property
+    def form(self):
+        """Which form the iteration is issued in (tools/train_dp.py and bench.py report it): here always "eager"."""
+        return "eager"
 
     def train_iteration(self, var: AttrDict):
         var = self.graph.get_ray_idx(self.opt, var)

@@ -8,7 +8,7 @@ from texpose_amd.gan_modules import Discriminator, PerceptualLoss
 from texpose_amd.graph import Graph
 from texpose_amd.options import default_options, AttrDict
 from texpose_amd.synthetic import training_batch
-from texpose_amd.trainer import GraphedGanTrainer
+from texpose_amd.graphed_trainer import LINEAR_GRAPHS, GraphedGanTrainer
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 torch.manual_seed(0)
@@ -34,8 +34,7 @@ e1.record()
 torch.cuda.synchronize()
 print("iteration, free-running: %.1f us (%.0f it/s)" % (e0.elapsed_time(e1) / 200 * 1e3, 200 / e0.elapsed_time(e1) * 1e3))
 tr.flush_flags()
-streams = {"D1": tr._side, "G1": tr._capture_stream, "F": tr.graph.feat_stream, "G2a": tr._capture_stream, "G2b": tr._capture_stream,
-           "D2": tr._side, "D2a": tr._side, "D2b": tr._side, "D1b": tr._side}
+streams = {name: tr._stream(row.captured_on) for name, row in LINEAR_GRAPHS.items()}     # (alone, each on the stream that captured it)
 print("graph   us per replay, alone on the GPU (%d back-to-back replays between two HIP events)" % reps)
 total = 0.0
 for name in [n for n in ("G1", "F", "G2a", "G2b", "D1", "D1b", "D2", "D2a", "D2b") if n in tr._graphs]:

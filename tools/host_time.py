@@ -6,7 +6,7 @@ from texpose_amd.gan_modules import Discriminator, PerceptualLoss
 from texpose_amd.graph import Graph
 from texpose_amd.options import default_options, AttrDict
 from texpose_amd.synthetic import training_batch
-from texpose_amd.trainer import GraphedGanTrainer
+from texpose_amd.graphed_trainer import LINEAR_GRAPHS, GraphedGanTrainer
 torch.manual_seed(0)
 opt = default_options(H=128, W=128, device="cuda:0")
 opt.batch_size, opt.patch_size, opt.nerf.sample_intvs = 4, 16, 64
@@ -30,7 +30,7 @@ print("50 iterations: host issue %.1f us/iter, with final sync %.1f us/iter" % (
 if tr._linear:
     print("mode:", "six linear graphs on three streams" if tr._linear else "four graphs on two streams")
     for name, g in tr._graphs.items():
-        s = tr._side if name[0] == "D" else tr.graph.feat_stream if name == "F" else torch.cuda.current_stream()
+        s = tr._stream(LINEAR_GRAPHS[name].captured_on)
         ts = []
         for _ in range(20):
             torch.cuda.synchronize()

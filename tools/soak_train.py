@@ -31,7 +31,7 @@ sd = graph.state_dict()
 assert all(torch.isfinite(v).all() for v in sd.values() if v.dtype.is_floating_point)
 assert all(all(abs(v) < 1e6 for v in h.values()) for h in hist)      # (random-noise target images: no loss trend to expect)
 assert tr.skipped_steps == 0 and not graph.discriminator._sn_queue
-counter = int(tr._rng_counter) if getattr(tr, "_rng_counter", None) is not None else None
+counter = int(tr._rng_counter) if tr._rng_counter is not None else None
 assert counter is None or counter >= N_IT, counter            # (+ the warm-up iterations of the capture)
 import hashlib
 h = hashlib.sha256()

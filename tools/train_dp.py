@@ -92,7 +92,7 @@ def measure(device, rank, world, global_batch=32, iters=50, warm=5, graphed=True
     # HIP events around the step's gradient all-reduces (the xGMI figure), in a short loop of its own BEHIND the timed one: the event
     # records sit between graph replays and would cost the timed loop a few microseconds each
     coll = coll_by = None
-    if graphed and (getattr(trainer, "_graph_b", None) is not None or getattr(trainer, "_dp", False)):
+    if trainer.form in ("linear_dp", "two_graphs_eager_collectives"):
         trainer.collective_events = []
         for i in range(min(iters, 20)):
             trainer.train_iteration(AttrDict(dict(batches[i % 2])))
@@ -105,17 +105,14 @@ def measure(device, rank, world, global_batch=32, iters=50, warm=5, graphed=True
         coll = sum(coll_by.values())                       # (every name occurs once per iteration)
     if hasattr(trainer, "flush_flags"):
         trainer.flush_flags()                              # (the last replay's gate words: a withheld final step raises here)
-    counts = getattr(trainer, "launch_counts", None)
-    return dict(collective_ms=coll, collective_ms_by_step=coll_by, ranks_seen=tdist.ranks_seen(), form=_form(trainer, graphed),
+    counts = trainer.launch_counts
+    return dict(collective_ms=coll, collective_ms_by_step=coll_by, ranks_seen=tdist.ranks_seen(), form=trainer.form,
                 # nodes of the captured graphs of ONE iteration + the tp_step_inputs launch in front of them (None: eager loop)
                 launches=(sum(v for v in counts.values() if v) + 1) if counts and all(v is not None for v in counts.values()) else None,
-                launch_counts=counts, queues=getattr(trainer, "queue_probe", None),
+                launch_counts=counts, queues=trainer.queue_probe,
                 metric="train iters/sec", value=1.0 / dt, ms_per_iter=dt * 1e3, n_gpus=world, global_batch=global_batch,
                 per_gpu_batch=global_batch // world, rays_per_iter=global_batch * 256, samples_per_iter=global_batch * 256 * 64,
-                launch=("linear hipGraph replays on three streams with one flat all-reduce between each gradient graph and its optimiser graph (render | D(fake) + its backward | generator backward, pack | all-reduce | Adam || feature chain || spectral norm | discriminator step, pack | all-reduce | RMSprop)" if getattr(trainer, "_dp", False)
-                        else "six linear hipGraph replays on three streams (render | D(fake) + its backward | generator backward + Adam || feature chain || spectral norm | discriminator step)" if getattr(trainer, "_linear", False)
-                        else "hipGraph replay" if getattr(trainer, "_graph_b", None) is None
-                        else "two hipGraph replays with the gradient all-reduces between them") if graphed else "eager", recording_forward=graph.nerf.train_precision,
+                launch=LAUNCH[trainer.form], recording_forward=graph.nerf.train_precision,
                 collective="one flat all-reduce per optimiser step (%.1f MB nerf, %.1f MB discriminator)"
                            % (trainer.red_nerf.nbytes / 1e6, (trainer.red_disc.nbytes if trainer.red_disc else 0) / 1e6),
                 loop="full GAN (render fwd+bwd, gathers, random-init VGG19[:15] feature loss, PatchGAN + R1, Adam + RMSprop)"
@@ -124,14 +121,14 @@ def measure(device, rank, world, global_batch=32, iters=50, warm=5, graphed=True
                 skipped_steps=trainer.skipped_steps)
 
 
-def _form(trainer, graphed):
-    if not graphed:
-        return "eager"
-    if getattr(trainer, "_dp", False):
-        return "linear_dp"
-    if getattr(trainer, "_linear", False):
-        return "linear"
-    return "one_graph" if getattr(trainer, "_graph_b", None) is None else "two_graphs_eager_collectives"
+# how each `trainer.form` issues the iteration (the bench line's `launch`)
+LAUNCH = {
+    "eager": "eager",
+    "linear_dp": "linear hipGraph replays on three streams with one flat all-reduce between each gradient graph and its optimiser graph (render | D(fake) + its backward | generator backward, pack | all-reduce | Adam || feature chain || spectral norm | discriminator step, pack | all-reduce | RMSprop)",
+    "linear": "six linear hipGraph replays on three streams (render | D(fake) + its backward | generator backward + Adam || feature chain || spectral norm | discriminator step)",
+    "one_graph": "hipGraph replay",
+    "two_graphs_eager_collectives": "two hipGraph replays with the gradient all-reduces between them",
+}
 
 
 def run(global_batch=32, iters=50, warm=5, graphed=True, full=True, train_precision="f16x3", seed=0):
