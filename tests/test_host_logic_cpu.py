@@ -431,10 +431,13 @@ def test_knobs_are_parsed_once_warn_on_unknown_names_and_are_all_documented(monk
         if path.endswith(("knobs.py", "_lib.py", "dist.py")):      # (_lib: TEXPOSE_AMD_LIB; dist: the launcher's RANK / WORLD_SIZE)
             continue
         assert not re.search(r"os\.environ|getenv", open(path).read()), path
-    # every switch the library itself reads is a known name
+    # every switch the library itself reads is a known name, and every name listed as a library switch is read by the library
+    read = set()
     for path in glob.glob(os.path.join(repo, "texpose_amd", "csrc", "*.h*")):
         for name in re.findall(r'getenv\("(TP_[A-Z0-9_]+)"\)', open(path).read()):
             assert name in knobs.LIBRARY_SWITCHES, (path, name)
+            read.add(name)
+    assert read == set(knobs.LIBRARY_SWITCHES), sorted(set(knobs.LIBRARY_SWITCHES) - read)
 
 
 def test_bench_stdout_carries_only_the_result_line():

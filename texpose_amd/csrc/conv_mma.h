@@ -34,35 +34,26 @@ struct ConvP {
 // Sum NT accumulator tiles over the 4 wavefronts of the workgroup and over the S workgroups of the tile.  True in the one
 // workgroup that ends up with the totals: thread (w, lane) then holds registers 4w..4w+3 of each tile, i.e. tile rows
 // 8w + 4(lane>>5) + 0..3 of column lane & 31.
-#ifdef TP_REDUCE_LDS_8K                            // (A/B build `make reduce8k`: eight registers per round, 8 KB of LDS per workgroup)
-constexpr int kReduceRegs = 8;
-#else
-constexpr int kReduceRegs = 16;
-#endif
+constexpr int kReduceRegs = 16;                              // a whole accumulator tile per round
 constexpr int kReduceLdsFloats = kReduceRegs * 4 * 64;       // the LDS floats reduce_tiles needs, whatever NT
 
 template <int NT>
 __device__ __forceinline__ bool reduce_tiles(const f32x16 (&acc)[NT], float (&out)[NT][4], float* lds, const ConvP& p, int tile, int s) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  // The four wavefronts' partial tiles meet in LDS, kReduceRegs accumulator registers per round.  With 8 (TP_REDUCE_LDS_8K) a
-  // workgroup needs 8 KB instead of 16 KB per tile and fits into the LDS the training MLP's backward kernels leave free on a CU (40 KB
-  // beside the data gradient, 16 KB beside the weight gradient): measured on one box, the discriminator chain then runs BESIDE the
-  // render's backward, slows it by 20 us and finishes no earlier (its tail kernels, 73-81 KB of LDS, still wait) -- 0.5 % slower per
-  // iteration, so 16 stays (profiles/r5).  Same operands and order of additions either way: bit-identical results.
+  // The four wavefronts' partial tiles meet in LDS, kReduceRegs accumulator registers (16 KB per workgroup) per round.
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-    for (int half = 0; half < 16 / kReduceRegs; ++half) {
+    for (int half = 0; half < 16 / kReduceRegs; ++half) {        // (one round per tile)
       if (nt + half > 0) __syncthreads();                      // (the previous round's reads are done)
 #pragma unroll
       for (int r = 0; r < kReduceRegs; ++r) lds[(r * 4 + w) * 64 + lane] = acc[nt][kReduceRegs * half + r];
       __syncthreads();
-      if (kReduceRegs == 16 || (w >> 1) == half)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float* q = lds + (((4 * w + i) & (kReduceRegs - 1)) * 4) * 64 + lane;
-          out[nt][i] = ((q[0] + q[64]) + q[128]) + q[192];
-        }
+      for (int i = 0; i < 4; ++i) {
+        const float* q = lds + ((4 * w + i) * 4) * 64 + lane;
+        out[nt][i] = ((q[0] + q[64]) + q[128]) + q[192];
+      }
     }
   if (p.S == 1) return true;
   // Cross-workgroup hand-over WITHOUT device-scope fences: on gfx950 a fence is buffer_wbl2 + buffer_inv of the XCD's whole

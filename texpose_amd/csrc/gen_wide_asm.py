@@ -9,7 +9,7 @@ hand-scheduled gfx950 inline-asm blocks with FIXED registers:
     v[232:247]  accumulator tile of a narrow head
 
 Why asm: with one wave per SIMD every issue slot that is not an MFMA is exposed, and the kernel needs all 512
-registers.  hipcc's schedule of the C++ version clusters the operand-conversion VALU work unevenly, waits for LDS with
+registers.  Compiled from C++, the same layer body clusters the operand-conversion VALU work unevenly, waits for LDS with
 lgkmcnt(0), moves the sets between AGPRs and VGPRs and cannot keep a third 128-register set (the trunk feature, held
 from L7 to R0) next to them without spilling it.  Here every MFMA gap carries at most four VALU instructions, or one
 LDS-DMA piece, or two ds_read_b128; a ring slot is refilled as soon as its last MFMA has issued; waits are counted.
@@ -20,8 +20,7 @@ Blocks (C++ wrappers in mlp_fwd_f16x3.hip), each for both set roles:
     EXTRA  one chunk of "extra input" k-steps (positional encodings, latents): B operands read from the LDS stage
     HEAD   1..5-row output layer over relu(source set): one chunk, 16 k-steps, one accumulator tile in VGPRs
     INIT   seed a set with bias * 2^8 from LDS
-Arithmetic and accumulation order are those of the C++ version (mma_wide16 / part_gen16 / part_head16): results are
-bit-identical.
+Per (k-step, tile) pair the three products accumulate in the order Whi xhi, Whi xlo, Wlo xhi.
 
 Ring protocol (shared by all blocks): three 32 KiB LDS slots; on entry chunk c is published and its pairs 0..3 are in
 the fragment registers, the DMA of c+1 is fully issued, that of c+2 not started; a block issues the 8 DMA pieces of c+2
@@ -30,18 +29,9 @@ lgkmcnt(0), s_barrier) 4 pairs before the end of c and leaves with pairs 0..3 of
 
     python3 gen_wide_asm.py > wide_asm.inc.h        (the Makefile does this)
 """
-import os
 import sys
 
 NCH = 115
-# timing experiments only (results are WRONG): TP_ASM_EXPERIMENT = nodma | nobarrier | noconv | recnostore (recording
-# blocks issue no vector stores) | recnolds (no staging-tile writes / reads either)
-EXPERIMENT = os.environ.get("TP_ASM_EXPERIMENT", "")
-# hi / lo split of a converted operand: "mix" (round 4) = v_cvt_pkrtz of the two values IS the truncation to 11 significand bits,
-# and lo = v - float(hi) comes from v_fma_mix_f32 reading hi as fp16 (exact; also right when hi is an fp16 subnormal, where the
-# masked fp32 value kept bits the fp16 conversion then dropped): 11 VALU instructions per two elements.  "and" = rounds 2-3:
-# hi = v & 0xFFFFE000, lo = v - hi, two conversions: 13 (A/B build: make split_and).
-SPLIT = os.environ.get("TP_ASM_SPLIT", "mix")
 
 VB = 160
 def F_hi(slot): return VB + 8 * slot
@@ -70,7 +60,7 @@ def mfma(dst, a, b, c=None):
 
 
 def conv(src_base, tile, g, bank):
-    """11 (13 with SPLIT = "and") VALU instructions: elements 2g, 2g+1 of source tile `tile` -> packed word g of the hi / lo operands in `bank`"""
+    """11 VALU instructions: elements 2g, 2g+1 of source tile `tile` -> packed word g of the hi / lo operands in `bank`"""
     xh = XB[bank] + (g >> 2) * 4 + (g & 3)
     xl = XB[bank] + 8 + (g >> 2) * 4 + (g & 3)
     t0, t1, h0, h1 = T, T + 1, T + 2, T + 3
@@ -85,14 +75,9 @@ def conv(src_base, tile, g, bank):
 
 
 def split_ops(t0, t1, h0, h1, xh, xl):
-    """(t0, t1) fp32 -> packed fp16 hi (xh) and lo (xl) words; t0 / t1 keep their values in the "mix" form"""
-    if SPLIT == "and":
-        return ["v_and_b32 v%d, %%[mask], v%d" % (h0, t0),
-                "v_and_b32 v%d, %%[mask], v%d" % (h1, t1),
-                "v_sub_f32 v%d, v%d, v%d" % (t0, t0, h0),
-                "v_sub_f32 v%d, v%d, v%d" % (t1, t1, h1),
-                "v_cvt_pkrtz_f16_f32 v%d, v%d, v%d" % (xh, h0, h1),
-                "v_cvt_pkrtz_f16_f32 v%d, v%d, v%d" % (xl, t0, t1)]
+    """(t0, t1) fp32 -> packed fp16 hi (xh) and lo (xl) words; t0 / t1 keep their values.  v_cvt_pkrtz of the two values IS the
+    truncation to 11 significand bits, and lo = v - float(hi) comes from v_fma_mix_f32 reading hi as fp16 (exact, also where hi
+    is an fp16 subnormal)"""
     return ["v_cvt_pkrtz_f16_f32 v%d, v%d, v%d" % (xh, t0, t1),
             "v_fma_mix_f32 v%d, -v%d, 1.0, v%d op_sel_hi:[1,0,0]" % (h0, xh, t0),
             "v_fma_mix_f32 v%d, -v%d, 1.0, v%d op_sel:[1,0,0] op_sel_hi:[1,0,0]" % (h1, xh, t1),
@@ -103,7 +88,7 @@ def split_ops(t0, t1, h0, h1, xh, xl):
 # Training (mlp_fwd_f16x3_kernel<true>): the activation record of a layer is written by the block that CONSUMES that layer's
 # accumulators -- its conversion already forms h = relu(acc * 2^-8) in t0 / t1 -- instead of a separate pass over the set
 # after the layer (round 2: ~34 of 164 us per tile, compiled code reading the tiles back through v_accvgpr_read).  Per
-# converted element: one ds_write_b32 into the wave's private 4 KB staging tile (features on rows, as the C++ pass did it)
+# converted element: one ds_write_b32 into the wave's private 4 KB staging tile (features on rows)
 # and v_cmp + v_addc (sign bit of the ReLU mask word); per 32 x 32 tile: four ds_read_b128 of the transposed tile and four
 # nontemporal 16-byte stores one chunk / group later; per two tiles: one mask word.  All of it rides in MFMA issue gaps.
 #   %[recw] / %[recr]  VGPR: LDS byte address of this lane's writes / 16-byte reads (mlp_fwd_f16x3.hip: rec_ctx)
@@ -126,11 +111,8 @@ def conv_rec(src_base, tile, g, bank, mask=True):
     t0, t1 = T, T + 1
     r0, r1 = 2 * g, 2 * g + 1
     out = c[0:6]
-    if EXPERIMENT != "recnolds":
-        out += ["ds_write_b32 %%[recw], v%d offset:%d" % (t0, rec_wr_off(r0)),
-                "ds_write_b32 %%[recw], v%d offset:%d" % (t1, rec_wr_off(r1))]
-    else:
-        out += ["s_nop 0", "s_nop 0"]
+    out += ["ds_write_b32 %%[recw], v%d offset:%d" % (t0, rec_wr_off(r0)),
+            "ds_write_b32 %%[recw], v%d offset:%d" % (t1, rec_wr_off(r1))]
     if mask:
         out += ["v_cmp_lt_f32_e32 vcc, 0, v%d" % t0,
                 "v_addc_co_u32_e32 v%d, vcc, v%d, v%d, vcc" % (MK, MK, MK),
@@ -149,17 +131,12 @@ def rec_reads(set_base, tile):
     """the staged tile back out of LDS, transposed, into the accumulator registers of the SOURCE tile itself: they are dead
     from the tile's conversion until it is re-seeded (WIDE: moved behind the stores) or for good (HEAD); LDS loads may
     target AGPRs and vector stores may take their data from them on gfx950 -- no VGPR is spent on the record"""
-    if EXPERIMENT == "recnolds":
-        return []
     return ["ds_read_b128 %s, %%[recr] offset:%d" % (tile_regs(set_base, tile, k), k * 4096) for k in range(4)]
 
 
 def rec_store(set_base, tile, k):
     # units 2, 3 sit 16 rows (2 KB) behind units 0, 1 with the same swizzle: two offset registers, an immediate for the rest
-    if EXPERIMENT in ("recnostore", "recnolds"):
-        return "s_nop 0"
-    policy = {"recplain": "", "recsc1": " sc1", "recsc01": " sc0 sc1"}.get(EXPERIMENT, " nt")
-    return "global_store_dwordx4 %%[ro%d], %s, s[%d:%d] offset:%d%s" % (k & 1, tile_regs(set_base, tile, k), RB, RB + 1, (k >> 1) * 2048, policy)
+    return "global_store_dwordx4 %%[ro%d], %s, s[%d:%d] offset:%d nt" % (k & 1, tile_regs(set_base, tile, k), RB, RB + 1, (k >> 1) * 2048)
 
 
 def rec_advance():
@@ -168,8 +145,6 @@ def rec_advance():
 
 def rec_mask_store(w4):
     # bits were pushed MSB-first (tile 2 w4 register 0 first): reverse -> bit b <-> tile 2 w4 + b / 16, register b % 16
-    if EXPERIMENT in ("recnostore", "recnolds"):
-        return []
     return ["v_bfrev_b32_e32 v%d, v%d" % (MK, MK),
             "global_store_dword %%[mkoff], v%d, %%[rbase] offset:%d" % (MK, w4 * 256)]
 
@@ -222,8 +197,7 @@ def dma_piece(e, k, dma_slot):
         e("s_add_i32 m0, %%[m%da], 0x1000" % dma_slot)
         e("s_nop 0")
     base = "s[%d:%d]" % ((BA, BA + 1) if k < 4 else (BB, BB + 1))
-    if EXPERIMENT != "nodma":
-        e("global_load_lds_dwordx4 %%[laneoff], %s offset:%d" % (base, (k & 3) * 1024))
+    e("global_load_lds_dwordx4 %%[laneoff], %s offset:%d" % (base, (k & 3) * 1024))
 
 
 def ring_epilogue(e, n_chunks):
@@ -245,9 +219,8 @@ def refill(e, slot, pair, npairs, cur, nxt):
 
 
 def publish(e, young):
-    e("s_waitcnt vmcnt(%d) lgkmcnt(0)" % (0 if EXPERIMENT == "nodma" else young))
-    if EXPERIMENT != "nobarrier":
-        e("s_barrier")
+    e("s_waitcnt vmcnt(%d) lgkmcnt(0)" % young)
+    e("s_barrier")
 
 
 def chunk_groups(e, npairs, ts, mf, fill, free_after, pieces_per_group, tail=None, head=None, young_extra=0):
@@ -284,7 +257,7 @@ def chunk_groups(e, npairs, ts, mf, fill, free_after, pieces_per_group, tail=Non
                     # before this point; they retire in order with the pieces (MI355X_MICROARCH.md: loads, stores and
                     # LDS-DMA count together, in issue order), so the count must be exact: too small only waits longer,
                     # too large would let a piece of the chunk being published still be in flight
-                    publish(e, (g + 1) * pieces_per_group + (0 if EXPERIMENT in ("recnostore", "recnolds") else young_extra))
+                    publish(e, (g + 1) * pieces_per_group + young_extra)
                 refill(e, sa, q + 4, npairs, cur, nxt)
             if i + 1 == free_after[1]:
                 refill(e, sb, q + 5, npairs, cur, nxt)
@@ -361,8 +334,6 @@ def gen_wide(src, dst, rec=None):
             if ts == 7:
                 return [[], [], [], [], []]
             cv = conv(src, ts + 1, g, bank ^ 1)
-            if EXPERIMENT == "noconv":
-                return [[], [], [], [], []]
             return [[], cv[0:4], cv[4:8], cv[8:12], cv[12:13]]
 
         def tail(g, ts=ts):
@@ -464,7 +435,7 @@ def gen_head(src, rec=False):
         if not rec:
             if g == 7:
                 return [[], [], [], [], []]
-            # 88 (104) VALU instructions over five gaps: the head is conversion-bound (one tile per six MFMAs)
+            # 88 VALU instructions over five gaps: the head is conversion-bound (one tile per six MFMAs)
             return split_even(cv, 5)
         # tile g sits in its own accumulator registers again (read back at the end of the previous group / the prologue,
         # after its conversion): wait for those reads -- at
@@ -607,7 +578,7 @@ def gen_read_tile(src, tile):
 
 
 # ====================================================================================================== DATA GRADIENT
-# mlp_dgrad_f16x3_kernel (round 3): the backward chain dh = W^T dz of a head on the same blocks -- transposed f16x3 stream of
+# mlp_dgrad_f16x3_asm_kernel: the backward chain dh = W^T dz of a head on the same blocks -- transposed f16x3 stream of
 # 34 chunks, sets P / Q in ping-pong -- with the GATED conversion of the backward (the recorded ReLU sign words decide, not the
 # value) and the dz record written by the block that consumes the set (as the recording forward does).  No seeding: a
 # destination tile's first MFMA takes C = 0.  Extra operands:

@@ -585,11 +585,6 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_wgrad_f16x3_kernel(Wg2Params 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_wide = 6 * P.n_w;
-#if defined(WG2_ONLY_WIDE)                      // measurement builds: one kind of workgroup alone
-  if ((int)blockIdx.x >= n_wide) return;
-#elif defined(WG2_ONLY_NARROW)
-  if ((int)blockIdx.x < n_wide) return;
-#endif
   if ((int)blockIdx.x < n_wide) {
     const int gemm = (int)blockIdx.x % 6, slice = (int)blockIdx.x / 6;       // 0..5: mlp_trans.{2,1,0}, mlp_rgb.{2,1,0}
     if (gemm == 5) wg2_run_wide<true>(P, lds, gemm, slice, wave, lane);

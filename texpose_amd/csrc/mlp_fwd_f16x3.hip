@@ -16,11 +16,7 @@
 // 8s..8s+7 of a 32x32 tile, converted to fp16, ARE the B fragment of k-step s (rows 16s + 8(j>>2) + 4h + (j&3)),
 // and the packed weights absorb that row permutation (mlp_layout.h, "f16x3 stream").
 #include "mlp_mma.h"
-#ifndef TP_WIDE_ASM_INC
-#define TP_WIDE_ASM_INC "wide_asm.inc.h"
-#endif
-#include TP_WIDE_ASM_INC
-#include <cstdlib>
+#include "wide_asm.inc.h"
 #include <type_traits>
 
 namespace {
@@ -45,10 +41,6 @@ __device__ __forceinline__ half8 pack8(const half2v (&p)[4]) {
   return __builtin_bit_cast(half8, w);
 }
 
-__device__ __forceinline__ f32x16 mfma16(half8 a, half8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 // Three-slot ring instead of the fp32 kernel's double buffer: a chunk is only 48 MFMAs (1536 cycles, ~0.65 us)
 // here, shorter than an L2->LDS DMA round trip, so the prefetch runs TWO chunks ahead.  The DMA of chunk c+2 stays
 // in flight across the barrier: counted `s_waitcnt vmcnt(n)` (the n DMA instructions of the newest chunk issued so
@@ -60,7 +52,8 @@ __device__ __forceinline__ f32x16 mfma16(half8 a, half8 b, f32x16 c) {
 // iterations of chunk c already fetch the first pairs of chunk c+1.  With one wave per SIMD nothing else would hide
 // the LDS latency of a per-chunk prologue.  Slot safety: the DMA issued at the start of chunk c+1 (chunk c+3)
 // overwrites the slot of chunk c, and every wave has completed (lgkmcnt(0)) all its reads of chunk c before it
-// arrives at chunk c's barrier, which every wave passes before it starts chunk c+1.
+// arrives at chunk c's barrier, which every wave passes before it starts chunk c+1.  The generated blocks of
+// wide_asm.inc.h run this protocol; the compiled code only primes the ring at kernel start (frag_prime).
 constexpr int kDepth = 4;
 constexpr int kPairHalves = 1024;                  // one (k-step, tile) pair: 512 halves hi + 512 halves lo
 struct Frag { half8 h[kDepth], l[kDepth]; };
@@ -75,83 +68,14 @@ __device__ __forceinline__ long long tick() {
 #define TR_END(k, a) p.tr[k] += tick() - tr_##a
 #else
 // product build: the section marks stay compiler fences.  They keep hipcc from moving LDS / memory operations of
-// one section into another (e.g. hoisting the 32 bias reads of init_acc across a head), which lengthens live ranges
+// one section into another (e.g. hoisting a staging section's loads across a head), which lengthens live ranges
 // past what the 512-register budget next to two accumulator sets allows and ends in scratch spills.
 #define TR_BEGIN(a) asm volatile("" ::: "memory")
 #define TR_END(k, a) asm volatile("" ::: "memory")
 #endif
-// The DMA of chunk c+2 is not issued as one burst at the start of chunk c (eight LDS-DMA instructions cost ~30 issue
-// cycles each while the matrix pipe drains) but spread over the chunk's MFMA groups, one or two 1 KiB pieces per
-// group, so that each issue hides under the 6 MFMAs in flight.  `Dma` = where the pieces of the chunk being
-// prefetched go; piece k: global base + k KiB -> LDS slot base + k KiB (instruction immediates for k mod 4).
-struct Dma { const char* src[2]; float* dst[2]; };
-template <int NCH = kNumChunks>
-__device__ __forceinline__ Dma ring_begin(Pipe& p) {
-  int nxt = p.chunk + 2;
-  if (nxt >= NCH) nxt -= NCH;
-  int slot = p.buf + 2;
-  if (slot >= kBufs) slot -= kBufs;
-  const float* base = p.stream + (size_t)nxt * kChunkFloats + p.wave * 2048;
-  float* dst = p.lds + slot * kChunkFloats + p.wave * 2048;
-  const unsigned lane_off = (unsigned)p.lane * 16u;
-  Dma d;
-  d.src[0] = reinterpret_cast<const char*>(base) + lane_off;
-  d.src[1] = reinterpret_cast<const char*>(base + 1024) + lane_off;
-  d.dst[0] = dst;
-  d.dst[1] = dst + 1024;
-  return d;
-}
-template <int K>
-__device__ __forceinline__ void dma_piece(const Dma& d) {
-  __builtin_amdgcn_global_load_lds(AS1(d.src[K >> 2]), AS3(d.dst[K >> 2]), 16, (K & 3) * 1024, 0);
-}
-// pieces issued at the start of MFMA group `it` of a chunk with NG groups (8 pieces per chunk and wave); `it` is a
-// constant after unrolling, so the switch folds away
-template <int NG>
-__device__ __forceinline__ void dma_step(const Dma& d, int it) {
-  constexpr int PPI = 8 / NG;
-  static_assert(PPI * NG == 8, "8 pieces over NG groups");
-#pragma unroll
-  for (int k = 0; k < PPI; ++k)
-    switch (it * PPI + k) {
-      case 0: dma_piece<0>(d); break;
-      case 1: dma_piece<1>(d); break;
-      case 2: dma_piece<2>(d); break;
-      case 3: dma_piece<3>(d); break;
-      case 4: dma_piece<4>(d); break;
-      case 5: dma_piece<5>(d); break;
-      case 6: dma_piece<6>(d); break;
-      default: dma_piece<7>(d); break;
-    }
-}
-// YOUNG = DMA pieces of the chunk being prefetched that this chunk has issued before the publish point: they may stay
-// in flight, everything older (the next chunk, which is about to be read) has landed
-template <int YOUNG>
-__device__ __forceinline__ void ring_publish(Pipe& tr) {
-#ifdef TP_TRACE
-  const long long t0 = tick();
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(YOUNG) : "memory");
-  const long long t1 = tick();
-  __builtin_amdgcn_s_barrier();
-  const long long t2 = tick();
-  tr.tr[1] += t1 - t0; tr.tr[2] += t2 - t1;
-#else
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(YOUNG) : "memory");
-  __builtin_amdgcn_s_barrier();
-#endif
-  asm volatile("" ::: "memory");
-}
-template <int NCH = kNumChunks>
-__device__ __forceinline__ void ring_advance(Pipe& p) {
-  p.chunk = (p.chunk + 1 == NCH) ? 0 : p.chunk + 1;
-  p.buf = (p.buf + 1 == kBufs) ? 0 : p.buf + 1;
-}
+
 __device__ __forceinline__ const _Float16* chunk_ptr16(const Pipe& p) {
   return reinterpret_cast<const _Float16*>(p.lds + p.buf * kChunkFloats) + p.lane * 8;
-}
-__device__ __forceinline__ const _Float16* next_chunk_ptr16(const Pipe& p) {
-  const int nb = (p.buf + 1 == kBufs) ? 0 : p.buf + 1;
-  return reinterpret_cast<const _Float16*>(p.lds + nb * kChunkFloats) + p.lane * 8;
 }
 __device__ __forceinline__ void frag_fetch(Frag& f, int slot, const _Float16* src) {
   f.h[slot] = *reinterpret_cast<const half8*>(src);
@@ -163,153 +87,20 @@ __device__ __forceinline__ void frag_prime(const Pipe& p, Frag& f) {
 #pragma unroll
   for (int q = 0; q < kDepth; ++q) frag_fetch(f, q, l + q * kPairHalves);
 }
-// after the MFMAs of pairs q, q+1 of an NP-pair chunk: publish the next chunk when it is about to be fetched from,
-// then fetch pairs q+kDepth, q+kDepth+1 (of this chunk or the next)
-template <int NP>
-__device__ __forceinline__ void frag_step(Pipe& p, Frag& f, int q, const _Float16* l, const _Float16* ln) {
-  // groups 0 .. (NP - kDepth) / 2 have issued their DMA pieces by now
-  if (q == NP - kDepth) ring_publish<((NP - kDepth) / 2 + 1) * (8 / (NP / 2))>(p);
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const int g = q + d + kDepth;
-    frag_fetch(f, (q + d) % kDepth, g < NP ? l + g * kPairHalves : ln + (g - NP) * kPairHalves);
-  }
-  // the next fetches issue right AFTER the first MFMA of the group (not before it): the lgkmcnt wait hipcc places
-  // before that MFMA then covers only fetches that are already >= 5 MFMAs old
-  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-  __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-  __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
-}
 
-// (k-step, tile) pairs of a wide chunk; pair q = s*8 + t, two tiles at a time with their three products
-// interleaved: consecutive MFMAs never share an accumulator
-template <int KS, int NCH = kNumChunks, class BFn, class PostFn>
-__device__ __forceinline__ void mma_wide16(Pipe& p, Frag& f, f32x16 (&acc)[8], BFn b, PostFn post) {
-  constexpr int NP = KS * 8;
-  const Dma dma = ring_begin<NCH>(p);
-  const _Float16* l = chunk_ptr16(p);
-  const _Float16* ln = next_chunk_ptr16(p);
-  TR_BEGIN(w);
-#pragma unroll
-  for (int q = 0; q < NP; q += 2) {
-    const int s = q >> 3, t = q & 7;
-    const half8 wh0 = f.h[q % kDepth], wl0 = f.l[q % kDepth];
-    const half8 wh1 = f.h[(q + 1) % kDepth], wl1 = f.l[(q + 1) % kDepth];
-    half8 xh, xl;
-    b(s, xh, xl);
-    dma_step<NP / 2>(dma, q >> 1);
-    acc[t] = mfma16(wh0, xh, acc[t]);
-    acc[t + 1] = mfma16(wh1, xh, acc[t + 1]);
-    acc[t] = mfma16(wh0, xl, acc[t]);
-    acc[t + 1] = mfma16(wh1, xl, acc[t + 1]);
-    acc[t] = mfma16(wl0, xh, acc[t]);
-    acc[t + 1] = mfma16(wl1, xh, acc[t + 1]);
-    post(q);                   // VALU work that rides in the issue gaps of the six MFMAs above
-    frag_step<NP>(p, f, q, l, ln);
-    // keep this pair's fragment refills HERE, two pairs ahead of their use: left alone the scheduler sinks them to just
-    // before the MFMAs that read them and every pair then waits out a full LDS latency (s_waitcnt lgkmcnt(0))
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  TR_END(3, w);
-  ring_advance<NCH>(p);
-}
-
-// ---------------------------------------------------------------------------------------------- operand conversion
-// Two accumulator sets P and Q alternate: even layers read Q and accumulate into P, odd layers read P and
-// accumulate into Q (the layer loop is unrolled by two so that both roles are fixed registers -- no copy between
-// layers).  A set holds the raw accumulators, bias included (they start at bias * 2^8); the next layer's B operands
-// are produced from it on the fly: 2^-8, ReLU, hi/lo split, pack for source tile ts+1 while the MFMAs of source
-// tile ts issue.
-struct Xop { half8 h[2], l[2]; };     // B operands of one source tile (2 k-steps of 16 features)
-struct XBuild { half2v hp[8], lp[8]; };
-
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 // range guard: running maximum of the packed hi halves (v_pk_max_f16, two elements per instruction).  Round-to-zero
 // conversion saturates at 65504, so "amax >= 6e4" still detects every out-of-range activation.
 struct Guard { half2v m = {(__fp16)0.0f, (__fp16)0.0f}; };
-__device__ __forceinline__ void convert2(const f32x16& a, int e0, half2v& hp, half2v& lp, Guard& g) {
-  const f32x2 sc = f32x2{a[e0], a[e0 + 1]} * kInvScale;      // v_pk_mul_f32; its result is canonical, so the max
-  const float v0 = fmaxf(sc.x, 0.0f);                         // needs no extra canonicalising v_max
-  const float v1 = fmaxf(sc.y, 0.0f);
-  const float h0 = __uint_as_float(__float_as_uint(v0) & 0xFFFFE000u);   // 11 significant bits: exact in fp16
-  const float h1 = __uint_as_float(__float_as_uint(v1) & 0xFFFFE000u);
-  hp = __builtin_amdgcn_cvt_pkrtz(h0, h1);
-  lp = __builtin_amdgcn_cvt_pkrtz(v0 - h0, v1 - h1);
-  g.m = __builtin_elementwise_max(g.m, hp);
-}
-__device__ __forceinline__ Xop finish(const XBuild& b) {
-  Xop x;
-  const half2v h0[4] = {b.hp[0], b.hp[1], b.hp[2], b.hp[3]}, h1[4] = {b.hp[4], b.hp[5], b.hp[6], b.hp[7]};
-  const half2v l0[4] = {b.lp[0], b.lp[1], b.lp[2], b.lp[3]}, l1[4] = {b.lp[4], b.lp[5], b.lp[6], b.lp[7]};
-  x.h[0] = pack8(h0); x.h[1] = pack8(h1); x.l[0] = pack8(l0); x.l[1] = pack8(l1);
-  return x;
-}
-__device__ __forceinline__ Xop convert_tile(const f32x16& a, Guard& amax) {
-  XBuild xb;
-#pragma unroll
-  for (int e = 0; e < 16; e += 2) convert2(a, e, xb.hp[e >> 1], xb.lp[e >> 1], amax);
-  return finish(xb);
-}
-// accumulators start at bias * 2^8 (pre-scaled in LDS): `bl` = bias block of the layer being computed (this lane half)
-__device__ __forceinline__ void init_acc(f32x16 (&acc)[8], const float* bl) {
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(bl + t * 16 + g * 4);
-      acc[t][g * 4 + 0] = v.x; acc[t][g * 4 + 1] = v.y; acc[t][g * 4 + 2] = v.z; acc[t][g * 4 + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ void part_gen16(Pipe& p, Frag& f, f32x16 (&acc)[8], const f32x16 (&V)[8], Guard& amax) {
-  TR_BEGIN(g0);
-  Xop X = convert_tile(V[0], amax);
-  asm volatile("" :: "v"(X.h[0]), "v"(X.l[1]));
-  TR_END(12, g0);
-#pragma unroll
-  for (int ts = 0; ts < 8; ++ts) {
-    XBuild xb;
-    const auto bop = [&](int s, half8& xh, half8& xl) { xh = X.h[s]; xl = X.l[s]; };
-    const auto cvt = [&](int q) { if (ts < 7) convert2(V[ts < 7 ? ts + 1 : 0], q, xb.hp[q >> 1], xb.lp[q >> 1], amax); };
-    mma_wide16<2>(p, f, acc, bop, cvt);
-    if (ts < 7) X = finish(xb);
-  }
-}
-
-// 1..5-row output layer over relu(V): one chunk, 16 k-steps, one accumulator tile, operands converted just in time
-__device__ __forceinline__ f32x16 part_head16(Pipe& p, Frag& f, const f32x16 (&V)[8], Guard& amax) {
-  f32x16 acc = {0};
-  const Dma dma = ring_begin(p);
-  const _Float16* l = chunk_ptr16(p);
-  const _Float16* ln = next_chunk_ptr16(p);
-#pragma unroll
-  for (int ts = 0; ts < 8; ++ts) {
-    const Xop X = convert_tile(V[ts], amax);
-    const int q = ts * 2;                          // pair q = k-step 2 ts, pair q+1 = k-step 2 ts + 1
-    const half8 wh0 = f.h[q % kDepth], wl0 = f.l[q % kDepth];
-    const half8 wh1 = f.h[(q + 1) % kDepth], wl1 = f.l[(q + 1) % kDepth];
-    dma_step<8>(dma, ts);
-    acc = mfma16(wh0, X.h[0], acc);
-    acc = mfma16(wh0, X.l[0], acc);
-    acc = mfma16(wl0, X.h[0], acc);
-    acc = mfma16(wh1, X.h[1], acc);
-    acc = mfma16(wh1, X.l[1], acc);
-    acc = mfma16(wl1, X.h[1], acc);
-    frag_step<16>(p, f, q, l, ln);
-  }
-  ring_advance(p);
-  return acc;
-}
 
 __device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 
 // =====================================================================================================================
-// Everything of the FORWARD kernel that touches the two accumulator sets runs in the hand-scheduled asm blocks of
-// wide_asm.inc.h (generated by gen_wide_asm.py; the register map and the ring protocol are documented there): set P is
-// pinned to a[0:127], set Q to a[128:255], the fragment ring to v[160:191].  The C++ around them stages inputs, applies
-// the output non-linearities and stores.  (The dgrad kernel further down still uses the C++ layer body above.)
+// Everything that touches the two accumulator sets -- in the forward kernels and in the data gradient further down -- runs
+// in the hand-scheduled asm blocks of wide_asm.inc.h (generated by gen_wide_asm.py; the register map and the ring protocol
+// are documented there): set P is pinned to a[0:127], set Q to a[128:255], the fragment ring to v[160:191].  The C++ around
+// them stages inputs, applies the output non-linearities and stores.
 // =====================================================================================================================
 struct AsmCtx { unsigned lane16, laneoff, ldswave, stream_lo, stream_hi, bias0, stage0; int nch; };
 // The context is RE-DERIVED from the hardware thread id at every block instead of being carried in registers: the compiler
@@ -365,26 +156,6 @@ __device__ __forceinline__ AsmCtx asm_ctx_now(const float* packed, int nch = kNu
       "{v[112:127]}"(F[5]), "{v[128:143]}"(F[6]), "{v[144:159]}"(F[7])
 __device__ __forceinline__ void asm_stash_q(f32x16 (&F)[8]) { asm volatile(TP_ASM_STASH_Q : TP_SF_OUT(F) : : TP_ASM_ALL_AGPRS); }
 __device__ __forceinline__ void asm_restore_p(const f32x16 (&F)[8]) { asm volatile(TP_ASM_RESTORE_P : : TP_SF_IN(F) : TP_ASM_ALL_AGPRS); }
-// one tile of a set as a value (the training variant writes the activation record from compiled code)
-template <bool SET_P, int T>
-__device__ __forceinline__ f32x16 asm_read_tile() {
-  f32x16 v;
-#define TP_RD(NAME) asm volatile(NAME : "={v[232:247]}"(v) : : TP_ASM_ALL_AGPRS)
-  if constexpr (SET_P) {
-    if constexpr (T == 0) TP_RD(TP_ASM_READ_P0); else if constexpr (T == 1) TP_RD(TP_ASM_READ_P1);
-    else if constexpr (T == 2) TP_RD(TP_ASM_READ_P2); else if constexpr (T == 3) TP_RD(TP_ASM_READ_P3);
-    else if constexpr (T == 4) TP_RD(TP_ASM_READ_P4); else if constexpr (T == 5) TP_RD(TP_ASM_READ_P5);
-    else if constexpr (T == 6) TP_RD(TP_ASM_READ_P6); else TP_RD(TP_ASM_READ_P7);
-  } else {
-    if constexpr (T == 0) TP_RD(TP_ASM_READ_Q0); else if constexpr (T == 1) TP_RD(TP_ASM_READ_Q1);
-    else if constexpr (T == 2) TP_RD(TP_ASM_READ_Q2); else if constexpr (T == 3) TP_RD(TP_ASM_READ_Q3);
-    else if constexpr (T == 4) TP_RD(TP_ASM_READ_Q4); else if constexpr (T == 5) TP_RD(TP_ASM_READ_Q5);
-    else if constexpr (T == 6) TP_RD(TP_ASM_READ_Q6); else TP_RD(TP_ASM_READ_Q7);
-  }
-#undef TP_RD
-  return v;
-}
-
 // 256 -> 256 layer body; SRC_Q: read set Q, accumulate into set P, else the reverse
 template <bool SRC_Q>
 __device__ __forceinline__ void asm_wide(Pipe& p, Frag& f, Guard& amax, const AsmCtx& c, int next_li) {
@@ -606,13 +377,6 @@ __device__ __forceinline__ void stage_slot(_Float16* st, int tid_lo, int slot, f
   st[((ks * 2 + 1) * kThreads + owner) * 8 + jj] = (_Float16)(v - (float)hi);
 }
 
-// a[c] for a run-time c in 0..2 as pure ALU work (a three-way select of VARIABLES is rewritten by the optimiser into an
-// indexed load, which demotes them -- and everything captured next to them -- to scratch memory)
-__device__ __forceinline__ float pick3(int c, float a0, float a1, float a2) {
-  const uint32_t m0 = c == 0 ? 0xFFFFFFFFu : 0u, m1 = c == 1 ? 0xFFFFFFFFu : 0u, m2 = c == 2 ? 0xFFFFFFFFu : 0u;
-  return __uint_as_float((__float_as_uint(a0) & m0) | (__float_as_uint(a1) & m1) | (__float_as_uint(a2) & m2));
-}
-
 // Thread coordinates are RE-DERIVED from the hardware id at the top of every section of the tile loop (the empty volatile asm
 // keeps the derivations apart): carried through the asm blocks they lived in scratch memory, like the block context above.
 #define TP_THREAD_IDS                                                                                                  \
@@ -809,18 +573,6 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         if (li == L0) {
           TP_THREAD_IDS;
           const float x0 = save[0 * kThreads], x1 = save[1 * kThreads], x2 = save[2 * kThreads];
-#ifdef TP_PE_PER_OCTAVE
-          // (A/B build, make pe_octave: round 3's staging -- one fp64 range reduction per (coordinate, octave) pair, 15 per lane)
-#pragma unroll 5
-          for (int i = 0; i < 15; ++i) {
-            const int pi_ = hh * 15 + i, c = (pi_ * 205) >> 11, l = pi_ - c * 10;
-            const float xc = pick3(c, x0, x1, x2);
-            float sv, cv;
-            tp::sincos_both(tp::mul_rn(xc, ldexpf(3.14159274101257324f, l)), sv, cv);
-            stage_slot(st, tid & ~32, 20 * c + l, sv);
-            stage_slot(st, tid & ~32, 20 * c + 10 + l, cv);
-          }
-#else
           // ONE fp64 range reduction per coordinate, then the ten octaves by angle doubling (tp::sincos_f64: the argument of octave
           // l is exactly 2^l * fl32(x pi_f32)).  Lane hh of the sample's lane pair runs the chain of coordinate 2 hh and stages its
           // sin AND cos entries (slots 20 c + l, 20 c + 10 + l); both lanes run the chain of coordinate 1, lane 0 stages its sin
@@ -835,7 +587,6 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
             stage_slot(st, tid & ~32, 20 + 10 * hh + l, (float)(hh ? eb.c : eb.s));
             if (l < 9) { tp::sincos_double(ea); tp::sincos_double(eb); }
           }
-#endif
           if (hh) {
             stage(st, tid, 3, 4, x0); stage(st, tid, 3, 5, x1); stage(st, tid, 3, 6, x2); stage(st, tid, 3, 7, 0.0f);
           }
@@ -890,18 +641,6 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
         const float x0 = save[0 * kThreads], x1 = save[1 * kThreads], x2 = save[2 * kThreads];
         const float vu0 = save[3 * kThreads], vu1 = save[4 * kThreads], vu2 = save[5 * kThreads];
         const int br = __float_as_int(save[6 * kThreads]);
-#ifdef TP_PE_PER_OCTAVE
-#pragma unroll 3
-        for (int i = 0; i < 6; ++i) {
-          const int pi_ = hh * 6 + i, c = pi_ >> 2, l = pi_ & 3;
-          const float vc = pick3(c, vu0, vu1, vu2);
-          float sv, cv;
-          tp::sincos_both(tp::mul_rn(vc, ldexpf(3.14159274101257324f, l)), sv, cv);
-          stage_slot(st, tid & ~32, 3 + 8 * c + l, sv);
-          stage_slot(st, tid & ~32, 3 + 8 * c + 4 + l, cv);
-          if (SAVE && live) { sx[blk_off(3 + 8 * c + l, j)] = sv; sx[blk_off(3 + 8 * c + 4 + l, j)] = cv; }
-        }
-#else
         // the view encoding (4 octaves) the same way: chain of coordinate 2 hh (sin and cos), chain of coordinate 1 (lane 0 its sin
         // entries, lane 1 its cos entries); slot 3 + 8 c + l = sin, + 4 = cos
         {
@@ -919,7 +658,6 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_f16x3_kernel(Params P) {
             if (l < 3) { tp::sincos_double(ea); tp::sincos_double(eb); }
           }
         }
-#endif
         if (hh == 0) {
           stage(st, tid, 0, 0, vu0); stage(st, tid, 0, 1, vu1); stage(st, tid, 0, 2, vu2);
           if (SAVE && live) { sx[blk_off(0, j)] = vu0; sx[blk_off(1, j)] = vu1; sx[blk_off(2, j)] = vu2; }
@@ -1145,209 +883,10 @@ struct DgP {
   unsigned int* dz_max;
 };
 
-// gate bit of (tile t, register r) in the recorded ReLU sign words
-__device__ __forceinline__ bool gate(const uint32_t (&mask)[4], int t, int r) { return (mask[t >> 1] >> ((t & 1) * 16 + r)) & 1u; }
-
-// `sink(t, e0, v0, v1)` receives the gated, 2^-8-scaled pair: the dz record of the layer that produced `a` is written from
-// here, i.e. from the issue gaps of the NEXT layer's MFMAs, instead of in a store-only pass between the layers
-template <class Sink>
-__device__ __forceinline__ void convert2m(const f32x16& a, int t, int e0, const uint32_t (&mask)[4], half2v& hp, half2v& lp,
-                                          Sink& sink) {
-  const f32x2 sc = f32x2{a[e0], a[e0 + 1]} * kInvScale;
-  const float v0 = gate(mask, t, e0) ? sc.x : 0.0f, v1 = gate(mask, t, e0 + 1) ? sc.y : 0.0f;
-  const float h0 = __uint_as_float(__float_as_uint(v0) & 0xFFFFE000u);
-  const float h1 = __uint_as_float(__float_as_uint(v1) & 0xFFFFE000u);
-  hp = __builtin_amdgcn_cvt_pkrtz(h0, h1);
-  lp = __builtin_amdgcn_cvt_pkrtz(v0 - h0, v1 - h1);
-  sink(t, e0, v0, v1);
-}
-template <class Sink>
-__device__ __forceinline__ Xop convert_tile_m(const f32x16& a, int t, const uint32_t (&mask)[4], Sink& sink) {
-  XBuild xb;
-#pragma unroll
-  for (int e = 0; e < 16; e += 2) convert2m(a, t, e, mask, xb.hp[e >> 1], xb.lp[e >> 1], sink);
-  return finish(xb);
-}
-// one 256 -> 256 transposed layer: acc += W^T (gated S * 2^-8)
-template <class Sink>
-__device__ __forceinline__ void part_gen16m(Pipe& p, Frag& f, f32x16 (&acc)[8], const f32x16 (&S)[8], const uint32_t (&mask)[4],
-                                            Sink& sink) {
-  Xop X = convert_tile_m(S[0], 0, mask, sink);
-#pragma unroll
-  for (int ts = 0; ts < 8; ++ts) {
-    XBuild xb;
-    const auto bop = [&](int s, half8& xh, half8& xl) { xh = X.h[s]; xl = X.l[s]; };
-    const auto cvt = [&](int q) {
-      if (ts < 7) convert2m(S[ts < 7 ? ts + 1 : 0], ts + 1, q, mask, xb.hp[q >> 1], xb.lp[q >> 1], sink);
-      else if (q == 0) sink.flush_read(7);
-      else if (q == 8) sink.flush_store(7);
-    };
-    mma_wide16<2, kNumChunksT>(p, f, acc, bop, cvt);
-    if (ts < 7) X = finish(xb);
-  }
-}
-
-// Where the gated dz values of a layer go (convert2m's sink): each wave transposes its [32 feature][32 sample] tile through
-// two private 4 KB LDS tiles -- 16 ds_write_b32 of this lane's sample, 4 ds_read_b128 of four consecutive samples of one
-// feature -- so that the record is written with four 16-byte stores per tile and lane instead of sixteen 4-byte ones (the
-// store path is issue-bound: ~140 cycles per store instruction) at no VALU cost.  Tile t - 1 is flushed while tile t is
-// being filled (ping-pong; its reads early, its stores five callbacks later); LDS operations of one wave execute in order,
-// so no wait separates fill and flush.
-struct DzSink {
-  float* stg;            // this wave's two staging tiles
-  float* blk;            // dz block of the step being recorded
-  int o4[4];             // float offsets of this lane's four 16-byte stores inside a tile's 1024 floats
-  int row0, lane;        // staging row of register 0 (4 hh) * 32 + sample j
-  bool live; float isc;
-  float* dzm;
-  f32x4 hold[4];         // a flushed tile between its LDS reads and its stores (kept apart: the read latency is not waited for)
-  __device__ __forceinline__ void flush_read(int t) {
-    const float* s = stg + (t & 1) * 1024;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) hold[k] = *reinterpret_cast<const f32x4*>(s + (k * 64 + lane) * 4);
-  }
-  __device__ __forceinline__ void flush_store(int t) const {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(hold[k], reinterpret_cast<f32x4*>(blk + t * 1024 + o4[k]));
-  }
-  __device__ __forceinline__ void operator()(int t, int e0, float v0, float v1) {
-    const float a = live ? v0 * isc : 0.0f, b = live ? v1 * isc : 0.0f;
-    float* s = stg + (t & 1) * 1024 + row0;
-    s[(8 * (e0 >> 2) + (e0 & 3)) * 32] = a;                    // register r <-> feature 8 (r >> 2) + 4 hh + (r & 3) of the tile
-    s[(8 * ((e0 + 1) >> 2) + ((e0 + 1) & 3)) * 32] = b;
-    *dzm = fmaxf(*dzm, fmaxf(fabsf(a), fabsf(b)));
-    if (t > 0 && e0 == 2) flush_read(t - 1);
-    if (t > 0 && e0 == 12) flush_store(t - 1);
-  }
-};
-
-__global__ __launch_bounds__(kThreads, 1) void mlp_dgrad_f16x3_kernel(DgP P) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: record
-  const int j = lane & 31, hh = lane >> 5;                        //  addresses become an SGPR base + 32-bit lane offsets)
-  Pipe p;
-  p.stream = P.packed_t; p.lds = lds; p.chunk = 0; p.buf = 0; p.wave = wave; p.lane = lane;
-  dma_chunk(p, 0, 0);
-  dma_chunk(p, 1, 1);
-  __syncthreads();
-  Frag frag;
-  frag_prime(p, frag);
-
-  for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
-    const int64_t s_raw = tile * 128 + wave * 32 + j;
-    const bool live = s_raw < P.n_samples;
-    const int64_t s = live ? s_raw : 0;            // (dead lanes recompute sample 0: any valid index; a literal needs no register)
-    const int64_t gidx = tile * 4 + wave;
-    const float* sv = P.saved + gidx * (int64_t)kSavedGroupFloats;
-    float* dzg = P.dz + gidx * (int64_t)kDzGroupFloats;
-    float dzm = 0.0f;
-    f32x16 SP[8], SQ[8];
-    DzSink sink;
-    sink.stg = lds + kBufs * kChunkFloats + wave * 2048;
-    sink.row0 = (4 * hh) * 32 + j; sink.lane = lane; sink.live = live; sink.dzm = &dzm;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const int u = k * 64 + lane; sink.o4[k] = blk_off(u >> 3, (u & 7) * 4); }
-
-    // gate + store the last dz block of a head (no layer follows that could carry it)
-    const auto finish_step = [&](const f32x16 (&D)[8], const uint32_t (&mask)[4]) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 2)
-          sink(t, r, gate(mask, t, r) ? D[t][r] * kInvScale : 0.0f, gate(mask, t, r + 1) ? D[t][r + 1] * kInvScale : 0.0f);
-      }
-      sink.flush_read(7);
-      sink.flush_store(7);
-    };
-    const auto load_mask = [&](int slot, uint32_t (&mask)[4]) {
-      const uint32_t* mk = reinterpret_cast<const uint32_t*>(sv + kMaskOff) + (slot - 1) * 256 + lane;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) mask[w] = mk[w * 64];
-    };
-
-#pragma nounroll
-    for (int head = 0; head < 2; ++head) {
-      // derivative of the output non-linearities (sigmoid: y(1-y); softplus: 1-exp(-y))
-      float d[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (live) {
-        const int sel = head == 0 ? 1 : 0;          // head 0 = transient (last dim 1), head 1 = static rgb
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float y = P.rgb[s * 6 + c * 2 + sel];
-          d[c] = P.g_rgb[s * 6 + c * 2 + sel] * y * (1.0f - y);
-        }
-        if (head == 0) {
-          d[3] = P.g_density[s * 2 + 1] * (1.0f - expf(-P.density[s * 2 + 1]));
-          d[4] = P.g_uncert[s] * (1.0f - expf(-P.uncert[s]));
-        }
-      }
-      float* nb = dzg + (head == 0 ? kDzT3Off : kDzR3Off);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) nb[blk_off(r + 16 * hh, j)] = (hh == 0 && r < 6) ? d[r < 6 ? r : 0] : 0.0f;
-      // per-sample power-of-two scale: largest |d| -> [2^5, 2^6)
-      float dmax = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) dmax = fmaxf(dmax, fabsf(d[c]));
-      float sc = 1.0f, isc = 1.0f;
-      if (dmax > 1.0e-30f && dmax < 1.0e30f) {     // (outside: no scaling -- such gradients are lost or infinite anyway)
-        int e;
-        (void)frexpf(dmax, &e);
-        sc = ldexpf(1.0f, 6 - e);
-        isc = ldexpf(1.0f, e - 6);
-      }
-      // B operand of the narrow chunk: slots 8 h + j of k-step 0 = d[0..5] (lane half 0), zeros elsewhere
-      half8 dh, dl;
-      {
-        half2v hp[4], lp[4];
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          const float v0 = (hh == 0 && e < 6) ? d[e < 6 ? e : 0] * sc : 0.0f;
-          const float v1 = (hh == 0 && e + 1 < 6) ? d[e + 1 < 6 ? e + 1 : 0] * sc : 0.0f;
-          const float h0 = __uint_as_float(__float_as_uint(v0) & 0xFFFFE000u);
-          const float h1 = __uint_as_float(__float_as_uint(v1) & 0xFFFFE000u);
-          hp[e >> 1] = __builtin_amdgcn_cvt_pkrtz(h0, h1);
-          lp[e >> 1] = __builtin_amdgcn_cvt_pkrtz(v0 - h0, v1 - h1);
-        }
-        dh = pack8(hp);
-        dl = pack8(lp);
-      }
-      const int slot0 = head == 0 ? SV_T2 : SV_R2;
-      uint32_t m0[4], m1[4], m2[4];
-      load_mask(slot0, m0);
-      load_mask(slot0 - 1, m1);
-      load_mask(slot0 - 2, m2);
-      asm volatile("" ::: "memory");
-      // step 0: output layer (5 or 3 rows) -> dz of the last hidden layer
-#pragma unroll
-      for (int t = 0; t < 8; ++t) SP[t] = f32x16{0};
-      mma_wide16<1, kNumChunksT>(p, frag, SP, [&](int, half8& xh, half8& xl) { xh = dh; xl = dl; }, [](int) {});
-      asm volatile("" ::: "memory");
-      // steps 1 and 2: the dz block of the previous step is stored from inside the layer that consumes it
-      sink.isc = isc;
-      sink.blk = dzg + (head * 3 + 0) * kBlockFloats;
-#pragma unroll
-      for (int t = 0; t < 8; ++t) SQ[t] = f32x16{0};
-      part_gen16m(p, frag, SQ, SP, m0, sink);
-      asm volatile("" ::: "memory");
-      sink.blk = dzg + (head * 3 + 1) * kBlockFloats;
-#pragma unroll
-      for (int t = 0; t < 8; ++t) SP[t] = f32x16{0};
-      part_gen16m(p, frag, SP, SQ, m1, sink);
-      sink.blk = dzg + (head * 3 + 2) * kBlockFloats;
-      finish_step(SP, m2);
-      asm volatile("" ::: "memory");
-    }
-    for (int off = 32; off >= 1; off >>= 1) dzm = fmaxf(dzm, __shfl_xor(dzm, off, 64));
-    if (lane == 0 && P.dz_max != nullptr && dzm == dzm && dzm < 3.0e38f) atomicMax(P.dz_max, __float_as_uint(dzm));
-  }
-}
-
-
 // =====================================================================================================================
-// The same data gradient on the hand-scheduled blocks of wide_asm.inc.h (round 3; gen_wide_asm.py "DATA GRADIENT"): the
-// compiled layer body above runs the matrix pipe at ~40 % (its gated conversions, staging-tile traffic and record stores are
-// scheduled by hipcc), this one issues every conversion, staging write, read-back and 16-byte store in an MFMA gap of the
-// layer that consumes the set.  Per head: NARROW (W3^T d -> set P), WIDE P->Q (records dz of layer 2), WIDE Q->P (records dz
+// The kernel runs on the hand-scheduled blocks of wide_asm.inc.h (gen_wide_asm.py "DATA GRADIENT"): every gated conversion,
+// staging-tile write, read-back and 16-byte record store is issued in an MFMA gap of the layer that consumes the set.
+// Per head: NARROW (W3^T d -> set P), WIDE P->Q (records dz of layer 2), WIDE Q->P (records dz
 // of layer 1), FINISH (records dz of layer 0).  Sets P / Q live in a[0:255]; nothing seeds them (first MFMA of a tile: C = 0).
 // LDS: weight ring 96 KiB | narrow B operand 8 KiB (hi, lo: 16 B per lane each) | four 4 KiB record staging tiles.
 // =====================================================================================================================
@@ -1526,22 +1065,16 @@ int tp_launch_mlp_dgrad_f16x3(const tp_mlp_bwd_args* a, float* dz, unsigned int*
     for (int i = 0; i < 4; ++i) { w.w[W_RGB0 + i] = a->weights.rgb_w[i]; w.w[W_TRANS0 + i] = a->weights.trans_w[i]; }
     hipLaunchKernelGGL(packT16_kernel, dim3(512), dim3(256), 0, stream, w, (_Float16*)a->packed_t);
   }
-  constexpr int kDgLds = kBufs * kChunkFloats * 4 + 4 * 2048 * 4;     // weight ring + two staging tiles per wave
   static unsigned long long attr_devices = 0;
   if (tp::first_use_on_device(attr_devices)) {
-    hipError_t e = hipFuncSetAttribute((const void*)mlp_dgrad_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDgLds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mlp_dgrad_f16x3_asm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDgLdsBytes);
+    hipError_t e = hipFuncSetAttribute((const void*)mlp_dgrad_f16x3_asm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDgLdsBytes);
     if (e != hipSuccess) { tp::set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
   }
   DgP D;
   D.packed_t = (const float*)a->packed_t; D.saved = a->saved; D.rgb = a->rgb; D.density = a->density; D.uncert = a->uncert;
   D.g_rgb = a->g_rgb; D.g_density = a->g_density; D.g_uncert = a->g_uncert;
   D.n_samples = (int64_t)a->B * a->R * a->N; D.n_tiles = (D.n_samples + 127) / 128; D.dz = dz; D.dz_max = dz_max;
-  // TP_DGRAD_CXX=1 (read once): the compiled layer body of round 2, kept for same-device A/B runs
-  static const bool use_cxx = [] { const char* e = getenv("TP_DGRAD_CXX"); return e != nullptr && e[0] == '1'; }();
-  if (use_cxx) hipLaunchKernelGGL(mlp_dgrad_f16x3_kernel, dim3(grid), dim3(kThreads), kDgLds, stream, D);
-  else hipLaunchKernelGGL(mlp_dgrad_f16x3_asm_kernel, dim3(grid), dim3(kThreads), kDgLdsBytes, stream, D);
+  hipLaunchKernelGGL(mlp_dgrad_f16x3_asm_kernel, dim3(grid), dim3(kThreads), kDgLdsBytes, stream, D);
   return tp::check_launch("tp_mlp_bwd(dgrad f16x3)");
 }
 

@@ -65,7 +65,6 @@ _SPEC: Tuple[Tuple[str, str, object, str], ...] = (
 # read by libtexpose_amd.so itself (getenv in csrc/*): kernel-variant A/B switches, listed so that they are KNOWN names
 LIBRARY_SWITCHES: Dict[str, str] = {
     "TP_FP32_CXX": "1: the compiled exact-fp32 MLP kernels instead of the generated-assembly ones (bit-identical; read per call)",
-    "TP_DGRAD_CXX": "1: the compiled f16x3 data-gradient kernel instead of the generated-assembly one",
     "TP_SN_GRAD_ELEMS": "elements per workgroup of the spectral-norm backward's second launch",
     "TP_ADAM_BLOCKS": "upper bound on tp_adam_step's workgroups",
     "TP_CONV_TARGET_WGS": "split-K target of the stride-2 convolution kernels",
