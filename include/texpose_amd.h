@@ -1287,6 +1287,64 @@ typedef struct tp_depth_icp_args {
 size_t tp_depth_icp_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
 int tp_depth_icp_step(const tp_depth_icp_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K30  one step of batched photometric alignment: B poses refined against a photograph (texpose_amd/photo_align.py; restated in
+ *      tests/photo_ref.py; the project's own step, no reference code).  zbuf / rgb are K19's planes of the
+ *      vertex-coloured mesh rendered at pose; the call compares rgb with the photograph and takes one damped Gauss-Newton step of
+ *      the update x' = x + w x x + v in the camera frame (parameters (w, v), as tp_depth_icp_step): a surface point keeps its
+ *      colour, the pixel it lands on moves, and the photograph's own central-difference gradient says what it would see there.
+ *      Per pixel (row i, column j) of image b, with K = intr[b] (fx = K_00, fy = K_11, cx = K_02, cy = K_12) and the photograph
+ *      fr = frame ? frame[b] CLAMPED into [0, Ft) : (Ft == 1 ? 0 : b), everything in fp64 from the fp32 inputs, evaluated as
+ *      written (no contraction):
+ *        1. skipped unless 1 <= i <= H - 2 and 1 <= j <= W - 2 (an image with H < 3 or W < 3 keeps nothing)
+ *        2. z = zbuf[b,i,j];           skipped unless z > 0 and finite
+ *        3. skipped where mask is given and mask[fr,i,j] == 0
+ *        4. c_k = rgb[b,i,j,k], o_k = image[fr,i,j,k] and the four neighbours image[fr,i,j-1,k], image[fr,i,j+1,k],
+ *           image[fr,i-1,j,k], image[fr,i+1,j,k] for k = 0, 1, 2;  skipped unless all 18 values are finite
+ *        5. r_k = o_k - c_k;  kept iff (r_0^2 + r_1^2) + r_2^2 <= tau * tau          (a NaN fails)
+ *        6. gx_k = 0.5 (image[fr,i,j+1,k] - image[fr,i,j-1,k]),  gy_k = 0.5 (image[fr,i+1,j,k] - image[fr,i-1,j,k]),
+ *           rx = ((j + 0.5) - cx) / fx,  ry = ((i + 0.5) - cy) / fy,  P = (z rx, z ry, z),
+ *           a_k = (gx_k fx / z,  gy_k fy / z,  -((gx_k fx) rx + (gy_k fy) ry) / z),  J_k = [P x a_k, a_k]
+ *      and the 29 sums of tp_pnp_refine, accumulated over the three rows (J_k, r_k) of a kept pixel in channel order: the 21
+ *      upper-triangle entries of J^T J (row-major), the 6 of J^T r, sum r_k^2 and the count, + 1 per kept PIXEL.  A thread owns
+ *      four consecutive flat pixels (ascending), a workgroup 1024; butterfly sums inside a wave, the four waves in ascending
+ *      order, one record per workgroup, the records in ascending order: no atomics, the outputs are a function of the inputs
+ *      alone, bit-identical from run to run and under graph replay.  Per image:
+ *        inliers = count;  rms = sqrt(sum r_k^2 / count) in colour units (NaN at count 0): both describe `pose`
+ *        status  = 1 where count < 6; else 3 where J^T J is NOT POSITIVE DEFINITE by tp_pnp_refine's pivot rule (a Cholesky pivot
+ *                  that is not finite or <= 1e-10 x its diagonal entry), or, without evaluate_only, where the damped matrix does
+ *                  not factor or the stepped pose is not finite in fp32; else 0
+ *        pose_out = (status == 0 and not evaluate_only): (J^T J + damping diag(J^T J)) delta = -J^T r solved by Cholesky,
+ *                  R <- exp(w) R, t <- exp(w) t + v with Rodrigues' formula, Gram-Schmidt on R's first two columns (the third
+ *                  their cross product), rounded to fp32;  otherwise pose, bit for bit (pose_out may be NULL with evaluate_only)
+ *      Status is an output only: a failed step passes its pose through, so a loop over steps needs no state.  Non-positive sizes,
+ *      B > 65535, H * W >= 2^31, without frame an Ft that is neither 1 nor B, a tau that is not finite and positive, a damping
+ *      that is not finite and >= 0, null pointers, a workspace that is not 16-byte aligned and pose_out == pose are refused (-1,
+ *      tp_last_error) before anything is launched.  No input value (NaN, Inf, a frame index out of range, huge poses) causes an
+ *      access out of bounds: frame is the only index read from memory, and it is clamped.  Two launches.  No allocation, no host
+ *      synchronisation; outputs and workspace must not overlap inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_photo_align_args {
+  const float* zbuf;         /* [B,H,W] K19's depth of the mesh at pose: mm, <= 0 or NaN: background */
+  const float* rgb;          /* [B,H,W,3] K19's colours of the vertex-coloured mesh at pose */
+  const float* pose;         /* [B,3,4] the pose zbuf and rgb were rendered at */
+  const float* intr;         /* [B,3,3] */
+  const float* image;        /* [Ft,H,W,3] the photograph, channels last, in rgb's units */
+  const int32_t* frame;      /* [B] index into image (and mask), or NULL: b when Ft == B, 0 when Ft == 1 */
+  const uint8_t* mask;       /* [Ft,H,W] or NULL; 0: the pixel is skipped */
+  int B, Ft, H, W;
+  float tau;                 /* finite, > 0: the largest colour distance |o - c| of a kept pixel */
+  float damping;             /* finite, >= 0: relative Levenberg damping of the diagonal */
+  int evaluate_only;         /* non-zero: inliers, rms and status of pose; no step */
+  float* pose_out;           /* [B,3,4] out; may be NULL with evaluate_only; must not be pose */
+  int32_t* inliers;          /* [B] out */
+  float* rms;                /* [B] out, colour units */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels, 3 not positive definite */
+  void* workspace;           /* tp_photo_align_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_photo_align_args;
+size_t tp_photo_align_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
+int tp_photo_align_step(const tp_photo_align_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

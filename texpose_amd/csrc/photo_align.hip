@@ -1,0 +1,254 @@
+// K30 tp_photo_align_step: one step of batched photometric alignment, B poses against a photograph (the public
+// functions are in texpose_amd/photo_align.py, the rules in include/texpose_amd.h).
+//
+//   photo_reduce grid (ceil(H * W / 1024), B) x 256.  A thread owns four consecutive flat pixels: one 16-byte load of the rendered
+//                depth where the plane allows it, else guarded 4-byte loads.  A pixel on the image's border or without a rendered
+//                surface leaves before anything else is read (most of a frame is background); a thread with a pixel left reads the
+//                12 rendered and the 12 photographed colour values of its four pixels as three 16-byte loads each (guarded 4-byte
+//                loads of the pixels left where the planes do not allow it), then per pixel the mask byte and the photograph's four
+//                neighbours: the left and right ones of a thread's inner pixels are already in its registers, the rows above and
+//                below are the neighbouring threads' own lines in the cache.  The intrinsics and the frame index are wave-uniform
+//                and are read before the kernel's only global store, so they come through scalar loads; the pose is not needed.
+//                Each kept pixel gives three rows (one per channel) of the 6-parameter system.  The 29 fp64 sums of a thread are
+//                reduced in icp_reduce's order: xor-butterfly inside the wave (step-major), the four waves in ascending order
+//                through LDS, one 32-double record per workgroup.  A wave none of whose pixels is kept skips its butterflies: its
+//                sums are 29 zeros either way.
+//   photo_solve  grid B x 64.  The records come through LDS 64 at a time (coalesced, 32 loads in flight per thread), 29 threads add
+//                them in ascending tile order, thread 0 factors, steps (pose_gn.h, shared with K28 and K29) and writes the outputs.
+// No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
+#include "tp_common.h"
+#include "pose_gn.h"
+
+namespace {
+constexpr int kPhBlock = 256, kPhPix = 4, kPhTile = kPhBlock * kPhPix, kPhWaves = kPhBlock / tp::kWave;
+constexpr int kPhMinCount = 6;
+constexpr int kPhStage = 64;                          // records the solve kernel stages through LDS at a time
+
+__host__ __device__ inline int64_t photo_tiles(int64_t n) { return (n + kPhTile - 1) / kPhTile; }
+
+__device__ __forceinline__ bool finite3(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+
+// VEC: H * W is a multiple of four and zbuf / rgb / image are 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_args a, double* part) {
+  __shared__ double wave_part[kPhWaves][kGnPart];
+  const int b = blockIdx.y;
+  int fr = a.Ft == 1 ? 0 : b;
+  if (a.frame) {                                                                 // out of range is the caller's error: clamped, never read past
+    fr = a.frame[b];
+    fr = fr < 0 ? 0 : (fr >= a.Ft ? a.Ft - 1 : fr);
+  }
+  const int64_t plane = (int64_t)a.H * a.W;
+  const float* pz = a.zbuf + (int64_t)b * plane;
+  const float* pc = a.rgb + (int64_t)b * plane * 3;
+  const float* po = a.image + (int64_t)fr * plane * 3;
+  const uint8_t* pm = a.mask ? a.mask + (int64_t)fr * plane : nullptr;
+  const float* K = a.intr + (int64_t)b * 9;
+  const double fx = (double)K[0], cx = (double)K[2], fy = (double)K[4], cy = (double)K[5];
+  const double tau2 = (double)a.tau * (double)a.tau;
+
+  const int64_t p0 = (int64_t)blockIdx.x * kPhTile + (int)threadIdx.x * kPhPix;            // (< H * W + 1024 < 2^31 + 1024)
+  float zs[kPhPix];
+#pragma unroll
+  for (int k = 0; k < kPhPix; ++k) zs[k] = -1.f;
+  if constexpr (VEC) {
+    if (p0 < plane) {                                                            // (plane % 4 == 0: the four are inside together)
+      const float4 z4 = *reinterpret_cast<const float4*>(pz + p0);
+      zs[0] = z4.x; zs[1] = z4.y; zs[2] = z4.z; zs[3] = z4.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < kPhPix; ++k)
+      if (p0 + k < plane) zs[k] = pz[p0 + k];
+  }
+
+  // steps 1 and 2: the interior pixels with a rendered surface (a pixel past the plane has i >= H)
+  const int i0 = (int)((uint32_t)p0 / (uint32_t)a.W), j0 = (int)((uint32_t)p0 - (uint32_t)i0 * (uint32_t)a.W);
+  unsigned cand = 0u;                                                            // bit k: pixel k is a candidate
+  {
+    int i = i0, j = j0;
+#pragma unroll
+    for (int k = 0; k < kPhPix; ++k) {
+      if (i >= 1 && i <= a.H - 2 && j >= 1 && j <= a.W - 2 && zs[k] > 0.f && isfinite(zs[k])) cand |= 1u << k;
+      if (++j == a.W) { j = 0; ++i; }
+    }
+  }
+
+  float cs[kPhPix * 3], os[kPhPix * 3];
+#pragma unroll
+  for (int k = 0; k < kPhPix * 3; ++k) { cs[k] = 0.f; os[k] = 0.f; }
+  if (cand != 0u) {
+    if constexpr (VEC) {                                                         // (p0 * 12 bytes: a multiple of 48)
+      const float4* c4 = reinterpret_cast<const float4*>(pc + p0 * 3);
+      const float4* o4 = reinterpret_cast<const float4*>(po + p0 * 3);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const float4 c = c4[q], o = o4[q];
+        cs[4 * q] = c.x; cs[4 * q + 1] = c.y; cs[4 * q + 2] = c.z; cs[4 * q + 3] = c.w;
+        os[4 * q] = o.x; os[4 * q + 1] = o.y; os[4 * q + 2] = o.z; os[4 * q + 3] = o.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kPhPix; ++k)
+        if (cand >> k & 1u) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) { cs[3 * k + ch] = pc[(p0 + k) * 3 + ch]; os[3 * k + ch] = po[(p0 + k) * 3 + ch]; }
+        }
+    }
+  }
+
+  double s[kGnSums];
+#pragma unroll
+  for (int k = 0; k < kGnSums; ++k) s[k] = 0.0;
+  bool any = false;
+  int pi = i0, pj = j0 - 1;                                                      // row and column of pixel k, walked as above
+#pragma unroll
+  for (int k = 0; k < kPhPix; ++k) {
+    if (++pj == a.W) { pj = 0; ++pi; }
+    if (!(cand >> k & 1u)) continue;
+    const int64_t p = p0 + k;                                                    // (interior: p - W >= 0, p + W < plane, p -+ 1 in its row)
+    if (pm && pm[p] == 0) continue;
+    float lf[3], rt[3], up[3], dn[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      if (VEC && k > 0) lf[ch] = os[3 * (k - 1) + ch]; else lf[ch] = po[(p - 1) * 3 + ch];
+      if (VEC && k < kPhPix - 1) rt[ch] = os[3 * (k + 1) + ch]; else rt[ch] = po[(p + 1) * 3 + ch];
+      up[ch] = po[(p - a.W) * 3 + ch];
+      dn[ch] = po[(p + a.W) * 3 + ch];
+    }
+    if (!(finite3(cs + 3 * k) && finite3(os + 3 * k) && finite3(lf) && finite3(rt) && finite3(up) && finite3(dn))) continue;
+    double res[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) res[ch] = (double)os[3 * k + ch] - (double)cs[3 * k + ch];
+    if (!((res[0] * res[0] + res[1] * res[1]) + res[2] * res[2] <= tau2)) continue;
+    const double z = (double)zs[k];
+    const double rx = (((double)pj + 0.5) - cx) / fx, ry = (((double)pi + 0.5) - cy) / fy;
+    const V3 P = {z * rx, z * ry, z};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const double gx = 0.5 * ((double)rt[ch] - (double)lf[ch]), gy = 0.5 * ((double)dn[ch] - (double)up[ch]);
+      const double gfx = gx * fx, gfy = gy * fy;
+      const V3 av = {gfx / z, gfy / z, -(gfx * rx + gfy * ry) / z};
+      const V3 pa = cross(P, av);
+      const double J[6] = {pa.x, pa.y, pa.z, av.x, av.y, av.z};
+      int e = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int cc = r; cc < 6; ++cc) s[e++] += J[r] * J[cc];
+#pragma unroll
+      for (int r = 0; r < 6; ++r) s[21 + r] += J[r] * res[ch];
+      s[27] += res[ch] * res[ch];
+    }
+    s[28] += 1.0;
+    any = true;
+  }
+
+  const int lane = threadIdx.x & (tp::kWave - 1), wave = threadIdx.x / tp::kWave;
+  if (__ballot(any) != 0ull) {                                                   // (uniform per wave)
+    wave_sum_all(s);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < kGnSums; ++k) wave_part[wave][k] = s[k];
+    }
+  } else if (lane < kGnSums) {
+    wave_part[wave][lane] = 0.0;                                                 // what the butterflies of 64 zeros give
+  }
+  __syncthreads();
+  if (threadIdx.x < kGnSums) {
+    double t = wave_part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kPhWaves; ++w) t += wave_part[w][threadIdx.x];
+    part[((int64_t)b * gridDim.x + blockIdx.x) * kGnPart + threadIdx.x] = t;
+  }
+}
+
+// grid B, one wave
+__global__ __launch_bounds__(tp::kWave) void photo_solve_kernel(tp_photo_align_args a, const double* part, int G) {
+  __shared__ double sum[kGnPart], stage[kPhStage][kGnPart];
+  const int b = blockIdx.x;
+  const double* rec = part + (int64_t)b * G * kGnPart;
+  double t = 0.0;
+  for (int g0 = 0; g0 < G; g0 += kPhStage) {                                     // 64 records in flight as whole 512-byte rows
+    const int n = G - g0 < kPhStage ? G - g0 : kPhStage;
+    double v[kPhStage / 2];
+#pragma unroll
+    for (int u = 0; u < kPhStage / 2; ++u) {
+      const int e = (int)threadIdx.x + tp::kWave * u;                            // element e of the batch: record e / 32, entry e % 32
+      v[u] = e / kGnPart < n ? rec[(int64_t)g0 * kGnPart + e] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kPhStage / 2; ++u) (&stage[0][0])[(int)threadIdx.x + tp::kWave * u] = v[u];
+    __syncthreads();
+    if (threadIdx.x < kGnSums)
+      for (int g = 0; g < n; ++g) t += stage[g][threadIdx.x];                    // ascending tile order
+    __syncthreads();
+  }
+  if (threadIdx.x < kGnSums) sum[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const float* T = a.pose + (int64_t)b * 12;
+  const double count = sum[28];
+  int status = 0;
+  double Pn[12];
+  if (count < (double)kPhMinCount) {
+    status = 1;
+  } else if (a.evaluate_only) {
+    double A[6][6];
+    gn_matrix(sum, A);
+    if (!cholesky6(A, kGnPivotTol)) status = 3;
+  } else {
+    double cur[12];
+    for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
+    bool ok = gn_step(sum, cur, (double)a.damping, Pn);
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
+    if (!ok) status = 3;
+  }
+  a.inliers[b] = (int)count;
+  a.rms[b] = count > 0.0 ? (float)sqrt(sum[27] / count) : __int_as_float(0x7fc00000);
+  a.status[b] = status;
+  if (a.pose_out) {
+    const bool stepped = status == 0 && !a.evaluate_only;
+    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
+  }
+}
+}  // namespace
+
+extern "C" size_t tp_photo_align_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t bytes = (size_t)B * (size_t)photo_tiles((int64_t)H * W) * kGnPart * sizeof(double);
+  return (bytes + 15) & ~(size_t)15;
+}
+
+extern "C" int tp_photo_align_step(const tp_photo_align_args* a, tp_stream_t stream) {
+  if (!a) { tp::set_error("tp_photo_align_step: null args"); return -1; }
+  if (a->B <= 0 || a->B > 65535 || a->H <= 0 || a->W <= 0 || a->Ft <= 0 || (int64_t)a->H * a->W > 0x7FFFFFFFll) {
+    tp::set_error("tp_photo_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
+    return -1;
+  }
+  if (!a->frame && a->Ft != 1 && a->Ft != a->B) {
+    tp::set_error("tp_photo_align_step: Ft = %d is neither 1 nor B = %d and there is no frame map", a->Ft, a->B);
+    return -1;
+  }
+  if (!(a->tau > 0.f) || !isfinite(a->tau)) { tp::set_error("tp_photo_align_step: tau must be finite and positive"); return -1; }
+  if (!(a->damping >= 0.f) || !isfinite(a->damping)) { tp::set_error("tp_photo_align_step: damping must be finite and not negative"); return -1; }
+  if (!a->zbuf || !a->rgb || !a->pose || !a->intr || !a->image || !a->inliers || !a->rms || !a->status || !a->workspace ||
+      (!a->pose_out && !a->evaluate_only)) {
+    tp::set_error("tp_photo_align_step: null pointer");
+    return -1;
+  }
+  if ((uintptr_t)a->workspace & 15u) { tp::set_error("tp_photo_align_step: workspace must be 16-byte aligned"); return -1; }
+  if (a->pose_out) {
+    const uintptr_t in = (uintptr_t)a->pose, out = (uintptr_t)a->pose_out, bytes = (uintptr_t)a->B * 12 * sizeof(float);
+    if (in < out + bytes && out < in + bytes) { tp::set_error("tp_photo_align_step: pose_out must not overlap pose"); return -1; }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t plane = (int64_t)a->H * a->W;
+  const int G = (int)photo_tiles(plane);
+  double* part = static_cast<double*>(a->workspace);
+  const bool vec = plane % kPhPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->rgb | (uintptr_t)a->image) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(photo_reduce_kernel<true>, dim3(G, a->B), dim3(kPhBlock), 0, st, *a, part);
+  else hipLaunchKernelGGL(photo_reduce_kernel<false>, dim3(G, a->B), dim3(kPhBlock), 0, st, *a, part);
+  hipLaunchKernelGGL(photo_solve_kernel, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  return tp::check_launch("tp_photo_align_step");
+}

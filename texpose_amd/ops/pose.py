@@ -1,4 +1,4 @@
-"""K24-K26, K28, K29: nearest neighbours, the pose errors, VSD, PnP-RANSAC and the depth ICP."""
+"""K24-K26, K28-K30: nearest neighbours, the pose errors, VSD, PnP-RANSAC, the depth ICP and the photometric alignment."""
 from typing import Dict, Optional
 
 import torch
@@ -9,7 +9,7 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _lengths, _on_
 
 __all__ = ["NN1_MODES", "nn1", "pose_errors", "vsd", "PNP_MAX_HYP", "PNP_MAX_ITERS", "pnp_workspace", "_pnp_common", "corr_from_nocs",
            "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac", "depth_icp_workspace", "depth_icp_step",
-           "DEPTH_ICP_KEYS", "depth_icp"]
+           "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS", "photo_align"]
 
 # ------------------------------------------------------------------------------------------ K24, K25
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
@@ -380,6 +380,113 @@ def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: T
         r = mesh_raster(verts, faces, pose, intr, H=H, W=W, face_ids=True, normals=False)
         res = depth_icp_step(verts, faces, r["zbuf"], r["face"], pose, intr, depth, tau_mm=tau, damping=damping, frame=frame, mask=mask,
                              evaluate_only=it == iters, workspace=workspace)
+        first = res if first is None else first
+        status = res["status"] if it < iters or status is None else status
+        pose = res["pose"]
+    return dict(pose=res["pose"], inliers=res["inliers"], rms=res["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"])
+
+
+# ------------------------------------------------------------------------------------------ K30
+def photo_align_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for photo_align_step / photo_align at B images of H x W (tp_photo_align_workspace_bytes); needs no clearing."""
+    return _workspace_arg("photo_align", None, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), device)
+
+
+def _photo_align_planes(op: str, image: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
+    image = _f32(image.detach(), "image")
+    if image.dim() == 3:
+        image = image[None]
+    if image.dim() != 4 or tuple(image.shape[1:]) != (H, W, 3) or image.shape[0] == 0:
+        raise ValueError("%s: image [Ft,H=%d,W=%d,3] (channels last) expected, got %s" % (op, H, W, tuple(image.shape)))
+    Ft = image.shape[0]
+    frame = _lengths(op, frame, "frame", B, like)
+    if frame is None and Ft not in (1, B):
+        raise ValueError("%s: image must hold 1 or B = %d photographs without frame=, got %d" % (op, B, Ft))
+    if mask is not None:
+        if torch.is_tensor(mask) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+        if torch.is_tensor(mask) and mask.dim() == 2:
+            mask = mask[None]
+        mask = _want_gpu(op, mask, "mask", torch.uint8, (Ft, H, W))
+    return image, frame, mask, Ft
+
+
+@_on_tensor_device
+def photo_align_step(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau: float, damping: float = 1e-6,
+                     frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                     workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of photometric alignment for B poses (tp_photo_align_step; the rules are in the header): zbuf [B,H,W] / rgb [B,H,W,3]
+    (mesh_raster's planes of the vertex-coloured mesh at ``pose``; taken as they are), pose [B,3,4], intr [B,3,3] or one [3,3], image
+    [Ft,H,W,3] (the photograph, channels last, in rgb's units; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask [Ft,H,W] uint8 or
+    bool (0: skip the pixel) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a non-zero
+    status), 'inliers' [B] int32 and 'rms' [B] (colour units) of ``pose`` over the interior covered pixels whose colours differ by at
+    most ``tau``, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
+    photo_align_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches,
+    no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "photo_align_step"
+    pose = _poses(op, pose, "pose")
+    B = pose.shape[0]
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B=%d,H,W] expected, got %s" % (op, B, tuple(zbuf.shape)))
+    H, W = zbuf.shape[1:]
+    rgb = _want_gpu(op, rgb, "rgb", torch.float32, (B, H, W, 3))
+    intr = _intr_per_view(op, intr, B)
+    image, frame, mask, Ft = _photo_align_planes(op, image, frame, mask, B, H, W, zbuf)
+    dev = zbuf.device
+    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+                             "status": (torch.int32, (B,))}, dev, partial=True)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), dev, align=16)
+    a = _lib.PhotoAlignArgs()
+    a.zbuf, a.rgb, a.pose, a.intr = zbuf.data_ptr(), rgb.data_ptr(), pose.data_ptr(), intr.data_ptr()
+    a.image, a.frame, a.mask = image.data_ptr(), _ptr(frame), _ptr(mask)
+    a.B, a.Ft, a.H, a.W = B, Ft, H, W
+    a.tau, a.damping, a.evaluate_only = float(tau), float(damping), int(bool(evaluate_only))
+    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
+                                                           res["status"].data_ptr(), workspace.data_ptr())
+    _call("tp_photo_align_step", a)       # (tau, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
+
+
+@_on_tensor_device
+def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
+                damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
+    mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
+    ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
+    [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (colour units), 'status' [B] int32 of the last step taken (of the evaluation where
+    iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
+    rasteriser's, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "photo_align"
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
+    taus = [float(tau)] * (iters + 1) if isinstance(tau, (int, float)) else [float(t) for t in tau]
+    if len(taus) != iters + 1:
+        raise ValueError("%s: tau must be one value or iters + 1 = %d values, got %d" % (op, iters + 1, len(taus)))
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    vcolor = _f32(vcolor.detach(), "vcolor")
+    image = _f32(image.detach(), "image")
+    if image.dim() == 3:
+        image = image[None]
+    if image.dim() != 4 or image.shape[3] != 3 or image.numel() == 0:
+        raise ValueError("%s: image [Ft,H,W,3] (channels last) expected, got %s" % (op, tuple(image.shape)))
+    H, W = image.shape[1:3]
+    intr = _intr_per_view(op, intr, B)
+    image, frame, mask, _ = _photo_align_planes(op, image, frame, mask, B, H, W, pose)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), pose.device, align=16)
+    from .scene import mesh_raster
+    res, first, status = None, None, None
+    for it, t in enumerate(taus):
+        r = mesh_raster(verts, faces, pose, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False)
+        res = photo_align_step(r["zbuf"], r["rgb"], pose, intr, image, tau=t, damping=damping, frame=frame, mask=mask,
+                               evaluate_only=it == iters, workspace=workspace)
         first = res if first is None else first
         status = res["status"] if it < iters or status is None else status
         pose = res["pose"]

@@ -1,0 +1,136 @@
+"""Pose refinement against the photograph: batched photometric alignment on the device (K30).
+
+The RGB sibling of texpose_amd.icp: the vertex-coloured mesh (texpose_amd.texture_bake gives one from a checkpoint) is rendered at the
+current poses by the HIP rasteriser, every interior covered pixel whose rendered colour lies within ``tau`` of the photograph's gives
+three residuals, one per channel, against the photograph's own central-difference gradient, and one damped Gauss-Newton step in fp64
+moves the pose (``ops.photo_align_step``; ``ops.photo_align`` is the loop).  ``PhotoRefiner`` keeps the mesh and the workspace of a
+batch size.  ``step_torch`` says the step again in plain torch ops in fp64: the comparator of tools/photo_align_bench.py, and the one
+piece that also runs without a GPU.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import ops
+from .icp import MIN_COUNT, PIVOT_TOL, _cholesky6, _exp_so3
+from .options import AttrDict
+
+Tensor = torch.Tensor
+
+
+def step_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Tensor, tau: float, damping: float = 1e-6,
+               frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False) -> Dict[str, Tensor]:
+    """ops.photo_align_step's rules (include/texpose_amd.h, K30) in plain torch ops in fp64 on the tensors' device: the same arguments
+    -> 'pose' [B,3,4] float32, 'inliers' [B] int32, 'rms' [B] float32, 'status' [B] int32.  The sums run in torch's order, not the
+    kernel's: counts and statuses agree, the rest to rounding."""
+    f64 = torch.float64
+    dev = zbuf.device
+    B, H, W = zbuf.shape
+    pose32 = pose.float().reshape(B, 3, 4)
+    intr = intr.float()
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3)
+    image = image.float()
+    if image.dim() == 3:
+        image = image[None]
+    Ft = image.shape[0]
+    if frame is None:
+        if Ft not in (1, B):
+            raise ValueError("step_torch: image must hold 1 or B = %d photographs without frame=, got %d" % (B, Ft))
+        fr = torch.zeros(B, dtype=torch.long, device=dev) if Ft == 1 else torch.arange(B, device=dev)
+    else:
+        fr = frame.long().clamp(0, Ft - 1)
+    tau = float(torch.tensor(tau, dtype=torch.float32))
+    lam = float(torch.tensor(damping, dtype=torch.float32))
+    zf = zbuf.float()
+    cand = (zf > 0) & torch.isfinite(zf)
+    cand[:, :1], cand[:, H - 1:], cand[:, :, :1], cand[:, :, W - 1:] = False, False, False, False
+    if mask is not None:
+        m = mask if mask.dim() == 3 else mask[None]
+        cand = cand & (m[fr] != 0)
+    bi, ii, ji = torch.nonzero(cand, as_tuple=True)                                         # (interior: ii -+ 1 and ji -+ 1 exist)
+    fi = fr[bi]
+    c, o = rgb.float()[bi, ii, ji].to(f64), image[fi, ii, ji].to(f64)                       # [n,3]
+    lf, rt = image[fi, ii, ji - 1].to(f64), image[fi, ii, ji + 1].to(f64)
+    up, dn = image[fi, ii - 1, ji].to(f64), image[fi, ii + 1, ji].to(f64)
+    res = o - c
+    fin = torch.isfinite(torch.cat([c, o, lf, rt, up, dn], -1)).all(-1)
+    keep = fin & ((res[:, 0] * res[:, 0] + res[:, 1] * res[:, 1]) + res[:, 2] * res[:, 2] <= tau * tau)
+    bi, ii, ji, res, lf, rt, up, dn = bi[keep], ii[keep], ji[keep], res[keep], lf[keep], rt[keep], up[keep], dn[keep]
+    z = zf[bi, ii, ji].to(f64)
+    K = intr.to(f64)
+    fx, fy = K[bi, 0, 0], K[bi, 1, 1]
+    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / fx
+    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / fy
+    P = torch.stack([z * rx, z * ry, z], -1)[:, None, :].expand(-1, 3, -1)                  # [n,3 channels,3]
+    gfx, gfy = (0.5 * (rt - lf)) * fx[:, None], (0.5 * (dn - up)) * fy[:, None]             # [n,3 channels]
+    av = torch.stack([gfx / z[:, None], gfy / z[:, None], -(gfx * rx[:, None] + gfy * ry[:, None]) / z[:, None]], -1)
+    J = torch.cat([torch.cross(P, av, dim=-1), av], -1).reshape(-1, 6)                      # [3n,6]
+    r = res.reshape(-1)
+    b3 = bi.repeat_interleave(3)
+    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, b3, J[:, :, None] * J[:, None, :])
+    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, b3, J * r[:, None])
+    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, b3, r * r)
+    count = torch.bincount(bi, minlength=B)
+    rms = torch.sqrt(cost / count.to(f64))                                                  # (0 / 0: NaN)
+    few = count < MIN_COUNT
+    _, pd = _cholesky6(JtJ, PIVOT_TOL)
+    status = torch.where(few, 1, torch.where(pd, 0, 3))
+    out_pose = pose32.clone()
+    if not evaluate_only:
+        Dm = JtJ + lam * torch.diag_embed(torch.diagonal(JtJ, dim1=1, dim2=2))
+        L, ok = _cholesky6(Dm, 0.0)
+        ok = ok & pd & ~few
+        eye = torch.eye(6, dtype=f64, device=dev)[None]
+        L = torch.where(ok[:, None, None], L, eye)
+        y = torch.linalg.solve_triangular(L, -Jtr[:, :, None], upper=False)
+        delta = torch.linalg.solve_triangular(L.transpose(1, 2), y, upper=True)[:, :, 0]
+        delta = torch.where(ok[:, None], delta, torch.zeros_like(delta))
+        Pn = _exp_so3(delta[:, :3]) @ pose32.to(f64)
+        Pn[:, :, 3] = Pn[:, :, 3] + delta[:, 3:]
+        c1 = Pn[:, :, 0] / torch.linalg.norm(Pn[:, :, 0], dim=-1, keepdim=True)
+        c2 = Pn[:, :, 1] - c1 * (c1 * Pn[:, :, 1]).sum(-1, keepdim=True)
+        c2 = c2 / torch.linalg.norm(c2, dim=-1, keepdim=True)
+        Pn = torch.stack([c1, c2, torch.cross(c1, c2, dim=-1), Pn[:, :, 3]], -1)
+        new32 = Pn.float()
+        ok = ok & torch.isfinite(new32).reshape(B, -1).all(-1)
+        status = torch.where(few, 1, torch.where(ok, 0, 3))
+        out_pose = torch.where(ok[:, None, None], new32, pose32)
+    return dict(pose=out_pose, inliers=count.to(torch.int32), rms=rms.float(), status=status.to(torch.int32))
+
+
+class PhotoRefiner:
+    """Photometric alignment for batches of poses of one vertex-coloured mesh at H x W with the mesh on the device and a workspace per
+    batch size.
+
+    ``tau`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 0.5, in the colours' units), ``iters`` (Gauss-Newton steps, 10),
+    ``damping`` (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (interior covered pixels
+    within tau of the photograph), rms [B] (colour units), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was
+    not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+
+    def __init__(self, verts: Tensor, faces: Tensor, vcolor: Tensor, H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
+                 damping: float = 1e-6):
+        self.H, self.W, self.device = int(H), int(W), torch.device(device)
+        if self.device.type != "cuda":
+            raise ops._lib.TexposeLibraryError("PhotoRefiner runs the HIP kernels: a GPU device is needed (step_torch alone has a CPU route)")
+        self.verts = torch.as_tensor(verts).to(device=self.device, dtype=torch.float32).contiguous()
+        self.faces = torch.as_tensor(faces).to(device=self.device, dtype=torch.int32).contiguous()
+        self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(self.vcolor.shape) != tuple(self.verts.shape):
+            raise ValueError("PhotoRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
+        self.tau, self.iters, self.damping = tau, int(iters), float(damping)
+        self._workspaces: Dict[int, Tensor] = {}
+
+    def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
+        """pose [B,3,4], intr [B,3,3] or [3,3], image [Ft,H,W,3] (channels last, the vertex colours' units), frame [B] int32 (the
+        photograph of each pose; without it Ft is 1 or B), mask [Ft,H,W] uint8 / bool (0: do not use the pixel)."""
+        image = image if image.dim() == 4 else image[None]
+        if tuple(image.shape[1:]) != (self.H, self.W, 3):
+            raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
+        B = pose.shape[0]
+        if B not in self._workspaces:
+            self._workspaces[B] = ops.photo_align_workspace(B, self.H, self.W, self.device)
+        return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
+                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspaces[B]))

@@ -12,7 +12,13 @@ the current pose, the covered pixels within --tau-mm of the measurement along th
 values: a coarse-to-fine schedule of iters + 1 entries) and written with its score unchanged and the per-pose time of its batch added
 to its time.  --use-mask-visib: only the pixels of mask_visib/{frame:06d}_{k:06d}.png are used, k the object's first instance of the
 frame in scene_gt.json.  A pose whose last step failed (fewer than six usable pixels, a rank-deficient system) is written as the loop
-left it; the tool prints how many."""
+left it; the tool prints how many.
+
+--rgb: refine against the scene's rgb/{frame:06d}.png instead of its depth (texpose_amd.photo_align, K30): --ply is
+then the vertex-coloured mesh (texture_bake's output; the tool exits if it has no colours), the photograph is the 8-bit image / 255,
+the vertex colours' own range, and every interior covered pixel whose rendered colour lies within --tau-rgb of the photograph's pulls
+on the pose through the photograph's gradient, for --iters-rgb steps (--tau-rgb: one value or iters-rgb + 1).  --use-mask-visib,
+--damping, --batch and the output are as above; --tau-mm and --iters are not used."""
 import argparse
 import csv
 import json
@@ -61,6 +67,9 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--damping", type=float, default=1e-6)
     ap.add_argument("--use-mask-visib", action="store_true")
+    ap.add_argument("--rgb", action="store_true")
+    ap.add_argument("--tau-rgb", type=float, nargs="+", default=[0.5])
+    ap.add_argument("--iters-rgb", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -68,9 +77,11 @@ def main(argv=None):
         sys.exit("refine_poses: the refinement runs the HIP kernels, which have no CPU route; use --device cuda:N")
     if len(a.tau_mm) not in (1, a.iters + 1):
         sys.exit("refine_poses: --tau-mm takes one value or iters + 1 = %d values" % (a.iters + 1))
+    if a.rgb and len(a.tau_rgb) not in (1, a.iters_rgb + 1):
+        sys.exit("refine_poses: --tau-rgb takes one value or iters-rgb + 1 = %d values" % (a.iters_rgb + 1))
     import torch
     from PIL import Image
-    from texpose_amd import icp
+    from texpose_amd import icp, photo_align
     from texpose_amd.pose_error import depth_from_png
     from texpose_amd.surfel import load_ply
     if not torch.cuda.is_available():
@@ -78,10 +89,11 @@ def main(argv=None):
     meshes = {}
     for item in a.ply:
         oid, sep, path = item.partition("=")
-        if sep and oid.strip().isdigit():
-            meshes[int(oid)] = load_ply(path)[:2]
-        else:
-            meshes[None] = load_ply(item)[:2]
+        key, path = (int(oid), path) if sep and oid.strip().isdigit() else (None, item)
+        mesh = load_ply(path)
+        if a.rgb and mesh[2] is None:
+            sys.exit("refine_poses: --rgb needs a vertex-coloured mesh and %s has no colours" % path)
+        meshes[key] = mesh if a.rgb else mesh[:2]
     cam = json.load(open(os.path.join(a.scene, "scene_camera.json")))
     gt = None
     if a.use_mask_visib:
@@ -94,18 +106,23 @@ def main(argv=None):
                 sys.exit("refine_poses: frame %d is not in scene_camera.json" % row[1])
             jobs.setdefault(row[2], []).append(i)
     tau = a.tau_mm[0] if len(a.tau_mm) == 1 else a.tau_mm
+    tau_rgb = a.tau_rgb[0] if len(a.tau_rgb) == 1 else a.tau_rgb
     refined = failed = 0
     dev = a.device
     for oid, idx in jobs.items():
-        verts, faces = meshes.get(oid, meshes.get(None))
+        verts, faces = meshes.get(oid, meshes.get(None))[:2]
         refiner = None
         for s in range(0, len(idx), a.batch):
             part = idx[s:s + a.batch]
             frames = sorted({rows[i][1] for i in part})
-            planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
-                      for f in frames]
-            depth = torch.stack(planes)
-            H, W = depth.shape[1:]
+            if a.rgb:
+                planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
+                          for f in frames]
+            else:
+                planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
+                          for f in frames]
+            depth = torch.stack(planes)                          # (with --rgb: the photographs [Ft,H,W,3])
+            H, W = depth.shape[1:3]
             mask = None
             if a.use_mask_visib:
                 ms = []
@@ -117,7 +134,11 @@ def main(argv=None):
                     ms.append((np.asarray(Image.open(path)) != 0).astype(np.uint8))
                 mask = torch.from_numpy(np.stack(ms)).to(dev)
             if refiner is None or (refiner.H, refiner.W) != (H, W):
-                refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping)
+                if a.rgb:
+                    refiner = photo_align.PhotoRefiner(verts, faces, meshes.get(oid, meshes.get(None))[2], H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
+                                                       damping=a.damping)
+                else:
+                    refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
             K = np.stack([np.array(cam[str(rows[i][1])]["cam_K"], np.float32).reshape(3, 3) for i in part])
             index = torch.tensor([frames.index(rows[i][1]) for i in part], dtype=torch.int32, device=dev)
