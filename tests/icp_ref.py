@@ -8,10 +8,9 @@ margin | |d - z| |ray| - tau | is below NEAR_TIE mm."""
 import numpy as np
 
 import mesh_raster_ref as RR
-from pnp_ref import PIVOT_TOL, _cholesky, _exp_so3
+from gn_ref import MIN_COUNT, PIVOT_TOL, _exp_so3, loop_ref, solve_ref  # noqa: F401  (tests reach them through this module)
 
 NEAR_TIE = 1e-6          # mm
-MIN_COUNT = 6
 
 
 def frame_index(B, Ft, frame):
@@ -59,35 +58,6 @@ def sums_ref(verts, faces, zbuf, face, pose, K, depth, tau, mask=None):
     return dict(JtJ=J.T @ J, Jtr=J.T @ r, cost=float(r @ r), count=len(r), near_ties=ties, kept=kept)
 
 
-def solve_ref(s, pose, damping, evaluate_only):
-    """The per-image part: sums -> (pose_out fp32 [3,4], inliers, rms, status)."""
-    pose32 = np.asarray(pose, np.float32).reshape(3, 4)
-    with np.errstate(all="ignore"):
-        rms = np.sqrt(np.float64(s["cost"]) / np.float64(s["count"]))
-    if s["count"] < MIN_COUNT:
-        return pose32.copy(), s["count"], rms, 1
-    if _cholesky(s["JtJ"], PIVOT_TOL) is None:
-        return pose32.copy(), s["count"], rms, 3
-    if evaluate_only:
-        return pose32.copy(), s["count"], rms, 0
-    lam = float(np.float32(damping))
-    Ld = _cholesky(s["JtJ"] + lam * np.diag(np.diag(s["JtJ"])), 0.0)
-    if Ld is None:
-        return pose32.copy(), s["count"], rms, 3
-    delta = np.linalg.solve(Ld.T, np.linalg.solve(Ld, -s["Jtr"]))
-    Pn = _exp_so3(delta[:3]) @ pose32.astype(np.float64)
-    Pn[:, 3] += delta[3:]
-    c1 = Pn[:, 0] / np.linalg.norm(Pn[:, 0])
-    c2 = Pn[:, 1] - c1 * (c1 @ Pn[:, 1])
-    c2 /= np.linalg.norm(c2)
-    Pn[:, 0], Pn[:, 1], Pn[:, 2] = c1, c2, np.cross(c1, c2)
-    with np.errstate(all="ignore"):
-        new32 = Pn.astype(np.float32)
-    if not np.isfinite(new32).all():
-        return pose32.copy(), s["count"], rms, 3
-    return new32, s["count"], rms, 0
-
-
 def step_ref(verts, faces, zbuf, face, pose, K, depth, tau, damping=1e-6, frame=None, mask=None, evaluate_only=False):
     """The whole call: zbuf / face [B,H,W], pose [B,3,4], K [B,3,3], depth (and mask) [Ft,H,W] -> dict(pose [B,3,4] float32, inliers
     [B], rms [B] fp64, status [B], near_ties [B], kept [B,H,W])."""
@@ -112,22 +82,12 @@ def render_ref(verts, faces, pose, K, H, W):
 def icp_ref(verts, faces, pose, K, depth, tau=20.0, iters=5, damping=1e-6, frame=None, mask=None):
     """The loop of ops.depth_icp with its own raster: iters + 1 passes, the pose rounded to fp32 between them, the last evaluate-only
     -> dict(pose [B,3,4] float32, inliers, rms, status (of the last step taken), inliers0, rms0, near_ties (largest over the passes))."""
-    pose = np.asarray(pose, np.float32).copy()
-    B = len(pose)
     depth = np.asarray(depth, np.float32)
     H, W = depth.shape[1:]
-    taus = [float(tau)] * (iters + 1) if np.isscalar(tau) else [float(t) for t in tau]
-    assert len(taus) == iters + 1
-    first, status, ties, r = None, None, np.zeros(B, np.int64), None
-    for it, t in enumerate(taus):
-        planes = [render_ref(verts, faces, pose[b], K[b], H, W) for b in range(B)]
-        r = step_ref(verts, faces, np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes]), pose, K, depth, t, damping, frame, mask,
-                     evaluate_only=it == iters)
-        first = r if first is None else first
-        status = r["status"] if it < iters or status is None else status
-        ties = np.maximum(ties, r["near_ties"])
-        pose = r["pose"]
-    return dict(pose=r["pose"], inliers=r["inliers"], rms=r["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"], near_ties=ties)
+    render = lambda P: [render_ref(verts, faces, P[b], K[b], H, W) for b in range(len(P))]
+    step = lambda planes, P, t, last: step_ref(verts, faces, np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes]), P, K, depth, t,
+                                               damping, frame, mask, evaluate_only=last)
+    return loop_ref(render, step, pose, tau, iters)
 
 
 # ----------------------------------------------------------------------------------------------------------------- the loop's case

@@ -3,7 +3,7 @@ the rules in include/texpose_amd.h, not from the kernels.  Where the kernel is f
 gradients are whole-plane slices, the sums are matrix products over the kept pixels of an image at once (the kernel adds per thread,
 wave, workgroup and tile), the systems are solved with np.linalg.solve on the Cholesky factors, and the loop renders with the
 brute-force rasteriser of tests/mesh_raster_ref.py.  The per-image part (status, step, Gram-Schmidt, fp32 rounding) is K29's word for
-word, so it is icp_ref.solve_ref itself.
+word: both use gn_ref.solve_ref.
 
 Besides the results it reports what decides whether a comparison of counts can be exact: near-ties, kept-or-dropped decisions whose
 margin | |o - c| - tau | is below NEAR_TIE colour units."""
@@ -11,13 +11,12 @@ import functools
 
 import numpy as np
 
-import icp_ref as IREF
 import mesh_raster_ref as RR
 import pnp_ref as PREF
+from gn_ref import MIN_COUNT, loop_ref, solve_ref  # noqa: F401  (the per-image part is K29's word for word)
 from icp_ref import frame_index, perturbed  # noqa: F401  (the loop's start poses)
 
 NEAR_TIE = 1e-9          # colour units
-MIN_COUNT = IREF.MIN_COUNT
 BACKGROUND = 0.5
 
 
@@ -61,11 +60,6 @@ def sums_ref(zbuf, rgb, K, image, tau, mask=None):
     return dict(JtJ=J.T @ J, Jtr=J.T @ r, cost=float(r @ r), count=len(ii), near_ties=ties, kept=kept)
 
 
-def solve_ref(s, pose, damping, evaluate_only):
-    """The per-image part: sums -> (pose_out fp32 [3,4], inliers, rms, status); K29's rules, word for word."""
-    return IREF.solve_ref(s, pose, damping, evaluate_only)
-
-
 def step_ref(zbuf, rgb, pose, K, image, tau, damping=1e-6, frame=None, mask=None, evaluate_only=False):
     """The whole call: zbuf [B,H,W], rgb [B,H,W,3], pose [B,3,4], K [B,3,3], image [Ft,H,W,3] (and mask [Ft,H,W]) -> dict(pose
     [B,3,4] float32, inliers [B], rms [B] fp64, status [B], near_ties [B], kept [B,H,W])."""
@@ -104,22 +98,12 @@ def photo_ref(verts, faces, vcolor, pose, K, image, tau=0.5, iters=10, damping=1
     """The loop of ops.photo_align with its own raster: iters + 1 passes, the pose rounded to fp32 between them, the last
     evaluate-only -> dict(pose [B,3,4] float32, inliers, rms, status (of the last step taken), inliers0, rms0, near_ties (largest over
     the passes))."""
-    pose = np.asarray(pose, np.float32).copy()
-    B = len(pose)
     image = np.asarray(image, np.float32)
     H, W = image.shape[1:3]
-    taus = [float(tau)] * (iters + 1) if np.isscalar(tau) else [float(t) for t in tau]
-    assert len(taus) == iters + 1
-    first, status, ties, r = None, None, np.zeros(B, np.int64), None
-    for it, t in enumerate(taus):
-        planes = [render_ref(verts, faces, vcolor, pose[b], K[b], H, W) for b in range(B)]
-        r = step_ref(np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes]), pose, K, image, t, damping, frame, mask,
-                     evaluate_only=it == iters)
-        first = r if first is None else first
-        status = r["status"] if it < iters or status is None else status
-        ties = np.maximum(ties, r["near_ties"])
-        pose = r["pose"]
-    return dict(pose=r["pose"], inliers=r["inliers"], rms=r["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"], near_ties=ties)
+    render = lambda P: [render_ref(verts, faces, vcolor, P[b], K[b], H, W) for b in range(len(P))]
+    step = lambda planes, P, t, last: step_ref(np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes]), P, K, image, t, damping, frame,
+                                               mask, evaluate_only=last)
+    return loop_ref(render, step, pose, tau, iters)
 
 
 # ----------------------------------------------------------------------------------------------------------------- the loop's cases

@@ -10,11 +10,11 @@ import math
 
 import numpy as np
 
+from gn_ref import PIVOT_TOL, _cholesky, _exp_so3, gn_update  # noqa: F401  (tests reach them through this module)
 from oracle.texpose_oracle import LINEMOD_K, philox4x32
 
 NEAR_TIE = 1e-3          # px
 LAMBDA = 1e-3
-PIVOT_TOL = 1e-10
 PNP4 = 0x706E7034        # 'pnp4'
 
 
@@ -217,26 +217,6 @@ def _sums(xy, xyz, K, pose, tau):
     return J.T @ J, J.T @ r, float(r @ r), int(ok.sum()), ties
 
 
-def _cholesky(A, tol):
-    A = A.copy()
-    for j in range(6):
-        diag = A[j, j]
-        d = diag - (A[j, :j] ** 2).sum()
-        if not np.isfinite(d) or not d > tol * diag or not d > 0:
-            return None
-        A[j, j] = np.sqrt(d)
-        for i in range(j + 1, 6):
-            A[i, j] = (A[i, j] - A[i, :j] @ A[j, :j]) / A[j, j]
-    return np.tril(A)
-
-
-def _exp_so3(w):
-    th = np.linalg.norm(w)
-    Wx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-    sa, sb = (np.sin(th) / th, (1 - np.cos(th)) / th ** 2) if th > 1e-8 else (1 - th * th / 6, 0.5 - th * th / 24)
-    return np.eye(3) + sa * Wx + sb * (Wx @ Wx)
-
-
 def refine_ref(xy, xyz, n, K, pose0, tau, iters):
     """One image: entries 0 .. n-1, start pose [3,4] -> dict(pose fp64, inliers, rms, status, near_ties: the largest near-tie number
     over the poses evaluated)."""
@@ -251,20 +231,8 @@ def refine_ref(xy, xyz, n, K, pose0, tau, iters):
             best, best_key = cur.copy(), (count, cost)
         if it == iters:
             break
-        L = _cholesky(JtJ, PIVOT_TOL)
-        Ld = _cholesky(JtJ + LAMBDA * np.diag(np.diag(JtJ)), 0.0) if L is not None else None
-        if Ld is None:
-            status = 3
-            break
-        d = np.linalg.solve(Ld.T, np.linalg.solve(Ld, -Jtr))
-        E = _exp_so3(d[:3])
-        P = E @ cur
-        P[:, 3] += d[3:]
-        c1 = P[:, 0] / np.linalg.norm(P[:, 0])
-        c2 = P[:, 1] - c1 * (c1 @ P[:, 1])
-        c2 /= np.linalg.norm(c2)
-        P[:, 0], P[:, 1], P[:, 2] = c1, c2, np.cross(c1, c2)
-        if not np.isfinite(P).all():
+        P = gn_update(JtJ, Jtr, cur, LAMBDA)
+        if P is None:
             status = 3
             break
         cur = P

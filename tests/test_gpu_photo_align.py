@@ -14,20 +14,13 @@ import torch
 
 import photo_ref as REF
 import pnp_ref as PREF
+from gn_ref import compare, cu, host
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RE_FLOOR, TE_FLOOR = 1e-3, 1e-3          # deg, mm: about 16 fp32 ulp of a 900 mm depth and the angle it subtends on the 50 mm object
-
-
-def cu(x, dtype=None):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x, dtype=dtype).to(DEV)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def gpu_step(c, **kw):
@@ -38,25 +31,6 @@ def gpu_step(c, **kw):
 
 def ref_step(c, **kw):
     return REF.step_ref(c["zbuf"], c["rgb"], c["pose"], c["K"], c["image"], c["tau"], 1e-6, c["frame"], c["mask"], **kw)
-
-
-def compare(got, want, pose_in):
-    """test_gpu_icp.py's bars for the same fp64-sums-then-fp32 arithmetic: counts and statuses equal, rms to 1e-5 relative, the pose
-    to 1e-5 in R's entries and in t relative; a failed step returns its input bit for bit."""
-    assert (want["near_ties"] == 0).all(), "a near-tie in the case: change its seed"
-    assert np.array_equal(host(got["inliers"]), want["inliers"]), (host(got["inliers"]), want["inliers"])
-    assert np.array_equal(host(got["status"]), want["status"]), (host(got["status"]), want["status"])
-    rms = host(got["rms"]).astype(np.float64)
-    assert np.array_equal(np.isnan(rms), np.isnan(want["rms"]))
-    ok = ~np.isnan(rms)
-    assert (np.abs(rms[ok] - want["rms"][ok]) <= 1e-5 * want["rms"][ok] + 1e-30).all(), (rms, want["rms"])
-    pose = host(got["pose"])
-    for b in range(len(pose)):
-        if want["status"][b] != 0:
-            assert np.array_equal(pose[b].view(np.uint32), np.asarray(pose_in[b], np.float32).view(np.uint32)), b
-        else:
-            assert np.abs(pose[b, :, :3] - want["pose"][b, :, :3]).max() <= 1e-5, b
-            assert np.abs(pose[b, :, 3] - want["pose"][b, :, 3]).max() <= 1e-5 * np.abs(want["pose"][b, :, 3]).max(), b
 
 
 # ----------------------------------------------------------------------------- one step, exact inputs

@@ -5,33 +5,21 @@
 //                depth and one of the measured depth where the planes allow it, else guarded 4-byte loads.  A pixel without a rendered
 //                surface or without a measurement leaves before anything else is read (most of a frame is background); the others read
 //                their mask byte, their face index, the face's three vertex indices and the vertices.  The pose and the intrinsics of the
-//                image are wave-uniform and are read before the kernel's only global store, so they come through scalar loads.  The 29
-//                fp64 sums of a thread are reduced in pnp_reduce's order: xor-butterfly inside the wave (step-major: the 29 exchanges
-//                of a step are in flight together), the four waves in ascending order through LDS, one 32-double record per workgroup.
-//                A wave none of whose pixels is kept skips its butterflies: its sums are 29 zeros either way.
-//   icp_solve    grid B x 64.  The records come through LDS 64 at a time (coalesced, 32 loads in flight per thread), 29 threads add them
-//                in ascending tile order, thread 0 factors, steps (pose_gn.h, shared with K28) and writes the outputs.
+//                image are wave-uniform and are read before the kernel's only global store, so they come through scalar loads.  Each
+//                kept pixel gives one row of the 6-parameter system.
+// The rest is pose_gn.h's, shared with K28 and K30: the workgroup's 29 fp64 sums become one record (gn_block_reduce), and
+// gn_solve_kernel (grid B x 64) gathers an image's records, factors, steps and writes the outputs.
 // No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
 
 namespace {
-constexpr int kIcpBlock = 256, kIcpPix = 4, kIcpTile = kIcpBlock * kIcpPix, kIcpWaves = kIcpBlock / tp::kWave;
-constexpr int kIcpMinCount = 6;
-constexpr int kIcpStage = 64;                         // records the solve kernel stages through LDS at a time
-
-__host__ __device__ inline int64_t icp_tiles(int64_t n) { return (n + kIcpTile - 1) / kIcpTile; }
-
 // VEC: H * W is a multiple of four and zbuf / depth are 16-byte aligned
 template <bool VEC>
-__global__ __launch_bounds__(kIcpBlock) void icp_reduce_kernel(tp_depth_icp_args a, double* part) {
-  __shared__ double wave_part[kIcpWaves][kGnPart];
+__global__ __launch_bounds__(kGnBlock) void icp_reduce_kernel(tp_depth_icp_args a, double* part) {
+  __shared__ double wave_part[kGnWaves][kGnPart];
   const int b = blockIdx.y;
-  int fr = a.Ft == 1 ? 0 : b;
-  if (a.frame) {                                                                 // out of range is the caller's error: clamped, never read past
-    fr = a.frame[b];
-    fr = fr < 0 ? 0 : (fr >= a.Ft ? a.Ft - 1 : fr);
-  }
+  const int fr = gn_frame_of(a, b);
   const int64_t plane = (int64_t)a.H * a.W;
   const float* pz = a.zbuf + (int64_t)b * plane;
   const int32_t* pf = a.face + (int64_t)b * plane;
@@ -45,10 +33,10 @@ __global__ __launch_bounds__(kIcpBlock) void icp_reduce_kernel(tp_depth_icp_args
   for (int r = 0; r < 3; ++r) { R[3 * r] = (double)T[4 * r]; R[3 * r + 1] = (double)T[4 * r + 1]; R[3 * r + 2] = (double)T[4 * r + 2]; }
   const double tau2 = (double)a.tau_mm * (double)a.tau_mm;
 
-  const int64_t p0 = (int64_t)blockIdx.x * kIcpTile + (int)threadIdx.x * kIcpPix;          // (< H * W + 1024 < 2^31 + 1024)
-  float zs[kIcpPix], ds[kIcpPix];
+  const int64_t p0 = (int64_t)blockIdx.x * kGnTile + (int)threadIdx.x * kGnPix;          // (< H * W + 1024 < 2^31 + 1024)
+  float zs[kGnPix], ds[kGnPix];
 #pragma unroll
-  for (int k = 0; k < kIcpPix; ++k) { zs[k] = -1.f; ds[k] = 0.f; }
+  for (int k = 0; k < kGnPix; ++k) { zs[k] = -1.f; ds[k] = 0.f; }
   if constexpr (VEC) {
     if (p0 < plane) {                                                            // (plane % 4 == 0: the four are inside together)
       const float4 z4 = *reinterpret_cast<const float4*>(pz + p0), d4 = *reinterpret_cast<const float4*>(pd + p0);
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(kIcpBlock) void icp_reduce_kernel(tp_depth_icp_args
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < kIcpPix; ++k)
+    for (int k = 0; k < kGnPix; ++k)
       if (p0 + k < plane) { zs[k] = pz[p0 + k]; ds[k] = pd[p0 + k]; }
   }
 
@@ -66,7 +54,7 @@ __global__ __launch_bounds__(kIcpBlock) void icp_reduce_kernel(tp_depth_icp_args
   for (int k = 0; k < kGnSums; ++k) s[k] = 0.0;
   bool any = false;
 #pragma unroll
-  for (int k = 0; k < kIcpPix; ++k) {
+  for (int k = 0; k < kGnPix; ++k) {
     const float zf = zs[k], df = ds[k];
     if (!(zf > 0.f) || !isfinite(zf) || !(df > 0.f) || !isfinite(df)) continue;            // steps 1 and 3: nothing else was read
     const int64_t p = p0 + k;                                                    // (< plane: the others kept -1 / 0)
@@ -95,92 +83,18 @@ __global__ __launch_bounds__(kIcpBlock) void icp_reduce_kernel(tp_depth_icp_args
     const double res = dot(n, P - Q);
     const V3 pn = cross(P, n);
     const double J[6] = {pn.x, pn.y, pn.z, n.x, n.y, n.z};
-    int e = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int cc = r; cc < 6; ++cc) s[e++] += J[r] * J[cc];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) s[21 + r] += J[r] * res;
-    s[27] += res * res;
+    gn_add_row(s, J, res);
     s[28] += 1.0;
     any = true;
   }
 
-  const int lane = threadIdx.x & (tp::kWave - 1), wave = threadIdx.x / tp::kWave;
-  if (__ballot(any) != 0ull) {                                                   // (uniform per wave)
-    wave_sum_all(s);
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < kGnSums; ++k) wave_part[wave][k] = s[k];
-    }
-  } else if (lane < kGnSums) {
-    wave_part[wave][lane] = 0.0;                                                 // what the butterflies of 64 zeros give
-  }
-  __syncthreads();
-  if (threadIdx.x < kGnSums) {
-    double t = wave_part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kIcpWaves; ++w) t += wave_part[w][threadIdx.x];
-    part[((int64_t)b * gridDim.x + blockIdx.x) * kGnPart + threadIdx.x] = t;
-  }
-}
-
-// grid B, one wave
-__global__ __launch_bounds__(tp::kWave) void icp_solve_kernel(tp_depth_icp_args a, const double* part, int G) {
-  __shared__ double sum[kGnPart], stage[kIcpStage][kGnPart];
-  const int b = blockIdx.x;
-  const double* rec = part + (int64_t)b * G * kGnPart;
-  double t = 0.0;
-  for (int g0 = 0; g0 < G; g0 += kIcpStage) {                                    // 64 records in flight as whole 512-byte rows
-    const int n = G - g0 < kIcpStage ? G - g0 : kIcpStage;
-    double v[kIcpStage / 2];
-#pragma unroll
-    for (int u = 0; u < kIcpStage / 2; ++u) {
-      const int e = (int)threadIdx.x + tp::kWave * u;                            // element e of the batch: record e / 32, entry e % 32
-      v[u] = e / kGnPart < n ? rec[(int64_t)g0 * kGnPart + e] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kIcpStage / 2; ++u) (&stage[0][0])[(int)threadIdx.x + tp::kWave * u] = v[u];
-    __syncthreads();
-    if (threadIdx.x < kGnSums)
-      for (int g = 0; g < n; ++g) t += stage[g][threadIdx.x];                    // ascending tile order
-    __syncthreads();
-  }
-  if (threadIdx.x < kGnSums) sum[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const float* T = a.pose + (int64_t)b * 12;
-  const double count = sum[28];
-  int status = 0;
-  double Pn[12];
-  if (count < (double)kIcpMinCount) {
-    status = 1;
-  } else if (a.evaluate_only) {
-    double A[6][6];
-    gn_matrix(sum, A);
-    if (!cholesky6(A, kGnPivotTol)) status = 3;
-  } else {
-    double cur[12];
-    for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
-    bool ok = gn_step(sum, cur, (double)a.damping, Pn);
-    for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
-    if (!ok) status = 3;
-  }
-  a.inliers[b] = (int)count;
-  a.rms[b] = count > 0.0 ? (float)sqrt(sum[27] / count) : __int_as_float(0x7fc00000);
-  a.status[b] = status;
-  if (a.pose_out) {
-    const bool stepped = status == 0 && !a.evaluate_only;
-    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
-  }
+  gn_block_reduce(s, any, wave_part, part + ((int64_t)b * gridDim.x + blockIdx.x) * kGnPart);
 }
 }  // namespace
 
 extern "C" size_t tp_depth_icp_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  const size_t bytes = (size_t)B * (size_t)icp_tiles((int64_t)H * W) * kGnPart * sizeof(double);
-  return (bytes + 15) & ~(size_t)15;
+  return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
 }
 
 extern "C" int tp_depth_icp_step(const tp_depth_icp_args* a, tp_stream_t stream) {
@@ -189,29 +103,15 @@ extern "C" int tp_depth_icp_step(const tp_depth_icp_args* a, tp_stream_t stream)
     tp::set_error("tp_depth_icp_step: bad sizes (B 1..65535, Ft > 0, V > 0, F > 0, H > 0, W > 0, H * W < 2^31)");
     return -1;
   }
-  if (!a->frame && a->Ft != 1 && a->Ft != a->B) {
-    tp::set_error("tp_depth_icp_step: Ft = %d is neither 1 nor B = %d and there is no frame map", a->Ft, a->B);
-    return -1;
-  }
-  if (!(a->tau_mm > 0.f) || !isfinite(a->tau_mm)) { tp::set_error("tp_depth_icp_step: tau_mm must be finite and positive"); return -1; }
-  if (!(a->damping >= 0.f) || !isfinite(a->damping)) { tp::set_error("tp_depth_icp_step: damping must be finite and not negative"); return -1; }
-  if (!a->verts || !a->faces || !a->zbuf || !a->face || !a->pose || !a->intr || !a->depth || !a->inliers || !a->rms || !a->status || !a->workspace ||
-      (!a->pose_out && !a->evaluate_only)) {
-    tp::set_error("tp_depth_icp_step: null pointer");
-    return -1;
-  }
-  if ((uintptr_t)a->workspace & 15u) { tp::set_error("tp_depth_icp_step: workspace must be 16-byte aligned"); return -1; }
-  if (a->pose_out) {
-    const uintptr_t in = (uintptr_t)a->pose, out = (uintptr_t)a->pose_out, bytes = (uintptr_t)a->B * 12 * sizeof(float);
-    if (in < out + bytes && out < in + bytes) { tp::set_error("tp_depth_icp_step: pose_out must not overlap pose"); return -1; }
-  }
+  const bool missing = !a->verts || !a->faces || !a->zbuf || !a->face || !a->depth;
+  if (!gn_step_args_ok("tp_depth_icp_step", *a, "tau_mm", a->tau_mm, missing)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int64_t plane = (int64_t)a->H * a->W;
-  const int G = (int)icp_tiles(plane);
+  const int G = (int)gn_tiles(plane);
   double* part = static_cast<double*>(a->workspace);
-  const bool vec = plane % kIcpPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->depth) & 15u) == 0;
-  if (vec) hipLaunchKernelGGL(icp_reduce_kernel<true>, dim3(G, a->B), dim3(kIcpBlock), 0, st, *a, part);
-  else hipLaunchKernelGGL(icp_reduce_kernel<false>, dim3(G, a->B), dim3(kIcpBlock), 0, st, *a, part);
-  hipLaunchKernelGGL(icp_solve_kernel, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->depth) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(icp_reduce_kernel<true>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
+  else hipLaunchKernelGGL(icp_reduce_kernel<false>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
+  hipLaunchKernelGGL(gn_solve_kernel<tp_depth_icp_args>, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
   return tp::check_launch("tp_depth_icp_step");
 }

@@ -9,35 +9,24 @@
 //                neighbours: the left and right ones of a thread's inner pixels are already in its registers, the rows above and
 //                below are the neighbouring threads' own lines in the cache.  The intrinsics and the frame index are wave-uniform
 //                and are read before the kernel's only global store, so they come through scalar loads; the pose is not needed.
-//                Each kept pixel gives three rows (one per channel) of the 6-parameter system.  The 29 fp64 sums of a thread are
-//                reduced in icp_reduce's order: xor-butterfly inside the wave (step-major), the four waves in ascending order
-//                through LDS, one 32-double record per workgroup.  A wave none of whose pixels is kept skips its butterflies: its
-//                sums are 29 zeros either way.
-//   photo_solve  grid B x 64.  The records come through LDS 64 at a time (coalesced, 32 loads in flight per thread), 29 threads add
-//                them in ascending tile order, thread 0 factors, steps (pose_gn.h, shared with K28 and K29) and writes the outputs.
+//                Each kept pixel gives three rows (one per channel) of the 6-parameter system.
+// The rest is pose_gn.h's, shared with K28 and K29: the workgroup's 29 fp64 sums become one record (gn_block_reduce), and
+// gn_solve_kernel (grid B x 64) gathers an image's records, factors, steps and writes the outputs.
 // No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
 
 namespace {
-constexpr int kPhBlock = 256, kPhPix = 4, kPhTile = kPhBlock * kPhPix, kPhWaves = kPhBlock / tp::kWave;
-constexpr int kPhMinCount = 6;
-constexpr int kPhStage = 64;                          // records the solve kernel stages through LDS at a time
-
-__host__ __device__ inline int64_t photo_tiles(int64_t n) { return (n + kPhTile - 1) / kPhTile; }
-
 __device__ __forceinline__ bool finite3(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 
-// VEC: H * W is a multiple of four and zbuf / rgb / image are 16-byte aligned
+// VEC: H * W is a multiple of four and zbuf / rgb / image are 16-byte aligned.  Three waves per SIMD (at most 168 VGPRs) is what the
+// guarded path was tuned to; asked for here, since left to itself the allocator takes 174 once the rows go through gn_add_row (the
+// vector path fits either way and is left alone)
 template <bool VEC>
-__global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_args a, double* part) {
-  __shared__ double wave_part[kPhWaves][kGnPart];
+__global__ __launch_bounds__(kGnBlock, VEC ? 1 : 3) void photo_reduce_kernel(tp_photo_align_args a, double* part) {
+  __shared__ double wave_part[kGnWaves][kGnPart];
   const int b = blockIdx.y;
-  int fr = a.Ft == 1 ? 0 : b;
-  if (a.frame) {                                                                 // out of range is the caller's error: clamped, never read past
-    fr = a.frame[b];
-    fr = fr < 0 ? 0 : (fr >= a.Ft ? a.Ft - 1 : fr);
-  }
+  const int fr = gn_frame_of(a, b);
   const int64_t plane = (int64_t)a.H * a.W;
   const float* pz = a.zbuf + (int64_t)b * plane;
   const float* pc = a.rgb + (int64_t)b * plane * 3;
@@ -47,10 +36,10 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
   const double fx = (double)K[0], cx = (double)K[2], fy = (double)K[4], cy = (double)K[5];
   const double tau2 = (double)a.tau * (double)a.tau;
 
-  const int64_t p0 = (int64_t)blockIdx.x * kPhTile + (int)threadIdx.x * kPhPix;            // (< H * W + 1024 < 2^31 + 1024)
-  float zs[kPhPix];
+  const int64_t p0 = (int64_t)blockIdx.x * kGnTile + (int)threadIdx.x * kGnPix;            // (< H * W + 1024 < 2^31 + 1024)
+  float zs[kGnPix];
 #pragma unroll
-  for (int k = 0; k < kPhPix; ++k) zs[k] = -1.f;
+  for (int k = 0; k < kGnPix; ++k) zs[k] = -1.f;
   if constexpr (VEC) {
     if (p0 < plane) {                                                            // (plane % 4 == 0: the four are inside together)
       const float4 z4 = *reinterpret_cast<const float4*>(pz + p0);
@@ -58,7 +47,7 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < kPhPix; ++k)
+    for (int k = 0; k < kGnPix; ++k)
       if (p0 + k < plane) zs[k] = pz[p0 + k];
   }
 
@@ -68,15 +57,15 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
   {
     int i = i0, j = j0;
 #pragma unroll
-    for (int k = 0; k < kPhPix; ++k) {
+    for (int k = 0; k < kGnPix; ++k) {
       if (i >= 1 && i <= a.H - 2 && j >= 1 && j <= a.W - 2 && zs[k] > 0.f && isfinite(zs[k])) cand |= 1u << k;
       if (++j == a.W) { j = 0; ++i; }
     }
   }
 
-  float cs[kPhPix * 3], os[kPhPix * 3];
+  float cs[kGnPix * 3], os[kGnPix * 3];
 #pragma unroll
-  for (int k = 0; k < kPhPix * 3; ++k) { cs[k] = 0.f; os[k] = 0.f; }
+  for (int k = 0; k < kGnPix * 3; ++k) { cs[k] = 0.f; os[k] = 0.f; }
   if (cand != 0u) {
     if constexpr (VEC) {                                                         // (p0 * 12 bytes: a multiple of 48)
       const float4* c4 = reinterpret_cast<const float4*>(pc + p0 * 3);
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < kPhPix; ++k)
+      for (int k = 0; k < kGnPix; ++k)
         if (cand >> k & 1u) {
 #pragma unroll
           for (int ch = 0; ch < 3; ++ch) { cs[3 * k + ch] = pc[(p0 + k) * 3 + ch]; os[3 * k + ch] = po[(p0 + k) * 3 + ch]; }
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
   bool any = false;
   int pi = i0, pj = j0 - 1;                                                      // row and column of pixel k, walked as above
 #pragma unroll
-  for (int k = 0; k < kPhPix; ++k) {
+  for (int k = 0; k < kGnPix; ++k) {
     if (++pj == a.W) { pj = 0; ++pi; }
     if (!(cand >> k & 1u)) continue;
     const int64_t p = p0 + k;                                                    // (interior: p - W >= 0, p + W < plane, p -+ 1 in its row)
@@ -112,7 +101,7 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       if (VEC && k > 0) lf[ch] = os[3 * (k - 1) + ch]; else lf[ch] = po[(p - 1) * 3 + ch];
-      if (VEC && k < kPhPix - 1) rt[ch] = os[3 * (k + 1) + ch]; else rt[ch] = po[(p + 1) * 3 + ch];
+      if (VEC && k < kGnPix - 1) rt[ch] = os[3 * (k + 1) + ch]; else rt[ch] = po[(p + 1) * 3 + ch];
       up[ch] = po[(p - a.W) * 3 + ch];
       dn[ch] = po[(p + a.W) * 3 + ch];
     }
@@ -131,93 +120,19 @@ __global__ __launch_bounds__(kPhBlock) void photo_reduce_kernel(tp_photo_align_a
       const V3 av = {gfx / z, gfy / z, -(gfx * rx + gfy * ry) / z};
       const V3 pa = cross(P, av);
       const double J[6] = {pa.x, pa.y, pa.z, av.x, av.y, av.z};
-      int e = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int cc = r; cc < 6; ++cc) s[e++] += J[r] * J[cc];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) s[21 + r] += J[r] * res[ch];
-      s[27] += res[ch] * res[ch];
+      gn_add_row(s, J, res[ch]);
     }
     s[28] += 1.0;
     any = true;
   }
 
-  const int lane = threadIdx.x & (tp::kWave - 1), wave = threadIdx.x / tp::kWave;
-  if (__ballot(any) != 0ull) {                                                   // (uniform per wave)
-    wave_sum_all(s);
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < kGnSums; ++k) wave_part[wave][k] = s[k];
-    }
-  } else if (lane < kGnSums) {
-    wave_part[wave][lane] = 0.0;                                                 // what the butterflies of 64 zeros give
-  }
-  __syncthreads();
-  if (threadIdx.x < kGnSums) {
-    double t = wave_part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kPhWaves; ++w) t += wave_part[w][threadIdx.x];
-    part[((int64_t)b * gridDim.x + blockIdx.x) * kGnPart + threadIdx.x] = t;
-  }
-}
-
-// grid B, one wave
-__global__ __launch_bounds__(tp::kWave) void photo_solve_kernel(tp_photo_align_args a, const double* part, int G) {
-  __shared__ double sum[kGnPart], stage[kPhStage][kGnPart];
-  const int b = blockIdx.x;
-  const double* rec = part + (int64_t)b * G * kGnPart;
-  double t = 0.0;
-  for (int g0 = 0; g0 < G; g0 += kPhStage) {                                     // 64 records in flight as whole 512-byte rows
-    const int n = G - g0 < kPhStage ? G - g0 : kPhStage;
-    double v[kPhStage / 2];
-#pragma unroll
-    for (int u = 0; u < kPhStage / 2; ++u) {
-      const int e = (int)threadIdx.x + tp::kWave * u;                            // element e of the batch: record e / 32, entry e % 32
-      v[u] = e / kGnPart < n ? rec[(int64_t)g0 * kGnPart + e] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kPhStage / 2; ++u) (&stage[0][0])[(int)threadIdx.x + tp::kWave * u] = v[u];
-    __syncthreads();
-    if (threadIdx.x < kGnSums)
-      for (int g = 0; g < n; ++g) t += stage[g][threadIdx.x];                    // ascending tile order
-    __syncthreads();
-  }
-  if (threadIdx.x < kGnSums) sum[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const float* T = a.pose + (int64_t)b * 12;
-  const double count = sum[28];
-  int status = 0;
-  double Pn[12];
-  if (count < (double)kPhMinCount) {
-    status = 1;
-  } else if (a.evaluate_only) {
-    double A[6][6];
-    gn_matrix(sum, A);
-    if (!cholesky6(A, kGnPivotTol)) status = 3;
-  } else {
-    double cur[12];
-    for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
-    bool ok = gn_step(sum, cur, (double)a.damping, Pn);
-    for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
-    if (!ok) status = 3;
-  }
-  a.inliers[b] = (int)count;
-  a.rms[b] = count > 0.0 ? (float)sqrt(sum[27] / count) : __int_as_float(0x7fc00000);
-  a.status[b] = status;
-  if (a.pose_out) {
-    const bool stepped = status == 0 && !a.evaluate_only;
-    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
-  }
+  gn_block_reduce(s, any, wave_part, part + ((int64_t)b * gridDim.x + blockIdx.x) * kGnPart);
 }
 }  // namespace
 
 extern "C" size_t tp_photo_align_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  const size_t bytes = (size_t)B * (size_t)photo_tiles((int64_t)H * W) * kGnPart * sizeof(double);
-  return (bytes + 15) & ~(size_t)15;
+  return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
 }
 
 extern "C" int tp_photo_align_step(const tp_photo_align_args* a, tp_stream_t stream) {
@@ -226,29 +141,15 @@ extern "C" int tp_photo_align_step(const tp_photo_align_args* a, tp_stream_t str
     tp::set_error("tp_photo_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
     return -1;
   }
-  if (!a->frame && a->Ft != 1 && a->Ft != a->B) {
-    tp::set_error("tp_photo_align_step: Ft = %d is neither 1 nor B = %d and there is no frame map", a->Ft, a->B);
-    return -1;
-  }
-  if (!(a->tau > 0.f) || !isfinite(a->tau)) { tp::set_error("tp_photo_align_step: tau must be finite and positive"); return -1; }
-  if (!(a->damping >= 0.f) || !isfinite(a->damping)) { tp::set_error("tp_photo_align_step: damping must be finite and not negative"); return -1; }
-  if (!a->zbuf || !a->rgb || !a->pose || !a->intr || !a->image || !a->inliers || !a->rms || !a->status || !a->workspace ||
-      (!a->pose_out && !a->evaluate_only)) {
-    tp::set_error("tp_photo_align_step: null pointer");
-    return -1;
-  }
-  if ((uintptr_t)a->workspace & 15u) { tp::set_error("tp_photo_align_step: workspace must be 16-byte aligned"); return -1; }
-  if (a->pose_out) {
-    const uintptr_t in = (uintptr_t)a->pose, out = (uintptr_t)a->pose_out, bytes = (uintptr_t)a->B * 12 * sizeof(float);
-    if (in < out + bytes && out < in + bytes) { tp::set_error("tp_photo_align_step: pose_out must not overlap pose"); return -1; }
-  }
+  const bool missing = !a->zbuf || !a->rgb || !a->image;
+  if (!gn_step_args_ok("tp_photo_align_step", *a, "tau", a->tau, missing)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int64_t plane = (int64_t)a->H * a->W;
-  const int G = (int)photo_tiles(plane);
+  const int G = (int)gn_tiles(plane);
   double* part = static_cast<double*>(a->workspace);
-  const bool vec = plane % kPhPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->rgb | (uintptr_t)a->image) & 15u) == 0;
-  if (vec) hipLaunchKernelGGL(photo_reduce_kernel<true>, dim3(G, a->B), dim3(kPhBlock), 0, st, *a, part);
-  else hipLaunchKernelGGL(photo_reduce_kernel<false>, dim3(G, a->B), dim3(kPhBlock), 0, st, *a, part);
-  hipLaunchKernelGGL(photo_solve_kernel, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->rgb | (uintptr_t)a->image) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(photo_reduce_kernel<true>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
+  else hipLaunchKernelGGL(photo_reduce_kernel<false>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
+  hipLaunchKernelGGL(gn_solve_kernel<tp_photo_align_args>, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
   return tp::check_launch("tp_photo_align_step");
 }

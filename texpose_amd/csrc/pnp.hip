@@ -7,7 +7,8 @@
 //                       ballot + popcount, integer LDS sums across the waves, one integer atomic per (workgroup, pose); the inlier
 //                       mask of one chosen pose per image is a small launch of its own
 //   tp_pnp_refine       selection, then Gauss-Newton in fp64: a reduce launch (fixed-order partial sums into the workspace) and a
-//                       solve launch per step, keep-best, one final evaluation
+//                       solve launch per step, keep-best, one final evaluation; the block reduce, the record gather and the step
+//                       are pose_gn.h's, shared with K29 and K30
 // Integer atomics only; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
@@ -17,8 +18,6 @@ namespace {
 constexpr int kBlock = 256, kWaves = kBlock / tp::kWave;
 constexpr int kCorrTile = kBlock;                      // pixels per workgroup of tp_corr_from_nocs
 constexpr int kPts = 4, kTile = kBlock * kPts;         // points per workgroup of the score and reduce kernels
-constexpr int kSums = 29;                              // 21 (J^T J, upper triangle, row-major) + 6 (J^T r) + sum |r|^2 + count
-constexpr int kPart = 32;                              // doubles per partial record
 constexpr int kState = 32;                             // doubles per image: cur [12], best [12], best cost, best count, status, n, frozen
 constexpr int S_CUR = 0, S_BEST = 12, S_COST = 24, S_COUNT = 25, S_STATUS = 26, S_N = 27, S_FROZEN = 28;
 constexpr double kLambda = 1e-3;                      // the damping handed to pose_gn.h's step
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(kBlock) void pnp_select_kernel(tp_pnp_refine_args a
 
 // grid (ceil(N / 1024), B): the sums of the current pose over this workgroup's points -> part [b][tile][32]
 __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a, const double* state, double* part, int G) {
-  __shared__ double wave_part[kWaves][kPart];
+  __shared__ double wave_part[kWaves][kGnPart];
   const int b = blockIdx.y;
   const int64_t base = (int64_t)blockIdx.x * kTile;
   const double* st = state + (int64_t)b * kState;
@@ -426,9 +425,10 @@ __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a
   const float* K = a.intr + (int64_t)b * 9;
   const double fx = (double)K[0], fy = (double)K[4], cx = (double)K[2], cy = (double)K[5];
   const double tau2 = (double)a.tau_px * (double)a.tau_px;
-  double s[kSums];
+  double s[kGnSums];
 #pragma unroll
-  for (int k = 0; k < kSums; ++k) s[k] = 0.0;
+  for (int k = 0; k < kGnSums; ++k) s[k] = 0.0;
+  bool any = false;
   for (int k = 0; k < kPts; ++k) {
     const int64_t i = base + k * kBlock + (int)threadIdx.x;
     if (i >= n) continue;
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a
     const double xz = x * iz, yz = y * iz;
     const double ju[6] = {-fx * xz * yz, fx + fx * xz * xz, -fx * yz, fx * iz, 0.0, -fx * xz * iz};
     const double jv[6] = {-fy - fy * yz * yz, fy * xz * yz, fy * xz, 0.0, fy * iz, -fy * yz * iz};
-    int e = 0;
+    int e = 0;                                                                   // (both rows as one term per sum: not two gn_add_row)
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
@@ -453,34 +453,19 @@ __global__ __launch_bounds__(kBlock) void pnp_reduce_kernel(tp_pnp_refine_args a
     for (int r = 0; r < 6; ++r) s[21 + r] += ju[r] * ru + jv[r] * rv;
     s[27] += ru * ru + rv * rv;
     s[28] += 1.0;
+    any = true;
   }
-  const int wave = threadIdx.x / tp::kWave;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const double t = wave_sum(s[k]);
-    if (lane_id() == 0) wave_part[wave][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double t = wave_part[0][threadIdx.x];
-    for (int w = 1; w < kWaves; ++w) t += wave_part[w][threadIdx.x];
-    part[((int64_t)b * G + blockIdx.x) * kPart + threadIdx.x] = t;
-  }
+  gn_block_reduce(s, any, wave_part, part + ((int64_t)b * G + blockIdx.x) * kGnPart);
 }
 
 // grid B, one wave: the partials in ascending order, keep-best, then (unless `last`) one damped Gauss-Newton step; `last` writes the outputs
 __global__ __launch_bounds__(tp::kWave) void pnp_solve_kernel(tp_pnp_refine_args a, double* state, const double* part, int G, int last) {
-  __shared__ double sum[kPart];
+  __shared__ double sum[kGnPart], stage[kGnStage][kGnPart];
   const int b = blockIdx.x;
   double* st = state + (int64_t)b * kState;
   const int status = (int)st[S_STATUS];
   const bool dead = status == 1 || status == 2;
-  if (!dead && threadIdx.x < kSums) {
-    double t = 0.0;
-    for (int g = 0; g < G; ++g) t += part[((int64_t)b * G + g) * kPart + threadIdx.x];
-    sum[threadIdx.x] = t;
-  }
-  __syncthreads();
+  if (!dead) gn_gather(part + (int64_t)b * G * kGnPart, G, stage, sum);          // (uniform; nothing wrote a dead image's records)
   if (threadIdx.x != 0) return;
   if (!dead && st[S_FROZEN] == 0.0) {
     const double count = sum[28], cost = sum[27];
@@ -519,7 +504,7 @@ bool tau_ok(const char* who, float tau) {
 }
 // workspace: state [B][32] doubles, partials [B][G][32] doubles, tile counts [B][ceil(N / 256)] int32
 size_t state_bytes(int B) { return (size_t)B * kState * sizeof(double); }
-size_t part_bytes(int B, int N) { return (size_t)B * (size_t)tiles_of(N, kTile) * kPart * sizeof(double); }
+size_t part_bytes(int B, int N) { return (size_t)B * (size_t)tiles_of(N, kTile) * kGnPart * sizeof(double); }
 }  // namespace
 
 extern "C" size_t tp_pnp_workspace_bytes(int B, int N, int T) {

@@ -1,7 +1,13 @@
-// The 6-parameter Gauss-Newton machinery that K28 (pnp.hip, reprojection residuals) and K29 (depth_icp.hip, point-to-plane residuals)
-// share: fp64 3-vectors, the wave butterfly sum, the 6x6 Cholesky with the pivot rule, and one damped step of the update
-// x' = x + w x x + v in the camera frame (parameters (w, v)) followed by the exponential map and Gram-Schmidt.  Everything is evaluated
-// as written (the library is built without contraction): both users get the same bits from the same sums.
+// The 6-parameter Gauss-Newton core of the three pose refiners: K28 (pnp.hip, reprojection residuals), K29 (depth_icp.hip, point-to-plane
+// residuals) and K30 (photo_align.hip, colour residuals).  A refiner supplies its residual rows; everything after them is here:
+//   - fp64 3-vectors, the wave butterfly sum, the 6x6 Cholesky with the pivot rule, and one damped step of the update
+//     x' = x + w x x + v in the camera frame (parameters (w, v)) followed by the exponential map and Gram-Schmidt;
+//   - the row accumulation into the 29 sums (gn_add_row), their reduction over a workgroup into one 32-double record
+//     (gn_block_reduce) and the gather of an image's records in ascending tile order (gn_gather);
+//   - for the pixel-tiled refiners K29 and K30: the tiling constants, the frame choice (gn_frame_of), the workspace size, the
+//     step / evaluate kernel with its count, status and pass-through rules (gn_solve_kernel) and the host's argument checks.
+// Everything is evaluated as written (the library is built without contraction) and every sum has one fixed order: all users get the
+// same bits from the same sums, and their outputs are a function of the inputs alone.
 #pragma once
 #include "tp_common.h"
 #include <math.h>
@@ -18,13 +24,9 @@ constexpr int kGnSums = 29;                            // 21 (J^T J, upper trian
 constexpr int kGnPart = 32;                            // doubles per partial record
 constexpr double kGnPivotTol = 1e-10;
 
-__device__ __forceinline__ double wave_sum(double v) {                           // butterfly: the same order, and the same sum, in every lane
-  for (int m = 1; m < tp::kWave; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-// wave_sum of K values at once, step-major: the K exchanges of a step are in flight together instead of K x 6 round trips one after
-// the other; value by value the same additions in the same order as wave_sum, hence the same bits
+// The wave's sum of each of K values by an xor butterfly (v += shfl_xor(v, 1), 2, 4 .. 32: the same order, and the same sum, in every
+// lane), step-major: the K exchanges of a step are in flight together instead of K x 6 round trips one after the other; value by
+// value the additions and their order are those of K butterflies run one at a time, hence the same bits
 template <int K>
 __device__ __forceinline__ void wave_sum_all(double (&v)[K]) {
 #pragma unroll
@@ -104,5 +106,147 @@ __device__ bool gn_step(const double* sum, const double* cur, double lambda, dou
   bool ok = true;
   for (int k = 0; k < 12; ++k) ok = ok && isfinite(Pn[k]);
   return ok;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the 29 sums
+// one residual row: the 21 products of J^T J's upper triangle, the 6 of J^T r and r^2, each added to its sum; the count is the caller's
+__device__ __forceinline__ void gn_add_row(double (&s)[kGnSums], const double (&J)[6], double r) {
+  int e = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int c = i; c < 6; ++c) s[e++] += J[i] * J[c];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) s[21 + i] += J[i] * r;
+  s[27] += r * r;
+}
+
+// The sums of a workgroup of WAVES waves -> record [32]: xor-butterfly inside the wave (step-major), lane 0 to LDS, the waves in
+// ascending order by 29 threads.  `any`: this thread added something; a wave without one skips its butterflies and stores the
+// 29 zeros (+0.0) they would have given.  Every thread of the workgroup must call it.
+template <int WAVES>
+__device__ __forceinline__ void gn_block_reduce(double (&s)[kGnSums], bool any, double (&wave_part)[WAVES][kGnPart], double* record) {
+  const int lane = threadIdx.x & (tp::kWave - 1), wave = threadIdx.x / tp::kWave;
+  if (__ballot(any) != 0ull) {                                                   // (uniform per wave)
+    wave_sum_all(s);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < kGnSums; ++k) wave_part[wave][k] = s[k];
+    }
+  } else if (lane < kGnSums) {
+    wave_part[wave][lane] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < kGnSums) {
+    double t = wave_part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) t += wave_part[w][threadIdx.x];
+    record[threadIdx.x] = t;
+  }
+}
+
+constexpr int kGnStage = 64;                           // records gn_gather stages through LDS at a time
+
+// One wave: the G records at rec -> sum [0 .. 28].  The records come through LDS 64 at a time as whole 512-byte rows (coalesced, 32
+// loads in flight per thread); 29 threads add them in ascending tile order.  sum is ready for every thread on return.
+__device__ __forceinline__ void gn_gather(const double* rec, int G, double (&stage)[kGnStage][kGnPart], double (&sum)[kGnPart]) {
+  double t = 0.0;
+  for (int g0 = 0; g0 < G; g0 += kGnStage) {
+    const int n = G - g0 < kGnStage ? G - g0 : kGnStage;
+    double v[kGnStage / 2];
+#pragma unroll
+    for (int u = 0; u < kGnStage / 2; ++u) {
+      const int e = (int)threadIdx.x + tp::kWave * u;                            // element e of the batch: record e / 32, entry e % 32
+      v[u] = e / kGnPart < n ? rec[(int64_t)g0 * kGnPart + e] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kGnStage / 2; ++u) (&stage[0][0])[(int)threadIdx.x + tp::kWave * u] = v[u];
+    __syncthreads();
+    if (threadIdx.x < kGnSums)
+      for (int g = 0; g < n; ++g) t += stage[g][threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.x < kGnSums) sum[threadIdx.x] = t;
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the pixel-tiled refiners
+// K29 and K30: a workgroup of 256 threads owns a tile of 1024 flat pixels, four consecutive ones per thread; their args structs name
+// the shared fields alike (B, Ft, H, W, frame, pose, damping, evaluate_only, pose_out, inliers, rms, status, workspace).
+constexpr int kGnBlock = 256, kGnPix = 4, kGnTile = kGnBlock * kGnPix, kGnWaves = kGnBlock / tp::kWave;
+constexpr int kGnMinCount = 6;
+
+__host__ __device__ inline int64_t gn_tiles(int64_t n) { return (n + kGnTile - 1) / kGnTile; }
+inline size_t gn_workspace_bytes(int B, int64_t tiles) {                         // one record per (image, tile)
+  const size_t bytes = (size_t)B * (size_t)tiles * kGnPart * sizeof(double);
+  return (bytes + 15) & ~(size_t)15;
+}
+
+// the measured plane of image b: the only one, its own, or frame[b] (out of range is the caller's error: clamped, never read past)
+template <class Args>
+__device__ __forceinline__ int gn_frame_of(const Args& a, int b) {
+  int fr = a.Ft == 1 ? 0 : b;
+  if (a.frame) {
+    fr = a.frame[b];
+    fr = fr < 0 ? 0 : (fr >= a.Ft ? a.Ft - 1 : fr);
+  }
+  return fr;
+}
+
+// grid B, one wave: gathers the image's G records, then thread 0 applies the rules: fewer than six kept pixels: status 1; with
+// evaluate_only the pivot rule alone decides between 0 and 3; else one damped step, status 3 where it fails or leaves fp32's range.
+// inliers and rms (NaN without a pixel) are those of the pose that came in; pose_out is the stepped pose, or the input bit for bit.
+template <class Args>
+__global__ __launch_bounds__(tp::kWave) void gn_solve_kernel(Args a, const double* part, int G) {
+  __shared__ double sum[kGnPart], stage[kGnStage][kGnPart];
+  const int b = blockIdx.x;
+  gn_gather(part + (int64_t)b * G * kGnPart, G, stage, sum);
+  if (threadIdx.x != 0) return;
+  const float* T = a.pose + (int64_t)b * 12;
+  const double count = sum[28];
+  int status = 0;
+  double Pn[12];
+  if (count < (double)kGnMinCount) {
+    status = 1;
+  } else if (a.evaluate_only) {
+    double A[6][6];
+    gn_matrix(sum, A);
+    if (!cholesky6(A, kGnPivotTol)) status = 3;
+  } else {
+    double cur[12];
+    for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
+    bool ok = gn_step(sum, cur, (double)a.damping, Pn);
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
+    if (!ok) status = 3;
+  }
+  a.inliers[b] = (int)count;
+  a.rms[b] = count > 0.0 ? (float)sqrt(sum[27] / count) : __int_as_float(0x7fc00000);
+  a.status[b] = status;
+  if (a.pose_out) {
+    const bool stepped = status == 0 && !a.evaluate_only;
+    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
+  }
+}
+
+// The host checks both step calls make after their own size check, in the order callers see them.  `tau` is the caller's threshold
+// under the name `tau_word`; `missing`: one of the pointers the caller requires is null (each has its own list).
+template <class Args>
+bool gn_step_args_ok(const char* who, const Args& a, const char* tau_word, float tau, bool missing) {
+  if (!a.frame && a.Ft != 1 && a.Ft != a.B) {
+    tp::set_error("%s: Ft = %d is neither 1 nor B = %d and there is no frame map", who, a.Ft, a.B);
+    return false;
+  }
+  if (!(tau > 0.f) || !isfinite(tau)) { tp::set_error("%s: %s must be finite and positive", who, tau_word); return false; }
+  if (!(a.damping >= 0.f) || !isfinite(a.damping)) { tp::set_error("%s: damping must be finite and not negative", who); return false; }
+  if (missing || !a.pose || !a.intr || !a.inliers || !a.rms || !a.status || !a.workspace || (!a.pose_out && !a.evaluate_only)) {
+    tp::set_error("%s: null pointer", who);
+    return false;
+  }
+  if ((uintptr_t)a.workspace & 15u) { tp::set_error("%s: workspace must be 16-byte aligned", who); return false; }
+  if (a.pose_out) {
+    const uintptr_t in = (uintptr_t)a.pose, out = (uintptr_t)a.pose_out, bytes = (uintptr_t)a.B * 12 * sizeof(float);
+    if (in < out + bytes && out < in + bytes) { tp::set_error("%s: pose_out must not overlap pose", who); return false; }
+  }
+  return true;
 }
 }  // namespace

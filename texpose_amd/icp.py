@@ -12,40 +12,12 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
+from . import _gn_torch, ops
+from ._gn_torch import MIN_COUNT, PIVOT_TOL  # noqa: F401  (the header's constants, under the names callers know)
+from ._refiner import _MeshRefiner
 from .options import AttrDict
 
 Tensor = torch.Tensor
-PIVOT_TOL = 1e-10
-MIN_COUNT = 6
-
-
-def _cholesky6(A: Tensor, tol: float):
-    """Batched Cholesky of A [B,6,6] with the header's pivot rule -> (L [B,6,6], ok [B] bool); rows of a failed matrix hold garbage."""
-    B = A.shape[0]
-    L = torch.zeros_like(A)
-    ok = torch.ones(B, dtype=torch.bool, device=A.device)
-    for j in range(6):
-        diag = A[:, j, j]
-        d = diag - (L[:, j, :j] * L[:, j, :j]).sum(-1)
-        ok = ok & torch.isfinite(d) & (d > tol * diag) & (d > 0)
-        l = torch.sqrt(torch.where(ok, d, torch.ones_like(d)))
-        L[:, j, j] = l
-        for i in range(j + 1, 6):
-            L[:, i, j] = (A[:, i, j] - (L[:, i, :j] * L[:, j, :j]).sum(-1)) / l
-    return L, ok
-
-
-def _exp_so3(w: Tensor) -> Tensor:
-    th2 = (w * w).sum(-1)
-    th = torch.sqrt(th2)
-    big = th > 1e-8
-    safe, safe2 = torch.where(big, th, torch.ones_like(th)), torch.where(big, th2, torch.ones_like(th2))
-    sa = torch.where(big, torch.sin(safe) / safe, 1.0 - th2 / 6.0)[:, None, None]
-    sb = torch.where(big, (1.0 - torch.cos(safe)) / safe2, 0.5 - th2 / 24.0)[:, None, None]
-    Wx = torch.zeros(w.shape[0], 3, 3, dtype=w.dtype, device=w.device)
-    Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0], Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
-    return torch.eye(3, dtype=w.dtype, device=w.device)[None] + sa * Wx + sb * (Wx @ Wx)
 
 
 def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, tau_mm: float,
@@ -66,14 +38,8 @@ def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     if depth.dim() == 2:
         depth = depth[None]
     Ft = depth.shape[0]
-    if frame is None:
-        if Ft not in (1, B):
-            raise ValueError("step_torch: depth must hold 1 or B = %d planes without frame=, got %d" % (B, Ft))
-        fr = torch.zeros(B, dtype=torch.long, device=dev) if Ft == 1 else torch.arange(B, device=dev)
-    else:
-        fr = frame.long().clamp(0, Ft - 1)
+    fr = _gn_torch.frames_of(B, Ft, frame, "depth must hold 1 or B = %d planes", dev)
     tau = float(torch.tensor(tau_mm, dtype=torch.float32))
-    lam = float(torch.tensor(damping, dtype=torch.float32))
     d_all = depth[fr]                                                                       # [B,H,W]
     zf = zbuf.float()
     cand = (zf > 0) & torch.isfinite(zf) & (d_all > 0) & torch.isfinite(d_all) & (face >= 0) & (face < F)
@@ -108,48 +74,21 @@ def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
     cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
     count = torch.bincount(bi, minlength=B)
-    rms = torch.sqrt(cost / count.to(f64))                                                  # (0 / 0: NaN)
-    few = count < MIN_COUNT
-    _, pd = _cholesky6(JtJ, PIVOT_TOL)
-    status = torch.where(few, 1, torch.where(pd, 0, 3))
-    out_pose = pose32.clone()
-    if not evaluate_only:
-        Dm = JtJ + lam * torch.diag_embed(torch.diagonal(JtJ, dim1=1, dim2=2))
-        L, ok = _cholesky6(Dm, 0.0)
-        ok = ok & pd & ~few
-        eye = torch.eye(6, dtype=f64, device=dev)[None]
-        L = torch.where(ok[:, None, None], L, eye)
-        y = torch.linalg.solve_triangular(L, -Jtr[:, :, None], upper=False)
-        delta = torch.linalg.solve_triangular(L.transpose(1, 2), y, upper=True)[:, :, 0]
-        Pn = _exp_so3(delta[:, :3]) @ pose32.to(f64)
-        Pn[:, :, 3] = Pn[:, :, 3] + delta[:, 3:]
-        c1 = Pn[:, :, 0] / torch.linalg.norm(Pn[:, :, 0], dim=-1, keepdim=True)
-        c2 = Pn[:, :, 1] - c1 * (c1 * Pn[:, :, 1]).sum(-1, keepdim=True)
-        c2 = c2 / torch.linalg.norm(c2, dim=-1, keepdim=True)
-        Pn = torch.stack([c1, c2, torch.cross(c1, c2, dim=-1), Pn[:, :, 3]], -1)
-        new32 = Pn.float()
-        ok = ok & torch.isfinite(new32).reshape(B, -1).all(-1)
-        status = torch.where(few, 1, torch.where(ok, 0, 3))
-        out_pose = torch.where(ok[:, None, None], new32, pose32)
-    return dict(pose=out_pose, inliers=count.to(torch.int32), rms=rms.float(), status=status.to(torch.int32))
+    return _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
 
 
-class DepthRefiner:
+class DepthRefiner(_MeshRefiner):
     """Depth ICP for batches of poses of one mesh at H x W with the mesh on the device and a workspace per batch size.
 
     ``tau_mm`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 20.0), ``iters`` (Gauss-Newton steps, 5), ``damping``
     (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (pixels within tau of the
     measurement), rms [B] (mm, point-to-plane), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was not
     positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+    _new_workspace = staticmethod(ops.depth_icp_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6):
-        self.H, self.W, self.device = int(H), int(W), torch.device(device)
-        if self.device.type != "cuda":
-            raise ops._lib.TexposeLibraryError("DepthRefiner runs the HIP kernels: a GPU device is needed (step_torch alone has a CPU route)")
-        self.verts = torch.as_tensor(verts).to(device=self.device, dtype=torch.float32).contiguous()
-        self.faces = torch.as_tensor(faces).to(device=self.device, dtype=torch.int32).contiguous()
+        super().__init__(verts, faces, H, W, device)
         self.tau_mm, self.iters, self.damping = tau_mm, int(iters), float(damping)
-        self._workspaces: Dict[int, Tensor] = {}
 
     def refine(self, pose: Tensor, intr: Tensor, depth: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
         """pose [B,3,4], intr [B,3,3] or [3,3], depth [Ft,H,W] (mm; 0: no measurement), frame [B] int32 (the plane of each pose; without
@@ -157,8 +96,5 @@ class DepthRefiner:
         depth = depth if depth.dim() == 3 else depth[None]
         if tuple(depth.shape[1:]) != (self.H, self.W):
             raise ValueError("DepthRefiner.refine: depth planes of %d x %d expected, got %s" % (self.H, self.W, tuple(depth.shape)))
-        B = pose.shape[0]
-        if B not in self._workspaces:
-            self._workspaces[B] = ops.depth_icp_workspace(B, self.H, self.W, self.device)
         return AttrDict(ops.depth_icp(self.verts, self.faces, pose, intr, depth, tau_mm=self.tau_mm, iters=self.iters, damping=self.damping,
-                                      frame=frame, mask=mask, workspace=self._workspaces[B]))
+                                      frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))

@@ -278,29 +278,69 @@ def pnp_ransac(xy: Tensor, xyz: Tensor, count: Tensor, intr: Tensor, *, T: int =
     return res
 
 
-# ------------------------------------------------------------------------------------------ K29
-def depth_icp_workspace(B: int, H: int, W: int, device) -> Tensor:
-    """A workspace for depth_icp_step / depth_icp at B images of H x W (tp_depth_icp_workspace_bytes); needs no clearing."""
-    return _workspace_arg("depth_icp", None, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), device)
-
-
-def _depth_icp_planes(op: str, depth: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
-    depth = _f32(depth.detach(), "depth")
-    if depth.dim() == 2:
-        depth = depth[None]
-    if depth.dim() != 3 or tuple(depth.shape[1:]) != (H, W) or depth.shape[0] == 0:
-        raise ValueError("%s: depth [Ft,H=%d,W=%d] expected, got %s" % (op, H, W, tuple(depth.shape)))
-    Ft = depth.shape[0]
+# ------------------------------------------------------------------------------------------ K29, K30: what the two refiners share
+def _frame_planes(op: str, name: str, planes: Tensor, trailing_shape: tuple, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int,
+                  W: int, like: Tensor):
+    """The measured planes ``name`` [Ft,H,W] + trailing_shape (one plane: Ft = 1), the frame map and the mask [Ft,H,W] of a step ->
+    (planes, frame, mask, Ft)."""
+    planes = _f32(planes.detach(), name)
+    if planes.dim() == 2 + len(trailing_shape):
+        planes = planes[None]
+    if planes.dim() != 3 + len(trailing_shape) or tuple(planes.shape[1:]) != (H, W) + trailing_shape or planes.shape[0] == 0:
+        layout = "[Ft,H=%d,W=%d,3] (channels last)" % (H, W) if trailing_shape else "[Ft,H=%d,W=%d]" % (H, W)
+        raise ValueError("%s: %s %s expected, got %s" % (op, name, layout, tuple(planes.shape)))
+    Ft = planes.shape[0]
     frame = _lengths(op, frame, "frame", B, like)
     if frame is None and Ft not in (1, B):
-        raise ValueError("%s: depth must hold 1 or B = %d planes without frame=, got %d" % (op, B, Ft))
+        raise ValueError("%s: %s must hold 1 or B = %d %s without frame=, got %d" % (op, name, B, "photographs" if trailing_shape else "planes", Ft))
     if mask is not None:
         if torch.is_tensor(mask) and mask.dtype == torch.bool:
             mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
         if torch.is_tensor(mask) and mask.dim() == 2:
             mask = mask[None]
         mask = _want_gpu(op, mask, "mask", torch.uint8, (Ft, H, W))
-    return depth, frame, mask, Ft
+    return planes, frame, mask, Ft
+
+
+def _gn_step_outputs(op: str, a, out: Optional[Dict[str, Tensor]], workspace: Optional[Tensor], B: int, dev, workspace_bytes: int) -> Dict[str, Tensor]:
+    """The four outputs of a step (fresh, or those of ``out``) and its workspace, entered into the args struct ``a``."""
+    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+                             "status": (torch.int32, (B,))}, dev, partial=True)
+    workspace = _workspace_arg(op, workspace, workspace_bytes, dev, align=16)
+    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
+                                                           res["status"].data_ptr(), workspace.data_ptr())
+    return res
+
+
+def _tau_schedule(op: str, tau, tau_name: str, iters: int):
+    """A loop's thresholds, checked before anything else of the call: one value or ``iters`` + 1 host values -> iters + 1 floats."""
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
+    taus = [float(tau)] * (iters + 1) if isinstance(tau, (int, float)) else [float(t) for t in tau]
+    if len(taus) != iters + 1:
+        raise ValueError("%s: %s must be one value or iters + 1 = %d values, got %d" % (op, tau_name, iters + 1, len(taus)))
+    return taus
+
+
+def _refine_loop(pose: Tensor, taus, raster, step) -> Dict[str, Tensor]:
+    """One pass per threshold of ``raster(pose)`` and ``step(planes, pose, tau, evaluate_only)`` from ``pose`` on, the last
+    evaluate-only -> the last pass's pose, inliers and rms, the status of the last step taken (of the evaluation where there is no
+    step) and inliers0 / rms0 of the first pass."""
+    iters = len(taus) - 1
+    res, first, status = None, None, None
+    for it, t in enumerate(taus):
+        res = step(raster(pose), pose, t, it == iters)
+        first = res if first is None else first
+        status = res["status"] if it < iters or status is None else status
+        pose = res["pose"]
+    return dict(pose=res["pose"], inliers=res["inliers"], rms=res["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"])
+
+
+# ------------------------------------------------------------------------------------------ K29
+def depth_icp_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for depth_icp_step / depth_icp at B images of H x W (tp_depth_icp_workspace_bytes); needs no clearing."""
+    return _workspace_arg("depth_icp", None, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), device)
 
 
 @_on_tensor_device
@@ -327,18 +367,13 @@ def depth_icp_step(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pos
     H, W = zbuf.shape[1:]
     face = _want_gpu(op, face, "face", torch.int32, (B, H, W))
     intr = _intr_per_view(op, intr, B)
-    depth, frame, mask, Ft = _depth_icp_planes(op, depth, frame, mask, B, H, W, zbuf)
-    dev = zbuf.device
-    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
-                             "status": (torch.int32, (B,))}, dev, partial=True)
-    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), dev, align=16)
+    depth, frame, mask, Ft = _frame_planes(op, "depth", depth, (), frame, mask, B, H, W, zbuf)
     a = _lib.DepthIcpArgs()
+    res = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)))
     a.verts, a.faces, a.zbuf, a.face, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), zbuf.data_ptr(), face.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.depth, a.frame, a.mask = depth.data_ptr(), _ptr(frame), _ptr(mask)
     a.V, a.F, a.B, a.Ft, a.H, a.W = verts.shape[0], faces.shape[0], B, Ft, H, W
     a.tau_mm, a.damping, a.evaluate_only = float(tau_mm), float(damping), int(bool(evaluate_only))
-    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
-                                                           res["status"].data_ptr(), workspace.data_ptr())
     _call("tp_depth_icp_step", a)         # (tau_mm, damping out of range, out['pose'] overlapping pose: the library's error)
     return res
 
@@ -356,12 +391,7 @@ def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: T
     'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the rasteriser's,
     bit-identical from run to run, safe under torch.cuda.graph."""
     op = "depth_icp"
-    iters = int(iters)
-    if iters < 0:
-        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
-    taus = [float(tau_mm)] * (iters + 1) if isinstance(tau_mm, (int, float)) else [float(t) for t in tau_mm]
-    if len(taus) != iters + 1:
-        raise ValueError("%s: tau_mm must be one value or iters + 1 = %d values, got %d" % (op, iters + 1, len(taus)))
+    taus = _tau_schedule(op, tau_mm, "tau_mm", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
     B = pose.shape[0]
     faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
@@ -372,43 +402,19 @@ def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: T
         raise ValueError("%s: depth [Ft,H,W] expected, got %s" % (op, tuple(depth.shape)))
     H, W = depth.shape[1:]
     intr = _intr_per_view(op, intr, B)
-    depth, frame, mask, _ = _depth_icp_planes(op, depth, frame, mask, B, H, W, pose)
+    depth, frame, mask, _ = _frame_planes(op, "depth", depth, (), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    res, first, status = None, None, None
-    for it, tau in enumerate(taus):
-        r = mesh_raster(verts, faces, pose, intr, H=H, W=W, face_ids=True, normals=False)
-        res = depth_icp_step(verts, faces, r["zbuf"], r["face"], pose, intr, depth, tau_mm=tau, damping=damping, frame=frame, mask=mask,
-                             evaluate_only=it == iters, workspace=workspace)
-        first = res if first is None else first
-        status = res["status"] if it < iters or status is None else status
-        pose = res["pose"]
-    return dict(pose=res["pose"], inliers=res["inliers"], rms=res["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"])
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=True, normals=False)
+    step = lambda r, P, t, last: depth_icp_step(verts, faces, r["zbuf"], r["face"], P, intr, depth, tau_mm=t, damping=damping,
+                                                frame=frame, mask=mask, evaluate_only=last, workspace=workspace)
+    return _refine_loop(pose, taus, raster, step)
 
 
 # ------------------------------------------------------------------------------------------ K30
 def photo_align_workspace(B: int, H: int, W: int, device) -> Tensor:
     """A workspace for photo_align_step / photo_align at B images of H x W (tp_photo_align_workspace_bytes); needs no clearing."""
     return _workspace_arg("photo_align", None, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), device)
-
-
-def _photo_align_planes(op: str, image: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
-    image = _f32(image.detach(), "image")
-    if image.dim() == 3:
-        image = image[None]
-    if image.dim() != 4 or tuple(image.shape[1:]) != (H, W, 3) or image.shape[0] == 0:
-        raise ValueError("%s: image [Ft,H=%d,W=%d,3] (channels last) expected, got %s" % (op, H, W, tuple(image.shape)))
-    Ft = image.shape[0]
-    frame = _lengths(op, frame, "frame", B, like)
-    if frame is None and Ft not in (1, B):
-        raise ValueError("%s: image must hold 1 or B = %d photographs without frame=, got %d" % (op, B, Ft))
-    if mask is not None:
-        if torch.is_tensor(mask) and mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
-        if torch.is_tensor(mask) and mask.dim() == 2:
-            mask = mask[None]
-        mask = _want_gpu(op, mask, "mask", torch.uint8, (Ft, H, W))
-    return image, frame, mask, Ft
 
 
 @_on_tensor_device
@@ -432,18 +438,13 @@ def photo_align_step(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, imag
     H, W = zbuf.shape[1:]
     rgb = _want_gpu(op, rgb, "rgb", torch.float32, (B, H, W, 3))
     intr = _intr_per_view(op, intr, B)
-    image, frame, mask, Ft = _photo_align_planes(op, image, frame, mask, B, H, W, zbuf)
-    dev = zbuf.device
-    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
-                             "status": (torch.int32, (B,))}, dev, partial=True)
-    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), dev, align=16)
+    image, frame, mask, Ft = _frame_planes(op, "image", image, (3,), frame, mask, B, H, W, zbuf)
     a = _lib.PhotoAlignArgs()
+    res = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)))
     a.zbuf, a.rgb, a.pose, a.intr = zbuf.data_ptr(), rgb.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.image, a.frame, a.mask = image.data_ptr(), _ptr(frame), _ptr(mask)
     a.B, a.Ft, a.H, a.W = B, Ft, H, W
     a.tau, a.damping, a.evaluate_only = float(tau), float(damping), int(bool(evaluate_only))
-    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
-                                                           res["status"].data_ptr(), workspace.data_ptr())
     _call("tp_photo_align_step", a)       # (tau, damping out of range, out['pose'] overlapping pose: the library's error)
     return res
 
@@ -462,12 +463,7 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
     rasteriser's, bit-identical from run to run, safe under torch.cuda.graph."""
     op = "photo_align"
-    iters = int(iters)
-    if iters < 0:
-        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
-    taus = [float(tau)] * (iters + 1) if isinstance(tau, (int, float)) else [float(t) for t in tau]
-    if len(taus) != iters + 1:
-        raise ValueError("%s: tau must be one value or iters + 1 = %d values, got %d" % (op, iters + 1, len(taus)))
+    taus = _tau_schedule(op, tau, "tau", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
     B = pose.shape[0]
     faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
@@ -479,15 +475,10 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
         raise ValueError("%s: image [Ft,H,W,3] (channels last) expected, got %s" % (op, tuple(image.shape)))
     H, W = image.shape[1:3]
     intr = _intr_per_view(op, intr, B)
-    image, frame, mask, _ = _photo_align_planes(op, image, frame, mask, B, H, W, pose)
+    image, frame, mask, _ = _frame_planes(op, "image", image, (3,), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    res, first, status = None, None, None
-    for it, t in enumerate(taus):
-        r = mesh_raster(verts, faces, pose, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False)
-        res = photo_align_step(r["zbuf"], r["rgb"], pose, intr, image, tau=t, damping=damping, frame=frame, mask=mask,
-                               evaluate_only=it == iters, workspace=workspace)
-        first = res if first is None else first
-        status = res["status"] if it < iters or status is None else status
-        pose = res["pose"]
-    return dict(pose=res["pose"], inliers=res["inliers"], rms=res["rms"], status=status, inliers0=first["inliers"], rms0=first["rms"])
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False)
+    step = lambda r, P, t, last: photo_align_step(r["zbuf"], r["rgb"], P, intr, image, tau=t, damping=damping, frame=frame,
+                                                  mask=mask, evaluate_only=last, workspace=workspace)
+    return _refine_loop(pose, taus, raster, step)

@@ -13,8 +13,8 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
-from .icp import MIN_COUNT, PIVOT_TOL, _cholesky6, _exp_so3
+from . import _gn_torch, ops
+from ._refiner import _MeshRefiner
 from .options import AttrDict
 
 Tensor = torch.Tensor
@@ -36,14 +36,8 @@ def step_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Ten
     if image.dim() == 3:
         image = image[None]
     Ft = image.shape[0]
-    if frame is None:
-        if Ft not in (1, B):
-            raise ValueError("step_torch: image must hold 1 or B = %d photographs without frame=, got %d" % (B, Ft))
-        fr = torch.zeros(B, dtype=torch.long, device=dev) if Ft == 1 else torch.arange(B, device=dev)
-    else:
-        fr = frame.long().clamp(0, Ft - 1)
+    fr = _gn_torch.frames_of(B, Ft, frame, "image must hold 1 or B = %d photographs", dev)
     tau = float(torch.tensor(tau, dtype=torch.float32))
-    lam = float(torch.tensor(damping, dtype=torch.float32))
     zf = zbuf.float()
     cand = (zf > 0) & torch.isfinite(zf)
     cand[:, :1], cand[:, H - 1:], cand[:, :, :1], cand[:, :, W - 1:] = False, False, False, False
@@ -74,34 +68,10 @@ def step_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Ten
     Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, b3, J * r[:, None])
     cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, b3, r * r)
     count = torch.bincount(bi, minlength=B)
-    rms = torch.sqrt(cost / count.to(f64))                                                  # (0 / 0: NaN)
-    few = count < MIN_COUNT
-    _, pd = _cholesky6(JtJ, PIVOT_TOL)
-    status = torch.where(few, 1, torch.where(pd, 0, 3))
-    out_pose = pose32.clone()
-    if not evaluate_only:
-        Dm = JtJ + lam * torch.diag_embed(torch.diagonal(JtJ, dim1=1, dim2=2))
-        L, ok = _cholesky6(Dm, 0.0)
-        ok = ok & pd & ~few
-        eye = torch.eye(6, dtype=f64, device=dev)[None]
-        L = torch.where(ok[:, None, None], L, eye)
-        y = torch.linalg.solve_triangular(L, -Jtr[:, :, None], upper=False)
-        delta = torch.linalg.solve_triangular(L.transpose(1, 2), y, upper=True)[:, :, 0]
-        delta = torch.where(ok[:, None], delta, torch.zeros_like(delta))
-        Pn = _exp_so3(delta[:, :3]) @ pose32.to(f64)
-        Pn[:, :, 3] = Pn[:, :, 3] + delta[:, 3:]
-        c1 = Pn[:, :, 0] / torch.linalg.norm(Pn[:, :, 0], dim=-1, keepdim=True)
-        c2 = Pn[:, :, 1] - c1 * (c1 * Pn[:, :, 1]).sum(-1, keepdim=True)
-        c2 = c2 / torch.linalg.norm(c2, dim=-1, keepdim=True)
-        Pn = torch.stack([c1, c2, torch.cross(c1, c2, dim=-1), Pn[:, :, 3]], -1)
-        new32 = Pn.float()
-        ok = ok & torch.isfinite(new32).reshape(B, -1).all(-1)
-        status = torch.where(few, 1, torch.where(ok, 0, 3))
-        out_pose = torch.where(ok[:, None, None], new32, pose32)
-    return dict(pose=out_pose, inliers=count.to(torch.int32), rms=rms.float(), status=status.to(torch.int32))
+    return _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
 
 
-class PhotoRefiner:
+class PhotoRefiner(_MeshRefiner):
     """Photometric alignment for batches of poses of one vertex-coloured mesh at H x W with the mesh on the device and a workspace per
     batch size.
 
@@ -109,19 +79,15 @@ class PhotoRefiner:
     ``damping`` (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (interior covered pixels
     within tau of the photograph), rms [B] (colour units), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was
     not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+    _new_workspace = staticmethod(ops.photo_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, vcolor: Tensor, H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
                  damping: float = 1e-6):
-        self.H, self.W, self.device = int(H), int(W), torch.device(device)
-        if self.device.type != "cuda":
-            raise ops._lib.TexposeLibraryError("PhotoRefiner runs the HIP kernels: a GPU device is needed (step_torch alone has a CPU route)")
-        self.verts = torch.as_tensor(verts).to(device=self.device, dtype=torch.float32).contiguous()
-        self.faces = torch.as_tensor(faces).to(device=self.device, dtype=torch.int32).contiguous()
+        super().__init__(verts, faces, H, W, device)
         self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(self.vcolor.shape) != tuple(self.verts.shape):
             raise ValueError("PhotoRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
         self.tau, self.iters, self.damping = tau, int(iters), float(damping)
-        self._workspaces: Dict[int, Tensor] = {}
 
     def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
         """pose [B,3,4], intr [B,3,3] or [3,3], image [Ft,H,W,3] (channels last, the vertex colours' units), frame [B] int32 (the
@@ -129,8 +95,5 @@ class PhotoRefiner:
         image = image if image.dim() == 4 else image[None]
         if tuple(image.shape[1:]) != (self.H, self.W, 3):
             raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
-        B = pose.shape[0]
-        if B not in self._workspaces:
-            self._workspaces[B] = ops.photo_align_workspace(B, self.H, self.W, self.device)
         return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
-                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspaces[B]))
+                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))
