@@ -1345,6 +1345,89 @@ typedef struct tp_photo_align_args {
 size_t tp_photo_align_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
 int tp_photo_align_step(const tp_photo_align_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K31a the exact signed Euclidean distance field of F masks (texpose_amd/silhouette.py; restated in tests/silhouette_ref.py; the
+ *      project's own kernel, no reference code).  mask [F,H,W] uint8, any non-zero value is "set"; sdf [F,H,W]
+ *      float32.  For pixel p of a plane, d2_set(p) = min |p - q|^2 over the set pixels q of that plane and d2_clear(p) the same over
+ *      its clear pixels, both integers; where a plane has no such pixel the value is the sentinel H^2 + W^2, larger than any real
+ *      squared distance.  Pixels outside the image do not exist: they are neither set nor clear.
+ *        sdf = mask == 0 ? sqrtf((float)d2_set) - 0.5f : -(sqrtf((float)d2_clear) - 0.5f)
+ *      (sqrtf correctly rounded): positive outside the mask, negative inside, the zero level half-way between a set pixel and its
+ *      clear neighbour; always finite.  Integer minima do not depend on the order they are taken in: the field is a function of the
+ *      mask alone.  Two launches: a sweep down and up every column (the vertical distances to the nearest set and the nearest clear
+ *      pixel, 16 bits each, into the workspace), then one workgroup per row, which holds the row's pairs in LDS and takes
+ *      min over j' of (j - j')^2 + g[j']^2 for each of its pixels, outwards from j until (j - j')^2 reaches the best so far.
+ *      Non-positive sizes, H or W > 8192, F * H * W >= 2^31, null pointers, a workspace that is not 16-byte aligned and an sdf that
+ *      overlaps mask are refused (-1, tp_last_error) before anything is launched.  No atomics, no allocation, no host
+ *      synchronisation.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+size_t tp_mask_sdf_workspace_bytes(int F, int H, int W);   /* 4 * F * H * W, rounded up to 16; 0 for non-positive sizes; needs no clearing */
+int tp_mask_sdf(const uint8_t* mask, float* sdf, int F, int H, int W, void* workspace, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K31b one step of batched silhouette alignment: B poses refined against the outline of a mask (texpose_amd/silhouette.py; restated
+ *      in tests/silhouette_ref.py; the project's own step, no reference code).  zbuf is K19's depth of the mesh
+ *      rendered at pose, sdf the signed distance field of the measured mask (tp_mask_sdf's, or any field in pixels that is negative
+ *      inside); the call takes one damped Gauss-Newton step of the update x' = x + w x x + v in the camera frame (parameters
+ *      (w, v), as tp_photo_align_step): a surface point on the rendered rim moves in the image, and the field says how far from the
+ *      measured outline it would land.  A pixel is COVERED iff its z = zbuf[b,i,j] is > 0 and finite.  Per pixel (row i, column j)
+ *      of image b, with K = intr[b] (fx = K_00, fy = K_11, cx = K_02, cy = K_12) and the plane fr = frame ? frame[b] CLAMPED into
+ *      [0, Ft) : (Ft == 1 ? 0 : b), everything in fp64 from the fp32 inputs, evaluated as written (no contraction):
+ *        1. skipped unless 1 <= i <= H - 2 and 1 <= j <= W - 2 (an image with H < 3 or W < 3 keeps nothing) and the pixel is covered
+ *        2. skipped unless it is a RIM pixel: at least one of its four neighbours (i,j-1), (i,j+1), (i-1,j), (i+1,j) is not covered
+ *           (a NaN neighbour is not covered)
+ *        3. skipped where mask is given and mask[fr,i,j] == 0
+ *        4. d = sdf[fr,i,j] and the four neighbours sdf[fr,i,j-1], sdf[fr,i,j+1], sdf[fr,i-1,j], sdf[fr,i+1,j];  skipped unless all
+ *           five are finite
+ *        5. r = d + 0.5 (a rendered rim pixel that sits on the mask's own rim reads 0);  kept iff |r| <= tau_px
+ *        6. gx = 0.5 (sdf[fr,i,j+1] - sdf[fr,i,j-1]),  gy = 0.5 (sdf[fr,i+1,j] - sdf[fr,i-1,j]),
+ *           rx = ((j + 0.5) - cx) / fx,  ry = ((i + 0.5) - cy) / fy,  P = (z rx, z ry, z),
+ *           a = (gx fx / z,  gy fy / z,  -((gx fx) rx + (gy fy) ry) / z),  J = [P x a, a]
+ *      and the 29 sums of tp_pnp_refine over the rows (J, r) of the kept pixels: the 21 upper-triangle entries of J^T J (row-major),
+ *      the 6 of J^T r, sum r^2 and the count.  A thread owns four consecutive flat pixels (ascending), a workgroup 1024; butterfly
+ *      sums inside a wave, the four waves in ascending order, one record per workgroup, the records in ascending order: no atomics,
+ *      the outputs are a function of the inputs alone, bit-identical from run to run and under graph replay.  Per image:
+ *        inliers = count, the kept rim pixels;  rms = sqrt(sum r^2 / count) in pixels (NaN at count 0): both describe `pose`
+ *        status  = 1 where count < 6; else 3 where J^T J is NOT POSITIVE DEFINITE by tp_pnp_refine's pivot rule (a Cholesky pivot
+ *                  that is not finite or <= 1e-10 x its diagonal entry), or, without evaluate_only, where the damped matrix does
+ *                  not factor or the stepped pose is not finite in fp32; else 0
+ *        pose_out = (status == 0 and not evaluate_only): (J^T J + damping diag(J^T J)) delta = -J^T r solved by Cholesky,
+ *                  R <- exp(w) R, t <- exp(w) t + v with Rodrigues' formula, Gram-Schmidt on R's first two columns (the third
+ *                  their cross product), rounded to fp32;  otherwise pose, bit for bit (pose_out may be NULL with evaluate_only)
+ *        inter   = the pixels (all H * W, the border included) that are covered AND have sdf[fr,i,j] < 0;  uni = those where either
+ *                  holds.  A sdf value that is not finite counts as outside; mask is ignored.  Exact integer counts (ballots and
+ *                  popcounts, added as integers), the same from run to run.  They describe `pose`: its IoU with the measured mask
+ *                  is inter / uni.
+ *      Status is an output only: a failed step passes its pose through, so a loop over steps needs no state.  Non-positive sizes,
+ *      B > 65535, H * W >= 2^31, without frame an Ft that is neither 1 nor B, a tau_px that is not finite and positive, a damping
+ *      that is not finite and >= 0, null pointers, a workspace that is not 16-byte aligned and pose_out == pose are refused (-1,
+ *      tp_last_error) before anything is launched.  No input value (NaN, Inf, a frame index out of range, huge poses) causes an
+ *      access out of bounds: frame is the only index read from memory, and it is clamped; the interior test keeps every neighbour
+ *      read inside the plane.  Three launches.  No allocation, no host synchronisation; outputs and workspace must not overlap
+ *      inputs.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_silhouette_align_args {
+  const float* zbuf;         /* [B,H,W] K19's depth of the mesh at pose: mm, <= 0 or NaN: background */
+  const float* pose;         /* [B,3,4] the pose zbuf was rendered at */
+  const float* intr;         /* [B,3,3] */
+  const float* sdf;          /* [Ft,H,W] signed distance to the measured outline in pixels, negative inside (tp_mask_sdf) */
+  const int32_t* frame;      /* [B] index into sdf (and mask), or NULL: b when Ft == B, 0 when Ft == 1 */
+  const uint8_t* mask;       /* [Ft,H,W] or NULL; 0: the pixel gives no row */
+  int B, Ft, H, W;
+  float tau_px;              /* finite, > 0: the largest distance |d + 0.5| between a kept rim pixel and the measured outline */
+  float damping;             /* finite, >= 0: relative Levenberg damping of the diagonal */
+  int evaluate_only;         /* non-zero: inliers, rms, status, inter and uni of pose; no step */
+  float* pose_out;           /* [B,3,4] out; may be NULL with evaluate_only; must not be pose */
+  int32_t* inliers;          /* [B] out */
+  float* rms;                /* [B] out, pixels */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels, 3 not positive definite */
+  int32_t* inter;            /* [B] out: covered pixels inside the measured mask */
+  int32_t* uni;              /* [B] out: pixels covered or inside the measured mask */
+  void* workspace;           /* tp_silhouette_align_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_silhouette_align_args;
+size_t tp_silhouette_align_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
+int tp_silhouette_align_step(const tp_silhouette_align_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-"""K24-K26, K28-K30: nearest neighbours, the pose errors, VSD, PnP-RANSAC, the depth ICP and the photometric alignment."""
+"""K24-K26, K28-K31: nearest neighbours, the pose errors, VSD, PnP-RANSAC, the depth ICP, the photometric alignment, the masks' distance
+field and the silhouette alignment."""
 from typing import Dict, Optional
 
 import torch
@@ -9,7 +10,8 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _lengths, _on_
 
 __all__ = ["NN1_MODES", "nn1", "pose_errors", "vsd", "PNP_MAX_HYP", "PNP_MAX_ITERS", "pnp_workspace", "_pnp_common", "corr_from_nocs",
            "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac", "depth_icp_workspace", "depth_icp_step",
-           "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS", "photo_align"]
+           "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS", "photo_align", "mask_sdf_workspace", "mask_sdf",
+           "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align"]
 
 # ------------------------------------------------------------------------------------------ K24, K25
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
@@ -482,3 +484,118 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     step = lambda r, P, t, last: photo_align_step(r["zbuf"], r["rgb"], P, intr, image, tau=t, damping=damping, frame=frame,
                                                   mask=mask, evaluate_only=last, workspace=workspace)
     return _refine_loop(pose, taus, raster, step)
+
+
+# ------------------------------------------------------------------------------------------ K31
+def mask_sdf_workspace(F: int, H: int, W: int, device) -> Tensor:
+    """A workspace for mask_sdf at F masks of H x W (tp_mask_sdf_workspace_bytes); needs no clearing."""
+    return _workspace_arg("mask_sdf", None, int(_lib.load().tp_mask_sdf_workspace_bytes(F, H, W)), device)
+
+
+@_on_tensor_device
+def mask_sdf(mask: Tensor, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """The exact signed Euclidean distance field of F masks (tp_mask_sdf; the rules are in the header): mask [F,H,W] (or one [H,W])
+    uint8 or bool, non-zero: set -> sdf float32 of mask's shape, in pixels: sqrt(d2_set) - 0.5 on a clear pixel, -(sqrt(d2_clear) -
+    0.5) on a set one, with the squared distances to the nearest set / clear pixel of the plane (H^2 + W^2 where it has none).
+    ``out``: the tensor to write into; ``workspace``: mask_sdf_workspace(F, H, W).  H, W <= 8192.  Two launches, no atomics, a function
+    of the mask alone, safe under torch.cuda.graph."""
+    op = "mask_sdf"
+    if torch.is_tensor(mask) and not mask.is_cuda:
+        raise _lib.TexposeLibraryError("mask must live on the GPU (texpose_amd has no CPU path)")
+    if torch.is_tensor(mask) and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    mask = _want_gpu(op, mask, "mask", torch.uint8, None)
+    if mask.dim() not in (2, 3) or mask.numel() == 0:
+        raise ValueError("%s: mask [F,H,W] or [H,W] expected, got %s" % (op, tuple(mask.shape)))
+    F, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
+    sdf = torch.empty(mask.shape, device=mask.device) if out is None else _want_gpu(op, out, "out", torch.float32, tuple(mask.shape))
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_mask_sdf_workspace_bytes(F, H, W)), mask.device, align=16)
+    _call("tp_mask_sdf", mask.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())          # (H or W > 8192: the library's error)
+    return sdf
+
+
+def silhouette_align_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for silhouette_align_step / silhouette_align at B images of H x W (tp_silhouette_align_workspace_bytes); needs no
+    clearing."""
+    return _workspace_arg("silhouette_align", None, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)), device)
+
+
+@_on_tensor_device
+def silhouette_align_step(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px: float, damping: float = 1e-6,
+                          frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                          workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of silhouette alignment for B poses (tp_silhouette_align_step; the rules are in the header): zbuf [B,H,W]
+    (mesh_raster's depth of the mesh at ``pose``; taken as it is), pose [B,3,4], intr [B,3,3] or one [3,3], sdf [Ft,H,W] (mask_sdf's
+    field of the measured masks: pixels, negative inside; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask [Ft,H,W] uint8 or bool
+    (0: the pixel gives no row) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a
+    non-zero status), 'inliers' [B] int32 and 'rms' [B] (pixels) of ``pose`` over the interior rim pixels of the rendering within
+    ``tau_px`` of the measured outline, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite), 'inter' and
+    'uni' [B] int32 (the pixels covered and inside the measured mask, and those with either: IoU = inter / uni).  ``workspace``:
+    silhouette_align_workspace(B, H, W); ``out``: any of the six tensors to write into (out['pose'] must not be ``pose``).  Three
+    launches, no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "silhouette_align_step"
+    pose = _poses(op, pose, "pose")
+    B = pose.shape[0]
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B=%d,H,W] expected, got %s" % (op, B, tuple(zbuf.shape)))
+    H, W = zbuf.shape[1:]
+    intr = _intr_per_view(op, intr, B)
+    sdf, frame, mask, Ft = _frame_planes(op, "sdf", sdf, (), frame, mask, B, H, W, zbuf)
+    a = _lib.SilhouetteAlignArgs()
+    counts = _outputs(op, None if out is None else {k: v for k, v in out.items() if k in ("inter", "uni")},
+                      {"inter": (torch.int32, (B,)), "uni": (torch.int32, (B,))}, zbuf.device, partial=True)
+    res = _gn_step_outputs(op, a, None if out is None else {k: v for k, v in out.items() if k not in ("inter", "uni")}, workspace, B,
+                           zbuf.device, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)))
+    res.update(counts)
+    a.zbuf, a.pose, a.intr, a.sdf, a.frame, a.mask = zbuf.data_ptr(), pose.data_ptr(), intr.data_ptr(), sdf.data_ptr(), _ptr(frame), _ptr(mask)
+    a.B, a.Ft, a.H, a.W = B, Ft, H, W
+    a.tau_px, a.damping, a.evaluate_only = float(tau_px), float(damping), int(bool(evaluate_only))
+    a.inter, a.uni = res["inter"].data_ptr(), res["uni"].data_ptr()
+    _call("tp_silhouette_align_step", a)  # (tau_px, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+SILHOUETTE_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0", "iou", "iou0")
+
+
+@_on_tensor_device
+def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px=4.0, iters: int = 10,
+                     damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                     workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against the outlines of measured masks (the rules are in the header, K31): ``iters`` + 1 passes of
+    mesh_raster at the current poses (depth alone, H x W = sdf's) followed by silhouette_align_step, the last with evaluate_only.
+    ``sdf`` [Ft,H,W]: mask_sdf of the measured masks.  ``tau_px``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule
+    (the last is the final evaluation's).  -> 'pose' [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (pixels), 'status' [B] int32 of the
+    last step taken (of the evaluation where iters = 0), 'inliers0' / 'rms0' of the start pose and 'iou' / 'iou0' [B] float32, the
+    intersection over union of the rendering's coverage and the measured mask at the last and at the start pose (NaN where both are
+    empty).  A step that fails passes its pose on.  It closes the OUTLINE: a pose parameter the outline does not see (a rotation about
+    a symmetry axis, depth at a small radius) stays where it was, and a measured mask cut by an occluder pulls the rim to the cut.
+    3 (iters + 1) launches besides the rasteriser's, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "silhouette_align"
+    taus = _tau_schedule(op, tau_px, "tau_px", iters)
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    sdf = _f32(sdf.detach(), "sdf")
+    if sdf.dim() == 2:
+        sdf = sdf[None]
+    if sdf.dim() != 3 or sdf.numel() == 0:
+        raise ValueError("%s: sdf [Ft,H,W] expected, got %s" % (op, tuple(sdf.shape)))
+    H, W = sdf.shape[1:]
+    intr = _intr_per_view(op, intr, B)
+    sdf, frame, mask, _ = _frame_planes(op, "sdf", sdf, (), frame, mask, B, H, W, pose)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)), pose.device, align=16)
+    from .scene import mesh_raster
+    passes = []
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=False, normals=False)
+
+    def step(r, P, t, last):
+        passes.append(silhouette_align_step(r["zbuf"], P, intr, sdf, tau_px=t, damping=damping, frame=frame, mask=mask, evaluate_only=last,
+                                            workspace=workspace))
+        return passes[-1]
+
+    res = _refine_loop(pose, taus, raster, step)
+    iou = lambda r: r["inter"].float() / r["uni"].float()
+    res.update(iou=iou(passes[-1]), iou0=iou(passes[0]))
+    return res

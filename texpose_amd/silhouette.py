@@ -1,0 +1,133 @@
+"""Pose refinement against a mask: the exact distance field of the mask and batched silhouette alignment on the device (K31; DESIGN
+section 21).
+
+The refiner for where there is neither a depth sensor (texpose_amd.icp) nor a coloured mesh (texpose_amd.photo_align): a textureless
+mesh, a pose estimate and the object's measured mask.  ``ops.mask_sdf`` turns the masks into their exact signed Euclidean distance
+fields (pixels, negative inside); the mesh is rendered at the current poses by the HIP rasteriser, every interior rim pixel of the
+rendering within ``tau_px`` of the measured outline gives one residual, its distance to that outline, against the field's own
+central-difference gradient, and one damped Gauss-Newton step in fp64 moves the pose (``ops.silhouette_align_step``;
+``ops.silhouette_align`` is the loop).  ``SilhouetteRefiner`` keeps the mesh and the workspaces of a batch size.  ``step_torch`` and
+``sdf_torch`` say the step and the field again in plain torch ops: the comparators of tools/silhouette_bench.py, and the pieces that
+also run without a GPU.
+
+What it does is close the outline.  On a shape with a symmetry the outline closes and the pose need not (a rotation about the
+symmetry axis is invisible, and so, at a radius of some thirty pixels, is most of the depth); a measured mask with a straight
+occluder cut through it makes the loop diverge, since rim pixels near the false edge are pulled to it.  It is the step before
+photo_align, whose basin is about a pixel, not a replacement for it or for the depth ICP.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import _gn_torch, ops
+from ._refiner import _MeshRefiner
+from .options import AttrDict
+
+Tensor = torch.Tensor
+
+
+def sdf_torch(mask: Tensor) -> Tensor:
+    """ops.mask_sdf's rules (include/texpose_amd.h, K31a) by brute force over all pixel pairs of a plane, for small planes: mask
+    [F,H,W] or [H,W], non-zero: set -> sdf float32 of the same shape on the mask's device."""
+    m = mask if mask.dim() == 3 else mask[None]
+    F, H, W = m.shape
+    ii, jj = torch.meshgrid(torch.arange(H, device=m.device), torch.arange(W, device=m.device), indexing="ij")
+    pts = torch.stack([ii.reshape(-1), jj.reshape(-1)], 1)                                  # [n,2] int64
+    d2 = ((pts[:, None, :] - pts[None, :, :]) ** 2).sum(-1)                                 # [n,n]
+    none2 = H * H + W * W
+    out = torch.empty(F, H * W, dtype=torch.float32, device=m.device)
+    for f in range(F):
+        is_set = m[f].reshape(-1) != 0
+        to_set = torch.where(is_set[None, :], d2, torch.full_like(d2, none2)).min(1).values
+        to_clear = torch.where(is_set[None, :], torch.full_like(d2, none2), d2).min(1).values
+        out[f] = torch.where(is_set, -(torch.sqrt(to_clear.float()) - 0.5), torch.sqrt(to_set.float()) - 0.5)
+    return out.reshape(mask.shape)
+
+
+def step_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: float, damping: float = 1e-6,
+               frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False) -> Dict[str, Tensor]:
+    """ops.silhouette_align_step's rules (include/texpose_amd.h, K31b) in plain torch ops in fp64 on the tensors' device: the same
+    arguments -> 'pose' [B,3,4] float32, 'inliers' [B] int32, 'rms' [B] float32, 'status', 'inter', 'uni' [B] int32.  The sums run in
+    torch's order, not the kernel's: the counts and statuses agree, the rest to rounding."""
+    f64 = torch.float64
+    dev = zbuf.device
+    B, H, W = zbuf.shape
+    pose32 = pose.float().reshape(B, 3, 4)
+    intr = intr.float()
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3)
+    sdf = sdf.float()
+    if sdf.dim() == 2:
+        sdf = sdf[None]
+    Ft = sdf.shape[0]
+    fr = _gn_torch.frames_of(B, Ft, frame, "sdf must hold 1 or B = %d planes", dev)
+    tau = float(torch.tensor(tau_px, dtype=torch.float32))
+    zf = zbuf.float()
+    cov = (zf > 0) & torch.isfinite(zf)
+    field = sdf[fr]                                                                         # [B,H,W]
+    inside = (field < 0) & torch.isfinite(field)
+    inter, uni = (cov & inside).reshape(B, -1).sum(1), (cov | inside).reshape(B, -1).sum(1)
+    cand = torch.zeros_like(cov)
+    if H >= 3 and W >= 3:
+        c = cov[:, 1:-1, 1:-1]
+        all_four = cov[:, 1:-1, :-2] & cov[:, 1:-1, 2:] & cov[:, :-2, 1:-1] & cov[:, 2:, 1:-1]
+        cand[:, 1:-1, 1:-1] = c & ~all_four
+    if mask is not None:
+        m = mask if mask.dim() == 3 else mask[None]
+        cand = cand & (m[fr] != 0)
+    bi, ii, ji = torch.nonzero(cand, as_tuple=True)                                         # (interior: ii -+ 1 and ji -+ 1 exist)
+    d = field[bi, ii, ji].to(f64)
+    lf, rt, up, dn = (field[bi, ii, ji - 1].to(f64), field[bi, ii, ji + 1].to(f64), field[bi, ii - 1, ji].to(f64),
+                      field[bi, ii + 1, ji].to(f64))
+    r = d + 0.5
+    keep = torch.isfinite(torch.stack([d, lf, rt, up, dn], -1)).all(-1) & (r.abs() <= tau)
+    bi, ii, ji, r, lf, rt, up, dn = bi[keep], ii[keep], ji[keep], r[keep], lf[keep], rt[keep], up[keep], dn[keep]
+    z = zf[bi, ii, ji].to(f64)
+    K = intr.to(f64)
+    fx, fy = K[bi, 0, 0], K[bi, 1, 1]
+    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / fx
+    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / fy
+    P = torch.stack([z * rx, z * ry, z], -1)
+    gfx, gfy = (0.5 * (rt - lf)) * fx, (0.5 * (dn - up)) * fy
+    av = torch.stack([gfx / z, gfy / z, -(gfx * rx + gfy * ry) / z], -1)
+    J = torch.cat([torch.cross(P, av, dim=-1), av], -1)                                     # [n,6]
+    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, bi, J[:, :, None] * J[:, None, :])
+    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
+    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
+    count = torch.bincount(bi, minlength=B)
+    res = _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
+    res.update(inter=inter.to(torch.int32), uni=uni.to(torch.int32))
+    return res
+
+
+class SilhouetteRefiner(_MeshRefiner):
+    """Silhouette alignment for batches of poses of one mesh at H x W with the mesh on the device and a workspace per batch size.
+
+    ``tau_px`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 4 pixels), ``iters`` (Gauss-Newton steps, 10), ``damping``
+    (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (rim pixels of the rendering within
+    tau_px of the measured outline), rms [B] (pixels), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was not
+    positive definite: the pose went through unchanged), inliers0 / rms0 of the start pose and iou / iou0 [B], the intersection over
+    union of rendering and mask at the last and the start pose."""
+    _new_workspace = staticmethod(ops.silhouette_align_workspace)
+
+    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_px=4.0, iters: int = 10, damping: float = 1e-6):
+        super().__init__(verts, faces, H, W, device)
+        self.tau_px, self.iters, self.damping = tau_px, int(iters), float(damping)
+        self._sdf_workspaces: Dict[int, Tensor] = {}
+
+    def refine(self, pose: Tensor, intr: Tensor, mask_or_sdf: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
+        """pose [B,3,4], intr [B,3,3] or [3,3], mask_or_sdf [Ft,H,W]: the measured masks (uint8 or bool; run through ops.mask_sdf
+        first) or their distance fields (a float tensor, taken as it is), frame [B] int32 (the plane of each pose; without it Ft is 1
+        or B), mask [Ft,H,W] uint8 / bool (0: do not use the pixel)."""
+        planes = mask_or_sdf if mask_or_sdf.dim() == 3 else mask_or_sdf[None]
+        if tuple(planes.shape[1:]) != (self.H, self.W):
+            raise ValueError("SilhouetteRefiner.refine: planes of %d x %d expected, got %s" % (self.H, self.W, tuple(planes.shape)))
+        if not planes.dtype.is_floating_point:
+            Ft = planes.shape[0]
+            if Ft not in self._sdf_workspaces:
+                self._sdf_workspaces[Ft] = ops.mask_sdf_workspace(Ft, self.H, self.W, self.device)
+            planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft])
+        return AttrDict(ops.silhouette_align(self.verts, self.faces, pose, intr, planes, tau_px=self.tau_px, iters=self.iters,
+                                             damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))

@@ -3,6 +3,7 @@
 (texpose_amd.icp, K29), written as the same CSV format, so that tools/pose_errors.py --est scores it unchanged.
 
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
+                                 [--silhouette [--depth | --rgb]] [--rgb]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -18,7 +19,15 @@ left it; the tool prints how many.
 then the vertex-coloured mesh (texture_bake's output; the tool exits if it has no colours), the photograph is the 8-bit image / 255,
 the vertex colours' own range, and every interior covered pixel whose rendered colour lies within --tau-rgb of the photograph's pulls
 on the pose through the photograph's gradient, for --iters-rgb steps (--tau-rgb: one value or iters-rgb + 1).  --use-mask-visib,
---damping, --batch and the output are as above; --tau-mm and --iters are not used."""
+--damping, --batch and the output are as above; --tau-mm and --iters are not used.
+
+--silhouette: first refine against the OUTLINE of the object's mask (texpose_amd.silhouette, K31): --ply may be a
+textureless mesh, the masks are the scene's mask_visib/{frame:06d}_{k:06d}.png (k the object's first instance of the frame in
+scene_gt.json) or the files of the same names in --masks DIR, and every rim pixel of the rendering within --tau-px of the mask's
+outline pulls on the pose through the gradient of the mask's distance field, for --iters-sil steps (--tau-px: one value or iters-sil +
+1).  Alone it is the whole refinement (no depth, no colours: adaptation loop 0); with --depth or --rgb that refiner then starts from
+the silhouette's poses.  It closes the outline, not necessarily the pose (a symmetric shape, depth at a small radius), and a mask cut
+by an occluder misleads it.  The tool prints the mean intersection over union of rendering and mask before and after."""
 import argparse
 import csv
 import json
@@ -70,6 +79,11 @@ def main(argv=None):
     ap.add_argument("--rgb", action="store_true")
     ap.add_argument("--tau-rgb", type=float, nargs="+", default=[0.5])
     ap.add_argument("--iters-rgb", type=int, default=10)
+    ap.add_argument("--silhouette", action="store_true")
+    ap.add_argument("--depth", action="store_true", help="with --silhouette: go on with the depth refinement")
+    ap.add_argument("--tau-px", type=float, nargs="+", default=[4.0])
+    ap.add_argument("--iters-sil", type=int, default=10)
+    ap.add_argument("--masks", default=None, metavar="DIR")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -79,9 +93,13 @@ def main(argv=None):
         sys.exit("refine_poses: --tau-mm takes one value or iters + 1 = %d values" % (a.iters + 1))
     if a.rgb and len(a.tau_rgb) not in (1, a.iters_rgb + 1):
         sys.exit("refine_poses: --tau-rgb takes one value or iters-rgb + 1 = %d values" % (a.iters_rgb + 1))
+    if a.silhouette and len(a.tau_px) not in (1, a.iters_sil + 1):
+        sys.exit("refine_poses: --tau-px takes one value or iters-sil + 1 = %d values" % (a.iters_sil + 1))
+    if a.rgb and a.depth:
+        sys.exit("refine_poses: --depth and --rgb exclude each other")
     import torch
     from PIL import Image
-    from texpose_amd import icp, photo_align
+    from texpose_amd import icp, photo_align, silhouette
     from texpose_amd.pose_error import depth_from_png
     from texpose_amd.surfel import load_ply
     if not torch.cuda.is_available():
@@ -96,7 +114,7 @@ def main(argv=None):
         meshes[key] = mesh if a.rgb else mesh[:2]
     cam = json.load(open(os.path.join(a.scene, "scene_camera.json")))
     gt = None
-    if a.use_mask_visib:
+    if a.use_mask_visib or a.silhouette:
         gt = json.load(open(os.path.join(a.scene, "scene_gt.json")))
     rows = read_rows(a.est, a.scene_id)
     jobs = {}                                                   # object id -> indices into rows
@@ -107,33 +125,40 @@ def main(argv=None):
             jobs.setdefault(row[2], []).append(i)
     tau = a.tau_mm[0] if len(a.tau_mm) == 1 else a.tau_mm
     tau_rgb = a.tau_rgb[0] if len(a.tau_rgb) == 1 else a.tau_rgb
+    tau_px = a.tau_px[0] if len(a.tau_px) == 1 else a.tau_px
+    second = a.rgb or a.depth or not a.silhouette                # the depth / RGB refinement runs (after the silhouette's, if any)
+    iou_sum = np.zeros(2)
     refined = failed = 0
     dev = a.device
     for oid, idx in jobs.items():
         verts, faces = meshes.get(oid, meshes.get(None))[:2]
-        refiner = None
+        refiner = outline = None
         for s in range(0, len(idx), a.batch):
             part = idx[s:s + a.batch]
             frames = sorted({rows[i][1] for i in part})
-            if a.rgb:
-                planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
-                          for f in frames]
-            else:
-                planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
-                          for f in frames]
-            depth = torch.stack(planes)                          # (with --rgb: the photographs [Ft,H,W,3])
-            H, W = depth.shape[1:3]
-            mask = None
-            if a.use_mask_visib:
+            def masks_of(folder, option):
                 ms = []
                 for f in frames:
                     ks = [k for k, e in enumerate(gt[str(f)]) if int(e["obj_id"]) == oid]
-                    path = os.path.join(a.scene, "mask_visib", "%06d_%06d.png" % (f, ks[0])) if ks else None
+                    path = os.path.join(folder, "%06d_%06d.png" % (f, ks[0])) if ks else None
                     if path is None or not os.path.exists(path):
-                        sys.exit("refine_poses: --use-mask-visib: no mask_visib image of object %d in frame %d" % (oid, f))
+                        sys.exit("refine_poses: %s: no %s image of object %d in frame %d" % (option, os.path.basename(os.path.normpath(folder)), oid, f))
                     ms.append((np.asarray(Image.open(path)) != 0).astype(np.uint8))
-                mask = torch.from_numpy(np.stack(ms)).to(dev)
-            if refiner is None or (refiner.H, refiner.W) != (H, W):
+                return torch.from_numpy(np.stack(ms)).to(dev)
+
+            mask = masks_of(os.path.join(a.scene, "mask_visib"), "--use-mask-visib") if a.use_mask_visib else None
+            measured = masks_of(a.masks or os.path.join(a.scene, "mask_visib"), "--silhouette") if a.silhouette else None
+            if a.rgb:
+                planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
+                          for f in frames]
+            elif second:
+                planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
+                          for f in frames]
+            depth = torch.stack(planes) if second else measured  # (with --rgb: the photographs [Ft,H,W,3])
+            H, W = depth.shape[1:3]
+            if a.silhouette and (outline is None or (outline.H, outline.W) != (H, W)):
+                outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping)
+            if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
                     refiner = photo_align.PhotoRefiner(verts, faces, meshes.get(oid, meshes.get(None))[2], H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
                                                        damping=a.damping)
@@ -144,7 +169,13 @@ def main(argv=None):
             index = torch.tensor([frames.index(rows[i][1]) for i in part], dtype=torch.int32, device=dev)
             torch.cuda.synchronize()
             t0 = time.time()
-            r = refiner.refine(torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev), depth.to(dev), frame=index, mask=mask)
+            start, K = torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev)
+            if a.silhouette:
+                r = outline.refine(start, K, measured, frame=index, mask=mask)
+                start = r.pose
+                iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
+            if second:
+                r = refiner.refine(start, K, depth.to(dev), frame=index, mask=mask)
             out, status = r.pose.double().cpu().numpy(), r.status.cpu().numpy()
             dt = (time.time() - t0) / len(part)
             for k, i in enumerate(part):
@@ -152,6 +183,8 @@ def main(argv=None):
                 refined += 1
                 failed += int(status[k] != 0)
     write_rows(a.out, rows)
+    if a.silhouette and refined:
+        print("refine_poses: --silhouette: mean IoU %.4f -> %.4f" % (iou_sum[0] / refined, iou_sum[1] / refined))
     print("refine_poses: %d rows, %d refined (%d with a failed last step) -> %s" % (len(rows), refined, failed, a.out))
     return rows
 
