@@ -1365,6 +1365,36 @@ size_t tp_mask_sdf_workspace_bytes(int F, int H, int W);   /* 4 * F * H * W, rou
 int tp_mask_sdf(const uint8_t* mask, float* sdf, int F, int H, int W, void* workspace, tp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K31c the field of a mask with UNKNOWN pixels (texpose_amd/silhouette.py; restated in tests/occlusion_ref.py; the project's own
+ *      kernel, no reference code).  known [F,H,W] uint8, non-zero: the pixel's mask value is a measurement.  Per
+ *      plane a pixel is SET (mask != 0 and known != 0), CLEAR (mask == 0 and known != 0) or UNKNOWN (known == 0, whatever mask
+ *      holds: behind an occluder, say).  d2_set(p) and d2_clear(p) are K31a's integers taken over the SET and the CLEAR pixels only,
+ *      the sentinel H^2 + W^2 where the plane has none; an unknown pixel is neither, so no distance is ever measured to it.
+ *        sdf = SET ? -(sqrtf((float)d2_clear) - 0.5f) : CLEAR ? sqrtf((float)d2_set) - 0.5f : quiet NaN
+ *      (sqrtf correctly rounded).  K31b drops a rim pixel whose field value or any of whose four neighbours' values is not finite and
+ *      counts a non-finite value as outside: it takes this field as it is.  With known all non-zero the result is tp_mask_sdf's bit
+ *      for bit.  The workspace is tp_mask_sdf_workspace_bytes'; the refusals are K31a's with known among the pointers, and an sdf that
+ *      overlaps known.  The same two launches (an unknown pixel advances both distances of the column sweep, and the row kernel
+ *      knows it by neither being 0), no atomics, integer minima: a function of (mask, known) alone.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+int tp_mask_sdf_known(const uint8_t* mask, const uint8_t* known, float* sdf, int F, int H, int W, void* workspace, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K32  who hides whom, from the instance masks of ONE frame (texpose_amd/silhouette.py; restated in tests/occlusion_ref.py; the
+ *      project's own kernel, no reference code).  sdf [N,H,W] holds tp_mask_sdf's fields of the frame's N instance
+ *      masks, known [N,H,W] uint8 is written.  near(m,p) = sdf[m,p] <= band_px - 0.5f, in fp32 as written (a NaN is not near): pixel
+ *      p lies within band_px pixels of a set pixel of instance m; band_px = 0 is the instance's own pixels.
+ *        known[n,p] = 0 iff near(m,p) for some m != n;  else 1
+ *      Conservative by construction: along the contour between two touching instances both lose the pixels within band_px of the
+ *      other, the one in front too, whose contour there is real.  One launch: a thread owns four consecutive flat pixels, walks the
+ *      N planes once counting the near instances and keeping the index of one, then writes the N bytes: 0 iff count > 1 or (count
+ *      == 1 and index != n).  Non-positive sizes, N > 65535, N * H * W >= 2^31, null pointers, a band_px that is not finite and
+ *      >= 0 and a known that overlaps sdf are refused (-1, tp_last_error) before the launch.  No workspace, no atomics.  Safe to
+ *      capture.
+ * ------------------------------------------------------------------------------------------ */
+int tp_mask_known_from_others(const float* sdf, uint8_t* known, int N, int H, int W, float band_px, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K31b one step of batched silhouette alignment: B poses refined against the outline of a mask (texpose_amd/silhouette.py; restated
  *      in tests/silhouette_ref.py; the project's own step, no reference code).  zbuf is K19's depth of the mesh
  *      rendered at pose, sdf the signed distance field of the measured mask (tp_mask_sdf's, or any field in pixels that is negative

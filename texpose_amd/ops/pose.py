@@ -11,7 +11,7 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _lengths, _on_
 __all__ = ["NN1_MODES", "nn1", "pose_errors", "vsd", "PNP_MAX_HYP", "PNP_MAX_ITERS", "pnp_workspace", "_pnp_common", "corr_from_nocs",
            "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac", "depth_icp_workspace", "depth_icp_step",
            "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS", "photo_align", "mask_sdf_workspace", "mask_sdf",
-           "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align"]
+           "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align"]
 
 # ------------------------------------------------------------------------------------------ K24, K25
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
@@ -493,25 +493,53 @@ def mask_sdf_workspace(F: int, H: int, W: int, device) -> Tensor:
 
 
 @_on_tensor_device
-def mask_sdf(mask: Tensor, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+def mask_sdf(mask: Tensor, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None, known: Optional[Tensor] = None) -> Tensor:
     """The exact signed Euclidean distance field of F masks (tp_mask_sdf; the rules are in the header): mask [F,H,W] (or one [H,W])
     uint8 or bool, non-zero: set -> sdf float32 of mask's shape, in pixels: sqrt(d2_set) - 0.5 on a clear pixel, -(sqrt(d2_clear) -
     0.5) on a set one, with the squared distances to the nearest set / clear pixel of the plane (H^2 + W^2 where it has none).
     ``out``: the tensor to write into; ``workspace``: mask_sdf_workspace(F, H, W).  H, W <= 8192.  Two launches, no atomics, a function
-    of the mask alone, safe under torch.cuda.graph."""
+    of the mask alone, safe under torch.cuda.graph.  ``known`` (uint8 or bool, of mask's shape, non-zero: the pixel's mask value is a
+    measurement) makes the rest UNKNOWN, neither set nor clear (tp_mask_sdf_known, K31c): no distance is measured to such a pixel and
+    its own value is NaN, which silhouette_align_step drops; with every pixel known the field is the plain one bit for bit."""
     op = "mask_sdf"
     if torch.is_tensor(mask) and not mask.is_cuda:
         raise _lib.TexposeLibraryError("mask must live on the GPU (texpose_amd has no CPU path)")
     if torch.is_tensor(mask) and mask.dtype == torch.bool:
         mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
     mask = _want_gpu(op, mask, "mask", torch.uint8, None)
+    if known is not None:
+        if torch.is_tensor(known) and known.dtype == torch.bool:
+            known = known.view(torch.uint8) if known.is_contiguous() else known.to(torch.uint8)
+        known = _want_gpu(op, known, "known", torch.uint8, tuple(mask.shape))
     if mask.dim() not in (2, 3) or mask.numel() == 0:
         raise ValueError("%s: mask [F,H,W] or [H,W] expected, got %s" % (op, tuple(mask.shape)))
     F, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
     sdf = torch.empty(mask.shape, device=mask.device) if out is None else _want_gpu(op, out, "out", torch.float32, tuple(mask.shape))
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_mask_sdf_workspace_bytes(F, H, W)), mask.device, align=16)
-    _call("tp_mask_sdf", mask.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())          # (H or W > 8192: the library's error)
+    if known is None:
+        _call("tp_mask_sdf", mask.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())      # (H or W > 8192: the library's error)
+    else:
+        _call("tp_mask_sdf_known", mask.data_ptr(), known.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())
     return sdf
+
+
+@_on_tensor_device
+def mask_known_from_others(sdf: Tensor, band_px: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """Who hides whom among the N instances of ONE frame (tp_mask_known_from_others, K32; the rules are in the header): sdf [N,H,W]
+    float32, mask_sdf's fields of the frame's instance masks (taken as they are) -> known [N,H,W] uint8: 0 where the pixel lies within
+    ``band_px`` pixels of a set pixel of ANOTHER instance (sdf[m,p] <= band_px - 0.5 in fp32 for some m != n; a NaN is not near), else
+    1: mask_sdf's ``known``.  Conservative: where two instances touch, both lose the contour between them.  ``out``: the uint8 tensor
+    to write into.  One launch, no workspace, no atomics, safe under torch.cuda.graph."""
+    op = "mask_known_from_others"
+    if torch.is_tensor(sdf) and not sdf.is_cuda:
+        raise _lib.TexposeLibraryError("sdf must live on the GPU (texpose_amd has no CPU path)")
+    sdf = _want_gpu(op, sdf, "sdf", torch.float32, None)
+    if sdf.dim() != 3 or sdf.numel() == 0:
+        raise ValueError("%s: sdf [N,H,W] expected, got %s" % (op, tuple(sdf.shape)))
+    N, H, W = sdf.shape
+    known = torch.empty(sdf.shape, device=sdf.device, dtype=torch.uint8) if out is None else _want_gpu(op, out, "out", torch.uint8, tuple(sdf.shape))
+    _call("tp_mask_known_from_others", sdf.data_ptr(), known.data_ptr(), N, H, W, float(band_px))  # (band_px, N > 65535: the library's error)
+    return known
 
 
 def silhouette_align_workspace(B: int, H: int, W: int, device) -> Tensor:
@@ -562,7 +590,7 @@ SILHOUETTE_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0",
 @_on_tensor_device
 def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px=4.0, iters: int = 10,
                      damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-                     workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                     workspace: Optional[Tensor] = None, visible_iou: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against the outlines of measured masks (the rules are in the header, K31): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth alone, H x W = sdf's) followed by silhouette_align_step, the last with evaluate_only.
     ``sdf`` [Ft,H,W]: mask_sdf of the measured masks.  ``tau_px``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule
@@ -571,7 +599,11 @@ def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, s
     intersection over union of the rendering's coverage and the measured mask at the last and at the start pose (NaN where both are
     empty).  A step that fails passes its pose on.  It closes the OUTLINE: a pose parameter the outline does not see (a rotation about
     a symmetry axis, depth at a small radius) stays where it was, and a measured mask cut by an occluder pulls the rim to the cut.
-    3 (iters + 1) launches besides the rasteriser's, bit-identical from run to run, safe under torch.cuda.graph."""
+    3 (iters + 1) launches besides the rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.
+    ``visible_iou``: for a field with unknown pixels (mask_sdf's ``known``; NaN there) also 'iou_visible' / 'iou0_visible' [B] float32,
+    inter / (uni - hidden) at the last and at the start pose, ``hidden`` the covered pixels of the plane whose field value is NaN: the
+    IoU over the pixels that were measured (NaN where none is left).  Exact integer counts by torch reductions on the first and the
+    last rendering; without the flag nothing else runs and the keys are those above."""
     op = "silhouette_align"
     taus = _tau_schedule(op, tau_px, "tau_px", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -587,15 +619,27 @@ def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, s
     sdf, frame, mask, _ = _frame_planes(op, "sdf", sdf, (), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    passes = []
+    passes, hidden = [], []
+    if visible_iou:
+        unknown = torch.isnan(sdf)                               # [Ft,H,W]; the plane of image b by the step's frame rule
+        if frame is not None:
+            unknown = unknown[frame.clamp(0, sdf.shape[0] - 1).long()]
     raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=False, normals=False)
 
     def step(r, P, t, last):
         passes.append(silhouette_align_step(r["zbuf"], P, intr, sdf, tau_px=t, damping=damping, frame=frame, mask=mask, evaluate_only=last,
                                             workspace=workspace))
+        if visible_iou and (len(passes) == 1 or last):
+            z = r["zbuf"]
+            hidden.append(((z > 0) & torch.isfinite(z) & unknown).flatten(1).sum(1))
         return passes[-1]
 
     res = _refine_loop(pose, taus, raster, step)
     iou = lambda r: r["inter"].float() / r["uni"].float()
     res.update(iou=iou(passes[-1]), iou0=iou(passes[0]))
+    if visible_iou:
+        def seen(r, h):
+            left = r["uni"] - h                                  # (>= inter: a hidden pixel is covered and not inside)
+            return torch.where(left == 0, torch.full_like(left, float("nan"), dtype=torch.float32), r["inter"].float() / left.float())
+        res.update(iou_visible=seen(passes[-1], hidden[-1]), iou0_visible=seen(passes[0], hidden[0]))
     return res

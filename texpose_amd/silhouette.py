@@ -11,9 +11,17 @@ central-difference gradient, and one damped Gauss-Newton step in fp64 moves the 
 also run without a GPU.
 
 What it does is close the outline.  On a shape with a symmetry the outline closes and the pose need not (a rotation about the
-symmetry axis is invisible, and so, at a radius of some thirty pixels, is most of the depth); a measured mask with a straight
-occluder cut through it makes the loop diverge, since rim pixels near the false edge are pulled to it.  It is the step before
-photo_align, whose basin is about a pixel, not a replacement for it or for the depth ICP.
+symmetry axis is invisible, and so, at a radius of some thirty pixels, is most of the depth).  It is the step before photo_align,
+whose basin is about a pixel, not a replacement for it or for the depth ICP.
+
+Occlusion (K31c, K32).  A VISIBLE mask cut by an occluder has a false edge, and the plain field of it pulls rim
+pixels to that edge: the loop diverges.  Say which pixels were measured instead: ``ops.mask_sdf(mask, known=...)`` treats the rest
+as neither set nor clear, so no distance is measured to them and the field is NaN on them, which the step already drops;
+``SilhouetteRefiner.refine(..., known=...)`` does that and also returns the IoU over the known pixels.
+``ops.mask_known_from_others`` makes the known planes of a frame from the fields of all its instance masks (unknown: within a band
+of another instance; conservative, the contour between two touching instances is lost to both).  ``known_from_others_torch`` says
+it again in torch.  With this the outline over the visible part closes; with less than about half of the object visible the pose
+still need not follow.
 """
 from __future__ import annotations
 
@@ -28,10 +36,14 @@ from .options import AttrDict
 Tensor = torch.Tensor
 
 
-def sdf_torch(mask: Tensor) -> Tensor:
-    """ops.mask_sdf's rules (include/texpose_amd.h, K31a) by brute force over all pixel pairs of a plane, for small planes: mask
-    [F,H,W] or [H,W], non-zero: set -> sdf float32 of the same shape on the mask's device."""
+def sdf_torch(mask: Tensor, known: Optional[Tensor] = None) -> Tensor:
+    """ops.mask_sdf's rules (include/texpose_amd.h, K31a and K31c) by brute force over all pixel pairs of a plane, for small planes:
+    mask [F,H,W] or [H,W], non-zero: set, known of the same shape, zero: the pixel is neither set nor clear -> sdf float32 of the same
+    shape on the mask's device, NaN on the unknown pixels."""
     m = mask if mask.dim() == 3 else mask[None]
+    k = torch.ones_like(m, dtype=torch.bool) if known is None else (known if known.dim() == 3 else known[None]) != 0
+    if k.shape != m.shape:
+        raise ValueError("sdf_torch: known of mask's shape expected, got %s and %s" % (tuple(known.shape), tuple(mask.shape)))
     F, H, W = m.shape
     ii, jj = torch.meshgrid(torch.arange(H, device=m.device), torch.arange(W, device=m.device), indexing="ij")
     pts = torch.stack([ii.reshape(-1), jj.reshape(-1)], 1)                                  # [n,2] int64
@@ -39,11 +51,21 @@ def sdf_torch(mask: Tensor) -> Tensor:
     none2 = H * H + W * W
     out = torch.empty(F, H * W, dtype=torch.float32, device=m.device)
     for f in range(F):
-        is_set = m[f].reshape(-1) != 0
+        seen = k[f].reshape(-1)
+        is_set, is_clear = (m[f].reshape(-1) != 0) & seen, (m[f].reshape(-1) == 0) & seen
         to_set = torch.where(is_set[None, :], d2, torch.full_like(d2, none2)).min(1).values
-        to_clear = torch.where(is_set[None, :], torch.full_like(d2, none2), d2).min(1).values
+        to_clear = torch.where(is_clear[None, :], d2, torch.full_like(d2, none2)).min(1).values
         out[f] = torch.where(is_set, -(torch.sqrt(to_clear.float()) - 0.5), torch.sqrt(to_set.float()) - 0.5)
+        out[f][~seen] = float("nan")
     return out.reshape(mask.shape)
+
+
+def known_from_others_torch(sdf: Tensor, band_px: float) -> Tensor:
+    """ops.mask_known_from_others' rule (include/texpose_amd.h, K32) in plain torch ops: sdf [N,H,W] float32, the fields of one
+    frame's instance masks -> known [N,H,W] uint8, 0 where another instance has sdf <= band_px - 0.5 (fp32) at the pixel."""
+    near = sdf.float() <= (torch.tensor(band_px, dtype=torch.float32) - torch.tensor(0.5, dtype=torch.float32)).to(sdf.device)
+    others = near.sum(0, keepdim=True) - near.to(torch.int64)                                # the near instances besides n itself
+    return (others == 0).to(torch.uint8)
 
 
 def step_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: float, damping: float = 1e-6,
@@ -109,7 +131,8 @@ class SilhouetteRefiner(_MeshRefiner):
     (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (rim pixels of the rendering within
     tau_px of the measured outline), rms [B] (pixels), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was not
     positive definite: the pose went through unchanged), inliers0 / rms0 of the start pose and iou / iou0 [B], the intersection over
-    union of rendering and mask at the last and the start pose."""
+    union of rendering and mask at the last and the start pose; with ``known`` also iou_visible / iou0_visible [B], the same over the
+    known pixels only."""
     _new_workspace = staticmethod(ops.silhouette_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_px=4.0, iters: int = 10, damping: float = 1e-6):
@@ -117,17 +140,26 @@ class SilhouetteRefiner(_MeshRefiner):
         self.tau_px, self.iters, self.damping = tau_px, int(iters), float(damping)
         self._sdf_workspaces: Dict[int, Tensor] = {}
 
-    def refine(self, pose: Tensor, intr: Tensor, mask_or_sdf: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
+    def refine(self, pose: Tensor, intr: Tensor, mask_or_sdf: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+               known: Optional[Tensor] = None) -> AttrDict:
         """pose [B,3,4], intr [B,3,3] or [3,3], mask_or_sdf [Ft,H,W]: the measured masks (uint8 or bool; run through ops.mask_sdf
         first) or their distance fields (a float tensor, taken as it is), frame [B] int32 (the plane of each pose; without it Ft is 1
-        or B), mask [Ft,H,W] uint8 / bool (0: do not use the pixel)."""
+        or B), mask [Ft,H,W] uint8 / bool (0: do not use the pixel), known [Ft,H,W] uint8 / bool (0: the mask's value there is no
+        measurement, the pixel is behind an occluder, say; ops.mask_known_from_others makes such planes from a frame's instance masks).
+        ``known`` goes with masks only (a field already says what it knows) and adds iou_visible / iou0_visible [B], the IoU over the
+        known pixels."""
         planes = mask_or_sdf if mask_or_sdf.dim() == 3 else mask_or_sdf[None]
         if tuple(planes.shape[1:]) != (self.H, self.W):
             raise ValueError("SilhouetteRefiner.refine: planes of %d x %d expected, got %s" % (self.H, self.W, tuple(planes.shape)))
+        if known is not None and planes.dtype.is_floating_point:
+            raise ValueError("SilhouetteRefiner.refine: known= goes with masks; mask_or_sdf is a field (pass ops.mask_sdf(mask, known=known))")
         if not planes.dtype.is_floating_point:
             Ft = planes.shape[0]
+            if known is not None:
+                known = (known if known.dim() == 3 else known[None]).to(self.device).contiguous()
             if Ft not in self._sdf_workspaces:
                 self._sdf_workspaces[Ft] = ops.mask_sdf_workspace(Ft, self.H, self.W, self.device)
-            planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft])
+            planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft], known=known)
         return AttrDict(ops.silhouette_align(self.verts, self.faces, pose, intr, planes, tau_px=self.tau_px, iters=self.iters,
-                                             damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))
+                                             damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]),
+                                             visible_iou=known is not None))

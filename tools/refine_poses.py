@@ -3,7 +3,7 @@
 (texpose_amd.icp, K29), written as the same CSV format, so that tools/pose_errors.py --est scores it unchanged.
 
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
-                                 [--silhouette [--depth | --rgb]] [--rgb]
+                                 [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -27,7 +27,15 @@ scene_gt.json) or the files of the same names in --masks DIR, and every rim pixe
 outline pulls on the pose through the gradient of the mask's distance field, for --iters-sil steps (--tau-px: one value or iters-sil +
 1).  Alone it is the whole refinement (no depth, no colours: adaptation loop 0); with --depth or --rgb that refiner then starts from
 the silhouette's poses.  It closes the outline, not necessarily the pose (a symmetric shape, depth at a small radius), and a mask cut
-by an occluder misleads it.  The tool prints the mean intersection over union of rendering and mask before and after."""
+by an occluder misleads it.  The tool prints the mean intersection over union of rendering and mask before and after.
+
+--occluders (with --silhouette): mask_visib is the VISIBLE mask, and where another object hides part of this one
+its edge is not the object's.  Per frame the masks of EVERY instance in scene_gt.json are read (from --masks DIR or mask_visib/), and
+a pixel within --occluder-band pixels (default 1.0; not tuned on anything) of another instance's mask becomes UNKNOWN: neither set
+nor clear in the distance field, and no rim pixel there pulls on the pose.  Conservative: where two instances touch, both lose the
+contour between them, the one in front too.  --known DIR gives such planes directly: PNGs with the mask files' names, non-zero:
+the pixel was measured.  The two exclude each other.  With either the tool also prints the mean visible IoU, the IoU over the known
+pixels only, before and after.  With less than about half of an object visible the outline still closes and the pose need not."""
 import argparse
 import csv
 import json
@@ -84,6 +92,9 @@ def main(argv=None):
     ap.add_argument("--tau-px", type=float, nargs="+", default=[4.0])
     ap.add_argument("--iters-sil", type=int, default=10)
     ap.add_argument("--masks", default=None, metavar="DIR")
+    ap.add_argument("--occluders", action="store_true", help="with --silhouette: pixels near another instance's mask are unknown")
+    ap.add_argument("--occluder-band", type=float, default=1.0, metavar="PX")
+    ap.add_argument("--known", default=None, metavar="DIR", help="with --silhouette: PNGs with the mask files' names, non-zero: known")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -97,9 +108,13 @@ def main(argv=None):
         sys.exit("refine_poses: --tau-px takes one value or iters-sil + 1 = %d values" % (a.iters_sil + 1))
     if a.rgb and a.depth:
         sys.exit("refine_poses: --depth and --rgb exclude each other")
+    if a.occluders and a.known:
+        sys.exit("refine_poses: --occluders and --known exclude each other")
+    if (a.occluders or a.known) and not a.silhouette:
+        sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
     from PIL import Image
-    from texpose_amd import icp, photo_align, silhouette
+    from texpose_amd import icp, ops, photo_align, silhouette
     from texpose_amd.pose_error import depth_from_png
     from texpose_amd.surfel import load_ply
     if not torch.cuda.is_available():
@@ -127,7 +142,7 @@ def main(argv=None):
     tau_rgb = a.tau_rgb[0] if len(a.tau_rgb) == 1 else a.tau_rgb
     tau_px = a.tau_px[0] if len(a.tau_px) == 1 else a.tau_px
     second = a.rgb or a.depth or not a.silhouette                # the depth / RGB refinement runs (after the silhouette's, if any)
-    iou_sum = np.zeros(2)
+    iou_sum, visible_sum = np.zeros(2), np.zeros(2)
     refined = failed = 0
     dev = a.device
     for oid, idx in jobs.items():
@@ -148,6 +163,18 @@ def main(argv=None):
 
             mask = masks_of(os.path.join(a.scene, "mask_visib"), "--use-mask-visib") if a.use_mask_visib else None
             measured = masks_of(a.masks or os.path.join(a.scene, "mask_visib"), "--silhouette") if a.silhouette else None
+            known = masks_of(a.known, "--known") if a.known else None
+            if a.occluders:                                      # per frame: every instance's mask -> their fields -> who is near whom
+                folder, per_frame = a.masks or os.path.join(a.scene, "mask_visib"), []
+                for f in frames:
+                    paths = [os.path.join(folder, "%06d_%06d.png" % (f, k)) for k in range(len(gt[str(f)]))]
+                    for path in paths:
+                        if not os.path.exists(path):
+                            sys.exit("refine_poses: --occluders: no %s image %s" % (os.path.basename(os.path.normpath(folder)), os.path.basename(path)))
+                    every = torch.from_numpy(np.stack([(np.asarray(Image.open(path)) != 0).astype(np.uint8) for path in paths])).to(dev)
+                    own = [k for k, e in enumerate(gt[str(f)]) if int(e["obj_id"]) == oid][0]
+                    per_frame.append(ops.mask_known_from_others(ops.mask_sdf(every), a.occluder_band)[own])
+                known = torch.stack(per_frame)
             if a.rgb:
                 planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
                           for f in frames]
@@ -171,9 +198,11 @@ def main(argv=None):
             t0 = time.time()
             start, K = torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev)
             if a.silhouette:
-                r = outline.refine(start, K, measured, frame=index, mask=mask)
+                r = outline.refine(start, K, measured, frame=index, mask=mask, known=known)
                 start = r.pose
                 iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
+                if known is not None:
+                    visible_sum += [float(r.iou0_visible.double().sum()), float(r.iou_visible.double().sum())]
             if second:
                 r = refiner.refine(start, K, depth.to(dev), frame=index, mask=mask)
             out, status = r.pose.double().cpu().numpy(), r.status.cpu().numpy()
@@ -185,6 +214,8 @@ def main(argv=None):
     write_rows(a.out, rows)
     if a.silhouette and refined:
         print("refine_poses: --silhouette: mean IoU %.4f -> %.4f" % (iou_sum[0] / refined, iou_sum[1] / refined))
+        if a.occluders or a.known:
+            print("refine_poses: --silhouette: mean visible IoU %.4f -> %.4f" % (visible_sum[0] / refined, visible_sum[1] / refined))
     print("refine_poses: %d rows, %d refined (%d with a failed last step) -> %s" % (len(rows), refined, failed, a.out))
     return rows
 
