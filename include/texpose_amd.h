@@ -1458,6 +1458,50 @@ typedef struct tp_silhouette_align_args {
 size_t tp_silhouette_align_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
 int tp_silhouette_align_step(const tp_silhouette_align_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K33  one JOINT step of the render-and-compare refiners: the residual rows of K31b (silhouette), K30 (photometric) and K29 (depth)
+ *      in ONE normal system (texpose_amd/joint.py; restated in tests/joint_ref.py; the project's own step, no reference code; DESIGN
+ *      section 23).  The three terms share the six parameters (w, v), the 29 fp64 sums and the record per (image, 1024-pixel tile);
+ *      each term that is present (its pointer is not NULL) is its own args struct, unchanged, with its own planes, threshold, frame
+ *      map, mask, outputs and workspace.  The call
+ *        1. evaluates every present term exactly as that term's own step would with evaluate_only = 1: the term's inliers, rms and
+ *           status (and inter / uni of the silhouette) and the records in its workspace are bit for bit those of the standalone
+ *           call.  The term's pose_out and evaluate_only fields are ignored (nothing is written through that pose_out);
+ *        2. per image gathers each term's records in ascending tile order into that term's sums S_t[0 .. 28], terms in the order
+ *           silhouette, photometric, depth, and forms over the terms that are present AND have a weight > 0
+ *             sum[k] = w_a S_a[k] (+ w_b S_b[k] (+ w_c S_c[k]))     for k = 0 .. 27, in fp64 as written (no contraction)
+ *           with the float weights widened to fp64.  A term that is absent or has weight 0 is skipped, not added as zero.
+ *           inliers = the sum of the counts S_t[28] of those terms;  chi2 = sum[27], rounded to fp32: the weighted sum of squares;
+ *        3. applies K29's rules to the combined sums: status 1 where inliers < 6; else 3 where the combined J^T J is not positive
+ *           definite by the pivot rule, or, without evaluate_only, where the damped matrix does not factor or the stepped pose is not
+ *           finite in fp32; else 0.  pose_out = (status == 0 and not evaluate_only) the damped step of K29 on the combined sums,
+ *           rounded to fp32; otherwise pose, bit for bit (pose_out may be NULL with evaluate_only).
+ *      A weight is 1 / sigma^2 of that term's residual unit (pixels, colour units, mm).  With one term present at weight exactly 1
+ *      pose_out and status are that term's own step's, bit for bit.  Refused (-1, tp_last_error) before anything is launched: a
+ *      null args; no term present, or none with a weight > 0; a weight that is negative or not finite; a damping that is not finite
+ *      and >= 0; null pose, status, inliers or chi2; pose_out missing without evaluate_only, or overlapping pose; a present term
+ *      whose B or pose differs from args', or whose H, W or intr differs from another term's; two terms whose workspaces overlap;
+ *      and whatever the term's own step refuses.  Per present term that term's reduce launches and its evaluating solve, then one
+ *      launch of the joint solve (grid B, one wave).  No atomics, no allocation, no host synchronisation; bit-identical from run to
+ *      run.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_joint_align_args {
+  int B;
+  const float* pose;         /* [B,3,4] the pose every term's planes were rendered at (each term's pose must be this pointer) */
+  float w_sil, w_photo, w_icp; /* finite, >= 0: 1 / sigma^2 of the term's residual unit; 0: evaluated, not in the step */
+  float damping;             /* finite, >= 0: relative Levenberg damping of the combined diagonal */
+  int evaluate_only;         /* non-zero: inliers, chi2 and status of pose; no step */
+  float* pose_out;           /* [B,3,4] out; may be NULL with evaluate_only; must not overlap pose */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels over the weighted terms, 3 not positive definite */
+  int32_t* inliers;          /* [B] out: the kept pixels of the weighted terms, added */
+  float* chi2;               /* [B] out: the weighted sum of squared residuals */
+} tp_joint_align_args;
+int tp_joint_align_step(const tp_joint_align_args* j,
+                        const tp_silhouette_align_args* sil,   /* may be NULL */
+                        const tp_photo_align_args* photo,      /* may be NULL */
+                        const tp_depth_icp_args* icp,          /* may be NULL */
+                        tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 // No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
+#include "pose_terms.h"
 
 namespace {
 // VEC: H * W is a multiple of four and zbuf / depth are 16-byte aligned
@@ -97,21 +98,28 @@ extern "C" size_t tp_depth_icp_workspace_bytes(int B, int H, int W) {
   return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
 }
 
+bool tp::depth_icp_args_ok(const tp_depth_icp_args& a) {
+  if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || a.V <= 0 || a.F <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
+    tp::set_error("tp_depth_icp_step: bad sizes (B 1..65535, Ft > 0, V > 0, F > 0, H > 0, W > 0, H * W < 2^31)");
+    return false;
+  }
+  const bool missing = !a.verts || !a.faces || !a.zbuf || !a.face || !a.depth;
+  return gn_step_args_ok("tp_depth_icp_step", a, "tau_mm", a.tau_mm, missing);
+}
+
+void tp::depth_icp_launch(const tp_depth_icp_args& a, hipStream_t st) {
+  const int64_t plane = (int64_t)a.H * a.W;
+  const int G = (int)gn_tiles(plane);
+  double* part = static_cast<double*>(a.workspace);
+  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a.zbuf | (uintptr_t)a.depth) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(icp_reduce_kernel<true>, dim3(G, a.B), dim3(kGnBlock), 0, st, a, part);
+  else hipLaunchKernelGGL(icp_reduce_kernel<false>, dim3(G, a.B), dim3(kGnBlock), 0, st, a, part);
+  hipLaunchKernelGGL(gn_solve_kernel<tp_depth_icp_args>, dim3(a.B), dim3(tp::kWave), 0, st, a, (const double*)part, G);
+}
+
 extern "C" int tp_depth_icp_step(const tp_depth_icp_args* a, tp_stream_t stream) {
   if (!a) { tp::set_error("tp_depth_icp_step: null args"); return -1; }
-  if (a->B <= 0 || a->B > 65535 || a->H <= 0 || a->W <= 0 || a->Ft <= 0 || a->V <= 0 || a->F <= 0 || (int64_t)a->H * a->W > 0x7FFFFFFFll) {
-    tp::set_error("tp_depth_icp_step: bad sizes (B 1..65535, Ft > 0, V > 0, F > 0, H > 0, W > 0, H * W < 2^31)");
-    return -1;
-  }
-  const bool missing = !a->verts || !a->faces || !a->zbuf || !a->face || !a->depth;
-  if (!gn_step_args_ok("tp_depth_icp_step", *a, "tau_mm", a->tau_mm, missing)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t plane = (int64_t)a->H * a->W;
-  const int G = (int)gn_tiles(plane);
-  double* part = static_cast<double*>(a->workspace);
-  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->depth) & 15u) == 0;
-  if (vec) hipLaunchKernelGGL(icp_reduce_kernel<true>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
-  else hipLaunchKernelGGL(icp_reduce_kernel<false>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
-  hipLaunchKernelGGL(gn_solve_kernel<tp_depth_icp_args>, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  if (!tp::depth_icp_args_ok(*a)) return -1;
+  tp::depth_icp_launch(*a, (hipStream_t)stream);
   return tp::check_launch("tp_depth_icp_step");
 }

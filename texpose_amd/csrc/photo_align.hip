@@ -15,6 +15,7 @@
 // No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
+#include "pose_terms.h"
 
 namespace {
 __device__ __forceinline__ bool finite3(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
@@ -135,21 +136,28 @@ extern "C" size_t tp_photo_align_workspace_bytes(int B, int H, int W) {
   return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
 }
 
+bool tp::photo_align_args_ok(const tp_photo_align_args& a) {
+  if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
+    tp::set_error("tp_photo_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
+    return false;
+  }
+  const bool missing = !a.zbuf || !a.rgb || !a.image;
+  return gn_step_args_ok("tp_photo_align_step", a, "tau", a.tau, missing);
+}
+
+void tp::photo_align_launch(const tp_photo_align_args& a, hipStream_t st) {
+  const int64_t plane = (int64_t)a.H * a.W;
+  const int G = (int)gn_tiles(plane);
+  double* part = static_cast<double*>(a.workspace);
+  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a.zbuf | (uintptr_t)a.rgb | (uintptr_t)a.image) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(photo_reduce_kernel<true>, dim3(G, a.B), dim3(kGnBlock), 0, st, a, part);
+  else hipLaunchKernelGGL(photo_reduce_kernel<false>, dim3(G, a.B), dim3(kGnBlock), 0, st, a, part);
+  hipLaunchKernelGGL(gn_solve_kernel<tp_photo_align_args>, dim3(a.B), dim3(tp::kWave), 0, st, a, (const double*)part, G);
+}
+
 extern "C" int tp_photo_align_step(const tp_photo_align_args* a, tp_stream_t stream) {
   if (!a) { tp::set_error("tp_photo_align_step: null args"); return -1; }
-  if (a->B <= 0 || a->B > 65535 || a->H <= 0 || a->W <= 0 || a->Ft <= 0 || (int64_t)a->H * a->W > 0x7FFFFFFFll) {
-    tp::set_error("tp_photo_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
-    return -1;
-  }
-  const bool missing = !a->zbuf || !a->rgb || !a->image;
-  if (!gn_step_args_ok("tp_photo_align_step", *a, "tau", a->tau, missing)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t plane = (int64_t)a->H * a->W;
-  const int G = (int)gn_tiles(plane);
-  double* part = static_cast<double*>(a->workspace);
-  const bool vec = plane % kGnPix == 0 && (((uintptr_t)a->zbuf | (uintptr_t)a->rgb | (uintptr_t)a->image) & 15u) == 0;
-  if (vec) hipLaunchKernelGGL(photo_reduce_kernel<true>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
-  else hipLaunchKernelGGL(photo_reduce_kernel<false>, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
-  hipLaunchKernelGGL(gn_solve_kernel<tp_photo_align_args>, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  if (!tp::photo_align_args_ok(*a)) return -1;
+  tp::photo_align_launch(*a, (hipStream_t)stream);
   return tp::check_launch("tp_photo_align_step");
 }

@@ -12,6 +12,7 @@
 // steps and writes the outputs.  No atomics; every fp64 sum has one fixed order, the counts are integers.
 #include "tp_common.h"
 #include "pose_gn.h"
+#include "pose_terms.h"
 
 namespace {
 constexpr int kSilInter = 29, kSilUnion = 30;          // the record's entries of the two counts (exact: at most 1024 each)
@@ -111,19 +112,26 @@ extern "C" size_t tp_silhouette_align_workspace_bytes(int B, int H, int W) {
   return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
 }
 
+bool tp::silhouette_align_args_ok(const tp_silhouette_align_args& a) {
+  if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
+    tp::set_error("tp_silhouette_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
+    return false;
+  }
+  const bool missing = !a.zbuf || !a.sdf || !a.inter || !a.uni;
+  return gn_step_args_ok("tp_silhouette_align_step", a, "tau_px", a.tau_px, missing);
+}
+
+void tp::silhouette_align_launch(const tp_silhouette_align_args& a, hipStream_t st) {
+  const int G = (int)gn_tiles((int64_t)a.H * a.W);
+  double* part = static_cast<double*>(a.workspace);
+  hipLaunchKernelGGL(sil_reduce_kernel, dim3(G, a.B), dim3(kGnBlock), 0, st, a, part);
+  hipLaunchKernelGGL(gn_solve_kernel<tp_silhouette_align_args>, dim3(a.B), dim3(tp::kWave), 0, st, a, (const double*)part, G);
+  hipLaunchKernelGGL(sil_counts_kernel, dim3(a.B), dim3(tp::kWave), 0, st, a, (const double*)part, G);
+}
+
 extern "C" int tp_silhouette_align_step(const tp_silhouette_align_args* a, tp_stream_t stream) {
   if (!a) { tp::set_error("tp_silhouette_align_step: null args"); return -1; }
-  if (a->B <= 0 || a->B > 65535 || a->H <= 0 || a->W <= 0 || a->Ft <= 0 || (int64_t)a->H * a->W > 0x7FFFFFFFll) {
-    tp::set_error("tp_silhouette_align_step: bad sizes (B 1..65535, Ft > 0, H > 0, W > 0, H * W < 2^31)");
-    return -1;
-  }
-  const bool missing = !a->zbuf || !a->sdf || !a->inter || !a->uni;
-  if (!gn_step_args_ok("tp_silhouette_align_step", *a, "tau_px", a->tau_px, missing)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = (int)gn_tiles((int64_t)a->H * a->W);
-  double* part = static_cast<double*>(a->workspace);
-  hipLaunchKernelGGL(sil_reduce_kernel, dim3(G, a->B), dim3(kGnBlock), 0, st, *a, part);
-  hipLaunchKernelGGL(gn_solve_kernel<tp_silhouette_align_args>, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
-  hipLaunchKernelGGL(sil_counts_kernel, dim3(a->B), dim3(tp::kWave), 0, st, *a, (const double*)part, G);
+  if (!tp::silhouette_align_args_ok(*a)) return -1;
+  tp::silhouette_align_launch(*a, (hipStream_t)stream);
   return tp::check_launch("tp_silhouette_align_step");
 }

@@ -25,6 +25,14 @@ def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     """ops.depth_icp_step's rules (include/texpose_amd.h, K29) in plain torch ops in fp64 on the tensors' device: the same arguments ->
     'pose' [B,3,4] float32, 'inliers' [B] int32, 'rms' [B] float32, 'status' [B] int32.  The sums run in torch's order, not the
     kernel's: counts and statuses agree, the rest to rounding."""
+    JtJ, Jtr, cost, count, pose32 = sums_torch(verts, faces, zbuf, face, pose, intr, depth, tau_mm, frame, mask)
+    return _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
+
+
+def sums_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, tau_mm: float,
+               frame: Optional[Tensor] = None, mask: Optional[Tensor] = None):
+    """The sums of step_torch before the solve (what joint.step_torch weights and adds) -> (JtJ [B,6,6], Jtr [B,6], cost [B] fp64,
+    count [B], pose32 [B,3,4])."""
     f64 = torch.float64
     dev = zbuf.device
     B, H, W = zbuf.shape
@@ -74,7 +82,7 @@ def step_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
     cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
     count = torch.bincount(bi, minlength=B)
-    return _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
+    return JtJ, Jtr, cost, count, pose32
 
 
 class DepthRefiner(_MeshRefiner):

@@ -1,5 +1,5 @@
-"""K24-K26, K28-K31: nearest neighbours, the pose errors, VSD, PnP-RANSAC, the depth ICP, the photometric alignment, the masks' distance
-field and the silhouette alignment."""
+"""K24-K26, K28-K33: nearest neighbours, the pose errors, VSD, PnP-RANSAC, the depth ICP, the photometric alignment, the masks' distance
+field, the silhouette alignment and the joint step of the last three."""
 from typing import Dict, Optional
 
 import torch
@@ -11,7 +11,8 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _lengths, _on_
 __all__ = ["NN1_MODES", "nn1", "pose_errors", "vsd", "PNP_MAX_HYP", "PNP_MAX_ITERS", "pnp_workspace", "_pnp_common", "corr_from_nocs",
            "pnp_hypotheses", "pnp_score", "pnp_refine", "PNP_RANSAC_KEYS", "pnp_ransac", "depth_icp_workspace", "depth_icp_step",
            "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS", "photo_align", "mask_sdf_workspace", "mask_sdf",
-           "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align"]
+           "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align",
+           "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align"]
 
 # ------------------------------------------------------------------------------------------ K24, K25
 NN1_MODES = {"nearest": _lib.NN1_NEAREST, "farthest": _lib.NN1_FARTHEST}
@@ -304,14 +305,18 @@ def _frame_planes(op: str, name: str, planes: Tensor, trailing_shape: tuple, fra
     return planes, frame, mask, Ft
 
 
-def _gn_step_outputs(op: str, a, out: Optional[Dict[str, Tensor]], workspace: Optional[Tensor], B: int, dev, workspace_bytes: int) -> Dict[str, Tensor]:
-    """The four outputs of a step (fresh, or those of ``out``) and its workspace, entered into the args struct ``a``."""
-    res = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
-                             "status": (torch.int32, (B,))}, dev, partial=True)
+def _gn_step_outputs(op: str, a, out: Optional[Dict[str, Tensor]], workspace: Optional[Tensor], B: int, dev, workspace_bytes: int,
+                     with_pose: bool = True) -> Dict[str, Tensor]:
+    """The four outputs of a step (fresh, or those of ``out``) and its workspace, entered into the args struct ``a``; without
+    ``with_pose`` (a term of the joint step, which writes no pose of its own) the three others and a null pose_out -> (outputs, workspace)."""
+    spec = {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)), "status": (torch.int32, (B,))}
+    if not with_pose:
+        del spec["pose"]
+    res = _outputs(op, out, spec, dev, partial=True)
     workspace = _workspace_arg(op, workspace, workspace_bytes, dev, align=16)
-    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (res["pose"].data_ptr(), res["inliers"].data_ptr(), res["rms"].data_ptr(),
+    a.pose_out, a.inliers, a.rms, a.status, a.workspace = (_ptr(res.get("pose")), res["inliers"].data_ptr(), res["rms"].data_ptr(),
                                                            res["status"].data_ptr(), workspace.data_ptr())
-    return res
+    return res, workspace
 
 
 def _tau_schedule(op: str, tau, tau_name: str, iters: int):
@@ -357,7 +362,15 @@ def depth_icp_step(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pos
     the ray, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
     depth_icp_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches, no
     atomics, bit-identical from run to run, safe under torch.cuda.graph."""
-    op = "depth_icp_step"
+    a, res, _alive = _depth_icp_args("depth_icp_step", verts, faces, zbuf, face, pose, intr, depth, tau_mm=tau_mm, damping=damping, frame=frame, mask=mask,
+                                     evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_depth_icp_step", a)         # (tau_mm, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+def _depth_icp_args(op: str, verts, faces, zbuf, face, pose, intr, depth, *, tau_mm, damping=1e-6, frame=None, mask=None, evaluate_only=False,
+                    workspace=None, out=None, with_pose=True):
+    """depth_icp_step's arguments, checked, as (the filled tp_depth_icp_args, its outputs, the tensors it points into)."""
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
     B = pose.shape[0]
     faces = _want_gpu(op, faces, "faces", torch.int32, None)
@@ -371,13 +384,12 @@ def depth_icp_step(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pos
     intr = _intr_per_view(op, intr, B)
     depth, frame, mask, Ft = _frame_planes(op, "depth", depth, (), frame, mask, B, H, W, zbuf)
     a = _lib.DepthIcpArgs()
-    res = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)))
+    res, workspace = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), with_pose)
     a.verts, a.faces, a.zbuf, a.face, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), zbuf.data_ptr(), face.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.depth, a.frame, a.mask = depth.data_ptr(), _ptr(frame), _ptr(mask)
     a.V, a.F, a.B, a.Ft, a.H, a.W = verts.shape[0], faces.shape[0], B, Ft, H, W
     a.tau_mm, a.damping, a.evaluate_only = float(tau_mm), float(damping), int(bool(evaluate_only))
-    _call("tp_depth_icp_step", a)         # (tau_mm, damping out of range, out['pose'] overlapping pose: the library's error)
-    return res
+    return a, res, (workspace, verts, faces, zbuf, face, pose, intr, depth, frame, mask)       # (the struct holds addresses only)
 
 
 DEPTH_ICP_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
@@ -431,7 +443,15 @@ def photo_align_step(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, imag
     most ``tau``, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
     photo_align_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches,
     no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
-    op = "photo_align_step"
+    a, res, _alive = _photo_align_args("photo_align_step", zbuf, rgb, pose, intr, image, tau=tau, damping=damping, frame=frame, mask=mask,
+                                       evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_photo_align_step", a)       # (tau, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+def _photo_align_args(op: str, zbuf, rgb, pose, intr, image, *, tau, damping=1e-6, frame=None, mask=None, evaluate_only=False, workspace=None,
+                      out=None, with_pose=True):
+    """photo_align_step's arguments, checked, as (the filled tp_photo_align_args, its outputs, the tensors it points into)."""
     pose = _poses(op, pose, "pose")
     B = pose.shape[0]
     zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
@@ -442,13 +462,12 @@ def photo_align_step(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, imag
     intr = _intr_per_view(op, intr, B)
     image, frame, mask, Ft = _frame_planes(op, "image", image, (3,), frame, mask, B, H, W, zbuf)
     a = _lib.PhotoAlignArgs()
-    res = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)))
+    res, workspace = _gn_step_outputs(op, a, out, workspace, B, zbuf.device, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), with_pose)
     a.zbuf, a.rgb, a.pose, a.intr = zbuf.data_ptr(), rgb.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.image, a.frame, a.mask = image.data_ptr(), _ptr(frame), _ptr(mask)
     a.B, a.Ft, a.H, a.W = B, Ft, H, W
     a.tau, a.damping, a.evaluate_only = float(tau), float(damping), int(bool(evaluate_only))
-    _call("tp_photo_align_step", a)       # (tau, damping out of range, out['pose'] overlapping pose: the library's error)
-    return res
+    return a, res, (workspace, zbuf, rgb, pose, intr, image, frame, mask)       # (the struct holds addresses only)
 
 
 PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
@@ -561,7 +580,15 @@ def silhouette_align_step(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor,
     'uni' [B] int32 (the pixels covered and inside the measured mask, and those with either: IoU = inter / uni).  ``workspace``:
     silhouette_align_workspace(B, H, W); ``out``: any of the six tensors to write into (out['pose'] must not be ``pose``).  Three
     launches, no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
-    op = "silhouette_align_step"
+    a, res, _alive = _silhouette_align_args("silhouette_align_step", zbuf, pose, intr, sdf, tau_px=tau_px, damping=damping, frame=frame, mask=mask,
+                                            evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_silhouette_align_step", a)  # (tau_px, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+def _silhouette_align_args(op: str, zbuf, pose, intr, sdf, *, tau_px, damping=1e-6, frame=None, mask=None, evaluate_only=False, workspace=None,
+                           out=None, with_pose=True):
+    """silhouette_align_step's arguments, checked, as (the filled tp_silhouette_align_args, its outputs, the tensors it points into)."""
     pose = _poses(op, pose, "pose")
     B = pose.shape[0]
     zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
@@ -573,15 +600,14 @@ def silhouette_align_step(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor,
     a = _lib.SilhouetteAlignArgs()
     counts = _outputs(op, None if out is None else {k: v for k, v in out.items() if k in ("inter", "uni")},
                       {"inter": (torch.int32, (B,)), "uni": (torch.int32, (B,))}, zbuf.device, partial=True)
-    res = _gn_step_outputs(op, a, None if out is None else {k: v for k, v in out.items() if k not in ("inter", "uni")}, workspace, B,
-                           zbuf.device, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)))
+    res, workspace = _gn_step_outputs(op, a, None if out is None else {k: v for k, v in out.items() if k not in ("inter", "uni")}, workspace, B,
+                                      zbuf.device, int(_lib.load().tp_silhouette_align_workspace_bytes(B, H, W)), with_pose)
     res.update(counts)
     a.zbuf, a.pose, a.intr, a.sdf, a.frame, a.mask = zbuf.data_ptr(), pose.data_ptr(), intr.data_ptr(), sdf.data_ptr(), _ptr(frame), _ptr(mask)
     a.B, a.Ft, a.H, a.W = B, Ft, H, W
     a.tau_px, a.damping, a.evaluate_only = float(tau_px), float(damping), int(bool(evaluate_only))
     a.inter, a.uni = res["inter"].data_ptr(), res["uni"].data_ptr()
-    _call("tp_silhouette_align_step", a)  # (tau_px, damping out of range, out['pose'] overlapping pose: the library's error)
-    return res
+    return a, res, (workspace, zbuf, pose, intr, sdf, frame, mask)       # (the struct holds addresses only)
 
 
 SILHOUETTE_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0", "iou", "iou0")
@@ -641,5 +667,206 @@ def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, s
         def seen(r, h):
             left = r["uni"] - h                                  # (>= inter: a hidden pixel is covered and not inside)
             return torch.where(left == 0, torch.full_like(left, float("nan"), dtype=torch.float32), r["inter"].float() / left.float())
+        res.update(iou_visible=seen(passes[-1], hidden[-1]), iou0_visible=seen(passes[0], hidden[0]))
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K33
+JOINT_TERMS = ("silhouette", "photo", "depth")           # the order of the weights and of the sum; their result prefixes:
+_JOINT_PREFIX = {"silhouette": "sil_", "photo": "photo_", "depth": "icp_"}
+# 1 / sigma^2 per residual unit (pixels, colour units, mm).  w_photo = 100 is the only one of 25, 100 and 400 with which the twelve
+# occluded cases of DESIGN section 23 all converged; w_icp = 1 / 25 is sigma = 5 mm and is NOT tuned on anything.
+JOINT_WEIGHTS = (1.0, 100.0, 1.0 / 25.0)
+
+
+def _joint_weights(op: str, weights) -> tuple:
+    try:
+        w = tuple(float(x) for x in weights)
+    except TypeError:
+        w = ()
+    if len(w) != 3:
+        raise ValueError("%s: weights must be three host values (silhouette, photo, depth), got %r" % (op, weights))
+    if not all(x >= 0.0 and x != float("inf") for x in w):
+        raise ValueError("%s: weights must be finite and not negative, got %r" % (op, w))
+    return w
+
+
+def joint_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Tensor:
+    """A workspace for joint_align_step / joint_align at B images of H x W with ``terms`` terms present (each term's own
+    ``*_workspace_bytes``, one after the other); needs no clearing."""
+    lib = _lib.load()
+    sizes = (lib.tp_silhouette_align_workspace_bytes, lib.tp_photo_align_workspace_bytes, lib.tp_depth_icp_workspace_bytes)
+    return _workspace_arg("joint_align", None, sum(int(f(B, H, W)) for f in sizes[:int(terms)]), device)
+
+
+@_on_tensor_device
+def joint_align_step(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None, depth: Optional[dict] = None,
+                     weights=JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False, out: Optional[Dict[str, Tensor]] = None,
+                     workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """One JOINT Gauss-Newton step for B poses: the rows of the silhouette, the photometric and the depth term in one normal system
+    (tp_joint_align_step, K33; the rules are in the header).  pose [B,3,4], intr [B,3,3] or one [3,3]; each term that takes part is a
+    dict of that term's own step arguments (planes rendered at ``pose``, threshold, and optionally ``frame`` and ``mask``):
+    ``silhouette`` = dict(zbuf, sdf, tau_px), ``photo`` = dict(zbuf, rgb, image, tau), ``depth`` = dict(verts, faces, zbuf, face, depth,
+    tau_mm).  ``weights`` (w_sil, w_photo, w_icp): 1 / sigma^2 of the term's residual unit; a present term with weight 0 is evaluated
+    but takes no part in the step.  -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a
+    non-zero status), 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels over the weighted terms, 3 not positive definite),
+    'inliers' [B] int32 (their kept pixels, added), 'chi2' [B] (the weighted sum of squares), and per present term that term's own
+    evaluation of ``pose``, bit for bit its ``*_step(evaluate_only=True)``: 'sil_inliers', 'sil_rms', 'sil_status', 'sil_inter',
+    'sil_uni', 'photo_inliers', 'photo_rms', 'photo_status', 'icp_inliers', 'icp_rms', 'icp_status'.  ``workspace``:
+    joint_align_workspace(B, H, W, terms present); ``out``: any of these tensors to write into (out['pose'] must not be ``pose``).
+    With one term at weight 1 'pose' and 'status' are that term's own step's bit for bit.  Each term's launches and one more, no
+    atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "joint_align_step"
+    w = _joint_weights(op, weights)
+    given = dict(zip(JOINT_TERMS, (silhouette, photo, depth)))
+    if all(v is None for v in given.values()):
+        raise ValueError("%s: no term: give at least one of silhouette=, photo=, depth=" % op)
+    if not any(v is not None and x > 0 for v, x in zip(given.values(), w)):
+        raise ValueError("%s: no present term has a weight > 0 (weights %r)" % (op, w))
+    pose = _poses(op, pose, "pose")
+    B = pose.shape[0]
+    intr = _intr_per_view(op, intr, B)
+    shapes = {name: tuple(t["zbuf"].shape) if torch.is_tensor(t.get("zbuf")) else None for name, t in given.items() if t is not None}
+    shape = next(iter(shapes.values()))
+    if len(set(shapes.values())) != 1 or shape is None or len(shape) != 3:
+        raise ValueError("%s: every term needs a zbuf [B,H,W] of one shape, got %r" % (op, shapes))
+    H, W = shape[1:]
+    dev = pose.device
+    lib = _lib.load()
+    sizes = dict(zip(JOINT_TERMS, (lib.tp_silhouette_align_workspace_bytes, lib.tp_photo_align_workspace_bytes, lib.tp_depth_icp_workspace_bytes)))
+    need = {name: (int(sizes[name](B, H, W)) + 15) // 16 * 16 for name in shapes}
+    workspace = _workspace_arg(op, workspace, sum(need.values()), dev, align=16)
+    raw, offset = workspace.view(torch.uint8).reshape(-1), 0
+    builders = dict(silhouette=(_silhouette_align_args, ("zbuf",), ("sdf",), "tau_px"), photo=(_photo_align_args, ("zbuf", "rgb"), ("image",), "tau"),
+                    depth=(_depth_icp_args, ("verts", "faces", "zbuf", "face"), ("depth",), "tau_mm"))
+    res, structs, alive = {}, {}, [workspace]
+    for name in JOINT_TERMS:
+        t = given[name]
+        if t is None:
+            structs[name] = None
+            continue
+        build, before, after, tau_name = builders[name]
+        unknown = set(t) - set(before) - set(after) - {tau_name, "frame", "mask"}
+        missing = [k for k in before + after + (tau_name,) if k not in t]
+        if unknown or missing:
+            raise ValueError("%s: the %s term takes %s, frame and mask; missing %s, unknown %s"
+                             % (op, name, ", ".join(before + after + (tau_name,)), missing, sorted(unknown)))
+        prefix = _JOINT_PREFIX[name]
+        term_out = None if out is None else {k[len(prefix):]: v for k, v in out.items() if k.startswith(prefix)}
+        a, r, keep = build("%s (%s)" % (op, name), *[t[k] for k in before], pose, intr, *[t[k] for k in after], **{tau_name: t[tau_name]},
+                           damping=damping, frame=t.get("frame"), mask=t.get("mask"), evaluate_only=True,
+                           workspace=raw[offset:offset + need[name]], out=term_out, with_pose=False)
+        offset += need[name]
+        structs[name] = a
+        alive.append(keep)
+        res.update({prefix + k: v for k, v in r.items()})
+    joint = _outputs(op, None if out is None else {k: v for k, v in out.items() if k in ("pose", "status", "inliers", "chi2")},
+                     {"pose": (torch.float32, (B, 3, 4)), "status": (torch.int32, (B,)), "inliers": (torch.int32, (B,)), "chi2": (torch.float32, (B,))},
+                     dev, partial=True)
+    j = _lib.JointAlignArgs()
+    j.B, j.pose, j.w_sil, j.w_photo, j.w_icp, j.damping, j.evaluate_only = B, pose.data_ptr(), w[0], w[1], w[2], float(damping), int(bool(evaluate_only))
+    j.pose_out, j.status, j.inliers, j.chi2 = joint["pose"].data_ptr(), joint["status"].data_ptr(), joint["inliers"].data_ptr(), joint["chi2"].data_ptr()
+    _call("tp_joint_align_step", j, structs["silhouette"], structs["photo"], structs["depth"])
+    return dict(joint, **res)
+
+
+JOINT_ALIGN_KEYS = ("pose", "inliers", "chi2", "status", "inliers0", "chi20")
+
+
+@_on_tensor_device
+def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vcolor: Optional[Tensor] = None, sdf: Optional[Tensor] = None,
+                image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
+                iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
+                workspace: Optional[Tensor] = None, visible_iou: bool = False) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
+    (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
+    one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
+    only for the planes the present terms need, followed by joint_align_step, the last with evaluate_only.  The outline gives the
+    basin, the texture or the depth pins what the outline leaves loose: under occlusion the terms run one after the other end far
+    away where this loop converges.  ``weights`` (w_sil, w_photo, w_icp) = 1 / sigma^2 per residual unit, default (1, 100, 1 / 25):
+    w_photo = 100 is the only one of 25, 100 and 400 with which all twelve occluded cases of DESIGN section 23 converged; w_icp is
+    sigma = 5 mm and is NOT tuned on anything.  ``tau_px`` / ``tau`` / ``tau_mm``: each term's threshold, one value or ``iters`` + 1
+    host values.  ``frame`` [B] int32: the measured plane of each pose, for every term.  ``masks``: dict(silhouette=, photo=, depth=)
+    of [Ft,H,W] uint8 / bool planes (0: the term skips the pixel).  -> 'pose' [B,3,4], its 'inliers' [B] int32 and 'chi2' [B],
+    'status' [B] int32 of the last step taken (of the evaluation where iters = 0), 'inliers0' / 'chi20' of the start pose, and the
+    last pass's per-term keys of joint_align_step; with ``sdf`` also 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' /
+    'iou0_visible', as silhouette_align.  A step that fails passes its pose on.  Bit-identical from run to run, safe under
+    torch.cuda.graph."""
+    op = "joint_align"
+    w = _joint_weights(op, weights)
+    iters = int(iters)
+    taus = list(zip(_tau_schedule(op, tau_px, "tau_px", iters), _tau_schedule(op, tau, "tau", iters), _tau_schedule(op, tau_mm, "tau_mm", iters)))
+    if sdf is None and image is None and depth is None:
+        raise ValueError("%s: no term: give at least one of sdf=, image=, depth=" % op)
+    if image is not None and vcolor is None:
+        raise ValueError("%s: image= needs vcolor=, the mesh's colours [V,3]" % op)
+    masks = dict(masks or {})
+    if set(masks) - set(JOINT_TERMS):
+        raise ValueError("%s: masks takes the keys %s, got %s" % (op, JOINT_TERMS, sorted(masks)))
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    intr = _intr_per_view(op, intr, B)
+    planes = {}
+    for name, t, trailing in (("sdf", sdf, ()), ("image", image, (3,)), ("depth", depth, ())):
+        if t is None:
+            continue
+        t = _f32(t.detach(), name)
+        t = t[None] if t.dim() == 2 + len(trailing) else t
+        if t.dim() != 3 + len(trailing) or t.numel() == 0 or tuple(t.shape[3:]) != trailing:
+            raise ValueError("%s: %s [Ft,H,W%s] expected, got %s" % (op, name, ",3" if trailing else "", tuple(t.shape)))
+        planes[name] = t
+    sizes = {tuple(t.shape[1:3]) for t in planes.values()}
+    if len(sizes) != 1:
+        raise ValueError("%s: the measured planes must be of one size H x W, got %s" % (op, {k: tuple(v.shape) for k, v in planes.items()}))
+    H, W = sizes.pop()
+    term_of = dict(sdf="silhouette", image="photo", depth="depth")
+    for name, trailing in (("sdf", ()), ("image", (3,)), ("depth", ())):
+        if name in planes:
+            planes[name], _, masks[term_of[name]], _ = _frame_planes(op, name, planes[name], trailing, frame, masks.get(term_of[name]), B, H, W, pose)
+    if vcolor is not None:
+        vcolor = _f32(vcolor.detach(), "vcolor")
+    lib = _lib.load()
+    need = sum((int(f(B, H, W)) + 15) // 16 * 16 for f, name in ((lib.tp_silhouette_align_workspace_bytes, "sdf"), (lib.tp_photo_align_workspace_bytes, "image"),
+                                                                 (lib.tp_depth_icp_workspace_bytes, "depth")) if name in planes)
+    workspace = _workspace_arg(op, workspace, need, pose.device, align=16)
+    from .scene import mesh_raster
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor if "image" in planes else None, face_ids="depth" in planes,
+                                   normals=False)
+    passes, hidden = [], []
+    if visible_iou:
+        if "sdf" not in planes:
+            raise ValueError("%s: visible_iou needs sdf=" % op)
+        unknown = torch.isnan(planes["sdf"])
+        if frame is not None:
+            unknown = unknown[frame.clamp(0, planes["sdf"].shape[0] - 1).long()]
+
+    def step(r, P, t, last):
+        terms = {}
+        if "sdf" in planes:
+            terms["silhouette"] = dict(zbuf=r["zbuf"], sdf=planes["sdf"], tau_px=t[0], frame=frame, mask=masks.get("silhouette"))
+        if "image" in planes:
+            terms["photo"] = dict(zbuf=r["zbuf"], rgb=r["rgb"], image=planes["image"], tau=t[1], frame=frame, mask=masks.get("photo"))
+        if "depth" in planes:
+            terms["depth"] = dict(verts=verts, faces=faces, zbuf=r["zbuf"], face=r["face"], depth=planes["depth"], tau_mm=t[2], frame=frame,
+                                  mask=masks.get("depth"))
+        got = joint_align_step(P, intr, weights=w, damping=damping, evaluate_only=last, workspace=workspace, **terms)
+        got["rms"] = got["chi2"]                                 # (_refine_loop's name for the cost it carries)
+        passes.append(got)
+        if visible_iou and (len(passes) == 1 or last):
+            z = r["zbuf"]
+            hidden.append(((z > 0) & torch.isfinite(z) & unknown).flatten(1).sum(1))
+        return got
+
+    res = _refine_loop(pose, taus, raster, step)
+    res["chi2"], res["chi20"] = res.pop("rms"), res.pop("rms0")
+    res.update({k: v for k, v in passes[-1].items() if k.startswith(tuple(_JOINT_PREFIX.values()))})
+    if "sdf" in planes:
+        iou = lambda r: r["sil_inter"].float() / r["sil_uni"].float()
+        res.update(iou=iou(passes[-1]), iou0=iou(passes[0]))
+    if visible_iou:
+        def seen(r, h):
+            left = r["sil_uni"] - h                              # (>= inter: a hidden pixel is covered and not inside)
+            return torch.where(left == 0, torch.full_like(left, float("nan"), dtype=torch.float32), r["sil_inter"].float() / left.float())
         res.update(iou_visible=seen(passes[-1], hidden[-1]), iou0_visible=seen(passes[0], hidden[0]))
     return res

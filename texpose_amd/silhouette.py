@@ -73,6 +73,16 @@ def step_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: fl
     """ops.silhouette_align_step's rules (include/texpose_amd.h, K31b) in plain torch ops in fp64 on the tensors' device: the same
     arguments -> 'pose' [B,3,4] float32, 'inliers' [B] int32, 'rms' [B] float32, 'status', 'inter', 'uni' [B] int32.  The sums run in
     torch's order, not the kernel's: the counts and statuses agree, the rest to rounding."""
+    JtJ, Jtr, cost, count, pose32, inter, uni = sums_torch(zbuf, pose, intr, sdf, tau_px, frame, mask)
+    res = _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
+    res.update(inter=inter, uni=uni)
+    return res
+
+
+def sums_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: float, frame: Optional[Tensor] = None,
+               mask: Optional[Tensor] = None):
+    """The sums of step_torch before the solve (what joint.step_torch weights and adds) -> (JtJ [B,6,6], Jtr [B,6], cost [B] fp64,
+    count [B], pose32 [B,3,4], inter, uni [B] int32)."""
     f64 = torch.float64
     dev = zbuf.device
     B, H, W = zbuf.shape
@@ -119,9 +129,7 @@ def step_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: fl
     Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
     cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
     count = torch.bincount(bi, minlength=B)
-    res = _gn_torch.solve(JtJ, Jtr, cost, count, pose32, damping, evaluate_only)
-    res.update(inter=inter.to(torch.int32), uni=uni.to(torch.int32))
-    return res
+    return JtJ, Jtr, cost, count, pose32, inter.to(torch.int32), uni.to(torch.int32)
 
 
 class SilhouetteRefiner(_MeshRefiner):

@@ -4,6 +4,7 @@
 
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
+                                 [--joint [--iters-joint N] [--weights SIL RGB DEPTH]]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -35,7 +36,15 @@ a pixel within --occluder-band pixels (default 1.0; not tuned on anything) of an
 nor clear in the distance field, and no rim pixel there pulls on the pose.  Conservative: where two instances touch, both lose the
 contour between them, the one in front too.  --known DIR gives such planes directly: PNGs with the mask files' names, non-zero:
 the pixel was measured.  The two exclude each other.  With either the tool also prints the mean visible IoU, the IoU over the known
-pixels only, before and after.  With less than about half of an object visible the outline still closes and the pose need not."""
+pixels only, before and after.  With less than about half of an object visible the outline still closes and the pose need not.
+
+--joint: the terms named by --silhouette, --rgb and --depth (at least two; --rgb and --depth may go together here)
+in ONE loop of --iters-joint steps (default 20), all their residual rows in one Gauss-Newton system per step (texpose_amd.joint, K33),
+instead of one refiner after the other: under occlusion the silhouette stage alone walks off and the next stage cannot come back.
+--weights SIL RGB DEPTH: 1 / sigma^2 of each term's residual unit, default 1 100 0.04 (the photometric weight is the one that
+converged on the occluded cases of section 23; the depth weight is sigma = 5 mm and is not tuned on anything).  --tau-px, --tau-rgb and
+--tau-mm are the terms' thresholds (one value or iters-joint + 1 each); --occluders, --known and --use-mask-visib apply as above and
+also mask the other terms.  Without --joint nothing changes."""
 import argparse
 import csv
 import json
@@ -95,18 +104,30 @@ def main(argv=None):
     ap.add_argument("--occluders", action="store_true", help="with --silhouette: pixels near another instance's mask are unknown")
     ap.add_argument("--occluder-band", type=float, default=1.0, metavar="PX")
     ap.add_argument("--known", default=None, metavar="DIR", help="with --silhouette: PNGs with the mask files' names, non-zero: known")
+    ap.add_argument("--joint", action="store_true", help="the terms named by --silhouette, --rgb, --depth in one loop")
+    ap.add_argument("--iters-joint", type=int, default=20)
+    ap.add_argument("--weights", type=float, nargs=3, default=None, metavar=("SIL", "RGB", "DEPTH"))
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if not a.device.startswith("cuda"):
         sys.exit("refine_poses: the refinement runs the HIP kernels, which have no CPU route; use --device cuda:N")
+    if a.joint:
+        if a.silhouette + a.rgb + a.depth < 2:
+            sys.exit("refine_poses: --joint combines at least two of --silhouette, --rgb and --depth")
+        for name, values in (("--tau-px", a.tau_px), ("--tau-rgb", a.tau_rgb), ("--tau-mm", a.tau_mm)):
+            if len(values) not in (1, a.iters_joint + 1):
+                sys.exit("refine_poses: with --joint %s takes one value or iters-joint + 1 = %d values" % (name, a.iters_joint + 1))
+        a.iters = a.iters_rgb = a.iters_sil = a.iters_joint      # (the per-stage checks below then say the same)
+    elif a.weights is not None:
+        sys.exit("refine_poses: --weights goes with --joint")
     if len(a.tau_mm) not in (1, a.iters + 1):
         sys.exit("refine_poses: --tau-mm takes one value or iters + 1 = %d values" % (a.iters + 1))
     if a.rgb and len(a.tau_rgb) not in (1, a.iters_rgb + 1):
         sys.exit("refine_poses: --tau-rgb takes one value or iters-rgb + 1 = %d values" % (a.iters_rgb + 1))
     if a.silhouette and len(a.tau_px) not in (1, a.iters_sil + 1):
         sys.exit("refine_poses: --tau-px takes one value or iters-sil + 1 = %d values" % (a.iters_sil + 1))
-    if a.rgb and a.depth:
+    if a.rgb and a.depth and not a.joint:
         sys.exit("refine_poses: --depth and --rgb exclude each other")
     if a.occluders and a.known:
         sys.exit("refine_poses: --occluders and --known exclude each other")
@@ -114,7 +135,7 @@ def main(argv=None):
         sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
     from PIL import Image
-    from texpose_amd import icp, ops, photo_align, silhouette
+    from texpose_amd import icp, joint, ops, photo_align, silhouette
     from texpose_amd.pose_error import depth_from_png
     from texpose_amd.surfel import load_ply
     if not torch.cuda.is_available():
@@ -141,7 +162,7 @@ def main(argv=None):
     tau = a.tau_mm[0] if len(a.tau_mm) == 1 else a.tau_mm
     tau_rgb = a.tau_rgb[0] if len(a.tau_rgb) == 1 else a.tau_rgb
     tau_px = a.tau_px[0] if len(a.tau_px) == 1 else a.tau_px
-    second = a.rgb or a.depth or not a.silhouette                # the depth / RGB refinement runs (after the silhouette's, if any)
+    second = not a.joint and (a.rgb or a.depth or not a.silhouette)          # the depth / RGB refinement runs (after the silhouette's, if any)
     iou_sum, visible_sum = np.zeros(2), np.zeros(2)
     refined = failed = 0
     dev = a.device
@@ -175,15 +196,26 @@ def main(argv=None):
                     own = [k for k, e in enumerate(gt[str(f)]) if int(e["obj_id"]) == oid][0]
                     per_frame.append(ops.mask_known_from_others(ops.mask_sdf(every), a.occluder_band)[own])
                 known = torch.stack(per_frame)
-            if a.rgb:
-                planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
-                          for f in frames]
-            elif second:
-                planes = [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
-                          for f in frames]
-            depth = torch.stack(planes) if second else measured  # (with --rgb: the photographs [Ft,H,W,3])
+            read_rgb = lambda: [torch.from_numpy(np.asarray(Image.open(os.path.join(a.scene, "rgb", "%06d.png" % f)).convert("RGB"), np.float32) / 255.0)
+                                for f in frames]
+            read_depth = lambda: [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
+                                  for f in frames]
+            if a.joint:
+                photos = torch.stack(read_rgb()).to(dev) if a.rgb else None
+                ranges = torch.stack(read_depth()).to(dev) if a.depth else None
+                depth = measured if a.silhouette else photos     # (any of the measured planes: the size)
+            else:
+                if a.rgb:
+                    planes = read_rgb()
+                elif second:
+                    planes = read_depth()
+                depth = torch.stack(planes) if second else measured  # (with --rgb: the photographs [Ft,H,W,3])
             H, W = depth.shape[1:3]
-            if a.silhouette and (outline is None or (outline.H, outline.W) != (H, W)):
+            if a.joint and (refiner is None or (refiner.H, refiner.W) != (H, W)):
+                refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=meshes.get(oid, meshes.get(None))[2] if a.rgb else None,
+                                             weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
+                                             damping=a.damping)
+            if a.silhouette and not a.joint and (outline is None or (outline.H, outline.W) != (H, W)):
                 outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
@@ -197,7 +229,14 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.time()
             start, K = torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev)
-            if a.silhouette:
+            if a.joint:
+                r = refiner.refine(start, K, mask_or_sdf=measured, known=known, image=photos, depth=ranges, frame=index,
+                                   masks=None if mask is None else dict(silhouette=mask, photo=mask, depth=mask))
+                if a.silhouette:
+                    iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
+                    if known is not None:
+                        visible_sum += [float(r.iou0_visible.double().sum()), float(r.iou_visible.double().sum())]
+            elif a.silhouette:
                 r = outline.refine(start, K, measured, frame=index, mask=mask, known=known)
                 start = r.pose
                 iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
