@@ -807,6 +807,18 @@ typedef struct tp_mesh_raster_args {
 } tp_mesh_raster_args;
 size_t tp_mesh_raster_workspace_bytes(int B, int H, int W, int F);
 int tp_mesh_raster(const tp_mesh_raster_args* args, tp_stream_t stream);
+/* K34  tp_mesh_raster with the face chunks culled per tile: the same arguments, refusals and limits, and every output plane is
+ *      tp_mesh_raster's bit for bit for every input (any face order, dropped faces, NaN poses, a mesh outside the image;
+ *      normals_from_zbuf runs the normal stage alone, as there).  One launch more (four, three without normals): after the face
+ *      setup one int4 per (image, chunk of 256 face records) takes the union of the chunk's pixel boxes, and a 16 x 16 tile
+ *      enters a chunk only if that box overlaps it.  A pixel keeps the minimum of (bits of z, face index) over the faces shown to
+ *      it, and a skipped chunk holds no face whose box reaches the tile, so the minimum is unchanged.  The gain depends on how
+ *      compact the chunks are on screen: a face order that is coherent in space (texpose_amd.surfel.coherent_face_order) gives the
+ *      most, a shuffled one still skips every tile outside the object's box.
+ *      workspace: 64 B F bytes of face records, then 16 bytes per (image, chunk): 64 B F + 16 B ceil(F / 256), 16-byte aligned;
+ *      the query returns 0 for B <= 0 or F <= 0.  No allocation, no host synchronisation, no atomics; safe to capture. */
+size_t tp_mesh_raster_culled_workspace_bytes(int B, int H, int W, int F);
+int tp_mesh_raster_culled(const tp_mesh_raster_args* args, tp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K20  the data layer's finish of the surfel maps: from tp_mesh_raster's outputs to the four tensors the reference's data

@@ -11,8 +11,9 @@ Tensor = torch.Tensor
 class _MeshRefiner:
     _new_workspace = None                    # ops.<refiner>_workspace(B, H, W, device)
 
-    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device):
+    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device, cull: bool = False):
         self.H, self.W, self.device = int(H), int(W), torch.device(device)
+        self.cull = bool(cull)               # the loop's passes render with ops.mesh_raster(cull=True): the same bits (K34)
         if self.device.type != "cuda":
             raise ops._lib.TexposeLibraryError("%s runs the HIP kernels: a GPU device is needed (step_torch alone has a CPU route)"
                                                % type(self).__name__)

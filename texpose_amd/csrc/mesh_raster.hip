@@ -11,6 +11,11 @@
 //      (bits of z, face index): the winner does not depend on the order faces arrive in, and no atomics are needed.  Shading of the
 //      winner (perspective-correct vertex colour and NOCS) follows in the same kernel.
 //   3. normals from the depth map, one thread per pixel, in fp64 (compute_surfelinfo.normal_from_depth, see normal_kernel).
+//
+// K34  tp_mesh_raster_culled: the same planes, bit for bit, with one launch more.  Between 1 and 2 chunk_box_kernel stores the union of
+//      the pixel boxes of every chunk of 256 face records; raster_culled_kernel tests a tile against that one box before it enters the
+//      chunk.  A pixel's key minimum is taken over a superset of the faces whose boxes hold it, so skipping a chunk whose union box
+//      misses the tile removes only faces that could not have entered the minimum: no output bit changes.
 #include "tp_common.h"
 
 namespace {
@@ -186,6 +191,187 @@ __global__ void __launch_bounds__(kChunk) raster_kernel(RasterParams p, int tile
   }
 }
 
+// ---- K34: chunk boxes + the culled raster ---------------------------------------------------------------------------------------
+// The body of raster_kernel's chunk loop and its epilogue as functions for raster_culled_kernel: the same tests and the same rounded
+// operations per face, so the same keys.  raster_kernel above keeps its own text, so the parent's kernel compiles from unchanged
+// source.  Two things differ in how the chunk body WAITS, not in what it computes: a tile that enters few chunks gets nothing from
+// other tiles' loads, so (1) word 0 of the chunk's records comes from the caller, who loads the next surviving chunk's before this
+// one is processed (one dependent round of loads per chunk instead of two), and (2) the candidate loop reads record k + 1 from LDS
+// before it evaluates record k.
+struct TileCtx { int tid, lane, wave, b, tx0, ty0, tx1, ty1, j, i; };
+
+__device__ __forceinline__ TileCtx tile_ctx(const RasterParams& p, int tiles_x) {
+  TileCtx t;
+  t.tid = threadIdx.x; t.lane = t.tid & 63; t.wave = t.tid >> 6;
+  t.b = blockIdx.y;
+  t.tx0 = (blockIdx.x % tiles_x) * kTile; t.ty0 = (blockIdx.x / tiles_x) * kTile;
+  t.tx1 = min(t.tx0 + kTile, p.W) - 1; t.ty1 = min(t.ty0 + kTile, p.H) - 1;
+  t.j = t.tx0 + (t.tid % kTile); t.i = t.ty0 + (t.tid / kTile);
+  return t;
+}
+
+// word 0 of record base + tid (zeros for f >= F: tested by nobody)
+__device__ __forceinline__ float4 chunk_word0(const RasterParams& p, const TileCtx& t, const float4* rec, int base) {
+  const int f = base + t.tid;
+  return f < p.F ? rec[4 * (int64_t)f] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// one chunk of 256 records from ``base`` on, ``r0`` = chunk_word0(base): box test, ballot compaction into s_rec, the bary_at tests, the
+// key minimum.  Every thread of the workgroup calls it with the same ``base`` (three barriers inside).
+__device__ __forceinline__ void raster_chunk(const RasterParams& p, const TileCtx& t, const float4* rec, int base, float4 r0, float4 (*s_rec)[4],
+                                             int* s_wave_count, unsigned long long& best) {
+  const int f = base + t.tid;
+  const bool keep = f < p.F && __float_as_int(r0.x) <= t.tx1 && __float_as_int(r0.y) >= t.tx0 && __float_as_int(r0.z) <= t.ty1 &&
+                    __float_as_int(r0.w) >= t.ty0;
+  const unsigned long long m = __ballot(keep);
+  if (t.lane == 0) s_wave_count[t.wave] = __popcll(m);
+  __syncthreads();
+  int off = 0, n = 0;
+#pragma unroll
+  for (int w = 0; w < kChunk / tp::kWave; ++w) {
+    const int c = s_wave_count[w];
+    off += (w < t.wave) ? c : 0;
+    n += c;
+  }
+  if (keep) {
+    const int slot = off + __popcll(m & ((1ull << t.lane) - 1ull));
+    r0.y = __int_as_float(f);                          // the face index rides in the (already tested) jmax word
+    s_rec[slot][0] = r0;
+    s_rec[slot][1] = rec[4 * (int64_t)f + 1];
+    s_rec[slot][2] = rec[4 * (int64_t)f + 2];
+    s_rec[slot][3] = rec[4 * (int64_t)f + 3];
+  }
+  __syncthreads();
+  float4 n0 = s_rec[0][0], n1 = s_rec[0][1], n2 = s_rec[0][2], n3 = s_rec[0][3];      // (n = 0: read and never used)
+  for (int k = 0; k < n; ++k) {
+    const float4 r0k = n0, r1 = n1, r2 = n2, r3 = n3;
+    const int kn = min(k + 1, kChunk - 1);               // the next record, in flight while this one is evaluated (k + 1 = n: unused)
+    n0 = s_rec[kn][0]; n1 = s_rec[kn][1]; n2 = s_rec[kn][2]; n3 = s_rec[kn][3];
+    const Bary q = bary_at(r0k, r1, r2, r3, t.j, t.i);
+    if (q.b0 > 0.f && q.b1 > 0.f && q.b2 > 0.f) {
+      const float z = __fdiv_rn(1.0f, q.zinv);
+      if (z > 1e-8f && z < INFINITY) {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)__float_as_int(r0k.y);
+        best = key < best ? key : best;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// background values or the winner's planes of pixel (t.j, t.i)
+__device__ __forceinline__ void raster_epilogue(const RasterParams& p, const TileCtx& t, const float4* rec, unsigned long long best) {
+  const int j = t.j, i = t.i;
+  if (j >= p.W || i >= p.H) return;
+  const int64_t pix = ((int64_t)t.b * p.H + i) * p.W + j;
+  if (best == ~0ull) {
+    p.zbuf[pix] = -1.0f;
+    if (p.face) p.face[pix] = -1;
+    for (int c = 0; c < 3; ++c) {
+      if (p.rgb) p.rgb[3 * pix + c] = 0.0f;
+      if (p.nocs) p.nocs[3 * pix + c] = 0.0f;
+    }
+    return;
+  }
+  const int f = (int)(best & 0xffffffffu);
+  p.zbuf[pix] = __uint_as_float((unsigned)(best >> 32));
+  if (p.face) p.face[pix] = f;
+  if (!p.rgb && !p.nocs) return;
+  const float4* r = rec + 4 * (int64_t)f;
+  const float4 r3 = r[3];
+  const Bary q = bary_at(r[0], r[1], r[2], r3, j, i);
+  // perspective-corrected barycentrics (b_k / z_k) / sum_m (b_m / z_m)
+  const float w0 = __fdiv_rn(__fmul_rn(q.b0, r3.y), q.zinv), w1 = __fdiv_rn(__fmul_rn(q.b1, r3.z), q.zinv);
+  const float w2 = __fdiv_rn(__fmul_rn(q.b2, r3.w), q.zinv);
+  const int v0 = p.faces[3 * (int64_t)f], v1 = p.faces[3 * (int64_t)f + 1], v2 = p.faces[3 * (int64_t)f + 2];
+  for (int c = 0; c < 3; ++c) {
+    if (p.rgb) {
+      const float a0 = p.vcolor[3 * (int64_t)v0 + c], a1 = p.vcolor[3 * (int64_t)v1 + c], a2 = p.vcolor[3 * (int64_t)v2 + c];
+      p.rgb[3 * pix + c] = __fmaf_rn(w2, a2, __fmaf_rn(w1, a1, __fmul_rn(w0, a0)));
+    }
+    if (p.nocs) {
+      const float ct = p.nocs_center[c], sc = p.nocs_scale[c];
+      const float a0 = __fmul_rn(__fadd_rn(__fdiv_rn(__fsub_rn(p.verts[3 * (int64_t)v0 + c], ct), sc), 1.0f), 0.5f);
+      const float a1 = __fmul_rn(__fadd_rn(__fdiv_rn(__fsub_rn(p.verts[3 * (int64_t)v1 + c], ct), sc), 1.0f), 0.5f);
+      const float a2 = __fmul_rn(__fadd_rn(__fdiv_rn(__fsub_rn(p.verts[3 * (int64_t)v2 + c], ct), sc), 1.0f), 0.5f);
+      p.nocs[3 * pix + c] = __fmaf_rn(w2, a2, __fmaf_rn(w1, a1, __fmul_rn(w0, a0)));
+    }
+  }
+}
+
+// chunk c of image b: the union (jmin, jmax, imin, imax) of the boxes of records c * 256 .. c * 256 + 255.  A dropped face holds the
+// empty box (INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN), which is also what stands for f >= F and is neutral under min / max.
+__global__ void __launch_bounds__(kChunk) chunk_box_kernel(RasterParams p, int4* cbox, int n_chunks) {
+  __shared__ int4 s_box[kChunk / tp::kWave];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, f = (int)blockIdx.x * kChunk + tid;
+  int4 box = make_int4(INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN);
+  if (f < p.F) {
+    const float4 r0 = p.rec[4 * ((int64_t)b * p.F + f)];
+    box = make_int4(__float_as_int(r0.x), __float_as_int(r0.y), __float_as_int(r0.z), __float_as_int(r0.w));
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    box.x = min(box.x, __shfl_xor(box.x, s));
+    box.y = max(box.y, __shfl_xor(box.y, s));
+    box.z = min(box.z, __shfl_xor(box.z, s));
+    box.w = max(box.w, __shfl_xor(box.w, s));
+  }
+  if (lane == 0) s_box[wave] = box;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < kChunk / tp::kWave; ++w) {
+      const int4 o = s_box[w];
+      box.x = min(box.x, o.x); box.y = max(box.y, o.y); box.z = min(box.z, o.z); box.w = max(box.w, o.w);
+    }
+    cbox[(int64_t)b * n_chunks + blockIdx.x] = box;
+  }
+}
+
+// raster_kernel with the chunks culled first: rounds of 256 chunk boxes are tested against the tile (the four inclusive comparisons
+// of the face test), the survivors' indices are compacted in ascending order into s_list, and each runs raster_chunk.  A chunk whose
+// union box misses the tile holds no face whose box overlaps it, so the key minimum is taken over the same faces as in raster_kernel.
+// n_chunks, the rounds and the survivor count are workgroup-uniform: every barrier is reached by all 256 threads.
+__global__ void __launch_bounds__(kChunk) raster_culled_kernel(RasterParams p, int tiles_x, const int4* cbox, int n_chunks) {
+  __shared__ float4 s_rec[kChunk][4];
+  __shared__ int s_wave_count[kChunk / tp::kWave];
+  __shared__ int s_list[kChunk];
+  __shared__ int s_list_count[kChunk / tp::kWave];
+  const TileCtx t = tile_ctx(p, tiles_x);
+  const float4* rec = p.rec + 4 * (int64_t)t.b * p.F;
+  const int4* boxes = cbox + (int64_t)t.b * n_chunks;
+  unsigned long long best = ~0ull;
+  for (int cbase = 0; cbase < n_chunks; cbase += kChunk) {
+    const int c = cbase + t.tid;
+    bool keep = false;
+    if (c < n_chunks) {
+      const int4 bx = boxes[c];
+      keep = bx.x <= t.tx1 && bx.y >= t.tx0 && bx.z <= t.ty1 && bx.w >= t.ty0;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (t.lane == 0) s_list_count[t.wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, n = 0;
+#pragma unroll
+    for (int w = 0; w < kChunk / tp::kWave; ++w) {
+      const int cnt = s_list_count[w];
+      off += (w < t.wave) ? cnt : 0;
+      n += cnt;
+    }
+    if (keep) s_list[off + __popcll(m & ((1ull << t.lane) - 1ull))] = c;
+    __syncthreads();
+    float4 next = n > 0 ? chunk_word0(p, t, rec, s_list[0] * kChunk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < n; ++k) {
+      const float4 r0 = next;
+      if (k + 1 < n) next = chunk_word0(p, t, rec, s_list[k + 1] * kChunk);          // in flight while chunk k is processed
+      raster_chunk(p, t, rec, s_list[k] * kChunk, r0, s_rec, s_wave_count, best);
+    }
+    __syncthreads();          // (n = 0: s_list_count is rewritten next round only after every thread has read it)
+  }
+  raster_epilogue(p, t, rec, best);
+}
+
 // ---- 3. normals from depth ------------------------------------------------------------------------------------------------------
 // compute_surfelinfo.normal_from_depth: points = centre + ray * depth with ray = R^T K^-1 (u, v, 1) (camera z component 1, not
 // normalised) and centre = -R^T t; background neighbours enter with their depth of -1, unmasked; tu = p[i, j+1] - p[i, j-1],
@@ -243,24 +429,42 @@ extern "C" size_t tp_mesh_raster_workspace_bytes(int B, int H, int W, int F) {
   return (size_t)B * (size_t)F * kRecFloats * sizeof(float);
 }
 
-extern "C" int tp_mesh_raster(const tp_mesh_raster_args* a, tp_stream_t stream) {
-  TP_REQUIRE(a, "null pointer");
-  TP_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0 && a->H <= 16384 && a->W <= 16384, "bad sizes");
-  TP_REQUIRE(a->pose && a->intr && a->zbuf, "null pointer");
+// the face records as above, then one int4 per (image, chunk of 256 records); 64 B F is a multiple of 16, so the boxes are aligned
+extern "C" size_t tp_mesh_raster_culled_workspace_bytes(int B, int H, int W, int F) {
+  const size_t records = tp_mesh_raster_workspace_bytes(B, H, W, F);
+  if (records == 0) return 0;
+  return records + (size_t)B * (size_t)((F + kChunk - 1) / kChunk) * sizeof(int4);
+}
+
+namespace {
+
+// both entry points: one set of checks (the messages carry the caller's name), then three launches or, culled, four
+int mesh_raster_launch(const char* what, const tp_mesh_raster_args* a, tp_stream_t stream, bool culled) {
+#define RASTER_REQUIRE(cond, msg)          \
+  do {                                     \
+    if (!(cond)) {                         \
+      tp::set_error("%s: %s", what, msg);  \
+      return -1;                           \
+    }                                      \
+  } while (0)
+  RASTER_REQUIRE(a, "null pointer");
+  RASTER_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0 && a->H <= 16384 && a->W <= 16384, "bad sizes");
+  RASTER_REQUIRE(a->pose && a->intr && a->zbuf, "null pointer");
   if (a->normals_from_zbuf) {
-    TP_REQUIRE(a->normal, "normals_from_zbuf without a normal output");
+    RASTER_REQUIRE(a->normal, "normals_from_zbuf without a normal output");
     RasterParams p = {};
     p.pose = a->pose; p.intr = a->intr; p.B = a->B; p.H = a->H; p.W = a->W; p.zbuf = a->zbuf; p.normal = a->normal;
     const int64_t np = (int64_t)a->B * a->H * a->W;
     hipLaunchKernelGGL(normal_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return tp::check_launch("tp_mesh_raster");
+    return tp::check_launch(what);
   }
-  TP_REQUIRE(a->V > 0 && a->F > 0, "bad sizes");
-  TP_REQUIRE(a->verts && a->faces && a->workspace, "null pointer");
-  TP_REQUIRE(a->rgb == nullptr || a->vcolor != nullptr, "rgb requested without vertex colours");
-  TP_REQUIRE(a->nocs == nullptr || (a->nocs_scale[0] > 0.f && a->nocs_scale[1] > 0.f && a->nocs_scale[2] > 0.f),
-             "nocs requested with a non-positive normalisation scale");
-  TP_REQUIRE(((uintptr_t)a->workspace & 15) == 0, "workspace must be 16-byte aligned");
+  RASTER_REQUIRE(a->V > 0 && a->F > 0, "bad sizes");
+  RASTER_REQUIRE(a->verts && a->faces && a->workspace, "null pointer");
+  RASTER_REQUIRE(a->rgb == nullptr || a->vcolor != nullptr, "rgb requested without vertex colours");
+  RASTER_REQUIRE(a->nocs == nullptr || (a->nocs_scale[0] > 0.f && a->nocs_scale[1] > 0.f && a->nocs_scale[2] > 0.f),
+                 "nocs requested with a non-positive normalisation scale");
+  RASTER_REQUIRE(((uintptr_t)a->workspace & 15) == 0, "workspace must be 16-byte aligned");
+#undef RASTER_REQUIRE
   RasterParams p;
   p.verts = a->verts; p.faces = a->faces; p.vcolor = a->vcolor;
   for (int c = 0; c < 3; ++c) { p.nocs_center[c] = a->nocs_center[c]; p.nocs_scale[c] = a->nocs_scale[c]; }
@@ -272,10 +476,28 @@ extern "C" int tp_mesh_raster(const tp_mesh_raster_args* a, tp_stream_t stream) 
   const int64_t nf = (int64_t)a->B * a->F;
   hipLaunchKernelGGL(face_setup_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, p);
   const int tiles_x = (a->W + kTile - 1) / kTile, tiles_y = (a->H + kTile - 1) / kTile;
-  hipLaunchKernelGGL(raster_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)a->B), dim3(kChunk), 0, s, p, tiles_x);
+  if (culled) {
+    const int n_chunks = (a->F + kChunk - 1) / kChunk;
+    int4* cbox = (int4*)(p.rec + 4 * nf);
+    hipLaunchKernelGGL(chunk_box_kernel, dim3((unsigned)n_chunks, (unsigned)a->B), dim3(kChunk), 0, s, p, cbox, n_chunks);
+    hipLaunchKernelGGL(raster_culled_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)a->B), dim3(kChunk), 0, s, p, tiles_x,
+                       (const int4*)cbox, n_chunks);
+  } else {
+    hipLaunchKernelGGL(raster_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)a->B), dim3(kChunk), 0, s, p, tiles_x);
+  }
   if (a->normal) {
     const int64_t np = (int64_t)a->B * a->H * a->W;
     hipLaunchKernelGGL(normal_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, p);
   }
-  return tp::check_launch("tp_mesh_raster");
+  return tp::check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int tp_mesh_raster(const tp_mesh_raster_args* a, tp_stream_t stream) {
+  return mesh_raster_launch("tp_mesh_raster", a, stream, false);
+}
+
+extern "C" int tp_mesh_raster_culled(const tp_mesh_raster_args* a, tp_stream_t stream) {
+  return mesh_raster_launch("tp_mesh_raster_culled", a, stream, true);
 }

@@ -91,11 +91,13 @@ class DepthRefiner(_MeshRefiner):
     ``tau_mm`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 20.0), ``iters`` (Gauss-Newton steps, 5), ``damping``
     (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (pixels within tau of the
     measurement), rms [B] (mm, point-to-plane), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was not
-    positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+    positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose.  ``cull``: render with the culled
+    rasteriser (ops.mesh_raster(cull=True)), same bits."""
     _new_workspace = staticmethod(ops.depth_icp_workspace)
 
-    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6):
-        super().__init__(verts, faces, H, W, device)
+    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6,
+                 cull: bool = False):
+        super().__init__(verts, faces, H, W, device, cull=cull)
         self.tau_mm, self.iters, self.damping = tau_mm, int(iters), float(damping)
 
     def refine(self, pose: Tensor, intr: Tensor, depth: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
@@ -105,4 +107,4 @@ class DepthRefiner(_MeshRefiner):
         if tuple(depth.shape[1:]) != (self.H, self.W):
             raise ValueError("DepthRefiner.refine: depth planes of %d x %d expected, got %s" % (self.H, self.W, tuple(depth.shape)))
         return AttrDict(ops.depth_icp(self.verts, self.faces, pose, intr, depth, tau_mm=self.tau_mm, iters=self.iters, damping=self.damping,
-                                      frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))
+                                      frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull))

@@ -64,8 +64,8 @@ class JointRefiner(_MeshRefiner):
     _new_workspace = staticmethod(ops.joint_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, vcolor: Optional[Tensor] = None,
-                 weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6):
-        super().__init__(verts, faces, H, W, device)
+                 weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, cull: bool = False):
+        super().__init__(verts, faces, H, W, device, cull=cull)
         self.vcolor = None
         if vcolor is not None:
             self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
@@ -111,4 +111,4 @@ class JointRefiner(_MeshRefiner):
         return AttrDict(ops.joint_align(self.verts, self.faces, pose, intr, vcolor=self.vcolor, sdf=planes, image=image, depth=depth,
                                         weights=self.weights, tau_px=self.tau_px, tau=self.tau, tau_mm=self.tau_mm, iters=self.iters,
                                         damping=self.damping, frame=frame, masks=masks, workspace=self._workspace(pose.shape[0]),
-                                        visible_iou=known is not None))
+                                        visible_iou=known is not None, cull=self.cull))

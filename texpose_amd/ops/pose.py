@@ -397,13 +397,14 @@ DEPTH_ICP_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 
 @_on_tensor_device
 def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6,
-              frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+              frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+              cull: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against measured depth (the rules are in the header, K29): ``iters`` + 1 passes of mesh_raster at the
     current poses (depth and face index, H x W = depth's) followed by depth_icp_step, the last with evaluate_only.  ``tau_mm``: one
     value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose' [B,3,4], its
     'inliers' [B] int32 and 'rms' [B] (mm), 'status' [B] int32 of the last step taken (of the evaluation where iters = 0) and
     'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the rasteriser's,
-    bit-identical from run to run, safe under torch.cuda.graph."""
+    bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits."""
     op = "depth_icp"
     taus = _tau_schedule(op, tau_mm, "tau_mm", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -419,7 +420,7 @@ def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: T
     depth, frame, mask, _ = _frame_planes(op, "depth", depth, (), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_depth_icp_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=True, normals=False)
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=True, normals=False, cull=cull)
     step = lambda r, P, t, last: depth_icp_step(verts, faces, r["zbuf"], r["face"], P, intr, depth, tau_mm=t, damping=damping,
                                                 frame=frame, mask=mask, evaluate_only=last, workspace=workspace)
     return _refine_loop(pose, taus, raster, step)
@@ -476,13 +477,14 @@ PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 @_on_tensor_device
 def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
                 damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-                workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                workspace: Optional[Tensor] = None, cull: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
     ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
     [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (colour units), 'status' [B] int32 of the last step taken (of the evaluation where
     iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
-    rasteriser's, bit-identical from run to run, safe under torch.cuda.graph."""
+    rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with
+    mesh_raster(cull=True), same bits."""
     op = "photo_align"
     taus = _tau_schedule(op, tau, "tau", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -499,7 +501,7 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     image, frame, mask, _ = _frame_planes(op, "image", image, (3,), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False)
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False, cull=cull)
     step = lambda r, P, t, last: photo_align_step(r["zbuf"], r["rgb"], P, intr, image, tau=t, damping=damping, frame=frame,
                                                   mask=mask, evaluate_only=last, workspace=workspace)
     return _refine_loop(pose, taus, raster, step)
@@ -616,7 +618,7 @@ SILHOUETTE_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0",
 @_on_tensor_device
 def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px=4.0, iters: int = 10,
                      damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-                     workspace: Optional[Tensor] = None, visible_iou: bool = False) -> Dict[str, Tensor]:
+                     workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against the outlines of measured masks (the rules are in the header, K31): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth alone, H x W = sdf's) followed by silhouette_align_step, the last with evaluate_only.
     ``sdf`` [Ft,H,W]: mask_sdf of the measured masks.  ``tau_px``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule
@@ -629,7 +631,8 @@ def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, s
     ``visible_iou``: for a field with unknown pixels (mask_sdf's ``known``; NaN there) also 'iou_visible' / 'iou0_visible' [B] float32,
     inter / (uni - hidden) at the last and at the start pose, ``hidden`` the covered pixels of the plane whose field value is NaN: the
     IoU over the pixels that were measured (NaN where none is left).  Exact integer counts by torch reductions on the first and the
-    last rendering; without the flag nothing else runs and the keys are those above."""
+    last rendering; without the flag nothing else runs and the keys are those above.  ``cull``: the passes render with
+    mesh_raster(cull=True), same bits."""
     op = "silhouette_align"
     taus = _tau_schedule(op, tau_px, "tau_px", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -650,7 +653,7 @@ def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, s
         unknown = torch.isnan(sdf)                               # [Ft,H,W]; the plane of image b by the step's frame rule
         if frame is not None:
             unknown = unknown[frame.clamp(0, sdf.shape[0] - 1).long()]
-    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=False, normals=False)
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, face_ids=False, normals=False, cull=cull)
 
     def step(r, P, t, last):
         passes.append(silhouette_align_step(r["zbuf"], P, intr, sdf, tau_px=t, damping=damping, frame=frame, mask=mask, evaluate_only=last,
@@ -777,7 +780,7 @@ JOINT_ALIGN_KEYS = ("pose", "inliers", "chi2", "status", "inliers0", "chi20")
 def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vcolor: Optional[Tensor] = None, sdf: Optional[Tensor] = None,
                 image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
                 iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
-                workspace: Optional[Tensor] = None, visible_iou: bool = False) -> Dict[str, Tensor]:
+                workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
     (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
     one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
@@ -791,7 +794,7 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     'status' [B] int32 of the last step taken (of the evaluation where iters = 0), 'inliers0' / 'chi20' of the start pose, and the
     last pass's per-term keys of joint_align_step; with ``sdf`` also 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' /
     'iou0_visible', as silhouette_align.  A step that fails passes its pose on.  Bit-identical from run to run, safe under
-    torch.cuda.graph."""
+    torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits."""
     op = "joint_align"
     w = _joint_weights(op, weights)
     iters = int(iters)
@@ -832,7 +835,7 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     workspace = _workspace_arg(op, workspace, need, pose.device, align=16)
     from .scene import mesh_raster
     raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor if "image" in planes else None, face_ids="depth" in planes,
-                                   normals=False)
+                                   normals=False, cull=cull)
     passes, hidden = [], []
     if visible_iou:
         if "sdf" not in planes:

@@ -90,8 +90,8 @@ class PhotoRefiner(_MeshRefiner):
     _new_workspace = staticmethod(ops.photo_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, vcolor: Tensor, H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
-                 damping: float = 1e-6):
-        super().__init__(verts, faces, H, W, device)
+                 damping: float = 1e-6, cull: bool = False):
+        super().__init__(verts, faces, H, W, device, cull=cull)
         self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(self.vcolor.shape) != tuple(self.verts.shape):
             raise ValueError("PhotoRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
@@ -104,4 +104,4 @@ class PhotoRefiner(_MeshRefiner):
         if tuple(image.shape[1:]) != (self.H, self.W, 3):
             raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
         return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
-                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0])))
+                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull))

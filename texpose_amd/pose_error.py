@@ -365,10 +365,11 @@ def vsd_from_depth(z_est: Tensor, z_gt: Tensor, depth_test: Tensor, intr: Tensor
 
 
 def vsd(verts: Tensor, faces: Tensor, pose_est: Tensor, pose_gt: Tensor, intr: Tensor, depth_test: Tensor, diameter, *, H: int, W: int,
-        taus: Sequence[float] = BOP19_TAUS, delta: float = 15.0, frame: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        taus: Sequence[float] = BOP19_TAUS, delta: float = 15.0, frame: Optional[Tensor] = None, cull: bool = False) -> Dict[str, Tensor]:
     """VSD of B pose pairs of one mesh: ONE ops.mesh_raster call renders the 2 B stacked poses (depth only), `vsd_from_depth` does the
     rest.  verts [V,3] (mm), faces [F,3], pose_est / pose_gt [B,3,4] (t in mm), intr [B,3,3] or [3,3]; the other arguments are
-    `vsd_from_depth`'s.  GPU only: the rasteriser has no CPU route."""
+    `vsd_from_depth`'s.  ``cull``: render with ops.mesh_raster(cull=True) (K34), the same depth bit for bit.  GPU only: the rasteriser
+    has no CPU route."""
     pose_est, pose_gt = _poses(pose_est, "pose_est"), _poses(pose_gt, "pose_gt")
     if pose_est.shape != pose_gt.shape:
         raise ValueError("pose_est and pose_gt: the same number of poses expected")
@@ -379,7 +380,8 @@ def vsd(verts: Tensor, faces: Tensor, pose_est: Tensor, pose_gt: Tensor, intr: T
     B = pose_est.shape[0]
     intr = intr.detach()
     z = ops.mesh_raster(verts.detach(), faces, torch.cat([pose_est, pose_gt]).to(verts.device),
-                        (intr if intr.dim() == 2 else torch.cat([intr, intr])).to(verts.device), H=H, W=W, face_ids=False, normals=False)["zbuf"]
+                        (intr if intr.dim() == 2 else torch.cat([intr, intr])).to(verts.device), H=H, W=W, face_ids=False, normals=False,
+                        cull=cull)["zbuf"]
     return vsd_from_depth(z[:B], z[B:], depth_test, intr, diameter, taus=taus, delta=delta, frame=frame)
 
 

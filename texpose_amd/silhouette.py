@@ -143,8 +143,9 @@ class SilhouetteRefiner(_MeshRefiner):
     known pixels only."""
     _new_workspace = staticmethod(ops.silhouette_align_workspace)
 
-    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_px=4.0, iters: int = 10, damping: float = 1e-6):
-        super().__init__(verts, faces, H, W, device)
+    def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, tau_px=4.0, iters: int = 10, damping: float = 1e-6,
+                 cull: bool = False):
+        super().__init__(verts, faces, H, W, device, cull=cull)
         self.tau_px, self.iters, self.damping = tau_px, int(iters), float(damping)
         self._sdf_workspaces: Dict[int, Tensor] = {}
 
@@ -170,4 +171,4 @@ class SilhouetteRefiner(_MeshRefiner):
             planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft], known=known)
         return AttrDict(ops.silhouette_align(self.verts, self.faces, pose, intr, planes, tau_px=self.tau_px, iters=self.iters,
                                              damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]),
-                                             visible_iou=known is not None))
+                                             visible_iou=known is not None, cull=self.cull))

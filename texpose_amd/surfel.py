@@ -3,6 +3,7 @@
 
 load_ply (numpy only), SurfelRenderer (one mesh, batches of predicted poses; data_layer_maps = the tensors the data layer would load,
 tp_surfel_finish), SurfelMapStore (those tensors for a whole sequence, resident), write_surfel_frame / read_surfel_frame (the reference's files).
+coherent_face_order: a face order that is coherent in space, for the culled rasteriser (ops.mesh_raster(cull=True)).
 Conventions and what differs from PyTorch3D: DESIGN.md section 11."""
 from __future__ import annotations
 
@@ -165,6 +166,46 @@ def nocs_normalisation(verts) -> Tuple[np.ndarray, np.ndarray]:
     return ct.numpy(), (v - ct).abs().max(dim=0).values.numpy()
 
 
+def _spread_bits10(x: np.ndarray) -> np.ndarray:
+    """The low 10 bits of x with two zero bits after each: bit k -> bit 3 k."""
+    x = x.astype(np.uint32) & np.uint32(0x3FF)
+    x = (x | (x << np.uint32(16))) & np.uint32(0x030000FF)
+    x = (x | (x << np.uint32(8))) & np.uint32(0x0300F00F)
+    x = (x | (x << np.uint32(4))) & np.uint32(0x030C30C3)
+    x = (x | (x << np.uint32(2))) & np.uint32(0x09249249)
+    return x
+
+
+def coherent_face_order(verts, faces) -> np.ndarray:
+    """A face order that is coherent in space, for the culled rasteriser (ops.mesh_raster(cull=True)): the
+    permutation ``perm`` [F] int64 that sorts the faces by the 30-bit Morton code of their centroid, quantised to 10 bits per axis over
+    the largest extent of the mesh (of the vertices its faces use) (x in the highest bit of each triple), by a stable sort: faces with equal codes keep their order, and
+    the result is the same on every call.  Consecutive faces of ``faces[perm]`` are then neighbours in space, so a chunk of 256 of
+    them covers a small patch of the image at any pose, and a tile skips most chunks.  A face with an index outside the mesh or a
+    centroid that is not finite sorts first (the rasteriser drops the first and never shows the second).
+
+    Nothing applies it by default.  Render with ``faces[perm]``: the depth, colour, NOCS and normal planes are the same bit for bit
+    (a pixel keeps the nearest face whatever the order), the ``face`` plane then indexes ``faces[perm]``, so ``perm[face]`` is the
+    id in the original order (on covered pixels; where two faces tie in z exactly the smaller NEW index wins, which may be the other
+    face).  ops.depth_icp reads the faces through that plane: hand it the same permuted ``faces``."""
+    verts = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    valid = ((faces >= 0) & (faces < len(verts))).all(axis=1)
+    centroid = verts[np.where(valid[:, None], faces, 0)].mean(axis=1) if len(verts) else np.zeros((len(faces), 3))
+    valid &= np.isfinite(centroid).all(axis=1)
+    code = np.zeros(len(faces), dtype=np.uint32)
+    if valid.any():
+        c = centroid[valid]
+        used = verts[np.unique(faces[valid])]
+        lo = used.min(axis=0)
+        extent = float((used.max(axis=0) - lo).max())
+        # relative to the lowest corner, so that a translation of the mesh changes nothing but rounding in the last place
+        q = np.zeros_like(c) if extent <= 0 else np.minimum(np.floor((c - lo) * (1024.0 / extent)), 1023.0)
+        q = q.astype(np.uint32)
+        code[valid] = (_spread_bits10(q[:, 0]) << np.uint32(2)) | (_spread_bits10(q[:, 1]) << np.uint32(1)) | _spread_bits10(q[:, 2])
+    return np.argsort(code, kind="stable").astype(np.int64)
+
+
 def calibrate_pose(pose: torch.Tensor, depth_scale: float) -> torch.Tensor:
     """[B,3,4] pose in nerf.depth.scale units -> [R|t] in mm as compute_surfelinfo.py:107 and MVRenderer.calibrate_pose hand it to
     PyTorch3D: t * 1000 / depth_scale, R re-orthonormalised like the 6D round trip (Gram-Schmidt of the first two columns, third =
@@ -180,8 +221,9 @@ def calibrate_pose(pose: torch.Tensor, depth_scale: float) -> torch.Tensor:
 class SurfelRenderer:
     """The colour + NOCS renders and normals of compute_surfelinfo for one CAD mesh at batches of poses (one tp_mesh_raster call)."""
 
-    def __init__(self, verts, faces, vcolor=None, H: int = 480, W: int = 640, device="cuda:0"):
+    def __init__(self, verts, faces, vcolor=None, H: int = 480, W: int = 640, device="cuda:0", cull: bool = False):
         self.device = torch.device(device)
+        self.cull = bool(cull)                 # render with ops.mesh_raster(cull=True): the same bits (K34; DESIGN section 24)
         self.H, self.W = int(H), int(W)
         self.nocs_center, self.nocs_scale = nocs_normalisation(verts)
         self.verts = torch.as_tensor(np.asarray(verts, dtype=np.float32)).to(self.device)
@@ -194,7 +236,7 @@ class SurfelRenderer:
             pose = pose[None]
         intr = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
         return ops.mesh_raster(self.verts, self.faces, calibrate_pose(pose, depth_scale), intr, H=self.H, W=self.W, vcolor=self.vcolor,
-                               nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True)
+                               nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True, cull=self.cull)
 
     def __call__(self, pose, intr, depth_scale: float) -> AttrDict:
         """pose [B,3,4] (t in nerf.depth.scale units, like pose_init), intr [B,3,3] or [3,3] ->

@@ -4,7 +4,7 @@
 
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
-                                 [--joint [--iters-joint N] [--weights SIL RGB DEPTH]]
+                                 [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -44,7 +44,10 @@ instead of one refiner after the other: under occlusion the silhouette stage alo
 --weights SIL RGB DEPTH: 1 / sigma^2 of each term's residual unit, default 1 100 0.04 (the photometric weight is the one that
 converged on the occluded cases of section 23; the depth weight is sigma = 5 mm and is not tuned on anything).  --tau-px, --tau-rgb and
 --tau-mm are the terms' thresholds (one value or iters-joint + 1 each); --occluders, --known and --use-mask-visib apply as above and
-also mask the other terms.  Without --joint nothing changes."""
+also mask the other terms.  Without --joint nothing changes.
+
+--cull-raster: every refiner renders with the culled rasteriser (ops.mesh_raster(cull=True), K34), which skips whole
+chunks of 256 faces per 16 x 16 tile.  The planes are the same bit for bit, so the poses written are the same; only the time differs."""
 import argparse
 import csv
 import json
@@ -107,6 +110,7 @@ def main(argv=None):
     ap.add_argument("--joint", action="store_true", help="the terms named by --silhouette, --rgb, --depth in one loop")
     ap.add_argument("--iters-joint", type=int, default=20)
     ap.add_argument("--weights", type=float, nargs=3, default=None, metavar=("SIL", "RGB", "DEPTH"))
+    ap.add_argument("--cull-raster", action="store_true", help="render with the culled rasteriser: the same poses, faster on large meshes")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -214,15 +218,15 @@ def main(argv=None):
             if a.joint and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=meshes.get(oid, meshes.get(None))[2] if a.rgb else None,
                                              weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
-                                             damping=a.damping)
+                                             damping=a.damping, cull=a.cull_raster)
             if a.silhouette and not a.joint and (outline is None or (outline.H, outline.W) != (H, W)):
-                outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping)
+                outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping, cull=a.cull_raster)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
                     refiner = photo_align.PhotoRefiner(verts, faces, meshes.get(oid, meshes.get(None))[2], H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
-                                                       damping=a.damping)
+                                                       damping=a.damping, cull=a.cull_raster)
                 else:
-                    refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping)
+                    refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping, cull=a.cull_raster)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
             K = np.stack([np.array(cam[str(rows[i][1])]["cam_K"], np.float32).reshape(3, 3) for i in part])
             index = torch.tensor([frames.index(rows[i][1]) for i in part], dtype=torch.int32, device=dev)
