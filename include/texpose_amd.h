@@ -1514,6 +1514,43 @@ int tp_joint_align_step(const tp_joint_align_args* j,
                         const tp_depth_icp_args* icp,          /* may be NULL */
                         tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K35  shade the pixels of K19's face plane from a per-face texel texture ("mesh colours": texpose_amd/face_texels.py; restated in
+ *      tests/face_texels_ref.py; the project's own step, no reference code).  Resolution R, 1 <= R <=
+ *      TP_FACE_TEXEL_MAX_R.  Face f with vertices (v0, v1, v2) in its own order carries the nodes (i, j), i, j >= 0, i + j <= R; node
+ *      (i, j) sits at the barycentric weights ((R - i - j) / R, i / R, j / R) and is stored at n(i, j) = j (R + 1) - j (j - 1) / 2 + i
+ *      of the face's T(R) = (R + 1)(R + 2) / 2 texels: texels is [F, T, 3].  Per pixel (row i, column j) of image b with f = face:
+ *        u_k, v_k, 1 / z_k of the face's vertices in fp64 from verts, faces, pose[b], intr[b] exactly as K19's face setup forms them
+ *        area   = (u_1 - u_0)(v_2 - v_0) - (v_1 - v_0)(u_2 - u_0)                                   (twice the signed area)
+ *        b_k    = ((u_e - u_s)(py - v_s) - (v_e - v_s)(px - u_s)) / area,  s = (k + 1) % 3, e = (k + 2) % 3, (px, py) = (j + 0.5, i + 0.5)
+ *        t_k    = b_k * (1 / z_k),  w_k = t_k / ((t_0 + t_1) + t_2);  w_k < 0 becomes 0;  w_k = w_k / ((w_0 + w_1) + w_2)
+ *        a = R w_1, b = R w_2, ci = min(floor(a), R - 1), cj = min(floor(b), R - 1 - ci), fa = a - ci, fb = b - cj
+ *        fa + fb > 1 and ci + cj <= R - 2:  c = ((fa + fb) - 1) N(ci+1, cj+1) + (1 - fb) N(ci+1, cj) + (1 - fa) N(ci, cj+1)
+ *        otherwise:                         c = ((1 - fa) - fb) N(ci, cj) + fa N(ci+1, cj) + fb N(ci, cj+1)
+ *      (a cell of the last diagonal, ci + cj = R - 1, has no upper triangle: there fa + fb exceeds 1 by rounding alone), the three
+ *      products added left to right.  Piecewise linear and continuous; at R = 1 the perspective-correct vertex interpolation.  Every
+ *      step is fp64, evaluated as written (no contraction), and rounded to fp32 once.  rgb = (0, 0, 0), and nothing else is read,
+ *      for face < 0 or >= F, a vertex index outside 0 .. V-1, a vertex with z <= 0 or a non-finite camera-frame coordinate, |area| <=
+ *      1e-10 or not finite, and any non-finite w_k or colour.  Nothing is read out of bounds for any face plane or pose.  Point
+ *      sampling: no minification filter.  One launch, one thread per pixel; no LDS, no atomics, no workspace, no allocation, no host
+ *      synchronisation; the output is a function of the inputs alone.  Non-positive sizes, R outside 1 .. TP_FACE_TEXEL_MAX_R,
+ *      H * W >= 2^31, F * T >= 2^31, B * ceil(H W / 256) >= 2^31 and null pointers are refused (-1, tp_last_error) and launch
+ *      nothing.  Safe to capture.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_FACE_TEXEL_MAX_R 64
+typedef struct tp_face_texel_shade_args {
+  const float* verts;        /* [V,3] model frame, mm */
+  const int32_t* faces;      /* [F,3] */
+  const float* texels;       /* [F,T,3], T = tp_face_texel_count(R) */
+  const float* pose;         /* [B,3,4] [R|t] model -> camera (K19's convention) */
+  const float* intr;         /* [B,3,3] */
+  const int32_t* face;       /* [B,H,W] K19's face plane (any values: out-of-range entries shade to zero) */
+  int B, H, W, V, F, R;
+  float* rgb;                /* [B,H,W,3] out */
+} tp_face_texel_shade_args;
+int tp_face_texel_count(int R);                           /* T(R); 0 for R outside 1 .. TP_FACE_TEXEL_MAX_R */
+int tp_face_texel_shade(const tp_face_texel_shade_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,9 +64,17 @@ class JointRefiner(_MeshRefiner):
     _new_workspace = staticmethod(ops.joint_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, vcolor: Optional[Tensor] = None,
-                 weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, cull: bool = False):
+                 weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, cull: bool = False,
+                 texels: Optional[Tensor] = None):
         super().__init__(verts, faces, H, W, device, cull=cull)
+        if vcolor is not None and texels is not None:
+            raise ValueError("JointRefiner: vcolor= or texels=, not both")
         self.vcolor = None
+        self.texels = None                                       # [F,T,3] face texels (K35) in place of vertex colours
+        if texels is not None:
+            self.texels = torch.as_tensor(texels).to(device=self.device, dtype=torch.float32).contiguous()
+            if self.texels.dim() != 3 or self.texels.shape[0] != self.faces.shape[0] or self.texels.shape[2] != 3:
+                raise ValueError("JointRefiner: texels [F,T,3] expected, T texels per face, got %s" % (tuple(self.texels.shape),))
         if vcolor is not None:
             self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(self.vcolor.shape) != tuple(self.verts.shape):
@@ -104,11 +112,11 @@ class JointRefiner(_MeshRefiner):
                 if Ft not in self._sdf_workspaces:
                     self._sdf_workspaces[Ft] = ops.mask_sdf_workspace(Ft, self.H, self.W, self.device)
                 planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft], known=known)
-        if image is not None and self.vcolor is None:
-            raise ValueError("JointRefiner.refine: image= needs the refiner's vcolor=")
+        if image is not None and self.vcolor is None and self.texels is None:
+            raise ValueError("JointRefiner.refine: image= needs the refiner's vcolor= or texels=")
         masks = {k: v for k, v in masks.items() if (k == "silhouette" and planes is not None) or (k == "photo" and image is not None)
                  or (k == "depth" and depth is not None)}
-        return AttrDict(ops.joint_align(self.verts, self.faces, pose, intr, vcolor=self.vcolor, sdf=planes, image=image, depth=depth,
+        return AttrDict(ops.joint_align(self.verts, self.faces, pose, intr, vcolor=self.vcolor, texels=self.texels, sdf=planes, image=image, depth=depth,
                                         weights=self.weights, tau_px=self.tau_px, tau=self.tau, tau_mm=self.tau_mm, iters=self.iters,
                                         damping=self.damping, frame=frame, masks=masks, workspace=self._workspace(pose.shape[0]),
                                         visible_iou=known is not None, cull=self.cull))

@@ -477,20 +477,24 @@ PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 @_on_tensor_device
 def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
                 damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-                workspace: Optional[Tensor] = None, cull: bool = False) -> Dict[str, Tensor]:
+                workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
     ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
     [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (colour units), 'status' [B] int32 of the last step taken (of the evaluation where
     iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
     rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with
-    mesh_raster(cull=True), same bits."""
+    mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] with ``vcolor`` None: the passes colour the mesh from its face texels
+    (mesh_raster(texels=), K35); exactly one of the two."""
     op = "photo_align"
+    if (vcolor is None) == (texels is None):
+        raise ValueError("%s: exactly one of vcolor [V,3] and texels= [F,T,3] expected" % op)
     taus = _tau_schedule(op, tau, "tau", iters)
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
     B = pose.shape[0]
     faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
-    vcolor = _f32(vcolor.detach(), "vcolor")
+    vcolor = None if vcolor is None else _f32(vcolor.detach(), "vcolor")
+    texels = None if texels is None else _f32(texels.detach(), "texels")
     image = _f32(image.detach(), "image")
     if image.dim() == 3:
         image = image[None]
@@ -501,7 +505,7 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     image, frame, mask, _ = _frame_planes(op, "image", image, (3,), frame, mask, B, H, W, pose)
     workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_align_workspace_bytes(B, H, W)), pose.device, align=16)
     from .scene import mesh_raster
-    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor, face_ids=False, normals=False, cull=cull)
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor, texels=texels, face_ids=False, normals=False, cull=cull)
     step = lambda r, P, t, last: photo_align_step(r["zbuf"], r["rgb"], P, intr, image, tau=t, damping=damping, frame=frame,
                                                   mask=mask, evaluate_only=last, workspace=workspace)
     return _refine_loop(pose, taus, raster, step)
@@ -780,7 +784,8 @@ JOINT_ALIGN_KEYS = ("pose", "inliers", "chi2", "status", "inliers0", "chi20")
 def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vcolor: Optional[Tensor] = None, sdf: Optional[Tensor] = None,
                 image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
                 iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
-                workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False) -> Dict[str, Tensor]:
+                workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
+                texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
     (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
     one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
@@ -794,15 +799,18 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     'status' [B] int32 of the last step taken (of the evaluation where iters = 0), 'inliers0' / 'chi20' of the start pose, and the
     last pass's per-term keys of joint_align_step; with ``sdf`` also 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' /
     'iou0_visible', as silhouette_align.  A step that fails passes its pose on.  Bit-identical from run to run, safe under
-    torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits."""
+    torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] in place of ``vcolor``:
+    the photometric term's renders take their colour from the mesh's face texels (mesh_raster(texels=), K35); at most one of the two."""
     op = "joint_align"
+    if vcolor is not None and texels is not None:
+        raise ValueError("%s: vcolor= or texels=, not both" % op)
     w = _joint_weights(op, weights)
     iters = int(iters)
     taus = list(zip(_tau_schedule(op, tau_px, "tau_px", iters), _tau_schedule(op, tau, "tau", iters), _tau_schedule(op, tau_mm, "tau_mm", iters)))
     if sdf is None and image is None and depth is None:
         raise ValueError("%s: no term: give at least one of sdf=, image=, depth=" % op)
-    if image is not None and vcolor is None:
-        raise ValueError("%s: image= needs vcolor=, the mesh's colours [V,3]" % op)
+    if image is not None and vcolor is None and texels is None:
+        raise ValueError("%s: image= needs vcolor=, the mesh's colours [V,3], or texels= [F,T,3]" % op)
     masks = dict(masks or {})
     if set(masks) - set(JOINT_TERMS):
         raise ValueError("%s: masks takes the keys %s, got %s" % (op, JOINT_TERMS, sorted(masks)))
@@ -829,13 +837,15 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
             planes[name], _, masks[term_of[name]], _ = _frame_planes(op, name, planes[name], trailing, frame, masks.get(term_of[name]), B, H, W, pose)
     if vcolor is not None:
         vcolor = _f32(vcolor.detach(), "vcolor")
+    if texels is not None:
+        texels = _f32(texels.detach(), "texels")
     lib = _lib.load()
     need = sum((int(f(B, H, W)) + 15) // 16 * 16 for f, name in ((lib.tp_silhouette_align_workspace_bytes, "sdf"), (lib.tp_photo_align_workspace_bytes, "image"),
                                                                  (lib.tp_depth_icp_workspace_bytes, "depth")) if name in planes)
     workspace = _workspace_arg(op, workspace, need, pose.device, align=16)
     from .scene import mesh_raster
-    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor if "image" in planes else None, face_ids="depth" in planes,
-                                   normals=False, cull=cull)
+    raster = lambda P: mesh_raster(verts, faces, P, intr, H=H, W=W, vcolor=vcolor if "image" in planes else None,
+                                   texels=texels if "image" in planes else None, face_ids="depth" in planes, normals=False, cull=cull)
     passes, hidden = [], []
     if visible_iou:
         if "sdf" not in planes:

@@ -1,4 +1,5 @@
-"""K19-K22, K27: the mesh rasteriser, the surfel maps, the BOP scene writers and the texture bake."""
+"""K19-K22, K27, K35: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake and the face-texel shading."""
+import math
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -7,20 +8,25 @@ from .. import _lib
 from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg)
 
 __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
-           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake"]
+           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade"]
 
 
 # ------------------------------------------------------------------------------------------ K19
 @_on_tensor_device
 def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: int, W: int, vcolor: Optional[Tensor] = None,
                 nocs_norm: Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]] = None,
-                face_ids: bool = True, normals: bool = True, zbuf_out: Optional[Tensor] = None, cull: bool = False) -> Dict[str, Tensor]:
+                face_ids: bool = True, normals: bool = True, zbuf_out: Optional[Tensor] = None, cull: bool = False,
+                texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Hard rasterisation of one mesh at B poses (tp_mesh_raster).  verts [V,3] and pose [B,3,4] ([R|t], t) in the same units (mm),
     faces [F,3] int, intr [B,3,3] or [3,3].  Returns zbuf [B,H,W] (-1 on background) and, as asked, face [B,H,W] int32, rgb
     (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3].
     ``zbuf_out``: a contiguous float32 [B,H,W] tensor (e.g. one plane of a [K,B,H,W] stack) to write zbuf into.
     ``cull``: tp_mesh_raster_culled, which skips whole chunks of 256 faces per 16 x 16 tile by their union box: the same planes bit for
-    bit, one launch more (K34)."""
+    bit, one launch more (K34).
+    ``texels`` [F,T(R),3] instead of ``vcolor``: rgb comes from the per-face texel texture (face_texel_shade on the face plane, which
+    is then rendered and returned whatever ``face_ids`` says; K35)."""
+    if texels is not None and vcolor is not None:
+        raise ValueError("mesh_raster: vcolor or texels, not both")
     verts, pose = _f32(verts, "verts"), _f32(pose, "pose")
     if pose.dim() == 2:
         pose = pose[None]
@@ -37,7 +43,7 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
     out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else _want_gpu("mesh_raster", zbuf_out, "zbuf_out", torch.float32, (B, H, W))}
-    if face_ids:
+    if face_ids or texels is not None:
         out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
     if vcolor is not None:
         vcolor = _f32(vcolor, "vcolor")
@@ -59,6 +65,8 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
         _call("tp_mesh_raster_culled", a)
     else:
         _call("tp_mesh_raster", a)
+    if texels is not None:
+        out["rgb"] = face_texel_shade(out["face"], verts, faces, texels, pose, intr)
     return out
 
 
@@ -249,3 +257,35 @@ def texture_bake(verts: Tensor, normals: Tensor, pose: Tensor, intr: Tensor, rgb
     a.acc, a.count, a.workspace = acc.data_ptr(), count.data_ptr(), workspace.data_ptr()
     _call("tp_texture_bake", a)        # (thresholds out of range: the library's error)
     return {"acc": acc, "count": count}
+
+
+# ------------------------------------------------------------------------------------------ K35
+@_on_tensor_device
+def face_texel_shade(face: Tensor, verts: Tensor, faces: Tensor, texels: Tensor, pose: Tensor, intr: Tensor, *,
+                     out: Optional[Tensor] = None) -> Tensor:
+    """Colour mesh_raster's face plane from a per-face texel texture (tp_face_texel_shade; the rule is in the header): face [B,H,W]
+    int32 (taken as it is), verts [V,3], faces [F,3], texels [F,T,3] with T = (R + 1)(R + 2) / 2 for a resolution R in 1 .. 64 (R is
+    inferred from T), pose [B,3,4] and intr [B,3,3] or [3,3] as the rasteriser got them -> rgb [B,H,W,3] float32, zero where the
+    plane holds no face.  ``out``: the tensor to write into.  Not differentiable.  One launch, no workspace, bit-identical from run
+    to run, safe under torch.cuda.graph."""
+    op = "face_texel_shade"
+    _want_gpu(op, face, "face", torch.int32, None)
+    if face.dim() != 3 or face.numel() == 0:
+        raise ValueError("%s: face [B,H,W] expected, got %s" % (op, tuple(face.shape)))
+    B, H, W = face.shape
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose", B)
+    intr = _intr_per_view(op, intr, B)
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    texels = _f32(texels.detach(), "texels")
+    V, F = verts.shape[0], faces.shape[0]
+    T = texels.shape[1] if texels.dim() == 3 else 0
+    R = (math.isqrt(8 * T + 1) - 3) // 2
+    if tuple(faces.shape) != (F, 3) or F == 0 or tuple(texels.shape) != (F, T, 3) or _lib.load().tp_face_texel_count(R) != T:
+        raise ValueError("%s: faces [F,3] and texels [F,T,3] with T = (R + 1)(R + 2) / 2, R in 1 .. %d, expected, got %s and %s"
+                         % (op, _lib.FACE_TEXEL_MAX_R, tuple(faces.shape), tuple(texels.shape)))
+    rgb = torch.empty(B, H, W, 3, device=face.device) if out is None else _want_gpu(op, out, "out", torch.float32, (B, H, W, 3))
+    a = _lib.FaceTexelShadeArgs()
+    a.verts, a.faces, a.texels, a.pose, a.intr, a.face = (t.data_ptr() for t in (verts, faces, texels, pose, intr, face))
+    a.B, a.H, a.W, a.V, a.F, a.R, a.rgb = B, H, W, V, F, R, rgb.data_ptr()
+    _call("tp_face_texel_shade", a)
+    return rgb

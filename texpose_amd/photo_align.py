@@ -89,12 +89,17 @@ class PhotoRefiner(_MeshRefiner):
     not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
     _new_workspace = staticmethod(ops.photo_align_workspace)
 
-    def __init__(self, verts: Tensor, faces: Tensor, vcolor: Tensor, H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
-                 damping: float = 1e-6, cull: bool = False):
+    def __init__(self, verts: Tensor, faces: Tensor, vcolor: Optional[Tensor], H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
+                 damping: float = 1e-6, cull: bool = False, texels: Optional[Tensor] = None):
         super().__init__(verts, faces, H, W, device, cull=cull)
-        self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(self.vcolor.shape) != tuple(self.verts.shape):
+        if (vcolor is None) == (texels is None):
+            raise ValueError("PhotoRefiner: exactly one of vcolor [V,3] and texels= [F,T,3] (face texels, K35) expected")
+        self.vcolor = None if vcolor is None else torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
+        self.texels = None if texels is None else torch.as_tensor(texels).to(device=self.device, dtype=torch.float32).contiguous()
+        if self.vcolor is not None and tuple(self.vcolor.shape) != tuple(self.verts.shape):
             raise ValueError("PhotoRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
+        if self.texels is not None and (self.texels.dim() != 3 or self.texels.shape[0] != self.faces.shape[0] or self.texels.shape[2] != 3):
+            raise ValueError("PhotoRefiner: texels [F,T,3] expected, T texels per face, got %s" % (tuple(self.texels.shape),))
         self.tau, self.iters, self.damping = tau, int(iters), float(damping)
 
     def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
@@ -104,4 +109,5 @@ class PhotoRefiner(_MeshRefiner):
         if tuple(image.shape[1:]) != (self.H, self.W, 3):
             raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
         return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
-                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull))
+                                        damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull,
+                                        texels=self.texels))

@@ -12,6 +12,10 @@ rgb_static is baked with opacity_static as the weight against those depth planes
 --report JSON: vertices, views, coverage (share of vertices some view reached), coloured (share with a positive weight), mean views per
 vertex, filled and unseen counts, thresholds, seconds.  --verify re-renders the baked mesh with ops.mesh_raster at the bake poses and
 prints (and stores) the PSNR against the NeRF views inside the mask; nothing is asserted on it.
+--texel-res R (1 .. 64): also bake a face-texel texture of resolution R (texpose_amd.face_texels, K35: R x finer than
+the vertices along every edge, no UV unwrap) from the same views and write it as <out>.texels.npz beside the PLY (texels, R and the
+faces it belongs to; refine_poses.py --texels reads it).  The PLY still holds the vertex colours, now the texture's corner nodes;
+--verify then re-renders through the texels, and the report gains 'texels' (R, nodes, coloured, filled, unseen, file).
 Out of scope: texture atlases, view-dependent textures, photographs."""
 import argparse
 import json
@@ -35,6 +39,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="the coloured .ply")
     ap.add_argument("--report", default=None, metavar="JSON")
     ap.add_argument("--verify", action="store_true", help="re-render the baked mesh and print the PSNR against the NeRF views")
+    ap.add_argument("--texel-res", type=int, default=None, metavar="R", help="also write <out>.texels.npz: face texels of resolution R")
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--samples", type=int, default=None, help="nerf.sample_intvs")
@@ -52,8 +57,11 @@ def main(argv=None):
         ap.error("either --scene or --sphere N --distance-mm D expected")
     if a.sphere is not None and not (a.sphere >= 1 and a.distance_mm and a.distance_mm > 0):
         ap.error("--sphere N needs N >= 1 and --distance-mm D > 0")
+    if a.texel_res is not None and not 1 <= a.texel_res <= 64:
+        ap.error("--texel-res R needs R in 1 .. 64")
     import torch
     from texpose_amd import checkpoint as ck, ops
+    from texpose_amd import face_texels as ft
     from texpose_amd import texture_bake as tb
     from texpose_amd.graph import Graph
     from texpose_amd.options import default_options
@@ -89,7 +97,9 @@ def main(argv=None):
     bounds = SceneBounds({int(oid): (SurfelRenderer(verts, faces, None, a.H, a.W, a.device), verts.min(axis=0), verts.max(axis=0))},
                          a.H, a.W, scale, bg)
     thresholds = {k: v for k, v in dict(cos_min=a.cos_min, cover_min=a.cover_min, z_tol_mm=a.z_tol_mm, slope=a.slope).items() if v is not None}
-    baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds)
+    # with --texel-res the nodes of the subdivided mesh are baked; its first V rows are the mesh's vertices, so the PLY comes from them
+    texel_baker = None if a.texel_res is None else ft.FaceTexelBaker(verts, faces, a.texel_res, a.H, a.W, a.device, **thresholds)
+    baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds) if texel_baker is None else texel_baker.nodes
     light = torch.tensor(a.light_index, device=dev)
     kept = []                                                         # (rgb, mask) of every view, for --verify
     torch.cuda.synchronize(dev)
@@ -107,24 +117,37 @@ def main(argv=None):
                                              sample_idx=light, mode="eval")
                 rgb[i] = ret.rgb_static.view(a.H, a.W, 3)
                 weight[i] = ret.opacity_static.view(a.H, a.W)
-            baker.add_views(rgb, tb.poses_to_mm(p, scale), k, zbuf=sb.zbuf[0], weight=weight)
+            baker.add_views(rgb, tb.poses_to_mm(p, scale), k, zbuf=sb.zbuf[0], weight=weight)      # (the base mesh's depth planes)
             if a.verify:
                 kept.append((rgb, sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)))
-    res = baker.result(fill=True)
+    V = len(verts)
+    texels = None
+    if texel_baker is None:
+        res = baker.result(fill=True)
+    else:
+        sub = texel_baker.result(fill=True)
+        texels = sub.texels
+        res = tb.AttrDict(vcolor=sub.vcolor_sub[:V].contiguous(), count=sub.count[:V], seen=sub.seen[:V], filled=sub.filled, unseen=sub.unseen)
     torch.cuda.synchronize(dev)
     seconds = time.perf_counter() - t0
     ops.check_mlp_status(dev)
     tb.write_ply(a.out, verts, faces, res.vcolor.cpu().numpy())
-    V = len(verts)
     report = dict(vertices=V, faces=int(len(faces)), views=N, H=a.H, W=a.W, coverage=float((res.count > 0).sum()) / V,
                   coloured=float(res.seen.sum()) / V, mean_views_per_vertex=float(res.count.double().mean()), filled=res.filled,
                   unseen=res.unseen, thresholds=baker.thresholds, seconds_render_and_bake=seconds, mlp=graph.nerf.precision, out=a.out)
+    if texels is not None:
+        texel_file = os.path.splitext(a.out)[0] + ".texels.npz"
+        ft.save_texels(texel_file, texels, faces)
+        U = len(texel_baker.verts_sub)
+        report["texels"] = dict(R=a.texel_res, per_face=int(texels.shape[1]), nodes=U, coloured=float(sub.seen.sum()) / U, filled=sub.filled,
+                                unseen=sub.unseen, file=texel_file)
     if a.verify:
         se, px = 0.0, 0
+        base_verts, base_faces = (baker.verts, baker.faces) if texel_baker is None else (texel_baker.verts, texel_baker.faces)
         with torch.no_grad():
             for c, (rgb, mask) in zip(range(0, N, a.chunk), kept):
-                r = ops.mesh_raster(baker.verts, baker.faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
-                                    H=a.H, W=a.W, vcolor=res.vcolor, face_ids=False, normals=False)
+                r = ops.mesh_raster(base_verts, base_faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
+                                    H=a.H, W=a.W, vcolor=res.vcolor if texels is None else None, texels=texels, face_ids=False, normals=False)
                 m = mask & (r["zbuf"] > 0)
                 se += float((((r["rgb"] - rgb.clamp(0, 1)) ** 2).sum(-1) * m).double().sum())
                 px += int(m.sum())

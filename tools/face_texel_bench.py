@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Time the three ways to render colour detail below the mesh's vertex spacing (K35) on the rippled sphere of the
+bake bench (V = 20,000, F = 39,200), B = 64 Fibonacci views of 480 x 640, in one run on one device:
+
+  base          ops.mesh_raster(vcolor=) of the base mesh: today's vertex colours (the resolution limit)
+  texels R      ops.mesh_raster(texels=) of the base mesh: depth + face plane + tp_face_texel_shade, R in {1, 4, 8}, plain and cull=True
+  shade R       tp_face_texel_shade alone on a given face plane (the kernel's own time: 16 B per pixel + the gather)
+  subdivided R  ops.mesh_raster(vcolor=) of the mesh subdivided R times (F R^2 faces), plain and cull=True, R in {4, 8}
+
+    python tools/face_texel_bench.py [--out profiles/face_texels/shade.json] [--iters 20]
+
+The outputs are compared before anything is timed: R = 1 against the base route within 1e-5; the texel route against the subdivided
+route on the pixels where both see the same surface: at most 0.01 % of them may differ by more than 5e-5 (the bar of
+tests/test_gpu_face_texels.py) and none by more than 2e-3, with coverage differing on at most 0.5 %.  The gate is wider than the tests'
+because the subdivided route shades with the rasteriser's fp32 barycentrics, and its sub-faces at the silhouette of a 480 x 640 view
+project to slivers far thinner than a pixel; the kernel itself is held to the fp64 restatement by the tests.  Device events around
+many calls after a warm-up, three repeats per route, alternating, medians; the shader clock comes from ops.clock_probe before and after."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+import kernel_bench as KB  # noqa: E402
+from texture_bake_ref import uv_sphere  # noqa: E402  (numpy only: the tests' mesh generators; needs the repository's tests/ folder)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    KB.add_timing_args(ap, iters=20, warmup=3, repeats=3)
+    ap.add_argument("--lat", type=int, default=99)
+    ap.add_argument("--lon", type=int, default=200)
+    ap.add_argument("--views", type=int, default=64)
+    ap.add_argument("--H", type=int, default=480)
+    ap.add_argument("--W", type=int, default=640)
+    a = ap.parse_args(argv)
+    import torch
+    from texpose_amd import face_texels as FT, ops, texture_bake as TB
+    if not torch.cuda.is_available():
+        raise SystemExit("face_texel_bench: needs a GPU (a CPU run cannot give a time)")
+    dev = torch.device("cuda:0")
+    clock_before = KB.shader_clock()
+    t_start = time.time()
+    H, W, B, focal, dist = a.H, a.W, a.views, 1000.0 * a.W / 640.0, 400.0
+    pose = torch.from_numpy(TB.sphere_view_poses(B, dist).astype(np.float32)).to(dev)
+    K = torch.tensor([[focal, 0.0, W / 2.0], [0.0, focal, H / 2.0], [0.0, 0.0, 1.0]], device=dev)[None].repeat(B, 1, 1).contiguous()
+    v_np, f_np = uv_sphere(a.lat, a.lon, ripple=0.15)
+    colour = lambda p: (0.5 + 0.5 * np.sin(np.asarray(p, np.float64) / 3.0 + np.array([0.0, 1.0, 2.0]))).astype(np.float32)      # 3 mm period
+    verts, faces = torch.from_numpy(v_np).to(dev), torch.from_numpy(f_np).to(dev)
+    vcol = torch.from_numpy(colour(v_np)).to(dev)
+    raster = lambda **kw: ops.mesh_raster(verts, faces, pose, K, H=H, W=W, face_ids=False, normals=False, **kw)
+    base = raster(vcolor=vcol)
+    covered = base["zbuf"] > 0
+    n_cov = int(covered.sum())
+    routes, iters, checks, meshes = {"base": lambda: raster(vcolor=vcol), "base cull": lambda: raster(vcolor=vcol, cull=True)}, {}, {}, {}
+    heavy = max(2, a.iters // 10)
+    for R in (1, 4, 8):
+        vs, fs, ni = FT.subdivide(v_np, f_np, R)
+        texels = torch.from_numpy(FT.texels_from_nodes(colour(vs), ni)).to(dev)
+        got = raster(texels=texels)
+        face = got["face"]
+        out = torch.empty(B, H, W, 3, device=dev)
+        routes["texels R=%d" % R] = lambda texels=texels: raster(texels=texels)
+        routes["texels R=%d cull" % R] = lambda texels=texels: raster(texels=texels, cull=True)
+        routes["shade R=%d" % R] = lambda texels=texels, face=face, out=out: ops.face_texel_shade(face, verts, faces, texels, pose, K, out=out)
+        meshes[R] = dict(R=R, texels_per_face=int(texels.shape[1]), texel_bytes=int(texels.numel() * 4), nodes=len(vs), faces_subdivided=len(fs))
+        if R == 1:
+            d = float((got["rgb"] - base["rgb"]).abs().max())
+            checks["R=1 against base"] = d
+            if not d <= 1e-5:
+                raise SystemExit("face_texel_bench: R = 1 differs from the vertex-colour route by %.3g; nothing was timed" % d)
+            continue
+        vs_d, fs_d, col_d = torch.from_numpy(vs).to(dev), torch.from_numpy(fs).to(dev), torch.from_numpy(colour(vs)).to(dev)
+        sub = lambda cull, vs_d=vs_d, fs_d=fs_d, col_d=col_d: ops.mesh_raster(vs_d, fs_d, pose, K, H=H, W=W, vcolor=col_d, face_ids=False, normals=False, cull=cull)
+        for cull in (False, True):
+            s = sub(cull)
+            # the same surface won in both routes: at a fold of the rippled sphere the two meshes' fp32 depth tests may pick different
+            # layers for a pixel, which is the rasteriser's difference, not the shading's; such pixels count as differing coverage
+            both = covered & (s["zbuf"] > 0) & ((got["zbuf"] - s["zbuf"]).abs() <= 1e-4 * got["zbuf"].abs())
+            diff = (got["rgb"] - s["rgb"]).abs()[both]
+            d, above = float(diff.max()), int((diff.max(-1).values > 5e-5).sum())
+            differ = int((covered != (s["zbuf"] > 0)).sum()) + int((covered & (s["zbuf"] > 0) & ~both).sum())
+            checks["R=%d against subdivided%s" % (R, " cull" if cull else "")] = dict(max_colour_difference=d, pixels_above_5e_5=above, pixels_compared=int(both.sum()),
+                                                                                   coverage_differs=differ)
+            if not d <= 2e-3 or above > 1e-4 * int(both.sum()) or differ > 0.005 * n_cov:
+                raise SystemExit("face_texel_bench: R = %d: the texel route and the subdivided route disagree (%.3g, %d pixels); nothing was timed" % (R, d, differ))
+            name = "subdivided R=%d%s" % (R, " cull" if cull else "")
+            routes[name] = lambda cull=cull, sub=sub: sub(cull)
+            if not cull:
+                iters[name] = heavy
+    iters = {name: iters.get(name, a.iters) for name in routes}
+    med, times = KB.race(routes, iters, a.warmup, a.repeats)
+    pixels = B * H * W
+    rows = [dict(route=name, us_per_call=med[name], us_all_repeats=times[name], frames_per_second=B / (med[name] * 1e-6), iters=iters[name]) for name in routes]
+    for row in rows:
+        if row["route"].startswith("shade"):
+            row["streamed_bytes"] = 16 * pixels                      # 4 B face read + 12 B rgb written per pixel
+            row["streamed_bytes_per_second"] = 16 * pixels / (row["us_per_call"] * 1e-6)
+        print(json.dumps(row), flush=True)
+    res = dict(bench="face_texels", device=torch.cuda.get_device_name(0), V=len(v_np), F=len(f_np), B=B, H=H, W=W, covered_pixels=n_cov,
+               covered_share=n_cov / pixels, iters=a.iters, warmup=a.warmup, repeats=a.repeats, shader_clock_ghz_before=clock_before,
+               shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start, textures=list(meshes.values()), checks=checks, rows=rows)
+    KB.finish(res, a.out)
+
+
+if __name__ == "__main__":
+    main()

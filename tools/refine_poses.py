@@ -4,7 +4,7 @@
 
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
-                                 [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster]
+                                 [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster] [--texels [ID=]PATH]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -47,7 +47,11 @@ converged on the occluded cases of section 23; the depth weight is sigma = 5 mm 
 also mask the other terms.  Without --joint nothing changes.
 
 --cull-raster: every refiner renders with the culled rasteriser (ops.mesh_raster(cull=True), K34), which skips whole
-chunks of 256 faces per 16 x 16 tile.  The planes are the same bit for bit, so the poses written are the same; only the time differs."""
+chunks of 256 faces per 16 x 16 tile.  The planes are the same bit for bit, so the poses written are the same; only the time differs.
+
+--texels [ID=]PATH (with --rgb): the mesh's face-texel texture, the .texels.npz that bake_texture.py --texel-res
+writes beside its PLY (keyed like --ply).  The photometric renders then take their colour from the texels (K35) instead of the vertex
+colours, --ply may be colourless, and the file is refused if it was baked for other faces than the mesh's."""
 import argparse
 import csv
 import json
@@ -111,6 +115,7 @@ def main(argv=None):
     ap.add_argument("--iters-joint", type=int, default=20)
     ap.add_argument("--weights", type=float, nargs=3, default=None, metavar=("SIL", "RGB", "DEPTH"))
     ap.add_argument("--cull-raster", action="store_true", help="render with the culled rasteriser: the same poses, faster on large meshes")
+    ap.add_argument("--texels", action="append", default=[], metavar="[ID=]PATH", help="with --rgb: face texels (bake_texture --texel-res)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -135,23 +140,32 @@ def main(argv=None):
         sys.exit("refine_poses: --depth and --rgb exclude each other")
     if a.occluders and a.known:
         sys.exit("refine_poses: --occluders and --known exclude each other")
+    if a.texels and not a.rgb:
+        sys.exit("refine_poses: --texels goes with --rgb")
     if (a.occluders or a.known) and not a.silhouette:
         sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
     from PIL import Image
     from texpose_amd import icp, joint, ops, photo_align, silhouette
     from texpose_amd.pose_error import depth_from_png
+    from texpose_amd.face_texels import load_texels
     from texpose_amd.surfel import load_ply
     if not torch.cuda.is_available():
         sys.exit("refine_poses: needs a GPU")
+    by_id = lambda item: (lambda oid, sep, path: (int(oid), path) if sep and oid.strip().isdigit() else (None, item))(*item.partition("="))
+    texel_files = dict(by_id(item) for item in a.texels)
     meshes = {}
     for item in a.ply:
         oid, sep, path = item.partition("=")
         key, path = (int(oid), path) if sep and oid.strip().isdigit() else (None, item)
         mesh = load_ply(path)
-        if a.rgb and mesh[2] is None:
-            sys.exit("refine_poses: --rgb needs a vertex-coloured mesh and %s has no colours" % path)
-        meshes[key] = mesh if a.rgb else mesh[:2]
+        if a.rgb and key in texel_files:                         # (colour from the face texels: the PLY's own colours are not used)
+            mesh = (mesh[0], mesh[1], None, load_texels(texel_files[key], mesh[1])[0])
+        elif a.rgb and mesh[2] is None:
+            sys.exit("refine_poses: --rgb needs a vertex-coloured mesh (or --texels) and %s has no colours" % path)
+        meshes[key] = (tuple(mesh) + (None,))[:4] if a.rgb else mesh[:2]
+    if set(texel_files) - set(meshes):
+        sys.exit("refine_poses: --texels names an object without a --ply: %s" % sorted(map(str, set(texel_files) - set(meshes))))
     cam = json.load(open(os.path.join(a.scene, "scene_camera.json")))
     gt = None
     if a.use_mask_visib or a.silhouette:
@@ -172,6 +186,7 @@ def main(argv=None):
     dev = a.device
     for oid, idx in jobs.items():
         verts, faces = meshes.get(oid, meshes.get(None))[:2]
+        vcolor, texels = meshes.get(oid, meshes.get(None))[2:4] if a.rgb else (None, None)
         refiner = outline = None
         for s in range(0, len(idx), a.batch):
             part = idx[s:s + a.batch]
@@ -216,15 +231,15 @@ def main(argv=None):
                 depth = torch.stack(planes) if second else measured  # (with --rgb: the photographs [Ft,H,W,3])
             H, W = depth.shape[1:3]
             if a.joint and (refiner is None or (refiner.H, refiner.W) != (H, W)):
-                refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=meshes.get(oid, meshes.get(None))[2] if a.rgb else None,
+                refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=vcolor, texels=texels,
                                              weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
                                              damping=a.damping, cull=a.cull_raster)
             if a.silhouette and not a.joint and (outline is None or (outline.H, outline.W) != (H, W)):
                 outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping, cull=a.cull_raster)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
-                    refiner = photo_align.PhotoRefiner(verts, faces, meshes.get(oid, meshes.get(None))[2], H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
-                                                       damping=a.damping, cull=a.cull_raster)
+                    refiner = photo_align.PhotoRefiner(verts, faces, vcolor, H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
+                                                       damping=a.damping, cull=a.cull_raster, texels=texels)
                 else:
                     refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping, cull=a.cull_raster)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
