@@ -1,7 +1,8 @@
-"""The per-image half of the Gauss-Newton refiners in plain torch ops in fp64, shared by icp.step_torch and photo_align.step_torch:
-the frame choice, the 6x6 Cholesky with the header's pivot rule, the exponential map and everything from the summed system to the
-output dict (count and status rules, the damped step, Gram-Schmidt, the fp32 rounding, the pass-through of a failed pose).  Each
-refiner builds its residual rows and calls ``solve``."""
+"""The per-image half of the Gauss-Newton refiners in plain torch ops in fp64, shared by the step_torch of icp, photo_align, silhouette
+and joint: the frame choice, the 6x6 Cholesky with the header's pivot rule, the exponential map and everything from the summed system
+to the output dict (count and status rules, the damped step, Gram-Schmidt, the fp32 rounding, the pass-through of a failed pose).
+Each refiner builds its residual rows between ``sums_head`` and ``normal_sums`` (the two with an image gradient through
+``image_gradient_rows``) and calls ``solve``."""
 from typing import Dict, Optional
 
 import torch
@@ -47,6 +48,54 @@ def frames_of(B: int, Ft: int, frame: Optional[Tensor], what: str, device=None) 
             raise ValueError("step_torch: %s without frame=, got %d" % (what % B, Ft))
         return torch.zeros(B, dtype=torch.long, device=device) if Ft == 1 else torch.arange(B, device=device)
     return frame.long().clamp(0, Ft - 1)
+
+
+def sums_head(zbuf: Tensor, pose: Tensor, intr: Tensor, planes: Tensor, trailing: int, frame: Optional[Tensor], what: str, tau: float):
+    """What every sums_torch starts from: ``planes`` the measured planes [Ft,H,W] + ``trailing`` dimensions (or one plane), ``what``
+    their name for frames_of -> (B, H, W, pose32 [B,3,4], intr [B,3,3] float32, planes [Ft,...] float32, fr [B] long, tau rounded to
+    fp32, zbuf as float32)."""
+    B, H, W = zbuf.shape
+    pose32 = pose.float().reshape(B, 3, 4)
+    intr = intr.float()
+    if intr.dim() == 2:
+        intr = intr[None].expand(B, 3, 3)
+    planes = planes.float()
+    if planes.dim() == 2 + trailing:
+        planes = planes[None]
+    fr = frames_of(B, planes.shape[0], frame, what, zbuf.device)
+    return B, H, W, pose32, intr, planes, fr, float(torch.tensor(tau, dtype=torch.float32)), zbuf.float()
+
+
+def masked(cand: Tensor, mask: Optional[Tensor], fr: Tensor) -> Tensor:
+    """``cand`` [B,H,W] without the pixels whose mask [Ft,H,W] (or one [H,W]) is 0 in the image's plane."""
+    if mask is None:
+        return cand
+    m = mask if mask.dim() == 3 else mask[None]
+    return cand & (m[fr] != 0)
+
+
+def image_gradient_rows(zf: Tensor, intr: Tensor, bi: Tensor, ii: Tensor, ji: Tensor, lf: Tensor, rt: Tensor, up: Tensor, dn: Tensor) -> Tensor:
+    """The Jacobian rows of n interior pixels (bi, ii, ji) whose residuals are read off an image with C channels: lf, rt, up, dn [n,C]
+    fp64, the image at the four neighbours (central differences) -> J [n C,6], the channels of a pixel one after the other."""
+    f64 = torch.float64
+    z = zf[bi, ii, ji].to(f64)
+    K = intr.to(f64)
+    fx, fy = K[bi, 0, 0], K[bi, 1, 1]
+    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / fx
+    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / fy
+    P = torch.stack([z * rx, z * ry, z], -1)[:, None, :].expand(-1, lf.shape[1], -1)        # [n,C,3]
+    gfx, gfy = (0.5 * (rt - lf)) * fx[:, None], (0.5 * (dn - up)) * fy[:, None]             # [n,C]
+    av = torch.stack([gfx / z[:, None], gfy / z[:, None], -(gfx * rx[:, None] + gfy * ry[:, None]) / z[:, None]], -1)
+    return torch.cat([torch.cross(P, av, dim=-1), av], -1).reshape(-1, 6)
+
+
+def normal_sums(B: int, bi: Tensor, J: Tensor, r: Tensor):
+    """The rows J [n,6] with residuals r [n] of images bi [n] summed per image -> (JtJ [B,6,6], Jtr [B,6], cost [B]) fp64."""
+    f64, dev = torch.float64, J.device
+    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, bi, J[:, :, None] * J[:, None, :])
+    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
+    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
+    return JtJ, Jtr, cost
 
 
 def solve(JtJ: Tensor, Jtr: Tensor, cost: Tensor, count: Tensor, pose32: Tensor, damping: float, evaluate_only: bool) -> Dict[str, Tensor]:

@@ -93,10 +93,7 @@ __global__ __launch_bounds__(kGnBlock) void icp_reduce_kernel(tp_depth_icp_args 
 }
 }  // namespace
 
-extern "C" size_t tp_depth_icp_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
-}
+extern "C" size_t tp_depth_icp_workspace_bytes(int B, int H, int W) { return tp::term_workspace_bytes(B, H, W); }
 
 bool tp::depth_icp_args_ok(const tp_depth_icp_args& a) {
   if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || a.V <= 0 || a.F <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
@@ -118,8 +115,5 @@ void tp::depth_icp_launch(const tp_depth_icp_args& a, hipStream_t st) {
 }
 
 extern "C" int tp_depth_icp_step(const tp_depth_icp_args* a, tp_stream_t stream) {
-  if (!a) { tp::set_error("tp_depth_icp_step: null args"); return -1; }
-  if (!tp::depth_icp_args_ok(*a)) return -1;
-  tp::depth_icp_launch(*a, (hipStream_t)stream);
-  return tp::check_launch("tp_depth_icp_step");
+  return tp::term_step("tp_depth_icp_step", a, tp::depth_icp_args_ok, tp::depth_icp_launch, stream);
 }

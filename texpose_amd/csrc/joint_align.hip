@@ -7,8 +7,8 @@
 //                exactly as the standalone call would.
 //   joint_solve  grid B x 64.  Gathers each term's G records with gn_gather (ascending tile order; silhouette, photometric, depth),
 //                29 threads form sum[k] = w_a S_a[k] + w_b S_b[k] + w_c S_c[k] over the weighted terms in fp64 as written, and
-//                thread 0 applies gn_solve_kernel's rules to the combined sums: count, pivot rule, gn_step, fp32 rounding, the
-//                pass-through of a failed pose.
+//                thread 0 applies gn_solve_kernel's rules to the combined sums (pose_gn.h's gn_decide: count, pivot rule, gn_step,
+//                fp32 rounding, the pass-through of a failed pose).
 // No atomics; every fp64 sum has one fixed order, so all outputs are a function of the inputs alone.
 #include "tp_common.h"
 #include "pose_gn.h"
@@ -40,31 +40,13 @@ __global__ __launch_bounds__(tp::kWave) void joint_solve_kernel(tp_joint_align_a
   if (threadIdx.x < kGnSums) sum[threadIdx.x] = s;
   __syncthreads();
   if (threadIdx.x != 0) return;
-  // from here on gn_solve_kernel's rules, word for word, on the combined sums
-  const float* T = j.pose + (int64_t)b * 12;
-  const double count = sum[28];
-  int status = 0;
-  double Pn[12];
-  if (count < (double)kGnMinCount) {
-    status = 1;
-  } else if (j.evaluate_only) {
-    double A[6][6];
-    gn_matrix(sum, A);
-    if (!cholesky6(A, kGnPivotTol)) status = 3;
-  } else {
-    double cur[12];
-    for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
-    bool ok = gn_step(sum, cur, (double)j.damping, Pn);
-    for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
-    if (!ok) status = 3;
-  }
-  j.inliers[b] = (int)count;
+  float out[12];
+  const int status = gn_decide(sum, j.pose + (int64_t)b * 12, (double)j.damping, j.evaluate_only != 0, out);          // gn_solve_kernel's rules
+  j.inliers[b] = (int)sum[28];
   j.chi2[b] = (float)sum[27];
   j.status[b] = status;
-  if (j.pose_out) {
-    const bool stepped = status == 0 && !j.evaluate_only;
-    for (int k = 0; k < 12; ++k) j.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
-  }
+  if (j.pose_out)
+    for (int k = 0; k < 12; ++k) j.pose_out[(int64_t)b * 12 + k] = out[k];
 }
 
 // what the joint step needs to know of a term, whichever struct it is

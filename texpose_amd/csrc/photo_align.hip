@@ -131,10 +131,7 @@ __global__ __launch_bounds__(kGnBlock, VEC ? 1 : 3) void photo_reduce_kernel(tp_
 }
 }  // namespace
 
-extern "C" size_t tp_photo_align_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
-}
+extern "C" size_t tp_photo_align_workspace_bytes(int B, int H, int W) { return tp::term_workspace_bytes(B, H, W); }
 
 bool tp::photo_align_args_ok(const tp_photo_align_args& a) {
   if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
@@ -156,8 +153,5 @@ void tp::photo_align_launch(const tp_photo_align_args& a, hipStream_t st) {
 }
 
 extern "C" int tp_photo_align_step(const tp_photo_align_args* a, tp_stream_t stream) {
-  if (!a) { tp::set_error("tp_photo_align_step: null args"); return -1; }
-  if (!tp::photo_align_args_ok(*a)) return -1;
-  tp::photo_align_launch(*a, (hipStream_t)stream);
-  return tp::check_launch("tp_photo_align_step");
+  return tp::term_step("tp_photo_align_step", a, tp::photo_align_args_ok, tp::photo_align_launch, stream);
 }

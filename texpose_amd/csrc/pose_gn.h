@@ -193,39 +193,46 @@ __device__ __forceinline__ int gn_frame_of(const Args& a, int b) {
   return fr;
 }
 
-// grid B, one wave: gathers the image's G records, then thread 0 applies the rules: fewer than six kept pixels: status 1; with
+// The decision of a solve kernel's thread 0 on the 29 sums of one image at pose T: fewer than six kept pixels: status 1; with
 // evaluate_only the pivot rule alone decides between 0 and 3; else one damped step, status 3 where it fails or leaves fp32's range.
-// inliers and rms (NaN without a pixel) are those of the pose that came in; pose_out is the stepped pose, or the input bit for bit.
-template <class Args>
-__global__ __launch_bounds__(tp::kWave) void gn_solve_kernel(Args a, const double* part, int G) {
-  __shared__ double sum[kGnPart], stage[kGnStage][kGnPart];
-  const int b = blockIdx.x;
-  gn_gather(part + (int64_t)b * G * kGnPart, G, stage, sum);
-  if (threadIdx.x != 0) return;
-  const float* T = a.pose + (int64_t)b * 12;
-  const double count = sum[28];
+// out: the stepped pose in fp32, or T bit for bit with evaluate_only or a non-zero status.  -> the status.
+__device__ inline int gn_decide(const double* sum, const float* T, double damping, bool evaluate_only, float (&out)[12]) {
   int status = 0;
   double Pn[12];
-  if (count < (double)kGnMinCount) {
+  if (sum[28] < (double)kGnMinCount) {
     status = 1;
-  } else if (a.evaluate_only) {
+  } else if (evaluate_only) {
     double A[6][6];
     gn_matrix(sum, A);
     if (!cholesky6(A, kGnPivotTol)) status = 3;
   } else {
     double cur[12];
     for (int k = 0; k < 12; ++k) cur[k] = (double)T[k];
-    bool ok = gn_step(sum, cur, (double)a.damping, Pn);
+    bool ok = gn_step(sum, cur, damping, Pn);
     for (int k = 0; k < 12; ++k) ok = ok && isfinite((float)Pn[k]);
     if (!ok) status = 3;
   }
+  const bool stepped = status == 0 && !evaluate_only;
+  for (int k = 0; k < 12; ++k) out[k] = stepped ? (float)Pn[k] : T[k];
+  return status;
+}
+
+// grid B, one wave: gathers the image's G records, then thread 0 decides (gn_decide).  inliers and rms (NaN without a pixel) are
+// those of the pose that came in; pose_out is the stepped pose, or the input bit for bit.
+template <class Args>
+__global__ __launch_bounds__(tp::kWave) void gn_solve_kernel(Args a, const double* part, int G) {
+  __shared__ double sum[kGnPart], stage[kGnStage][kGnPart];
+  const int b = blockIdx.x;
+  gn_gather(part + (int64_t)b * G * kGnPart, G, stage, sum);
+  if (threadIdx.x != 0) return;
+  const double count = sum[28];
+  float out[12];
+  const int status = gn_decide(sum, a.pose + (int64_t)b * 12, (double)a.damping, a.evaluate_only != 0, out);
   a.inliers[b] = (int)count;
   a.rms[b] = count > 0.0 ? (float)sqrt(sum[27] / count) : __int_as_float(0x7fc00000);
   a.status[b] = status;
-  if (a.pose_out) {
-    const bool stepped = status == 0 && !a.evaluate_only;
-    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = stepped ? (float)Pn[k] : T[k];
-  }
+  if (a.pose_out)
+    for (int k = 0; k < 12; ++k) a.pose_out[(int64_t)b * 12 + k] = out[k];
 }
 
 // The host checks both step calls make after their own size check, in the order callers see them.  `tau` is the caller's threshold

@@ -107,10 +107,7 @@ __global__ __launch_bounds__(tp::kWave) void sil_counts_kernel(tp_silhouette_ali
 }
 }  // namespace
 
-extern "C" size_t tp_silhouette_align_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return gn_workspace_bytes(B, gn_tiles((int64_t)H * W));
-}
+extern "C" size_t tp_silhouette_align_workspace_bytes(int B, int H, int W) { return tp::term_workspace_bytes(B, H, W); }
 
 bool tp::silhouette_align_args_ok(const tp_silhouette_align_args& a) {
   if (a.B <= 0 || a.B > 65535 || a.H <= 0 || a.W <= 0 || a.Ft <= 0 || (int64_t)a.H * a.W > 0x7FFFFFFFll) {
@@ -130,8 +127,5 @@ void tp::silhouette_align_launch(const tp_silhouette_align_args& a, hipStream_t 
 }
 
 extern "C" int tp_silhouette_align_step(const tp_silhouette_align_args* a, tp_stream_t stream) {
-  if (!a) { tp::set_error("tp_silhouette_align_step: null args"); return -1; }
-  if (!tp::silhouette_align_args_ok(*a)) return -1;
-  tp::silhouette_align_launch(*a, (hipStream_t)stream);
-  return tp::check_launch("tp_silhouette_align_step");
+  return tp::term_step("tp_silhouette_align_step", a, tp::silhouette_align_args_ok, tp::silhouette_align_launch, stream);
 }

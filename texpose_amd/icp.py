@@ -34,26 +34,11 @@ def sums_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     """The sums of step_torch before the solve (what joint.step_torch weights and adds) -> (JtJ [B,6,6], Jtr [B,6], cost [B] fp64,
     count [B], pose32 [B,3,4])."""
     f64 = torch.float64
-    dev = zbuf.device
-    B, H, W = zbuf.shape
+    B, H, W, pose32, intr, depth, fr, tau, zf = _gn_torch.sums_head(zbuf, pose, intr, depth, 0, frame, "depth must hold 1 or B = %d planes", tau_mm)
     V, F = verts.shape[0], faces.shape[0]
     verts64, faces = verts.float().to(f64), faces.long()
-    pose32 = pose.float().reshape(B, 3, 4)
-    intr = intr.float()
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3)
-    depth = depth.float()
-    if depth.dim() == 2:
-        depth = depth[None]
-    Ft = depth.shape[0]
-    fr = _gn_torch.frames_of(B, Ft, frame, "depth must hold 1 or B = %d planes", dev)
-    tau = float(torch.tensor(tau_mm, dtype=torch.float32))
     d_all = depth[fr]                                                                       # [B,H,W]
-    zf = zbuf.float()
-    cand = (zf > 0) & torch.isfinite(zf) & (d_all > 0) & torch.isfinite(d_all) & (face >= 0) & (face < F)
-    if mask is not None:
-        m = mask if mask.dim() == 3 else mask[None]
-        cand = cand & (m[fr] != 0)
+    cand = _gn_torch.masked((zf > 0) & torch.isfinite(zf) & (d_all > 0) & torch.isfinite(d_all) & (face >= 0) & (face < F), mask, fr)
     bi, ii, ji = torch.nonzero(cand, as_tuple=True)
     tri = faces[face[bi, ii, ji].long()]                                                    # [n,3]
     good = ((tri >= 0) & (tri < V)).all(-1)
@@ -78,11 +63,7 @@ def sums_torch(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: T
     P, Q = ray * z[:, None], ray * d[:, None]
     r = (n * (P - Q)).sum(-1)
     J = torch.cat([torch.cross(P, n, dim=-1), n], -1)                                       # [n,6]
-    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, bi, J[:, :, None] * J[:, None, :])
-    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
-    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
-    count = torch.bincount(bi, minlength=B)
-    return JtJ, Jtr, cost, count, pose32
+    return _gn_torch.normal_sums(B, bi, J, r) + (torch.bincount(bi, minlength=B), pose32)
 
 
 class DepthRefiner(_MeshRefiner):

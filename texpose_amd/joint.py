@@ -69,19 +69,9 @@ class JointRefiner(_MeshRefiner):
         super().__init__(verts, faces, H, W, device, cull=cull)
         if vcolor is not None and texels is not None:
             raise ValueError("JointRefiner: vcolor= or texels=, not both")
-        self.vcolor = None
-        self.texels = None                                       # [F,T,3] face texels (K35) in place of vertex colours
-        if texels is not None:
-            self.texels = torch.as_tensor(texels).to(device=self.device, dtype=torch.float32).contiguous()
-            if self.texels.dim() != 3 or self.texels.shape[0] != self.faces.shape[0] or self.texels.shape[2] != 3:
-                raise ValueError("JointRefiner: texels [F,T,3] expected, T texels per face, got %s" % (tuple(self.texels.shape),))
-        if vcolor is not None:
-            self.vcolor = torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(self.vcolor.shape) != tuple(self.verts.shape):
-                raise ValueError("JointRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
+        self._colours(vcolor, texels)
         self.weights = ops._joint_weights("JointRefiner", weights)
         self.tau_px, self.tau, self.tau_mm, self.iters, self.damping = tau_px, tau, tau_mm, int(iters), float(damping)
-        self._sdf_workspaces: Dict[int, Tensor] = {}
 
     def refine(self, pose: Tensor, intr: Tensor, *, mask_or_sdf: Optional[Tensor] = None, known: Optional[Tensor] = None,
                image: Optional[Tensor] = None, depth: Optional[Tensor] = None, frame: Optional[Tensor] = None,
@@ -97,21 +87,11 @@ class JointRefiner(_MeshRefiner):
         if known is not None and mask_or_sdf is None:
             raise ValueError("JointRefiner.refine: known= goes with the measured masks (mask_or_sdf=)")
         if mask_or_sdf is not None:
-            planes = mask_or_sdf if mask_or_sdf.dim() == 3 else mask_or_sdf[None]
-            if tuple(planes.shape[1:]) != (self.H, self.W):
-                raise ValueError("JointRefiner.refine: planes of %d x %d expected, got %s" % (self.H, self.W, tuple(planes.shape)))
-            if known is not None and planes.dtype.is_floating_point:
-                raise ValueError("JointRefiner.refine: known= goes with masks; mask_or_sdf is a field (pass ops.mask_sdf(mask, known=known))")
-            if not planes.dtype.is_floating_point:
-                Ft = planes.shape[0]
-                if known is not None:
-                    known = (known if known.dim() == 3 else known[None]).to(self.device).contiguous()
-                    for term in ("photo", "depth"):              # (with a mask of the caller's: both must allow the pixel)
-                        own = masks.get(term)
-                        masks[term] = known if own is None else ((own if own.dim() == 3 else own[None]).to(self.device) != 0) & (known != 0)
-                if Ft not in self._sdf_workspaces:
-                    self._sdf_workspaces[Ft] = ops.mask_sdf_workspace(Ft, self.H, self.W, self.device)
-                planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft], known=known)
+            planes, known = self._field_of(mask_or_sdf, known)
+            if known is not None:
+                for term in ("photo", "depth"):                  # (with a mask of the caller's: both must allow the pixel)
+                    own = masks.get(term)
+                    masks[term] = known if own is None else ((own if own.dim() == 3 else own[None]).to(self.device) != 0) & (known != 0)
         if image is not None and self.vcolor is None and self.texels is None:
             raise ValueError("JointRefiner.refine: image= needs the refiner's vcolor= or texels=")
         masks = {k: v for k, v in masks.items() if (k == "silhouette" and planes is not None) or (k == "photo" and image is not None)

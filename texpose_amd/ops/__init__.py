@@ -21,3 +21,4 @@ from .feat import *  # noqa: F401,F403
 from .step import *  # noqa: F401,F403
 from .scene import *  # noqa: F401,F403
 from .pose import *  # noqa: F401,F403
+from .refine import *  # noqa: F401,F403

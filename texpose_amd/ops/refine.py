@@ -1,0 +1,554 @@
+"""K29-K33: the render-and-compare pose refiners -- the depth ICP, the photometric alignment, the masks' distance field, the silhouette
+alignment and the joint step of the three -- behind one table of terms: what a term's step takes, asks of the rasteriser and returns
+is said once in ``_TERMS``; one builder fills any term's args struct, one helper sizes every workspace and one driver runs all four
+loops."""
+from dataclasses import dataclass
+from typing import Dict, Optional
+
+import torch
+
+from .. import _lib
+from ._base import Tensor, _call, _f32, _intr_per_view, _lengths, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg
+
+__all__ = ["depth_icp_workspace", "depth_icp_step", "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS",
+           "photo_align", "mask_sdf_workspace", "mask_sdf", "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step",
+           "SILHOUETTE_ALIGN_KEYS", "silhouette_align", "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step",
+           "JOINT_ALIGN_KEYS", "joint_align"]
+
+
+# ------------------------------------------------------------------------------------------ the terms
+@dataclass(frozen=True)
+class _Term:
+    """One residual term of the refiners, as its step (tp_<...>_step) and the layers above see it."""
+    name: str                    # as joint_align_step's keyword and in masks=
+    prefix: str                  # of its keys in the joint results (and, less the '_', of its weight in tp_joint_align_args)
+    args: type                   # the step's args struct
+    workspace_bytes: str         # the library's size query (B, H, W)
+    rendered: tuple              # the inputs before ``pose``: the mesh and mesh_raster's planes at the pose
+    plane: str                   # the measured planes [Ft,H,W] + trailing ...
+    trailing: tuple
+    word: str                    # ... and what the messages call them
+    threshold: str               # its threshold's name
+    counts: tuple = ()           # int32 [B] outputs beyond inliers / rms / status
+    colour: bool = False         # asks mesh_raster for rgb
+    face_ids: bool = False       # asks mesh_raster for the face index
+
+
+_TERMS = (_Term("silhouette", "sil_", _lib.SilhouetteAlignArgs, "tp_silhouette_align_workspace_bytes", ("zbuf",), "sdf", (), "planes", "tau_px",
+                counts=("inter", "uni")),
+          _Term("photo", "photo_", _lib.PhotoAlignArgs, "tp_photo_align_workspace_bytes", ("zbuf", "rgb"), "image", (3,), "photographs", "tau", colour=True),
+          _Term("depth", "icp_", _lib.DepthIcpArgs, "tp_depth_icp_workspace_bytes", ("verts", "faces", "zbuf", "face"), "depth", (), "planes", "tau_mm",
+                face_ids=True))
+_SILHOUETTE, _PHOTO, _DEPTH = _TERMS
+JOINT_TERMS = tuple(t.name for t in _TERMS)              # the order of the weights and of the sum
+
+
+def _term_bytes(terms, B: int, H: int, W: int, align: int = 1) -> list:
+    """Each term's ``*_workspace_bytes`` at B images of H x W, rounded up to ``align``."""
+    lib = _lib.load()
+    return [(int(getattr(lib, t.workspace_bytes)(B, H, W)) + align - 1) // align * align for t in terms]
+
+
+def _new_workspace(op: str, terms, B: int, H: int, W: int, device) -> Tensor:
+    return _workspace_arg(op, None, sum(_term_bytes(terms, B, H, W)), device)
+
+
+def _frame_planes(op: str, term: _Term, planes: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
+    """The measured planes of ``term`` [Ft,H,W] + trailing (one plane: Ft = 1), the frame map and the mask [Ft,H,W] of a step ->
+    (planes, frame, mask, Ft)."""
+    name, trailing = term.plane, term.trailing
+    planes = _f32(planes.detach(), name)
+    if planes.dim() == 2 + len(trailing):
+        planes = planes[None]
+    if planes.dim() != 3 + len(trailing) or tuple(planes.shape[1:]) != (H, W) + trailing or planes.shape[0] == 0:
+        layout = "[Ft,H=%d,W=%d,3] (channels last)" % (H, W) if trailing else "[Ft,H=%d,W=%d]" % (H, W)
+        raise ValueError("%s: %s %s expected, got %s" % (op, name, layout, tuple(planes.shape)))
+    Ft = planes.shape[0]
+    frame = _lengths(op, frame, "frame", B, like)
+    if frame is None and Ft not in (1, B):
+        raise ValueError("%s: %s must hold 1 or B = %d %s without frame=, got %d" % (op, name, B, term.word, Ft))
+    if mask is not None:
+        if torch.is_tensor(mask) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+        if torch.is_tensor(mask) and mask.dim() == 2:
+            mask = mask[None]
+        mask = _want_gpu(op, mask, "mask", torch.uint8, (Ft, H, W))
+    return planes, frame, mask, Ft
+
+
+def _term_args(term: _Term, op: str, tensors: dict, *, threshold, damping=1e-6, frame=None, mask=None, evaluate_only=False, workspace=None, out=None,
+               with_pose=True):
+    """The arguments of ``term``'s step, checked: ``tensors`` holds its rendered inputs, ``pose``, ``intr`` and its measured planes by
+    name -> (the filled args struct, its outputs, the tensors it points into).  Without ``with_pose`` (a term of the joint step, which
+    writes no pose of its own) there is no 'pose' among the outputs and pose_out is null."""
+    t = dict(tensors)
+    if "verts" in t:
+        t["verts"] = _points(op, t["verts"], "verts")
+    pose = t["pose"] = _poses(op, t["pose"], "pose")
+    B = pose.shape[0]
+    if "faces" in t:
+        faces = _want_gpu(op, t["faces"], "faces", torch.int32, None)
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+            raise ValueError("%s: faces [F,3] expected, got %s" % (op, tuple(faces.shape)))
+    zbuf = _want_gpu(op, t["zbuf"], "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.shape[0] != B or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B=%d,H,W] expected, got %s" % (op, B, tuple(zbuf.shape)))
+    H, W = zbuf.shape[1:]
+    if "face" in t:
+        _want_gpu(op, t["face"], "face", torch.int32, (B, H, W))
+    if "rgb" in t:
+        _want_gpu(op, t["rgb"], "rgb", torch.float32, (B, H, W, 3))
+    t["intr"] = _intr_per_view(op, t["intr"], B)
+    t[term.plane], frame, mask, Ft = _frame_planes(op, term, t[term.plane], frame, mask, B, H, W, zbuf)
+    spec = {"pose": (torch.float32, (B, 3, 4)), "inliers": (torch.int32, (B,)), "rms": (torch.float32, (B,)), "status": (torch.int32, (B,))}
+    spec.update({k: (torch.int32, (B,)) for k in term.counts})
+    if not with_pose:
+        del spec["pose"]
+    res = _outputs(op, out, spec, zbuf.device, partial=True)
+    workspace = _workspace_arg(op, workspace, _term_bytes((term,), B, H, W)[0], zbuf.device, align=16)
+    a = term.args()
+    for k, v in t.items():
+        setattr(a, k, v.data_ptr())
+    for k, v in res.items():
+        setattr(a, "pose_out" if k == "pose" else k, v.data_ptr())          # (pose_out stays null without with_pose)
+    a.frame, a.mask, a.workspace = _ptr(frame), _ptr(mask), workspace.data_ptr()
+    a.B, a.Ft, a.H, a.W = B, Ft, H, W
+    if "verts" in t:
+        a.V, a.F = t["verts"].shape[0], t["faces"].shape[0]
+    setattr(a, term.threshold, float(threshold))
+    a.damping, a.evaluate_only = float(damping), int(bool(evaluate_only))
+    return a, res, (workspace, frame, mask) + tuple(t.values())             # (the struct holds addresses only)
+
+
+# ------------------------------------------------------------------------------------------ the loops
+def _tau_schedule(op: str, tau, tau_name: str, iters: int):
+    """A loop's thresholds, checked before anything else of the call: one value or ``iters`` + 1 host values -> iters + 1 floats."""
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("%s: iters >= 0 expected, got %d" % (op, iters))
+    taus = [float(tau)] * (iters + 1) if isinstance(tau, (int, float)) else [float(t) for t in tau]
+    if len(taus) != iters + 1:
+        raise ValueError("%s: %s must be one value or iters + 1 = %d values, got %d" % (op, tau_name, iters + 1, len(taus)))
+    return taus
+
+
+def _schedules(op: str, given, iters: int) -> list:
+    """The thresholds of a loop over ``given`` = [(term, measured planes or None, threshold(s), mask)], absent terms' too -> per pass one
+    value per entry of ``given``."""
+    return list(zip(*[_tau_schedule(op, th, term.threshold, iters) for term, _, th, _ in given]))
+
+
+def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, given, taus, *, damping, frame, workspace, cull,
+            vcolor=None, texels=None, visible_iou=False, weights=None) -> Dict[str, Tensor]:
+    """The loop of every refiner over the terms of ``given`` that have planes: one pass per entry of ``taus`` (_schedules) of ONE
+    mesh_raster call at the current poses, asked only for what these terms need, and one step from it, the last evaluate-only; a step
+    that fails passes its pose on.  Without ``weights`` the step is the single term's own (its 'rms' is the cost carried); with them it
+    is joint_align_step ('chi2'), and the last pass's per-term keys are returned too.  -> ``keys``: the last pass's pose, inliers and
+    cost, the status of the last step taken (of the evaluation where there is no step), inliers0 / <cost>0 of the first pass; with a
+    term that counts coverage 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' / 'iou0_visible'."""
+    joint = weights is not None
+    cost = "chi2" if joint else "rms"
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
+    B = pose.shape[0]
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    intr = _intr_per_view(op, intr, B)
+    terms, planes, masks = [], {}, {}
+    for i, (term, p, _, m) in enumerate(given):
+        if p is None:
+            continue
+        p = _f32(p.detach(), term.plane)
+        p = p[None] if p.dim() == 2 + len(term.trailing) else p
+        if p.dim() != 3 + len(term.trailing) or p.numel() == 0 or tuple(p.shape[3:]) != term.trailing:
+            raise ValueError("%s: %s [Ft,H,W%s]%s expected, got %s" % (op, term.plane, ",3" if term.trailing else "",
+                                                                        "" if joint or not term.trailing else " (channels last)", tuple(p.shape)))
+        terms.append((i, term))
+        planes[term.plane], masks[term.name] = p, m
+    sizes = {tuple(p.shape[1:3]) for p in planes.values()}
+    if len(sizes) != 1:
+        raise ValueError("%s: the measured planes must be of one size H x W, got %s" % (op, {k: tuple(v.shape) for k, v in planes.items()}))
+    H, W = sizes.pop()
+    for _, term in terms:
+        planes[term.plane], frame, masks[term.name], _ = _frame_planes(op, term, planes[term.plane], frame, masks[term.name], B, H, W, pose)
+    vcolor = None if vcolor is None else _f32(vcolor.detach(), "vcolor")
+    texels = None if texels is None else _f32(texels.detach(), "texels")
+    workspace = _workspace_arg(op, workspace, sum(_term_bytes([t for _, t in terms], B, H, W, 16 if joint else 1)), pose.device, align=16)
+    counting = next((t for _, t in terms if t.counts), None)
+    if visible_iou:
+        if counting is None:
+            raise ValueError("%s: visible_iou needs %s=" % (op, next(t.plane for t in _TERMS if t.counts)))
+        unknown = torch.isnan(planes[counting.plane])            # [Ft,H,W]; the plane of image b by the step's frame rule
+        if frame is not None:
+            unknown = unknown[frame.clamp(0, unknown.shape[0] - 1).long()]
+    colour = any(t.colour for _, t in terms)
+    ask = dict(H=H, W=W, vcolor=vcolor if colour else None, texels=texels if colour else None, face_ids=any(t.face_ids for _, t in terms),
+               normals=False, cull=cull)
+    from .scene import mesh_raster                               # (looked up per call: tests and tools replace ops.scene.mesh_raster)
+    mesh = dict(verts=verts, faces=faces)
+    fixed = [(i, term, dict({k: mesh[k] for k in term.rendered if k in mesh}, **{term.plane: planes[term.plane]}, frame=frame, mask=masks[term.name]),
+              [k for k in term.rendered if k not in mesh]) for i, term in terms]
+    step = _STEPS[terms[0][1].name]
+    hidden = []
+
+    def one_pass(pose, th, last):                                # (a function: the rendered planes are released before the next pass renders)
+        r = mesh_raster(verts, faces, pose, intr, **ask)
+        own = {term.name: dict(kw, **{k: r[k] for k in rendered}, **{term.threshold: th[i]}) for i, term, kw, rendered in fixed}
+        if joint:
+            got = joint_align_step(pose, intr, weights=weights, damping=damping, evaluate_only=last, workspace=workspace, **own)
+        else:
+            got = step(pose=pose, intr=intr, damping=damping, evaluate_only=last, workspace=workspace, **own[terms[0][1].name])
+        if visible_iou and (not hidden or last):                 # (the first and the last rendering)
+            z = r["zbuf"]
+            hidden.append(((z > 0) & torch.isfinite(z) & unknown).flatten(1).sum(1))
+        return got
+
+    first = status = None
+    for it, th in enumerate(taus):
+        last = it == len(taus) - 1
+        got = one_pass(pose, th, last)
+        first = got if first is None else first
+        status = got["status"] if not last or status is None else status
+        pose = got["pose"]
+    res = {"pose": got["pose"], "inliers": got["inliers"], cost: got[cost], "status": status, "inliers0": first["inliers"], cost + "0": first[cost]}
+    res = {k: res[k] for k in keys}
+    if joint:
+        res.update({k: v for k, v in got.items() if k.startswith(tuple(t.prefix for t in _TERMS))})
+    if counting is not None:
+        inter, uni = ((counting.prefix if joint else "") + k for k in counting.counts)
+        res.update(iou=got[inter].float() / got[uni].float(), iou0=first[inter].float() / first[uni].float())
+        if visible_iou:
+            def seen(r, h):
+                left = r[uni] - h                                # (>= inter: a hidden pixel is covered and not inside)
+                return torch.where(left == 0, torch.full_like(left, float("nan"), dtype=torch.float32), r[inter].float() / left.float())
+            res.update(iou_visible=seen(got, hidden[-1]), iou0_visible=seen(first, hidden[0]))
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K29
+def depth_icp_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for depth_icp_step / depth_icp at B images of H x W (tp_depth_icp_workspace_bytes); needs no clearing."""
+    return _new_workspace("depth_icp", (_DEPTH,), B, H, W, device)
+
+
+@_on_tensor_device
+def depth_icp_step(verts: Tensor, faces: Tensor, zbuf: Tensor, face: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, *, tau_mm: float,
+                   damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                   workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of projective point-to-plane ICP for B poses (tp_depth_icp_step; the rules are in the header): verts [V,3], faces [F,3]
+    int32, zbuf / face [B,H,W] (mesh_raster's planes of the mesh at ``pose``; taken as they are), pose [B,3,4], intr [B,3,3] or one
+    [3,3], depth [Ft,H,W] (the measured depth in mm; <= 0, NaN, Inf: no value; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask
+    [Ft,H,W] uint8 or bool (0: skip the pixel) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with
+    ``evaluate_only`` or a non-zero status), 'inliers' [B] int32 and 'rms' [B] (mm) of ``pose`` over the pixels within tau_mm along
+    the ray, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
+    depth_icp_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches, no
+    atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    a, res, _alive = _term_args(_DEPTH, "depth_icp_step", dict(verts=verts, faces=faces, zbuf=zbuf, face=face, pose=pose, intr=intr, depth=depth),
+                                threshold=tau_mm, damping=damping, frame=frame, mask=mask, evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_depth_icp_step", a)         # (tau_mm, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+DEPTH_ICP_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
+
+
+@_on_tensor_device
+def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: Tensor, *, tau_mm=20.0, iters: int = 5, damping: float = 1e-6,
+              frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+              cull: bool = False) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against measured depth (the rules are in the header, K29): ``iters`` + 1 passes of mesh_raster at the
+    current poses (depth and face index, H x W = depth's) followed by depth_icp_step, the last with evaluate_only.  ``tau_mm``: one
+    value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose' [B,3,4], its
+    'inliers' [B] int32 and 'rms' [B] (mm), 'status' [B] int32 of the last step taken (of the evaluation where iters = 0) and
+    'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the rasteriser's,
+    bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits."""
+    op, given = "depth_icp", [(_DEPTH, depth, tau_mm, mask)]
+    return _refine(op, DEPTH_ICP_KEYS, verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
+                   workspace=workspace, cull=cull)
+
+
+# ------------------------------------------------------------------------------------------ K30
+def photo_align_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for photo_align_step / photo_align at B images of H x W (tp_photo_align_workspace_bytes); needs no clearing."""
+    return _new_workspace("photo_align", (_PHOTO,), B, H, W, device)
+
+
+@_on_tensor_device
+def photo_align_step(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau: float, damping: float = 1e-6,
+                     frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                     workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of photometric alignment for B poses (tp_photo_align_step; the rules are in the header): zbuf [B,H,W] / rgb [B,H,W,3]
+    (mesh_raster's planes of the vertex-coloured mesh at ``pose``; taken as they are), pose [B,3,4], intr [B,3,3] or one [3,3], image
+    [Ft,H,W,3] (the photograph, channels last, in rgb's units; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask [Ft,H,W] uint8 or
+    bool (0: skip the pixel) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a non-zero
+    status), 'inliers' [B] int32 and 'rms' [B] (colour units) of ``pose`` over the interior covered pixels whose colours differ by at
+    most ``tau``, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite).  ``workspace``:
+    photo_align_workspace(B, H, W); ``out``: any of the four tensors to write into (out['pose'] must not be ``pose``).  Two launches,
+    no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    a, res, _alive = _term_args(_PHOTO, "photo_align_step", dict(zbuf=zbuf, rgb=rgb, pose=pose, intr=intr, image=image), threshold=tau, damping=damping,
+                                frame=frame, mask=mask, evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_photo_align_step", a)       # (tau, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
+
+
+@_on_tensor_device
+def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
+                damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
+    mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
+    ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
+    [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (colour units), 'status' [B] int32 of the last step taken (of the evaluation where
+    iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
+    rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with
+    mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] with ``vcolor`` None: the passes colour the mesh from its face texels
+    (mesh_raster(texels=), K35); exactly one of the two."""
+    op, given = "photo_align", [(_PHOTO, image, tau, mask)]
+    if (vcolor is None) == (texels is None):
+        raise ValueError("%s: exactly one of vcolor [V,3] and texels= [F,T,3] expected" % op)
+    return _refine(op, PHOTO_ALIGN_KEYS, verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels)
+
+
+# ------------------------------------------------------------------------------------------ K31
+def mask_sdf_workspace(F: int, H: int, W: int, device) -> Tensor:
+    """A workspace for mask_sdf at F masks of H x W (tp_mask_sdf_workspace_bytes); needs no clearing."""
+    return _workspace_arg("mask_sdf", None, int(_lib.load().tp_mask_sdf_workspace_bytes(F, H, W)), device)
+
+
+@_on_tensor_device
+def mask_sdf(mask: Tensor, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None, known: Optional[Tensor] = None) -> Tensor:
+    """The exact signed Euclidean distance field of F masks (tp_mask_sdf; the rules are in the header): mask [F,H,W] (or one [H,W])
+    uint8 or bool, non-zero: set -> sdf float32 of mask's shape, in pixels: sqrt(d2_set) - 0.5 on a clear pixel, -(sqrt(d2_clear) -
+    0.5) on a set one, with the squared distances to the nearest set / clear pixel of the plane (H^2 + W^2 where it has none).
+    ``out``: the tensor to write into; ``workspace``: mask_sdf_workspace(F, H, W).  H, W <= 8192.  Two launches, no atomics, a function
+    of the mask alone, safe under torch.cuda.graph.  ``known`` (uint8 or bool, of mask's shape, non-zero: the pixel's mask value is a
+    measurement) makes the rest UNKNOWN, neither set nor clear (tp_mask_sdf_known, K31c): no distance is measured to such a pixel and
+    its own value is NaN, which silhouette_align_step drops; with every pixel known the field is the plain one bit for bit."""
+    op = "mask_sdf"
+    if torch.is_tensor(mask) and not mask.is_cuda:
+        raise _lib.TexposeLibraryError("mask must live on the GPU (texpose_amd has no CPU path)")
+    if torch.is_tensor(mask) and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    mask = _want_gpu(op, mask, "mask", torch.uint8, None)
+    if known is not None:
+        if torch.is_tensor(known) and known.dtype == torch.bool:
+            known = known.view(torch.uint8) if known.is_contiguous() else known.to(torch.uint8)
+        known = _want_gpu(op, known, "known", torch.uint8, tuple(mask.shape))
+    if mask.dim() not in (2, 3) or mask.numel() == 0:
+        raise ValueError("%s: mask [F,H,W] or [H,W] expected, got %s" % (op, tuple(mask.shape)))
+    F, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
+    sdf = torch.empty(mask.shape, device=mask.device) if out is None else _want_gpu(op, out, "out", torch.float32, tuple(mask.shape))
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_mask_sdf_workspace_bytes(F, H, W)), mask.device, align=16)
+    if known is None:
+        _call("tp_mask_sdf", mask.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())      # (H or W > 8192: the library's error)
+    else:
+        _call("tp_mask_sdf_known", mask.data_ptr(), known.data_ptr(), sdf.data_ptr(), F, H, W, workspace.data_ptr())
+    return sdf
+
+
+@_on_tensor_device
+def mask_known_from_others(sdf: Tensor, band_px: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """Who hides whom among the N instances of ONE frame (tp_mask_known_from_others, K32; the rules are in the header): sdf [N,H,W]
+    float32, mask_sdf's fields of the frame's instance masks (taken as they are) -> known [N,H,W] uint8: 0 where the pixel lies within
+    ``band_px`` pixels of a set pixel of ANOTHER instance (sdf[m,p] <= band_px - 0.5 in fp32 for some m != n; a NaN is not near), else
+    1: mask_sdf's ``known``.  Conservative: where two instances touch, both lose the contour between them.  ``out``: the uint8 tensor
+    to write into.  One launch, no workspace, no atomics, safe under torch.cuda.graph."""
+    op = "mask_known_from_others"
+    if torch.is_tensor(sdf) and not sdf.is_cuda:
+        raise _lib.TexposeLibraryError("sdf must live on the GPU (texpose_amd has no CPU path)")
+    sdf = _want_gpu(op, sdf, "sdf", torch.float32, None)
+    if sdf.dim() != 3 or sdf.numel() == 0:
+        raise ValueError("%s: sdf [N,H,W] expected, got %s" % (op, tuple(sdf.shape)))
+    N, H, W = sdf.shape
+    known = torch.empty(sdf.shape, device=sdf.device, dtype=torch.uint8) if out is None else _want_gpu(op, out, "out", torch.uint8, tuple(sdf.shape))
+    _call("tp_mask_known_from_others", sdf.data_ptr(), known.data_ptr(), N, H, W, float(band_px))  # (band_px, N > 65535: the library's error)
+    return known
+
+
+def silhouette_align_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for silhouette_align_step / silhouette_align at B images of H x W (tp_silhouette_align_workspace_bytes); needs no
+    clearing."""
+    return _new_workspace("silhouette_align", (_SILHOUETTE,), B, H, W, device)
+
+
+@_on_tensor_device
+def silhouette_align_step(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px: float, damping: float = 1e-6,
+                          frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, evaluate_only: bool = False,
+                          workspace: Optional[Tensor] = None, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One step of silhouette alignment for B poses (tp_silhouette_align_step; the rules are in the header): zbuf [B,H,W]
+    (mesh_raster's depth of the mesh at ``pose``; taken as it is), pose [B,3,4], intr [B,3,3] or one [3,3], sdf [Ft,H,W] (mask_sdf's
+    field of the measured masks: pixels, negative inside; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask [Ft,H,W] uint8 or bool
+    (0: the pixel gives no row) -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a
+    non-zero status), 'inliers' [B] int32 and 'rms' [B] (pixels) of ``pose`` over the interior rim pixels of the rendering within
+    ``tau_px`` of the measured outline, 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not positive definite), 'inter' and
+    'uni' [B] int32 (the pixels covered and inside the measured mask, and those with either: IoU = inter / uni).  ``workspace``:
+    silhouette_align_workspace(B, H, W); ``out``: any of the six tensors to write into (out['pose'] must not be ``pose``).  Three
+    launches, no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    a, res, _alive = _term_args(_SILHOUETTE, "silhouette_align_step", dict(zbuf=zbuf, pose=pose, intr=intr, sdf=sdf), threshold=tau_px, damping=damping,
+                                frame=frame, mask=mask, evaluate_only=evaluate_only, workspace=workspace, out=out)
+    _call("tp_silhouette_align_step", a)  # (tau_px, damping out of range, out['pose'] overlapping pose: the library's error)
+    return res
+
+
+SILHOUETTE_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0", "iou", "iou0")
+
+
+@_on_tensor_device
+def silhouette_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, *, tau_px=4.0, iters: int = 10,
+                     damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                     workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against the outlines of measured masks (the rules are in the header, K31): ``iters`` + 1 passes of
+    mesh_raster at the current poses (depth alone, H x W = sdf's) followed by silhouette_align_step, the last with evaluate_only.
+    ``sdf`` [Ft,H,W]: mask_sdf of the measured masks.  ``tau_px``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule
+    (the last is the final evaluation's).  -> 'pose' [B,3,4], its 'inliers' [B] int32 and 'rms' [B] (pixels), 'status' [B] int32 of the
+    last step taken (of the evaluation where iters = 0), 'inliers0' / 'rms0' of the start pose and 'iou' / 'iou0' [B] float32, the
+    intersection over union of the rendering's coverage and the measured mask at the last and at the start pose (NaN where both are
+    empty).  A step that fails passes its pose on.  It closes the OUTLINE: a pose parameter the outline does not see (a rotation about
+    a symmetry axis, depth at a small radius) stays where it was, and a measured mask cut by an occluder pulls the rim to the cut.
+    3 (iters + 1) launches besides the rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.
+    ``visible_iou``: for a field with unknown pixels (mask_sdf's ``known``; NaN there) also 'iou_visible' / 'iou0_visible' [B] float32,
+    inter / (uni - hidden) at the last and at the start pose, ``hidden`` the covered pixels of the plane whose field value is NaN: the
+    IoU over the pixels that were measured (NaN where none is left).  Exact integer counts by torch reductions on the first and the
+    last rendering; without the flag nothing else runs and the keys are those above.  ``cull``: the passes render with
+    mesh_raster(cull=True), same bits."""
+    op, given = "silhouette_align", [(_SILHOUETTE, sdf, tau_px, mask)]
+    return _refine(op, SILHOUETTE_ALIGN_KEYS[:6], verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
+                   workspace=workspace, cull=cull, visible_iou=visible_iou)
+
+
+_STEPS = dict(zip(JOINT_TERMS, (silhouette_align_step, photo_align_step, depth_icp_step)))          # a single-term loop launches its own step
+
+
+# ------------------------------------------------------------------------------------------ K33
+# 1 / sigma^2 per residual unit (pixels, colour units, mm).  w_photo = 100 is the only one of 25, 100 and 400 with which the twelve
+# occluded cases of DESIGN section 23 all converged; w_icp = 1 / 25 is sigma = 5 mm and is NOT tuned on anything.
+JOINT_WEIGHTS = (1.0, 100.0, 1.0 / 25.0)
+
+
+def _joint_weights(op: str, weights) -> tuple:
+    try:
+        w = tuple(float(x) for x in weights)
+    except TypeError:
+        w = ()
+    if len(w) != 3:
+        raise ValueError("%s: weights must be three host values (silhouette, photo, depth), got %r" % (op, weights))
+    if not all(x >= 0.0 and x != float("inf") for x in w):
+        raise ValueError("%s: weights must be finite and not negative, got %r" % (op, w))
+    return w
+
+
+def joint_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Tensor:
+    """A workspace for joint_align_step / joint_align at B images of H x W with ``terms`` terms present (each term's own
+    ``*_workspace_bytes``, one after the other); needs no clearing."""
+    return _new_workspace("joint_align", _TERMS[:int(terms)], B, H, W, device)
+
+
+@_on_tensor_device
+def joint_align_step(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None, depth: Optional[dict] = None,
+                     weights=JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False, out: Optional[Dict[str, Tensor]] = None,
+                     workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """One JOINT Gauss-Newton step for B poses: the rows of the silhouette, the photometric and the depth term in one normal system
+    (tp_joint_align_step, K33; the rules are in the header).  pose [B,3,4], intr [B,3,3] or one [3,3]; each term that takes part is a
+    dict of that term's own step arguments (planes rendered at ``pose``, threshold, and optionally ``frame`` and ``mask``):
+    ``silhouette`` = dict(zbuf, sdf, tau_px), ``photo`` = dict(zbuf, rgb, image, tau), ``depth`` = dict(verts, faces, zbuf, face, depth,
+    tau_mm).  ``weights`` (w_sil, w_photo, w_icp): 1 / sigma^2 of the term's residual unit; a present term with weight 0 is evaluated
+    but takes no part in the step.  -> 'pose' [B,3,4] (the stepped pose; ``pose`` itself, bit for bit, with ``evaluate_only`` or a
+    non-zero status), 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels over the weighted terms, 3 not positive definite),
+    'inliers' [B] int32 (their kept pixels, added), 'chi2' [B] (the weighted sum of squares), and per present term that term's own
+    evaluation of ``pose``, bit for bit its ``*_step(evaluate_only=True)``: 'sil_inliers', 'sil_rms', 'sil_status', 'sil_inter',
+    'sil_uni', 'photo_inliers', 'photo_rms', 'photo_status', 'icp_inliers', 'icp_rms', 'icp_status'.  ``workspace``:
+    joint_align_workspace(B, H, W, terms present); ``out``: any of these tensors to write into (out['pose'] must not be ``pose``).
+    With one term at weight 1 'pose' and 'status' are that term's own step's bit for bit.  Each term's launches and one more, no
+    atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "joint_align_step"
+    w = _joint_weights(op, weights)
+    given = dict(zip(JOINT_TERMS, (silhouette, photo, depth)))
+    if all(v is None for v in given.values()):
+        raise ValueError("%s: no term: give at least one of %s" % (op, ", ".join(name + "=" for name in JOINT_TERMS)))
+    if not any(v is not None and x > 0 for v, x in zip(given.values(), w)):
+        raise ValueError("%s: no present term has a weight > 0 (weights %r)" % (op, w))
+    pose = _poses(op, pose, "pose")
+    B = pose.shape[0]
+    intr = _intr_per_view(op, intr, B)
+    shapes = {name: tuple(t["zbuf"].shape) if torch.is_tensor(t.get("zbuf")) else None for name, t in given.items() if t is not None}
+    shape = next(iter(shapes.values()))
+    if len(set(shapes.values())) != 1 or shape is None or len(shape) != 3:
+        raise ValueError("%s: every term needs a zbuf [B,H,W] of one shape, got %r" % (op, shapes))
+    H, W = shape[1:]
+    dev = pose.device
+    present = [term for term in _TERMS if given[term.name] is not None]
+    need = dict(zip(present, _term_bytes(present, B, H, W, 16)))
+    workspace = _workspace_arg(op, workspace, sum(need.values()), dev, align=16)
+    raw, offset = workspace.view(torch.uint8).reshape(-1), 0
+    res, structs, alive = {}, [], [workspace]
+    for term in _TERMS:
+        t = given[term.name]
+        if t is None:
+            structs.append(None)
+            continue
+        takes = term.rendered + (term.plane, term.threshold)
+        unknown = set(t) - set(takes) - {"frame", "mask"}
+        missing = [k for k in takes if k not in t]
+        if unknown or missing:
+            raise ValueError("%s: the %s term takes %s, frame and mask; missing %s, unknown %s" % (op, term.name, ", ".join(takes), missing, sorted(unknown)))
+        term_out = None if out is None else {k[len(term.prefix):]: v for k, v in out.items() if k.startswith(term.prefix)}
+        a, r, keep = _term_args(term, "%s (%s)" % (op, term.name), dict({k: t[k] for k in term.rendered}, pose=pose, intr=intr, **{term.plane: t[term.plane]}),
+                                threshold=t[term.threshold], damping=damping, frame=t.get("frame"), mask=t.get("mask"), evaluate_only=True,
+                                workspace=raw[offset:offset + need[term]], out=term_out, with_pose=False)
+        offset += need[term]
+        structs.append(a)
+        alive.append(keep)
+        res.update({term.prefix + k: v for k, v in r.items()})
+    joint = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "status": (torch.int32, (B,)), "inliers": (torch.int32, (B,)),
+                               "chi2": (torch.float32, (B,))}, dev, partial=True)
+    j = _lib.JointAlignArgs()
+    j.B, j.pose, j.damping, j.evaluate_only = B, pose.data_ptr(), float(damping), int(bool(evaluate_only))
+    for term, x in zip(_TERMS, w):
+        setattr(j, "w_" + term.prefix[:-1], x)
+    j.pose_out, j.status, j.inliers, j.chi2 = joint["pose"].data_ptr(), joint["status"].data_ptr(), joint["inliers"].data_ptr(), joint["chi2"].data_ptr()
+    _call("tp_joint_align_step", j, *structs)
+    return dict(joint, **res)
+
+
+JOINT_ALIGN_KEYS = ("pose", "inliers", "chi2", "status", "inliers0", "chi20")
+
+
+@_on_tensor_device
+def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vcolor: Optional[Tensor] = None, sdf: Optional[Tensor] = None,
+                image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
+                iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
+                workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
+                texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
+    (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
+    one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
+    only for the planes the present terms need, followed by joint_align_step, the last with evaluate_only.  The outline gives the
+    basin, the texture or the depth pins what the outline leaves loose: under occlusion the terms run one after the other end far
+    away where this loop converges.  ``weights`` (w_sil, w_photo, w_icp) = 1 / sigma^2 per residual unit, default (1, 100, 1 / 25):
+    w_photo = 100 is the only one of 25, 100 and 400 with which all twelve occluded cases of DESIGN section 23 converged; w_icp is
+    sigma = 5 mm and is NOT tuned on anything.  ``tau_px`` / ``tau`` / ``tau_mm``: each term's threshold, one value or ``iters`` + 1
+    host values.  ``frame`` [B] int32: the measured plane of each pose, for every term.  ``masks``: dict(silhouette=, photo=, depth=)
+    of [Ft,H,W] uint8 / bool planes (0: the term skips the pixel).  -> 'pose' [B,3,4], its 'inliers' [B] int32 and 'chi2' [B],
+    'status' [B] int32 of the last step taken (of the evaluation where iters = 0), 'inliers0' / 'chi20' of the start pose, and the
+    last pass's per-term keys of joint_align_step; with ``sdf`` also 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' /
+    'iou0_visible', as silhouette_align.  A step that fails passes its pose on.  Bit-identical from run to run, safe under
+    torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] in place of ``vcolor``:
+    the photometric term's renders take their colour from the mesh's face texels (mesh_raster(texels=), K35); at most one of the two."""
+    op = "joint_align"
+    if vcolor is not None and texels is not None:
+        raise ValueError("%s: vcolor= or texels=, not both" % op)
+    w = _joint_weights(op, weights)
+    masks = dict(masks or {})
+    given = [(term, p, t, masks.get(term.name)) for term, p, t in zip(_TERMS, (sdf, image, depth), (tau_px, tau, tau_mm))]
+    taus = _schedules(op, given, iters)
+    if sdf is None and image is None and depth is None:
+        raise ValueError("%s: no term: give at least one of sdf=, image=, depth=" % op)
+    if image is not None and vcolor is None and texels is None:
+        raise ValueError("%s: image= needs vcolor=, the mesh's colours [V,3], or texels= [F,T,3]" % op)
+    if set(masks) - set(JOINT_TERMS):
+        raise ValueError("%s: masks takes the keys %s, got %s" % (op, JOINT_TERMS, sorted(masks)))
+    # (the dict has had its cost keys behind inliers0 since K33; JOINT_ALIGN_KEYS names them, not their order)
+    return _refine(op, ("pose", "inliers", "status", "inliers0", "chi2", "chi20"), verts, faces, pose, intr, given, taus, damping=damping, frame=frame,
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w)

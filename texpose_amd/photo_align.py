@@ -34,24 +34,10 @@ def sums_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Ten
     """The sums of step_torch before the solve (what joint.step_torch weights and adds) -> (JtJ [B,6,6], Jtr [B,6], cost [B] fp64,
     count [B], pose32 [B,3,4])."""
     f64 = torch.float64
-    dev = zbuf.device
-    B, H, W = zbuf.shape
-    pose32 = pose.float().reshape(B, 3, 4)
-    intr = intr.float()
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3)
-    image = image.float()
-    if image.dim() == 3:
-        image = image[None]
-    Ft = image.shape[0]
-    fr = _gn_torch.frames_of(B, Ft, frame, "image must hold 1 or B = %d photographs", dev)
-    tau = float(torch.tensor(tau, dtype=torch.float32))
-    zf = zbuf.float()
+    B, H, W, pose32, intr, image, fr, tau, zf = _gn_torch.sums_head(zbuf, pose, intr, image, 1, frame, "image must hold 1 or B = %d photographs", tau)
     cand = (zf > 0) & torch.isfinite(zf)
     cand[:, :1], cand[:, H - 1:], cand[:, :, :1], cand[:, :, W - 1:] = False, False, False, False
-    if mask is not None:
-        m = mask if mask.dim() == 3 else mask[None]
-        cand = cand & (m[fr] != 0)
+    cand = _gn_torch.masked(cand, mask, fr)
     bi, ii, ji = torch.nonzero(cand, as_tuple=True)                                         # (interior: ii -+ 1 and ji -+ 1 exist)
     fi = fr[bi]
     c, o = rgb.float()[bi, ii, ji].to(f64), image[fi, ii, ji].to(f64)                       # [n,3]
@@ -61,22 +47,8 @@ def sums_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Ten
     fin = torch.isfinite(torch.cat([c, o, lf, rt, up, dn], -1)).all(-1)
     keep = fin & ((res[:, 0] * res[:, 0] + res[:, 1] * res[:, 1]) + res[:, 2] * res[:, 2] <= tau * tau)
     bi, ii, ji, res, lf, rt, up, dn = bi[keep], ii[keep], ji[keep], res[keep], lf[keep], rt[keep], up[keep], dn[keep]
-    z = zf[bi, ii, ji].to(f64)
-    K = intr.to(f64)
-    fx, fy = K[bi, 0, 0], K[bi, 1, 1]
-    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / fx
-    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / fy
-    P = torch.stack([z * rx, z * ry, z], -1)[:, None, :].expand(-1, 3, -1)                  # [n,3 channels,3]
-    gfx, gfy = (0.5 * (rt - lf)) * fx[:, None], (0.5 * (dn - up)) * fy[:, None]             # [n,3 channels]
-    av = torch.stack([gfx / z[:, None], gfy / z[:, None], -(gfx * rx[:, None] + gfy * ry[:, None]) / z[:, None]], -1)
-    J = torch.cat([torch.cross(P, av, dim=-1), av], -1).reshape(-1, 6)                      # [3n,6]
-    r = res.reshape(-1)
-    b3 = bi.repeat_interleave(3)
-    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, b3, J[:, :, None] * J[:, None, :])
-    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, b3, J * r[:, None])
-    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, b3, r * r)
-    count = torch.bincount(bi, minlength=B)
-    return JtJ, Jtr, cost, count, pose32
+    J = _gn_torch.image_gradient_rows(zf, intr, bi, ii, ji, lf, rt, up, dn)                 # [3n,6]
+    return _gn_torch.normal_sums(B, bi.repeat_interleave(3), J, res.reshape(-1)) + (torch.bincount(bi, minlength=B), pose32)
 
 
 class PhotoRefiner(_MeshRefiner):
@@ -94,12 +66,7 @@ class PhotoRefiner(_MeshRefiner):
         super().__init__(verts, faces, H, W, device, cull=cull)
         if (vcolor is None) == (texels is None):
             raise ValueError("PhotoRefiner: exactly one of vcolor [V,3] and texels= [F,T,3] (face texels, K35) expected")
-        self.vcolor = None if vcolor is None else torch.as_tensor(vcolor).to(device=self.device, dtype=torch.float32).contiguous()
-        self.texels = None if texels is None else torch.as_tensor(texels).to(device=self.device, dtype=torch.float32).contiguous()
-        if self.vcolor is not None and tuple(self.vcolor.shape) != tuple(self.verts.shape):
-            raise ValueError("PhotoRefiner: vcolor [V,3] expected, one colour per vertex, got %s" % (tuple(self.vcolor.shape),))
-        if self.texels is not None and (self.texels.dim() != 3 or self.texels.shape[0] != self.faces.shape[0] or self.texels.shape[2] != 3):
-            raise ValueError("PhotoRefiner: texels [F,T,3] expected, T texels per face, got %s" % (tuple(self.texels.shape),))
+        self._colours(vcolor, texels)
         self.tau, self.iters, self.damping = tau, int(iters), float(damping)
 
     def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:

@@ -84,19 +84,7 @@ def sums_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: fl
     """The sums of step_torch before the solve (what joint.step_torch weights and adds) -> (JtJ [B,6,6], Jtr [B,6], cost [B] fp64,
     count [B], pose32 [B,3,4], inter, uni [B] int32)."""
     f64 = torch.float64
-    dev = zbuf.device
-    B, H, W = zbuf.shape
-    pose32 = pose.float().reshape(B, 3, 4)
-    intr = intr.float()
-    if intr.dim() == 2:
-        intr = intr[None].expand(B, 3, 3)
-    sdf = sdf.float()
-    if sdf.dim() == 2:
-        sdf = sdf[None]
-    Ft = sdf.shape[0]
-    fr = _gn_torch.frames_of(B, Ft, frame, "sdf must hold 1 or B = %d planes", dev)
-    tau = float(torch.tensor(tau_px, dtype=torch.float32))
-    zf = zbuf.float()
+    B, H, W, pose32, intr, sdf, fr, tau, zf = _gn_torch.sums_head(zbuf, pose, intr, sdf, 0, frame, "sdf must hold 1 or B = %d planes", tau_px)
     cov = (zf > 0) & torch.isfinite(zf)
     field = sdf[fr]                                                                         # [B,H,W]
     inside = (field < 0) & torch.isfinite(field)
@@ -106,30 +94,15 @@ def sums_torch(zbuf: Tensor, pose: Tensor, intr: Tensor, sdf: Tensor, tau_px: fl
         c = cov[:, 1:-1, 1:-1]
         all_four = cov[:, 1:-1, :-2] & cov[:, 1:-1, 2:] & cov[:, :-2, 1:-1] & cov[:, 2:, 1:-1]
         cand[:, 1:-1, 1:-1] = c & ~all_four
-    if mask is not None:
-        m = mask if mask.dim() == 3 else mask[None]
-        cand = cand & (m[fr] != 0)
-    bi, ii, ji = torch.nonzero(cand, as_tuple=True)                                         # (interior: ii -+ 1 and ji -+ 1 exist)
+    bi, ii, ji = torch.nonzero(_gn_torch.masked(cand, mask, fr), as_tuple=True)             # (interior: ii -+ 1 and ji -+ 1 exist)
     d = field[bi, ii, ji].to(f64)
     lf, rt, up, dn = (field[bi, ii, ji - 1].to(f64), field[bi, ii, ji + 1].to(f64), field[bi, ii - 1, ji].to(f64),
                       field[bi, ii + 1, ji].to(f64))
     r = d + 0.5
     keep = torch.isfinite(torch.stack([d, lf, rt, up, dn], -1)).all(-1) & (r.abs() <= tau)
     bi, ii, ji, r, lf, rt, up, dn = bi[keep], ii[keep], ji[keep], r[keep], lf[keep], rt[keep], up[keep], dn[keep]
-    z = zf[bi, ii, ji].to(f64)
-    K = intr.to(f64)
-    fx, fy = K[bi, 0, 0], K[bi, 1, 1]
-    rx = ((ji.to(f64) + 0.5) - K[bi, 0, 2]) / fx
-    ry = ((ii.to(f64) + 0.5) - K[bi, 1, 2]) / fy
-    P = torch.stack([z * rx, z * ry, z], -1)
-    gfx, gfy = (0.5 * (rt - lf)) * fx, (0.5 * (dn - up)) * fy
-    av = torch.stack([gfx / z, gfy / z, -(gfx * rx + gfy * ry) / z], -1)
-    J = torch.cat([torch.cross(P, av, dim=-1), av], -1)                                     # [n,6]
-    JtJ = torch.zeros(B, 6, 6, dtype=f64, device=dev).index_add_(0, bi, J[:, :, None] * J[:, None, :])
-    Jtr = torch.zeros(B, 6, dtype=f64, device=dev).index_add_(0, bi, J * r[:, None])
-    cost = torch.zeros(B, dtype=f64, device=dev).index_add_(0, bi, r * r)
-    count = torch.bincount(bi, minlength=B)
-    return JtJ, Jtr, cost, count, pose32, inter.to(torch.int32), uni.to(torch.int32)
+    J = _gn_torch.image_gradient_rows(zf, intr, bi, ii, ji, lf[:, None], rt[:, None], up[:, None], dn[:, None])          # [n,6]
+    return _gn_torch.normal_sums(B, bi, J, r) + (torch.bincount(bi, minlength=B), pose32, inter.to(torch.int32), uni.to(torch.int32))
 
 
 class SilhouetteRefiner(_MeshRefiner):
@@ -147,7 +120,6 @@ class SilhouetteRefiner(_MeshRefiner):
                  cull: bool = False):
         super().__init__(verts, faces, H, W, device, cull=cull)
         self.tau_px, self.iters, self.damping = tau_px, int(iters), float(damping)
-        self._sdf_workspaces: Dict[int, Tensor] = {}
 
     def refine(self, pose: Tensor, intr: Tensor, mask_or_sdf: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
                known: Optional[Tensor] = None) -> AttrDict:
@@ -157,18 +129,7 @@ class SilhouetteRefiner(_MeshRefiner):
         measurement, the pixel is behind an occluder, say; ops.mask_known_from_others makes such planes from a frame's instance masks).
         ``known`` goes with masks only (a field already says what it knows) and adds iou_visible / iou0_visible [B], the IoU over the
         known pixels."""
-        planes = mask_or_sdf if mask_or_sdf.dim() == 3 else mask_or_sdf[None]
-        if tuple(planes.shape[1:]) != (self.H, self.W):
-            raise ValueError("SilhouetteRefiner.refine: planes of %d x %d expected, got %s" % (self.H, self.W, tuple(planes.shape)))
-        if known is not None and planes.dtype.is_floating_point:
-            raise ValueError("SilhouetteRefiner.refine: known= goes with masks; mask_or_sdf is a field (pass ops.mask_sdf(mask, known=known))")
-        if not planes.dtype.is_floating_point:
-            Ft = planes.shape[0]
-            if known is not None:
-                known = (known if known.dim() == 3 else known[None]).to(self.device).contiguous()
-            if Ft not in self._sdf_workspaces:
-                self._sdf_workspaces[Ft] = ops.mask_sdf_workspace(Ft, self.H, self.W, self.device)
-            planes = ops.mask_sdf(planes.to(self.device).contiguous(), workspace=self._sdf_workspaces[Ft], known=known)
+        planes, known = self._field_of(mask_or_sdf, known)
         return AttrDict(ops.silhouette_align(self.verts, self.faces, pose, intr, planes, tau_px=self.tau_px, iters=self.iters,
                                              damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]),
                                              visible_iou=known is not None, cull=self.cull))

@@ -251,13 +251,10 @@ def main(argv=None):
             if a.joint:
                 r = refiner.refine(start, K, mask_or_sdf=measured, known=known, image=photos, depth=ranges, frame=index,
                                    masks=None if mask is None else dict(silhouette=mask, photo=mask, depth=mask))
-                if a.silhouette:
-                    iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
-                    if known is not None:
-                        visible_sum += [float(r.iou0_visible.double().sum()), float(r.iou_visible.double().sum())]
             elif a.silhouette:
                 r = outline.refine(start, K, measured, frame=index, mask=mask, known=known)
                 start = r.pose
+            if a.silhouette:
                 iou_sum += [float(r.iou0.double().sum()), float(r.iou.double().sum())]
                 if known is not None:
                     visible_sum += [float(r.iou0_visible.double().sum()), float(r.iou_visible.double().sum())]
