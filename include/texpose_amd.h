@@ -1551,6 +1551,49 @@ typedef struct tp_face_texel_shade_args {
 int tp_face_texel_count(int R);                           /* T(R); 0 for R outside 1 .. TP_FACE_TEXEL_MAX_R */
 int tp_face_texel_shade(const tp_face_texel_shade_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K36  the adjoint of K35 with respect to the texels (texpose_amd/face_texels.py: shade_nodes, FaceTexelFitter; restated in
+ *      tests/face_texel_fit_ref.py; the project's own step).  K35 is linear in the texels: a pixel p of face f that
+ *      K35 shades by rule reads the three slots and weights of its cell,
+ *        fa + fb > 1 and ci + cj <= R - 2:  (n(ci+1, cj+1), (fa + fb) - 1), (n(ci+1, cj), 1 - fb), (n(ci, cj+1), 1 - fa)
+ *        otherwise:                         (n(ci, cj), (1 - fa) - fb),     (n(ci+1, cj), fa),     (n(ci, cj+1), fb)
+ *      and the adjoint adds w_k grad_rgb[p] (3 channels) to the destination d(f, n_k): the slot f T + n_k itself (N = F T destinations)
+ *      when node_index is NULL, node_index[f T + n_k] otherwise (N = U destinations; an entry outside 0 .. U-1 is skipped).  weight,
+ *      where given, is the same sum with grad_rgb = 1: the coverage of each destination (the lumped diagonal of S^T S).  A pixel
+ *      contributes nothing where K35 writes zeros by its geometric rules (face < 0 or >= F, a vertex index outside 0 .. V-1, a vertex
+ *      with z <= 0 or a non-finite camera-frame coordinate, |area| <= 1e-10 or not finite, a non-finite w_k) and nothing where a
+ *      component of its grad_rgb is not finite.  K35's "non-finite colour -> zero" rule depends on the texel values: the adjoint
+ *      reads no texels and ignores it.
+ *      Deterministic without float atomics -- 64-bit fixed point; integer addition is associative, so neither the arrival order
+ *      nor a graph replay changes a bit.  With gmax = the maximum of |grad_rgb| over the components of the contributing pixels (found
+ *      on the device: an unsigned atomic maximum of the floats' bit patterns) and e = max(floor(log2 gmax), -126), every contribution
+ *      is q = llrint((w_k (double)g_c) 2^(36 - e)): an fp64 product rounded to nearest even, |q| <= 2^37 (1 + 2^-50), added to an
+ *      int64 by an integer atomic; the weights use llrint(w_k 2^36).  At the end grad = (float)((double)sum 2^(e - 36)), rounded
+ *      once; weight likewise; gmax = 0 gives grad = 0.  The weights of one pixel are >= -2^-50 and add up to 1 within 2^-50, so a
+ *      pixel adds at most 2^37 (1 + 2^-49) in magnitude to any one destination whatever node_index holds, and B H W <= 2^25 pixels
+ *      stay below 2^63: no sum can overflow.  Each q is within 1/2 of its exact value, so a result is within n_d gmax 2^-37 (the
+ *      coverage: n_d 2^-37) of the exact sum over the n_d contributions to d, plus its one rounding to fp32.
+ *      Four launches on the stream (one memset of the workspace, maximum, scatter, finalise), one thread per pixel; no host
+ *      synchronisation, no allocation; safe to capture.  Everything K35 refuses, B H W > 2^25, U <= 0 with a node index, 3 N >= 2^31,
+ *      a null or not 8-byte aligned workspace and a null grad_rgb or grad are refused (-1, tp_last_error) and launch nothing.
+ *      Left out: gradients with respect to the pose or the vertices, second order, one R per face, a minification filter.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_face_texel_shade_bwd_args {
+  const float* verts;        /* [V,3] as K35 */
+  const int32_t* faces;      /* [F,3] */
+  const float* pose;         /* [B,3,4] */
+  const float* intr;         /* [B,3,3] */
+  const int32_t* face;       /* [B,H,W] K19's face plane (any values) */
+  const float* grad_rgb;     /* [B,H,W,3] */
+  const int32_t* node_index; /* [F,T] or NULL */
+  int B, H, W, V, F, R, U;   /* U: destinations when node_index is given; ignored otherwise (N = F * T) */
+  void* workspace;           /* tp_face_texel_shade_bwd_workspace(N, weight != NULL) bytes, 8-byte aligned; cleared by the call */
+  float* grad;               /* [N,3] out */
+  float* weight;             /* [N] out or NULL */
+} tp_face_texel_shade_bwd_args;
+size_t tp_face_texel_shade_bwd_workspace(int64_t N, int want_weight);      /* 8 (3 N + (want_weight ? N : 0) + 1); 0 for N <= 0 or 3 N >= 2^31 */
+int tp_face_texel_shade_bwd(const tp_face_texel_shade_bwd_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

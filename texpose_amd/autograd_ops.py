@@ -7,6 +7,8 @@ sampler and get none.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import ops
@@ -652,3 +654,37 @@ def latent_rows(w_trans, w_light, idx, defer=False):
     job = []
     ot, ol = _LatentRows.apply(w_trans, w_light, idx, job)
     return ot, ol, job[0]
+
+
+class _FaceTexelShade(torch.autograd.Function):
+    """K35 forward, K36 backward: differentiable with respect to the texels (per slot, or per shared node with ``node_index``), first
+    order only.  The face plane, the mesh and the cameras are data.  The backward is 64-bit fixed point: bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, face, verts, faces, values, node_index, pose, intr):
+        texels = values if node_index is None else values[node_index.long()]
+        rgb = ops.face_texel_shade(face, verts, faces, texels, pose, intr)
+        ctx.save_for_backward(face, verts, faces, pose, intr, node_index)
+        ctx.R, ctx.U = (math.isqrt(8 * texels.shape[1] + 1) - 3) // 2, values.shape[0]
+        ctx.set_materialize_grads(False)
+        return rgb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb):
+        face, verts, faces, pose, intr, node_index = ctx.saved_tensors
+        if g_rgb is None or not ctx.needs_input_grad[3]:
+            return (None,) * 7
+        kw = {} if node_index is None else dict(node_index=node_index, U=ctx.U)
+        return None, None, None, ops.face_texel_shade_bwd(face, verts, faces, g_rgb, pose, intr, R=ctx.R, **kw), None, None, None
+
+
+def face_texel_shade(face, verts, faces, texels, pose, intr):
+    """ops.face_texel_shade, differentiable with respect to ``texels`` [F,T,3] through tp_face_texel_shade_bwd (K36); first order only."""
+    return _FaceTexelShade.apply(face, verts, faces, texels, None, pose, intr)
+
+
+def face_texel_shade_nodes(face, verts, faces, nodes, node_index, pose, intr):
+    """Shade from per-node colours ``nodes`` [U,3] shared between faces through ``node_index`` [F,T]: the forward gathers and shades, the
+    backward is K36 with the node index, straight into [U,3] (face_texels.shade_nodes)."""
+    return _FaceTexelShade.apply(face, verts, faces, nodes, node_index, pose, intr)

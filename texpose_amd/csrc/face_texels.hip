@@ -19,10 +19,93 @@
 // A gather: 4 B read and 12 B written per pixel; a covered pixel gathers 3 indices, 9 vertex floats and 9 texel floats, which
 // neighbouring pixels of a face share.  One thread per pixel, the image index uniform over the workgroup (pose[b] and intr[b] are scalar
 // loads).  One launch; no LDS, no atomics, no workspace: the output is a function of the inputs alone.
+//
+// K36 tp_face_texel_shade_bwd: the adjoint of K35 with respect to the texels (restated in tests/face_texel_fit_ref.py).
+// K35 is linear in the texels: a pixel that it shades by rule reads three slots n_a, n_b, n_c of its face f with the weights w_a, w_b,
+// w_c of step 2 (face_texel_cell below, the ONE source of steps 1 and 2 for both kernels).  The adjoint adds w_k g_p (3 channels) to the
+// destination d(f, n_k): the slot f T + n_k itself, or node_index[f T + n_k] where a node index is given (entries outside 0 .. U-1 are
+// skipped); `weight` is the same sum with g = 1 (the coverage: the lumped diagonal of S^T S).  A pixel contributes nothing where K35
+// writes zeros by its geometric rules, and nothing where a component of its grad_rgb is not finite.  K35's "non-finite colour -> zero"
+// rule depends on the texel VALUES; the adjoint reads no texels and ignores it.
+//
+// Deterministic without float atomics: 64-bit fixed point.  Integer addition is associative, so the arrival order of the atomics, and
+// a graph replay, cannot change a bit.  Launches, all on the caller's stream, no host synchronisation, no allocation:
+//   1. one asynchronous memset clears the workspace: acc int64 [N,3], wacc int64 [N] (where weight is wanted), the word gmax;
+//   2. gmax = max over the contributing pixels of max_c |g_c|, as the float's bit pattern under an unsigned atomic max (non-negative
+//      floats order like their bits), one atomic per wavefront;
+//   3. e = max(floor(log2 gmax), -126) (the float's exponent field; -126 for a subnormal or zero gmax).  Every contribution is
+//      q = llrint((w_k (double)g_c) 2^(36 - e)): an fp64 product, rounded to nearest even, |q| <= 2^37 (1 + 2^-50); it is added to
+//      acc[3 d + c] by a 64-bit integer atomic.  Weights use e = 0: llrint(w_k 2^36).  A zero q is not sent;
+//   4. grad[3 d + c] = (float)((double)acc 2^(e - 36)), rounded once; weight[d] likewise.
+// Overflow: the three weights of a pixel are >= -2^-50 and add up to 1 within 2^-50, so whatever node_index maps them to, one pixel adds
+// at most 2^37 (1 + 2^-49) in magnitude to one destination, and B H W <= 2^25 pixels at most 2^62 (1 + 2^-49) < 2^63: larger B H W is
+// refused.  Error: each q is within 1/2 of its exact value, so acc 2^(e-36) is within n_d 2^(e-37) <= n_d gmax 2^-37 of the exact sum
+// over the n_d contributions to d (weights: n_d 2^-37), plus the one fp32 rounding of the result.
+// One thread per pixel, 256 per workgroup, the image index uniform over the workgroup, no LDS.  A background pixel returns after one
+// 4-byte load; a pixel whose gradient is all zeros (a masked one) after 16 bytes unless the coverage is wanted.
 #include "tp_common.h"
 
 namespace {
 constexpr int kShadeBlock = 256;
+
+// Steps 1 and 2 of the rule for pixel (row i, column j) under face f, 0 <= f < F: the three slots of the face's T texels and their weights,
+// in the order the forward adds them (A, B, C).  false: the pixel is one that K35 shades to zero by rule.
+struct TexelCell {
+  int n[3];
+  double w[3];
+};
+
+__device__ __forceinline__ bool face_texel_cell(const float* __restrict__ verts, const int32_t* __restrict__ faces, const float* P, const float* K,
+                                                int V, int R, int f, int i, int j, TexelCell& cell) {
+  double u[3], v[3], iz[3];
+  for (int k = 0; k < 3; ++k) {
+    const int vi = faces[3 * (int64_t)f + k];
+    if (vi < 0 || vi >= V) return false;
+    const double X = verts[3 * (int64_t)vi], Y = verts[3 * (int64_t)vi + 1], Z = verts[3 * (int64_t)vi + 2];
+    double c[3];
+    for (int r = 0; r < 3; ++r) c[r] = (double)P[4 * r] * X + (double)P[4 * r + 1] * Y + (double)P[4 * r + 2] * Z + (double)P[4 * r + 3];
+    if (!(c[2] > 0.0) || !isfinite(c[0]) || !isfinite(c[1]) || !isfinite(c[2])) return false;
+    const double q0 = (double)K[0] * c[0] + (double)K[1] * c[1] + (double)K[2] * c[2];
+    const double q1 = (double)K[3] * c[0] + (double)K[4] * c[1] + (double)K[5] * c[2];
+    const double q2 = (double)K[6] * c[0] + (double)K[7] * c[1] + (double)K[8] * c[2];
+    u[k] = q0 / q2;
+    v[k] = q1 / q2;
+    iz[k] = 1.0 / c[2];
+  }
+  const double area = (u[1] - u[0]) * (v[2] - v[0]) - (v[1] - v[0]) * (u[2] - u[0]);
+  if (!(isfinite(area) && fabs(area) > 1e-10)) return false;
+  const double px = (double)j + 0.5, py = (double)i + 0.5;
+  double t[3], w[3];
+  for (int k = 0; k < 3; ++k) {
+    const int s = (k + 1) % 3, e = (k + 2) % 3;       // b_k: the edge opposite vertex k, from vertex s to vertex e
+    const double ex = u[e] - u[s], ey = v[e] - v[s];
+    t[k] = ((ex * (py - v[s]) - ey * (px - u[s])) / area) * iz[k];
+  }
+  const double sum = (t[0] + t[1]) + t[2];
+  for (int k = 0; k < 3; ++k) {
+    w[k] = t[k] / sum;
+    w[k] = w[k] < 0.0 ? 0.0 : w[k];
+  }
+  const double s2 = (w[0] + w[1]) + w[2];
+  for (int k = 0; k < 3; ++k) w[k] = w[k] / s2;
+  if (!(isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]))) return false;     // (then every w_k is in [0, 1])
+  const double ta = (double)R * w[1], tb = (double)R * w[2];
+  int ci = (int)floor(ta), cj = (int)floor(tb);
+  ci = ci < R - 1 ? ci : R - 1;
+  cj = cj < R - 1 - ci ? cj : R - 1 - ci;
+  const double fa = ta - (double)ci, fb = tb - (double)cj;
+  const bool upper = fa + fb > 1.0 && ci + cj <= R - 2;
+  // node (i, j) at j (R + 1) - j (j - 1) / 2 + i; the row above starts R + 1 - j further on
+  const int n00 = cj * (R + 1) - (cj * (cj - 1)) / 2 + ci;
+  const int n01 = n00 + (R + 1 - cj);                   // (i, j + 1)
+  cell.n[0] = upper ? n01 + 1 : n00;                    // (i + 1, j + 1) or (i, j)
+  cell.n[1] = n00 + 1;                                  // (i + 1, j)
+  cell.n[2] = n01;                                      // (i, j + 1)
+  cell.w[0] = upper ? (fa + fb) - 1.0 : (1.0 - fa) - fb;
+  cell.w[1] = upper ? 1.0 - fb : fa;
+  cell.w[2] = upper ? 1.0 - fa : fb;
+  return true;
+}
 
 __global__ __launch_bounds__(kShadeBlock) void face_texel_shade_kernel(tp_face_texel_shade_args a, int blocks_per_image, int T) {
   const int b = (int)(blockIdx.x / (unsigned)blocks_per_image);                  // workgroup-uniform
@@ -33,73 +116,108 @@ __global__ __launch_bounds__(kShadeBlock) void face_texel_shade_kernel(tp_face_t
   float* out = a.rgb + 3 * pix;
   double col[3] = {0.0, 0.0, 0.0};
   const int f = a.face[pix];
-  bool ok = f >= 0 && f < a.F;
-  if (ok) {
+  if (f >= 0 && f < a.F) {
     const int i = (int)(rem / a.W), j = (int)(rem - (int64_t)i * a.W);
-    const float* P = a.pose + 12 * (int64_t)b;
-    const float* K = a.intr + 9 * (int64_t)b;
-    double u[3], v[3], iz[3];
-    for (int k = 0; k < 3 && ok; ++k) {
-      const int vi = a.faces[3 * (int64_t)f + k];
-      if (vi < 0 || vi >= a.V) { ok = false; break; }
-      const double X = a.verts[3 * (int64_t)vi], Y = a.verts[3 * (int64_t)vi + 1], Z = a.verts[3 * (int64_t)vi + 2];
-      double c[3];
-      for (int r = 0; r < 3; ++r) c[r] = (double)P[4 * r] * X + (double)P[4 * r + 1] * Y + (double)P[4 * r + 2] * Z + (double)P[4 * r + 3];
-      if (!(c[2] > 0.0) || !isfinite(c[0]) || !isfinite(c[1]) || !isfinite(c[2])) { ok = false; break; }
-      const double q0 = (double)K[0] * c[0] + (double)K[1] * c[1] + (double)K[2] * c[2];
-      const double q1 = (double)K[3] * c[0] + (double)K[4] * c[1] + (double)K[5] * c[2];
-      const double q2 = (double)K[6] * c[0] + (double)K[7] * c[1] + (double)K[8] * c[2];
-      u[k] = q0 / q2;
-      v[k] = q1 / q2;
-      iz[k] = 1.0 / c[2];
-    }
-    double w[3] = {0.0, 0.0, 0.0};
-    if (ok) {
-      const double area = (u[1] - u[0]) * (v[2] - v[0]) - (v[1] - v[0]) * (u[2] - u[0]);
-      ok = isfinite(area) && fabs(area) > 1e-10;
-      if (ok) {
-        const double px = (double)j + 0.5, py = (double)i + 0.5;
-        double t[3];
-        for (int k = 0; k < 3; ++k) {
-          const int s = (k + 1) % 3, e = (k + 2) % 3;       // b_k: the edge opposite vertex k, from vertex s to vertex e
-          const double ex = u[e] - u[s], ey = v[e] - v[s];
-          t[k] = ((ex * (py - v[s]) - ey * (px - u[s])) / area) * iz[k];
-        }
-        const double sum = (t[0] + t[1]) + t[2];
-        for (int k = 0; k < 3; ++k) {
-          w[k] = t[k] / sum;
-          w[k] = w[k] < 0.0 ? 0.0 : w[k];
-        }
-        const double s2 = (w[0] + w[1]) + w[2];
-        for (int k = 0; k < 3; ++k) w[k] = w[k] / s2;
-        ok = isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]);     // (then every w_k is in [0, 1])
-      }
-    }
-    if (ok) {
-      const int R = a.R;
-      const double ta = (double)R * w[1], tb = (double)R * w[2];
-      int ci = (int)floor(ta), cj = (int)floor(tb);
-      ci = ci < R - 1 ? ci : R - 1;
-      cj = cj < R - 1 - ci ? cj : R - 1 - ci;
-      const double fa = ta - (double)ci, fb = tb - (double)cj;
-      const bool upper = fa + fb > 1.0 && ci + cj <= R - 2;
-      // node (i, j) at j (R + 1) - j (j - 1) / 2 + i; the row above starts R + 1 - j further on
-      const int n00 = cj * (R + 1) - (cj * (cj - 1)) / 2 + ci;
-      const int n01 = n00 + (R + 1 - cj);                   // (i, j + 1)
+    TexelCell cell;
+    if (face_texel_cell(a.verts, a.faces, a.pose + 12 * (int64_t)b, a.intr + 9 * (int64_t)b, a.V, a.R, f, i, j, cell)) {
       const float* tex = a.texels + 3 * ((int64_t)f * T);
-      const float* A = tex + 3 * (int64_t)(upper ? n01 + 1 : n00);   // (i + 1, j + 1) or (i, j)
-      const float* Bn = tex + 3 * (int64_t)(n00 + 1);                // (i + 1, j)
-      const float* Cn = tex + 3 * (int64_t)n01;                      // (i, j + 1)
-      const double wa = upper ? (fa + fb) - 1.0 : (1.0 - fa) - fb;
-      const double wb = upper ? 1.0 - fb : fa;
-      const double wc = upper ? 1.0 - fa : fb;
-      for (int c = 0; c < 3; ++c) col[c] = (wa * (double)A[c] + wb * (double)Bn[c]) + wc * (double)Cn[c];
+      const float* A = tex + 3 * (int64_t)cell.n[0];
+      const float* Bn = tex + 3 * (int64_t)cell.n[1];
+      const float* Cn = tex + 3 * (int64_t)cell.n[2];
+      for (int c = 0; c < 3; ++c) col[c] = (cell.w[0] * (double)A[c] + cell.w[1] * (double)Bn[c]) + cell.w[2] * (double)Cn[c];
       if (!(isfinite(col[0]) && isfinite(col[1]) && isfinite(col[2]))) col[0] = col[1] = col[2] = 0.0;
     }
   }
   out[0] = (float)col[0];
   out[1] = (float)col[1];
   out[2] = (float)col[2];
+}
+
+// ---- K36
+constexpr int kFixedBits = 36;                    // fractional bits below 2^e (gradient) or below 1 (coverage)
+constexpr int64_t kBwdMaxPixels = 1ll << 25;      // (see the overflow bound above)
+
+__device__ __forceinline__ int gmax_exponent(unsigned bits) {
+  const int biased = (int)((bits >> 23) & 0xFFu);
+  return (biased > 0 ? biased : 1) - 127;
+}
+
+// the pixel's gradient where it is finite -> max_c |g_c| as bits; false where a component is not finite
+__device__ __forceinline__ bool finite_grad(const float* __restrict__ g, float out[3], unsigned& mag) {
+  out[0] = g[0];
+  out[1] = g[1];
+  out[2] = g[2];
+  if (!(isfinite(out[0]) && isfinite(out[1]) && isfinite(out[2]))) return false;
+  mag = __float_as_uint(fmaxf(fmaxf(fabsf(out[0]), fabsf(out[1])), fabsf(out[2])));
+  return true;
+}
+
+__global__ __launch_bounds__(kShadeBlock) void face_texel_gmax_kernel(tp_face_texel_shade_bwd_args a, int blocks_per_image, unsigned* gmax) {
+  const int b = (int)(blockIdx.x / (unsigned)blocks_per_image);
+  const int64_t hw = (int64_t)a.H * a.W;
+  const int64_t rem = (int64_t)(blockIdx.x - (unsigned)b * (unsigned)blocks_per_image) * kShadeBlock + threadIdx.x;
+  unsigned m = 0;
+  if (rem < hw) {
+    const int64_t pix = (int64_t)b * hw + rem;
+    const int f = a.face[pix];
+    float g[3];
+    unsigned mag = 0;
+    if (f >= 0 && f < a.F && finite_grad(a.grad_rgb + 3 * pix, g, mag) && mag != 0) {      // (a zero gradient cannot raise the maximum)
+      const int i = (int)(rem / a.W), j = (int)(rem - (int64_t)i * a.W);
+      TexelCell cell;
+      if (face_texel_cell(a.verts, a.faces, a.pose + 12 * (int64_t)b, a.intr + 9 * (int64_t)b, a.V, a.R, f, i, j, cell)) m = mag;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {           // every lane of the wavefront is here: no lane returned above
+    const unsigned o = (unsigned)__shfl_xor((int)m, off, 64);
+    m = o > m ? o : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(gmax, m);
+}
+
+__global__ __launch_bounds__(kShadeBlock) void face_texel_scatter_kernel(tp_face_texel_shade_bwd_args a, int blocks_per_image, int T, int64_t N,
+                                                                         unsigned long long* acc, unsigned long long* wacc, const unsigned* gmax) {
+  const int b = (int)(blockIdx.x / (unsigned)blocks_per_image);
+  const int64_t hw = (int64_t)a.H * a.W;
+  const int64_t rem = (int64_t)(blockIdx.x - (unsigned)b * (unsigned)blocks_per_image) * kShadeBlock + threadIdx.x;
+  if (rem >= hw) return;
+  const int64_t pix = (int64_t)b * hw + rem;
+  const int f = a.face[pix];
+  if (f < 0 || f >= a.F) return;
+  float g[3];
+  unsigned mag = 0;
+  if (!finite_grad(a.grad_rgb + 3 * pix, g, mag)) return;
+  if (mag == 0 && !wacc) return;                      // nothing to add
+  const int i = (int)(rem / a.W), j = (int)(rem - (int64_t)i * a.W);
+  TexelCell cell;
+  if (!face_texel_cell(a.verts, a.faces, a.pose + 12 * (int64_t)b, a.intr + 9 * (int64_t)b, a.V, a.R, f, i, j, cell)) return;
+  const double scale = ldexp(1.0, kFixedBits - gmax_exponent(*gmax));
+  const double one = ldexp(1.0, kFixedBits);
+  for (int k = 0; k < 3; ++k) {
+    const int64_t slot = (int64_t)f * T + cell.n[k];
+    int64_t d = slot;
+    if (a.node_index) {
+      d = a.node_index[slot];
+      if (d < 0 || d >= N) continue;
+    }
+    if (mag != 0) {
+      for (int c = 0; c < 3; ++c) {
+        const long long q = llrint((cell.w[k] * (double)g[c]) * scale);
+        if (q != 0) atomicAdd(acc + 3 * d + c, (unsigned long long)q);
+      }
+    }
+    if (wacc) {
+      const long long q = llrint(cell.w[k] * one);
+      if (q != 0) atomicAdd(wacc + d, (unsigned long long)q);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kShadeBlock) void face_texel_finalise_kernel(const long long* acc, const long long* wacc, const unsigned* gmax, int64_t N,
+                                                                          float* grad, float* weight) {
+  const int64_t t = (int64_t)blockIdx.x * kShadeBlock + threadIdx.x;
+  if (t < 3 * N) grad[t] = (float)ldexp((double)acc[t], gmax_exponent(*gmax) - kFixedBits);
+  if (wacc && t < N) weight[t] = (float)ldexp((double)wacc[t], -kFixedBits);
 }
 }  // namespace
 
@@ -123,4 +241,44 @@ extern "C" int tp_face_texel_shade(const tp_face_texel_shade_args* a, tp_stream_
   if (bpi * a->B > 0x7FFFFFFFll) { tp::set_error("tp_face_texel_shade: bad sizes (B * ceil(H * W / 256) < 2^31)"); return -1; }
   hipLaunchKernelGGL(face_texel_shade_kernel, dim3((unsigned)(bpi * a->B)), dim3(kShadeBlock), 0, (hipStream_t)stream, *a, (int)bpi, T);
   return tp::check_launch("tp_face_texel_shade");
+}
+
+extern "C" size_t tp_face_texel_shade_bwd_workspace(int64_t N, int want_weight) {
+  if (N <= 0 || N > 0x7FFFFFFFll / 3) return 0;
+  return (size_t)8 * (size_t)(3 * N + (want_weight ? N : 0) + 1);
+}
+
+extern "C" int tp_face_texel_shade_bwd(const tp_face_texel_shade_bwd_args* a, tp_stream_t stream) {
+  const char* name = "tp_face_texel_shade_bwd";
+  if (!a) { tp::set_error("%s: null args", name); return -1; }
+  if (!a->verts || !a->faces || !a->pose || !a->intr || !a->face || !a->grad_rgb || !a->grad) {
+    tp::set_error("%s: null pointer", name);
+    return -1;
+  }
+  const int T = tp_face_texel_count(a->R);
+  if (a->B <= 0 || a->H <= 0 || a->W <= 0 || a->V <= 0 || a->F <= 0 || T == 0 || (int64_t)a->H * a->W > 0x7FFFFFFFll ||
+      (int64_t)a->F * T > 0x7FFFFFFFll) {
+    tp::set_error("%s: bad sizes (B, H, W, V, F > 0, R 1..%d, H * W < 2^31, F * T(R) < 2^31)", name, TP_FACE_TEXEL_MAX_R);
+    return -1;
+  }
+  if ((int64_t)a->B * a->H * a->W > kBwdMaxPixels) {
+    tp::set_error("%s: bad sizes (B * H * W <= 2^25: the 64-bit fixed-point sums cannot overflow below that)", name);
+    return -1;
+  }
+  if (a->node_index && a->U <= 0) { tp::set_error("%s: bad sizes (U > 0 with a node index)", name); return -1; }
+  const int64_t N = a->node_index ? (int64_t)a->U : (int64_t)a->F * T;
+  if (3 * N >= 0x80000000ll) { tp::set_error("%s: bad sizes (3 N < 2^31 destinations)", name); return -1; }
+  if (!a->workspace || ((uintptr_t)a->workspace & 7u)) { tp::set_error("%s: workspace null or not 8-byte aligned", name); return -1; }
+  const int64_t bpi = ((int64_t)a->H * a->W + kShadeBlock - 1) / kShadeBlock;      // (B * bpi <= 2^25 + B < 2^31)
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* acc = (unsigned long long*)a->workspace;
+  unsigned long long* wacc = a->weight ? acc + 3 * N : nullptr;
+  unsigned* gmax = (unsigned*)(acc + 3 * N + (a->weight ? N : 0));
+  hipError_t e = hipMemsetAsync(a->workspace, 0, tp_face_texel_shade_bwd_workspace(N, a->weight != nullptr), s);
+  if (e != hipSuccess) { tp::set_error("%s: hipMemsetAsync: %s", name, hipGetErrorString(e)); return (int)e; }
+  hipLaunchKernelGGL(face_texel_gmax_kernel, dim3((unsigned)(bpi * a->B)), dim3(kShadeBlock), 0, s, *a, (int)bpi, gmax);
+  hipLaunchKernelGGL(face_texel_scatter_kernel, dim3((unsigned)(bpi * a->B)), dim3(kShadeBlock), 0, s, *a, (int)bpi, T, N, acc, wacc, (const unsigned*)gmax);
+  hipLaunchKernelGGL(face_texel_finalise_kernel, dim3((unsigned)((3 * N + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s,
+                     (const long long*)acc, (const long long*)wacc, (const unsigned*)gmax, N, a->grad, a->weight);
+  return tp::check_launch(name);
 }

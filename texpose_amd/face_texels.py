@@ -8,7 +8,12 @@ subdivided R times (``subdivide``), which is how a texture is baked -- ``FaceTex
 points -- and what the shading is tested against: texels on the base mesh equal vertex colours on the subdivided one.
 
 Point sampling only (no minification filter: pick R with ``resolution_for`` so that a texel is about a pixel), one R per mesh, no UV
-atlas, no gradients with respect to texels.
+atlas.
+
+Gradients with respect to the texture come from K36 (tp_face_texel_shade_bwd), the deterministic adjoint of the
+shading: ``autograd_ops.face_texel_shade`` (per-slot texels), ``shade_nodes`` (node colours shared between faces) and
+``FaceTexelFitter``, which fits the node colours to photographs by preconditioned conjugate gradients on the quantity the refiners
+consume: the difference between the shaded render and the photograph.  No gradients with respect to pose or vertices, first order only.
 """
 from __future__ import annotations
 
@@ -186,6 +191,139 @@ class FaceTexelBaker:
         r = self.nodes.result(fill=fill)
         return AttrDict(texels=texels_from_nodes(r.vcolor, self.node_index), vcolor_sub=r.vcolor, seen=r.seen, filled=r.filled,
                         unseen=r.unseen, weight=r.weight, count=r.count)
+
+
+def shade_nodes(face: Tensor, verts: Tensor, faces: Tensor, nodes: Tensor, node_index, pose: Tensor, intr: Tensor) -> Tensor:
+    """ops.face_texel_shade of the texels ``nodes[node_index]`` (nodes [U,3], node_index [F,T] as ``subdivide`` gives it) -> rgb
+    [B,H,W,3], differentiable with respect to ``nodes``: the backward is K36 with the node index, straight into [U,3] -- 64-bit fixed
+    point, bit-identical from run to run, no index_add_.  First order only."""
+    from . import autograd_ops
+    return autograd_ops.face_texel_shade_nodes(face, verts, faces, nodes, torch.as_tensor(node_index, device=nodes.device), pose, intr)
+
+
+class FaceTexelFitter:
+    """Fits the U node colours x of a face-texel texture of resolution R to photographs: minimises
+        sum_p m_p |(S x)_p - I_p|^2 + lam |x - prior|^2
+    over the stored views, S the shading rule of K35 on the node colours (texels = x[node_index]), by ``iters`` steps of conjugate
+    gradients preconditioned with M = coverage + lam, coverage the per-node sum of shading weights over all covered pixels (K36's
+    ``weight``: the lumped diagonal of S^T S).  S x is ops.face_texel_shade, S^T g is ops.face_texel_shade_bwd with the node index:
+    deterministic, so a fit is bit-identical from run to run.  An iteration is one shade and one adjoint over the stored views for the
+    step and one more shade for the training rms it reports.  A quadratic loss only (a robust loss goes through ``shade_nodes`` and
+    an optimiser); the result is not clamped: the caller does that."""
+
+    def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", lam: float = 0.1, iters: int = 4, cull: bool = False):
+        self.R, self.T, self.H, self.W = int(R), texel_count(R), int(H), int(W)
+        if not (lam > 0 and int(iters) >= 0):
+            raise ValueError("FaceTexelFitter: lam > 0 and iters >= 0 expected")
+        self.lam, self.iters, self.cull, self.device = float(lam), int(iters), bool(cull), torch.device(device)
+        self.verts_host = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+        self.faces_host = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+        self.verts_sub, self.faces_sub, self.node_index_host = subdivide(self.verts_host, self.faces_host, self.R)
+        self.U = len(self.verts_sub)
+        self.verts = torch.from_numpy(self.verts_host).to(self.device)
+        self.faces = torch.from_numpy(self.faces_host).to(self.device)
+        self.node_index = torch.from_numpy(self.node_index_host).to(self.device)
+        self._node_index32 = self.node_index.to(torch.int32)
+        self._views = []                                 # (face, rgb, weight, pose, intr) per add_views call
+
+    @property
+    def views(self) -> int:
+        return sum(v[0].shape[0] for v in self._views)
+
+    def reset(self) -> None:
+        self._views = []
+
+    def add_views(self, rgb: Tensor, pose_mm: Tensor, intr: Tensor, face: Optional[Tensor] = None, weight: Optional[Tensor] = None) -> None:
+        """rgb [B,H,W,3] photographs, pose_mm [B,3,4] (t in mm), intr [B,3,3] or [3,3]; ``face`` [B,H,W] int32: the base mesh's face
+        plane at those poses (None: rasterised here); ``weight`` [B,H,W] per pixel (None: 1 on covered pixels whose four neighbours are
+        covered too, 0 elsewhere: the rim pixels of a photograph mix in background).  Face plane, photograph and weight stay on the
+        device until reset(): 20 bytes per pixel."""
+        pose = torch.as_tensor(pose_mm, dtype=torch.float32).to(self.device).contiguous()
+        B = pose.shape[0]
+        K = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
+        K = (K[None].expand(B, 3, 3) if K.dim() == 2 else K).contiguous()
+        rgb = torch.as_tensor(rgb).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(rgb.shape) != (B, self.H, self.W, 3):
+            raise ValueError("FaceTexelFitter.add_views: rgb %s expected, got %s" % ((B, self.H, self.W, 3), tuple(rgb.shape)))
+        if face is None:
+            face = ops.mesh_raster(self.verts, self.faces, pose, K, H=self.H, W=self.W, normals=False, cull=self.cull)["face"]
+        face = torch.as_tensor(face).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(face.shape) != (B, self.H, self.W):
+            raise ValueError("FaceTexelFitter.add_views: face %s expected, got %s" % ((B, self.H, self.W), tuple(face.shape)))
+        if weight is None:
+            weight = inner_coverage(face, self.faces.shape[0]).float()
+        weight = torch.as_tensor(weight).detach().to(device=self.device, dtype=torch.float32).reshape(B, self.H, self.W).contiguous()
+        self._views.append((face, rgb, weight, pose, K))
+
+    def _shade(self, view, x: Tensor) -> Tensor:
+        return ops.face_texel_shade(view[0], self.verts, self.faces, x[self.node_index], view[3], view[4])
+
+    def _adjoint(self, view, g: Tensor, weight: bool = False):
+        return ops.face_texel_shade_bwd(view[0], self.verts, self.faces, g, view[3], view[4], R=self.R, node_index=self._node_index32, U=self.U,
+                                        weight=weight)
+
+    def _sse(self, x: Tensor) -> Tensor:
+        """sum_p m_p |(S x)_p - I_p|^2 over the views, fp64, 0-dim"""
+        sse = torch.zeros((), device=self.device, dtype=torch.float64)
+        for view in self._views:
+            e = self._shade(view, x) - view[1]
+            sse = sse + ((e * e).sum(-1) * view[2]).double().sum()
+        return sse
+
+    def fit(self, prior: Optional[Tensor] = None, start: Optional[Tensor] = None) -> AttrDict:
+        """``prior`` [U,3] (e.g. FaceTexelBaker's vcolor_sub; None: 0.5), ``start`` [U,3] (None: the prior) -> AttrDict(texels [F,T,3],
+        nodes [U,3], coverage [U], rms [iters + 1]: sqrt(sum m |S x - I|^2 / (3 sum m)) at the start and after every iteration (a device
+        tensor), on_prior: the number of nodes with coverage < lam, which the prior decides)."""
+        if not self._views:
+            raise ValueError("FaceTexelFitter.fit: no views (add_views first)")
+        dev, U, lam = self.device, self.U, self.lam
+
+        def nodes_arg(t, name, default):
+            if t is None:
+                return default
+            t = torch.as_tensor(t).detach().to(device=dev, dtype=torch.float32)
+            if tuple(t.shape) != (U, 3):
+                raise ValueError("FaceTexelFitter.fit: %s [U=%d,3] expected, got %s" % (name, U, tuple(t.shape)))
+            return t
+
+        prior = nodes_arg(prior, "prior", torch.full((U, 3), 0.5, device=dev))
+        x = nodes_arg(start, "start", prior).clone()
+        dot = lambda a, b: (a.double() * b.double()).sum()
+        # r = b - A x = S^T m (I - S x) + lam (prior - x); the first adjoint also gives the coverage
+        r, coverage = lam * (prior - x), torch.zeros(U, device=dev)
+        sse, total = torch.zeros((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.float64)
+        for view in self._views:
+            e = view[1] - self._shade(view, x)
+            g, w = self._adjoint(view, e * view[2][..., None], weight=True)
+            r, coverage = r + g, coverage + w
+            sse, total = sse + ((e * e).sum(-1) * view[2]).double().sum(), total + view[2].double().sum()
+        m_inv = 1.0 / (coverage[:, None] + lam)
+        z = r * m_inv
+        p, rz = z.clone(), dot(r, z)
+        sses = [sse]
+        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
+        for _ in range(self.iters):
+            ap = lam * p
+            for view in self._views:
+                ap = ap + self._adjoint(view, self._shade(view, p) * view[2][..., None])
+            pap = dot(p, ap)
+            alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
+            x, r = x + alpha.float() * p, r - alpha.float() * ap
+            z = r * m_inv
+            rz_new = dot(r, z)
+            beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
+            p, rz = z + beta.float() * p, rz_new
+            sses.append(self._sse(x))
+        rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
+        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()))
+
+
+def inner_coverage(face: Tensor, F: int) -> Tensor:
+    """face [B,H,W] -> bool [B,H,W]: pixels that hold a face of 0 .. F-1 and whose four neighbours do (the frame's border does not)."""
+    c = (face >= 0) & (face < F)
+    inner = torch.zeros_like(c)
+    inner[:, 1:-1, 1:-1] = c[:, 1:-1, 1:-1] & c[:, :-2, 1:-1] & c[:, 2:, 1:-1] & c[:, 1:-1, :-2] & c[:, 1:-1, 2:]
+    return inner
 
 
 def save_texels(path: str, texels, faces) -> None:

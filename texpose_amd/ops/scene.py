@@ -1,4 +1,4 @@
-"""K19-K22, K27, K35: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake and the face-texel shading."""
+"""K19-K22, K27, K35, K36: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake, the face-texel shading and its adjoint."""
 import math
 from typing import Dict, Optional, Tuple
 
@@ -8,7 +8,7 @@ from .. import _lib
 from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg)
 
 __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
-           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade"]
+           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade", "face_texel_shade_bwd"]
 
 
 # ------------------------------------------------------------------------------------------ K19
@@ -266,8 +266,9 @@ def face_texel_shade(face: Tensor, verts: Tensor, faces: Tensor, texels: Tensor,
     """Colour mesh_raster's face plane from a per-face texel texture (tp_face_texel_shade; the rule is in the header): face [B,H,W]
     int32 (taken as it is), verts [V,3], faces [F,3], texels [F,T,3] with T = (R + 1)(R + 2) / 2 for a resolution R in 1 .. 64 (R is
     inferred from T), pose [B,3,4] and intr [B,3,3] or [3,3] as the rasteriser got them -> rgb [B,H,W,3] float32, zero where the
-    plane holds no face.  ``out``: the tensor to write into.  Not differentiable.  One launch, no workspace, bit-identical from run
-    to run, safe under torch.cuda.graph."""
+    plane holds no face.  ``out``: the tensor to write into.  Not differentiable (texels are detached): the differentiable routes are
+    autograd_ops.face_texel_shade (per-slot texels) and face_texels.shade_nodes (shared nodes), both through face_texel_shade_bwd.  One
+    launch, no workspace, bit-identical from run to run, safe under torch.cuda.graph."""
     op = "face_texel_shade"
     _want_gpu(op, face, "face", torch.int32, None)
     if face.dim() != 3 or face.numel() == 0:
@@ -289,3 +290,56 @@ def face_texel_shade(face: Tensor, verts: Tensor, faces: Tensor, texels: Tensor,
     a.B, a.H, a.W, a.V, a.F, a.R, a.rgb = B, H, W, V, F, R, rgb.data_ptr()
     _call("tp_face_texel_shade", a)
     return rgb
+
+
+# ------------------------------------------------------------------------------------------ K36
+@_on_tensor_device
+def face_texel_shade_bwd(face: Tensor, verts: Tensor, faces: Tensor, grad_rgb: Tensor, pose: Tensor, intr: Tensor, *, R: int,
+                         node_index: Optional[Tensor] = None, U: Optional[int] = None, weight: bool = False, out: Optional[Tensor] = None):
+    """The adjoint of face_texel_shade with respect to the texels (tp_face_texel_shade_bwd; the rule and the fixed-point scheme are in
+    the header): face [B,H,W] int32 (taken as it is), verts, faces, pose, intr as face_texel_shade got them, grad_rgb [B,H,W,3] ->
+    grad [F,T(R),3] float32, or, with ``node_index`` [F,T] (any integer type; the row of each slot, e.g. face_texels.subdivide's) and
+    ``U``, grad [U,3] summed over the slots of each node (entries outside 0 .. U-1 are skipped).  ``weight=True``: returns (grad,
+    weight) with weight [F,T] or [U], the same sum for grad_rgb = 1 (the coverage).  ``out``: the grad tensor to write into.  Pixels
+    with a non-finite grad_rgb contribute nothing.  64-bit fixed-point integer atomics: bit-identical from run to run and under
+    torch.cuda.graph; B H W <= 2^25.  The workspace (8 bytes per output value) is a torch allocation owned by the call."""
+    op = "face_texel_shade_bwd"
+    _want_gpu(op, face, "face", torch.int32, None)
+    if face.dim() != 3 or face.numel() == 0:
+        raise ValueError("%s: face [B,H,W] expected, got %s" % (op, tuple(face.shape)))
+    B, H, W = face.shape
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose", B)
+    intr = _intr_per_view(op, intr, B)
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    V, F = verts.shape[0], faces.shape[0]
+    lib = _lib.load()
+    T = lib.tp_face_texel_count(int(R))
+    if tuple(faces.shape) != (F, 3) or F == 0 or T == 0:
+        raise ValueError("%s: faces [F,3] and R in 1 .. %d expected, got %s and R = %r" % (op, _lib.FACE_TEXEL_MAX_R, tuple(faces.shape), R))
+    if not torch.is_tensor(grad_rgb) or not grad_rgb.is_cuda or not grad_rgb.is_floating_point() or tuple(grad_rgb.shape) != (B, H, W, 3):
+        raise ValueError("%s: grad_rgb must be a floating-point GPU tensor of shape %s" % (op, (B, H, W, 3)))
+    grad_rgb = _f32(grad_rgb.detach(), "grad_rgb")
+    if node_index is None:
+        if U is not None:
+            raise ValueError("%s: U comes with node_index" % op)
+        N, shape, wshape = F * T, (F, T, 3), (F, T)
+    else:
+        if (not torch.is_tensor(node_index) or node_index.is_floating_point() or node_index.dtype == torch.bool
+                or tuple(node_index.shape) != (F, T) or U is None or int(U) <= 0):
+            raise ValueError("%s: node_index must be an integer tensor of shape %s, with U > 0 destinations" % (op, (F, T)))
+        node_index = node_index.to(device=verts.device, dtype=torch.int32).contiguous()
+        N, shape, wshape = int(U), (int(U), 3), (int(U),)
+    need = int(lib.tp_face_texel_shade_bwd_workspace(N, int(bool(weight))))
+    if need == 0 or B * H * W > 1 << 25:
+        raise ValueError("%s: B * H * W <= 2^25 and fewer than 2^31 / 3 destinations expected, got %d pixels and %d destinations" % (op, B * H * W, N))
+    dev = face.device
+    grad = torch.empty(shape, device=dev) if out is None else _want_gpu(op, out, "out", torch.float32, shape)
+    wsum = torch.empty(wshape, device=dev) if weight else None
+    ws = torch.empty(need // 8, device=dev, dtype=torch.int64)
+    a = _lib.FaceTexelShadeBwdArgs()
+    a.verts, a.faces, a.pose, a.intr, a.face, a.grad_rgb = (t.data_ptr() for t in (verts, faces, pose, intr, face, grad_rgb))
+    a.node_index = _ptr(node_index)
+    a.B, a.H, a.W, a.V, a.F, a.R, a.U = B, H, W, V, F, int(R), (0 if node_index is None else N)
+    a.workspace, a.grad, a.weight = ws.data_ptr(), grad.data_ptr(), _ptr(wsum)
+    _call("tp_face_texel_shade_bwd", a)
+    return (grad, wsum) if weight else grad

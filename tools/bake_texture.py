@@ -16,6 +16,12 @@ prints (and stores) the PSNR against the NeRF views inside the mask; nothing is 
 the vertices along every edge, no UV unwrap) from the same views and write it as <out>.texels.npz beside the PLY (texels, R and the
 faces it belongs to; refine_poses.py --texels reads it).  The PLY still holds the vertex colours, now the texture's corner nodes;
 --verify then re-renders through the texels, and the report gains 'texels' (R, nodes, coloured, filled, unseen, file).
+--fit ITERS [--fit-lambda L] (with --texel-res): the views also go into a face_texels.FaceTexelFitter (inner pixels
+of the mask, weight 1), and after the bake ITERS steps of preconditioned conjugate gradients from the baked nodes, with the baked nodes
+as the prior (weight L, default 0.1), minimise the difference between the texel render and the views (K36 tp_face_texel_shade_bwd).
+The fitted texels, clamped to [0, 1], are what <out>.texels.npz holds and the PLY's vertex colours are the fitted corner nodes; the
+report gains 'fit' (iters, lam, rms_before, rms_after, on_prior: nodes too little seen to leave the prior); --verify prints and stores
+the PSNR through the baked and through the fitted texels.  Without --fit nothing changes.
 Out of scope: texture atlases, view-dependent textures, photographs."""
 import argparse
 import json
@@ -40,6 +46,8 @@ def main(argv=None):
     ap.add_argument("--report", default=None, metavar="JSON")
     ap.add_argument("--verify", action="store_true", help="re-render the baked mesh and print the PSNR against the NeRF views")
     ap.add_argument("--texel-res", type=int, default=None, metavar="R", help="also write <out>.texels.npz: face texels of resolution R")
+    ap.add_argument("--fit", type=int, default=None, metavar="ITERS", help="with --texel-res: fit the texels to the views by ITERS steps of CG")
+    ap.add_argument("--fit-lambda", type=float, default=0.1, metavar="L", help="weight of the baked texture as the fit's prior")
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--samples", type=int, default=None, help="nerf.sample_intvs")
@@ -59,6 +67,8 @@ def main(argv=None):
         ap.error("--sphere N needs N >= 1 and --distance-mm D > 0")
     if a.texel_res is not None and not 1 <= a.texel_res <= 64:
         ap.error("--texel-res R needs R in 1 .. 64")
+    if a.fit is not None and (a.texel_res is None or a.fit < 1 or not a.fit_lambda > 0):
+        ap.error("--fit ITERS needs --texel-res R, ITERS >= 1 and --fit-lambda L > 0")
     import torch
     from texpose_amd import checkpoint as ck, ops
     from texpose_amd import face_texels as ft
@@ -100,6 +110,7 @@ def main(argv=None):
     # with --texel-res the nodes of the subdivided mesh are baked; its first V rows are the mesh's vertices, so the PLY comes from them
     texel_baker = None if a.texel_res is None else ft.FaceTexelBaker(verts, faces, a.texel_res, a.H, a.W, a.device, **thresholds)
     baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds) if texel_baker is None else texel_baker.nodes
+    fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit)
     light = torch.tensor(a.light_index, device=dev)
     kept = []                                                         # (rgb, mask) of every view, for --verify
     torch.cuda.synchronize(dev)
@@ -118,6 +129,11 @@ def main(argv=None):
                 rgb[i] = ret.rgb_static.view(a.H, a.W, 3)
                 weight[i] = ret.opacity_static.view(a.H, a.W)
             baker.add_views(rgb, tb.poses_to_mm(p, scale), k, zbuf=sb.zbuf[0], weight=weight)      # (the base mesh's depth planes)
+            if fitter is not None:
+                pose_mm = tb.poses_to_mm(p, scale).contiguous()
+                face = ops.mesh_raster(fitter.verts, fitter.faces, pose_mm, k, H=a.H, W=a.W, normals=False)["face"]
+                inside = sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)
+                fitter.add_views(rgb.clamp(0, 1), pose_mm, k, face=face, weight=(ft.inner_coverage(face, len(faces)) & inside).float())
             if a.verify:
                 kept.append((rgb, sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)))
     V = len(verts)
@@ -128,6 +144,12 @@ def main(argv=None):
         sub = texel_baker.result(fill=True)
         texels = sub.texels
         res = tb.AttrDict(vcolor=sub.vcolor_sub[:V].contiguous(), count=sub.count[:V], seen=sub.seen[:V], filled=sub.filled, unseen=sub.unseen)
+    baked_texels, fit = texels, None
+    if fitter is not None:
+        got = fitter.fit(prior=sub.vcolor_sub, start=sub.vcolor_sub)
+        nodes = got.nodes.clamp(0, 1)
+        texels, res.vcolor = ft.texels_from_nodes(nodes, fitter.node_index), nodes[:V].contiguous()
+        fit = dict(iters=a.fit, lam=a.fit_lambda, rms_before=float(got.rms[0]), rms_after=float(got.rms[-1]), on_prior=got.on_prior)
     torch.cuda.synchronize(dev)
     seconds = time.perf_counter() - t0
     ops.check_mlp_status(dev)
@@ -141,20 +163,33 @@ def main(argv=None):
         U = len(texel_baker.verts_sub)
         report["texels"] = dict(R=a.texel_res, per_face=int(texels.shape[1]), nodes=U, coloured=float(sub.seen.sum()) / U, filled=sub.filled,
                                 unseen=sub.unseen, file=texel_file)
+    if fit is not None:
+        report["fit"] = fit
+        print("bake_texture: fit of %d nodes, %d iterations, lambda %g: training rms %.5f -> %.5f, %d nodes on the prior"
+              % (len(texel_baker.verts_sub), a.fit, a.fit_lambda, fit["rms_before"], fit["rms_after"], fit["on_prior"]))
     if a.verify:
-        se, px = 0.0, 0
         base_verts, base_faces = (baker.verts, baker.faces) if texel_baker is None else (texel_baker.verts, texel_baker.faces)
-        with torch.no_grad():
-            for c, (rgb, mask) in zip(range(0, N, a.chunk), kept):
-                r = ops.mesh_raster(base_verts, base_faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
-                                    H=a.H, W=a.W, vcolor=res.vcolor if texels is None else None, texels=texels, face_ids=False, normals=False)
-                m = mask & (r["zbuf"] > 0)
-                se += float((((r["rgb"] - rgb.clamp(0, 1)) ** 2).sum(-1) * m).double().sum())
-                px += int(m.sum())
-        mse = se / max(1, 3 * px)
-        report["verify"] = dict(pixels=px, mse=mse, psnr_db=(float("inf") if mse == 0 else -10.0 * float(np.log10(mse))) if px else None)
-        print("bake_texture: re-rendered mesh against the NeRF views inside the mask: PSNR %s dB over %d pixels"
-              % ("%.2f" % report["verify"]["psnr_db"] if px else "n/a", px))
+
+        def rerender(texels):
+            se, px = 0.0, 0
+            with torch.no_grad():
+                for c, (rgb, mask) in zip(range(0, N, a.chunk), kept):
+                    r = ops.mesh_raster(base_verts, base_faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
+                                        H=a.H, W=a.W, vcolor=res.vcolor if texels is None else None, texels=texels, face_ids=False, normals=False)
+                    m = mask & (r["zbuf"] > 0)
+                    se += float((((r["rgb"] - rgb.clamp(0, 1)) ** 2).sum(-1) * m).double().sum())
+                    px += int(m.sum())
+            mse = se / max(1, 3 * px)
+            return px, mse, ((float("inf") if mse == 0 else -10.0 * float(np.log10(mse))) if px else None)
+
+        px, mse, psnr = rerender(texels)
+        report["verify"] = dict(pixels=px, mse=mse, psnr_db=psnr)
+        if fit is not None:
+            report["verify"]["psnr_db_baked"] = rerender(baked_texels)[2]
+            print("bake_texture: re-rendered mesh through the BAKED texels against the NeRF views inside the mask: PSNR %s dB over %d pixels"
+                  % ("%.2f" % report["verify"]["psnr_db_baked"] if px else "n/a", px))
+        print("bake_texture: re-rendered mesh%s against the NeRF views inside the mask: PSNR %s dB over %d pixels"
+              % (" through the FITTED texels" if fit is not None else "", "%.2f" % psnr if px else "n/a", px))
     if a.report:
         with open(a.report, "w") as fh:
             json.dump(report, fh, indent=1)

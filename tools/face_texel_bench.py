@@ -14,7 +14,19 @@ route on the pixels where both see the same surface: at most 0.01 % of them may 
 tests/test_gpu_face_texels.py) and none by more than 2e-3, with coverage differing on at most 0.5 %.  The gate is wider than the tests'
 because the subdivided route shades with the rasteriser's fp32 barycentrics, and its sub-faces at the silhouette of a 480 x 640 view
 project to slivers far thinner than a pixel; the kernel itself is held to the fp64 restatement by the tests.  Device events around
-many calls after a warm-up, three repeats per route, alternating, medians; the shader clock comes from ops.clock_probe before and after."""
+many calls after a warm-up, three repeats per route, alternating, medians; the shader clock comes from ops.clock_probe before and after.
+
+--fit: the adjoint instead (K36 tp_face_texel_shade_bwd), on the same workload with a dense random gradient:
+
+  shade R          tp_face_texel_shade alone, as above: the forward beside which every adjoint time is read
+  adjoint R        ops.face_texel_shade_bwd per slot ([F,T,3]), R in {1, 4, 8}; "+weight" with the coverage output
+  adjoint nodes R  the same through the node index of the subdivided mesh ([U,3])
+  fit R=4          FaceTexelFitter.fit over the 64 views with 0 and with 1 iteration: the difference is one iteration
+
+    python tools/face_texel_bench.py --fit [--out profiles/face_texel_fit/adjoint.json]
+
+Each adjoint row carries the forward's time of the same run and the atomic bytes per second: 9 (12 with the coverage) 64-bit atomics, 72
+(96) bytes, per covered pixel.  Before anything is timed the identity <shade(t), g> = <t, adjoint(g)> is checked in fp64 on the host."""
 import argparse
 import json
 import os
@@ -37,6 +49,7 @@ def main(argv=None):
     ap.add_argument("--views", type=int, default=64)
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
+    ap.add_argument("--fit", action="store_true", help="time the adjoint (K36) and one fitter iteration instead")
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import face_texels as FT, ops, texture_bake as TB
@@ -56,6 +69,8 @@ def main(argv=None):
     base = raster(vcolor=vcol)
     covered = base["zbuf"] > 0
     n_cov = int(covered.sum())
+    if a.fit:
+        return bench_fit(a, locals())
     routes, iters, checks, meshes = {"base": lambda: raster(vcolor=vcol), "base cull": lambda: raster(vcolor=vcol, cull=True)}, {}, {}, {}
     heavy = max(2, a.iters // 10)
     for R in (1, 4, 8):
@@ -104,6 +119,56 @@ def main(argv=None):
     res = dict(bench="face_texels", device=torch.cuda.get_device_name(0), V=len(v_np), F=len(f_np), B=B, H=H, W=W, covered_pixels=n_cov,
                covered_share=n_cov / pixels, iters=a.iters, warmup=a.warmup, repeats=a.repeats, shader_clock_ghz_before=clock_before,
                shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start, textures=list(meshes.values()), checks=checks, rows=rows)
+    KB.finish(res, a.out)
+
+
+def bench_fit(a, env):
+    import torch
+    from texpose_amd import face_texels as FT, ops
+    dev, B, H, W, pose, K, verts, faces = (env[k] for k in ("dev", "B", "H", "W", "pose", "K", "verts", "faces"))
+    v_np, f_np, colour, covered, n_cov = (env[k] for k in ("v_np", "f_np", "colour", "covered", "n_cov"))
+    face = ops.mesh_raster(verts, faces, pose, K, H=H, W=W, normals=False)["face"]
+    g = torch.randn(B, H, W, 3, device=dev)
+    routes, checks, meshes = {}, {}, []
+    for R in (1, 4, 8):
+        vs, _, ni = FT.subdivide(v_np, f_np, R)
+        U = len(vs)
+        ni_d = torch.from_numpy(ni).to(dev).to(torch.int32)
+        texels = torch.from_numpy(FT.texels_from_nodes(colour(vs), ni)).to(dev)
+        out, grad, grad_n = torch.empty(B, H, W, 3, device=dev), torch.empty_like(texels), torch.empty(U, 3, device=dev)
+        lhs = float((ops.face_texel_shade(face, verts, faces, texels, pose, K).double() * g.double()).sum())
+        rhs = float((texels.double() * ops.face_texel_shade_bwd(face, verts, faces, g, pose, K, R=R).double()).sum())
+        checks["R=%d adjoint identity" % R] = dict(lhs=lhs, rhs=rhs)
+        if not abs(lhs - rhs) <= 1e-6 * float(g.abs().double().sum()):
+            raise SystemExit("face_texel_bench: R = %d: <S t, g> = %.9g but <t, S^T g> = %.9g; nothing was timed" % (R, lhs, rhs))
+        bwd = lambda R=R, **kw: ops.face_texel_shade_bwd(face, verts, faces, g, pose, K, R=R, **kw)
+        routes["shade R=%d" % R] = lambda texels=texels, out=out: ops.face_texel_shade(face, verts, faces, texels, pose, K, out=out)
+        routes["adjoint R=%d" % R] = lambda bwd=bwd, grad=grad: bwd(out=grad)
+        routes["adjoint R=%d +weight" % R] = lambda bwd=bwd, grad=grad: bwd(out=grad, weight=True)
+        routes["adjoint nodes R=%d" % R] = lambda bwd=bwd, ni_d=ni_d, U=U, grad_n=grad_n: bwd(node_index=ni_d, U=U, out=grad_n)
+        routes["adjoint nodes R=%d +weight" % R] = lambda bwd=bwd, ni_d=ni_d, U=U, grad_n=grad_n: bwd(node_index=ni_d, U=U, out=grad_n, weight=True)
+        meshes.append(dict(R=R, slots=int(texels.shape[0] * texels.shape[1]), nodes=U))
+    photo = ops.face_texel_shade(face, verts, faces, texels, pose, K)            # (the R = 8 render: a photograph finer than the R = 4 fit)
+    fitters = {}
+    for iters in (0, 1):
+        fitters[iters] = FT.FaceTexelFitter(v_np, f_np, 4, H, W, dev, iters=iters)
+        for c in range(0, B, 16):
+            fitters[iters].add_views(photo[c:c + 16], pose[c:c + 16], K[c:c + 16], face=face[c:c + 16])
+        routes["fit R=4 iters=%d" % iters] = fitters[iters].fit
+    med, times = KB.race(routes, a.iters, a.warmup, a.repeats)
+    rows = []
+    for name in routes:
+        row = dict(route=name, us_per_call=med[name], us_all_repeats=times[name])
+        if name.startswith("adjoint"):
+            per_pixel = 96 if name.endswith("+weight") else 72
+            row.update(forward_us_same_run=med["shade R=%s" % name.split("R=")[1].split()[0]], atomic_bytes=per_pixel * n_cov,
+                       atomic_bytes_per_second=per_pixel * n_cov / (med[name] * 1e-6))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    res = dict(bench="face_texel_fit", device=torch.cuda.get_device_name(0), V=len(v_np), F=len(f_np), B=B, H=H, W=W, covered_pixels=n_cov,
+               covered_share=n_cov / (B * H * W), iters=a.iters, warmup=a.warmup, repeats=a.repeats, shader_clock_ghz_before=env["clock_before"],
+               shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - env["t_start"], textures=meshes, checks=checks,
+               fit_iteration_us=med["fit R=4 iters=1"] - med["fit R=4 iters=0"], rows=rows)
     KB.finish(res, a.out)
 
 
