@@ -1594,6 +1594,70 @@ typedef struct tp_face_texel_shade_bwd_args {
 size_t tp_face_texel_shade_bwd_workspace(int64_t N, int want_weight);      /* 8 (3 N + (want_weight ? N : 0) + 1); 0 for N <= 0 or 3 N >= 2^31 */
 int tp_face_texel_shade_bwd(const tp_face_texel_shade_bwd_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K37  per-image, per-channel gain and bias between a rendering and its photograph (texpose_amd/ops/refine.py: photo_exposure;
+ *      restated in tests/photo_exposure_ref.py; the project's own step, no reference code).  zbuf / rgb are K19's
+ *      planes at the current poses; the call fits  o_k ~ g_k c_k + b_k  per image b and channel k by least squares over the pixels
+ *      the fit that came in (gain_in, bias_in; NULL: gain 1, bias 0) explains within tau, and, where rgb_out is given, applies the
+ *      new fit to the rendering, so that K30 / K33 compare colours under the photograph's exposure.  No neighbour pixel, pose or
+ *      intrinsics are read.  Per pixel (row i, column j) of image b, with the photograph fr = frame ? frame[b] CLAMPED into [0, Ft)
+ *      : (Ft == 1 ? 0 : b), everything in fp64 from the fp32 inputs, evaluated as written (no contraction):
+ *        1. skipped unless 1 <= i <= H - 2 and 1 <= j <= W - 2                       (K30's interior)
+ *        2. z = zbuf[b,i,j];           skipped unless z > 0 and finite
+ *        3. skipped where mask is given and mask[fr,i,j] == 0
+ *        4. c_k = rgb[b,i,j,k], o_k = image[fr,i,j,k] for k = 0, 1, 2;  skipped unless all six values are finite
+ *        5. r_k = o_k - (a_k c_k + d_k) with (a, d) = (gain_in[b], bias_in[b]);  kept iff (r_0^2 + r_1^2) + r_2^2 <= tau * tau
+ *      Sixteen sums over the kept pixels: [0] n (+ 1 per pixel) and, for channel k, [1 + 5 k ..]: c_k, o_k, c_k c_k, c_k o_k,
+ *      o_k o_k.  A thread owns four consecutive flat pixels (ascending, channels ascending), a workgroup 1024; butterfly sums
+ *      inside a wave, the four waves in ascending order, one 32-double record per workgroup (entries 16 .. 31 are zero), the
+ *      records in ascending order: K30's order; no atomics, the outputs are a function of the inputs alone, bit-identical from run
+ *      to run and under graph replay.  Per image and channel, in fp64 as written (Sc, So, Scc, Sco, Soo the channel's sums):
+ *        mc = Sc / n;  mo = So / n;  var = Scc / n - mc mc;  cov = Sco / n - mc mo;  voo = Soo / n - mo mo
+ *        var > min_var:  g = min(max(cov / var, gain_min), gain_max);  bit k of flags where g != cov / var      (the clamp acted)
+ *        otherwise:      g = 1;                                         bit 3 + k of flags                       (a flat channel)
+ *        b = mo - g mc;   sse_k = n ((voo - 2 (g cov)) + (g g) var)                  (the squared error at (g, b), from the sums)
+ *      count = n;  rms = sqrt(max(0, (sse_0 + sse_1) + sse_2) / n) in colour units, of the fit just made (NaN at n = 0);
+ *        status = 1 where n < 6; else 3 where one of g_k, b_k or rms rounded to fp32 is not finite; else 0
+ *        gain, bias = (g, b) rounded to fp32 where status == 0;  otherwise gain_in, bias_in bit for bit (1 and 0 where NULL);
+ *        flags are those of the fit just made whatever the status
+ *      Apply, where rgb_out is given: a pixel with zbuf > 0 and finite (border pixels included) becomes
+ *        rgb_out[b,i,j,k] = gain[b,k] * rgb[b,i,j,k] + bias[b,k]   as two fp32 operations (a product, then a sum)
+ *      with the gain and bias the call just wrote; every other pixel is copied bit for bit, and with rgb_out == rgb is not written.
+ *      Status is an output only: a failed fit passes the fit that came in through, so a loop needs no state.  Three launches on
+ *      the stream (reduce, solve, apply; two without rgb_out).  Non-positive sizes, B > 65535, H * W >= 2^31, without frame an Ft
+ *      that is neither 1 nor B, a tau that is not finite and positive, gain_min / gain_max outside 0 < gain_min <= 1 <= gain_max <
+ *      inf, a min_var that is not finite and >= 0, null pointers, a workspace that is not 16-byte aligned, an rgb_out that overlaps
+ *      rgb without being rgb, and gain or bias overlapping gain_in or bias_in are refused (-1, tp_last_error) before anything is
+ *      launched.  No input value causes an access out of bounds: frame is the only index read from memory, and it is clamped.  No
+ *      allocation, no host synchronisation; outputs and workspace must not overlap inputs otherwise.  Safe to capture.
+ *      Left out: a gain shared by the channels, a spatially varying model, exact elimination inside the pose step's system.
+ * ------------------------------------------------------------------------------------------ */
+#define TP_EXPOSURE_CLAMPED 1  /* flags: << k, channel k's gain was clamped into [gain_min, gain_max] */
+#define TP_EXPOSURE_FLAT 8     /* flags: << k, channel k's variance was <= min_var: gain 1 */
+typedef struct tp_photo_exposure_args {
+  const float* zbuf;         /* [B,H,W] K19's depth at the current poses: <= 0 or NaN: background */
+  const float* rgb;          /* [B,H,W,3] K19's colours at the current poses */
+  const float* image;        /* [Ft,H,W,3] the photograph, channels last */
+  const int32_t* frame;      /* [B] index into image (and mask), or NULL: b when Ft == B, 0 when Ft == 1 */
+  const uint8_t* mask;       /* [Ft,H,W] or NULL; 0: the pixel is skipped */
+  const float* gain_in;      /* [B,3] or NULL (1): the fit the keep rule judges by */
+  const float* bias_in;      /* [B,3] or NULL (0) */
+  int B, Ft, H, W;
+  float tau;                 /* finite, > 0: the largest colour distance |o - (a c + d)| of a kept pixel */
+  float gain_min, gain_max;  /* 0 < gain_min <= 1 <= gain_max, finite */
+  float min_var;             /* finite, >= 0, colour units squared: a channel whose variance is not above it keeps gain 1 */
+  float* gain;               /* [B,3] out */
+  float* bias;               /* [B,3] out */
+  int32_t* count;            /* [B] out */
+  float* rms;                /* [B] out, colour units */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels, 3 not finite */
+  int32_t* flags;            /* [B] out: TP_EXPOSURE_CLAMPED << k | TP_EXPOSURE_FLAT << k */
+  float* rgb_out;            /* [B,H,W,3] out, rgb itself (in place) or NULL (fit only) */
+  void* workspace;           /* tp_photo_exposure_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_photo_exposure_args;
+size_t tp_photo_exposure_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
+int tp_photo_exposure(const tp_photo_exposure_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """K29-K33: the render-and-compare pose refiners -- the depth ICP, the photometric alignment, the masks' distance field, the silhouette
 alignment and the joint step of the three -- behind one table of terms: what a term's step takes, asks of the rasteriser and returns
 is said once in ``_TERMS``; one builder fills any term's args struct, one helper sizes every workspace and one driver runs all four
-loops."""
+loops.  K37, the exposure fit that a loop with a photometric term may run in front of each step (photo_exposure), is here too."""
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -11,9 +11,9 @@ from .. import _lib
 from ._base import Tensor, _call, _f32, _intr_per_view, _lengths, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg
 
 __all__ = ["depth_icp_workspace", "depth_icp_step", "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS",
-           "photo_align", "mask_sdf_workspace", "mask_sdf", "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step",
-           "SILHOUETTE_ALIGN_KEYS", "silhouette_align", "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step",
-           "JOINT_ALIGN_KEYS", "joint_align"]
+           "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "mask_sdf_workspace", "mask_sdf",
+           "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align",
+           "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align"]
 
 
 # ------------------------------------------------------------------------------------------ the terms
@@ -139,13 +139,17 @@ def _schedules(op: str, given, iters: int) -> list:
 
 
 def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, given, taus, *, damping, frame, workspace, cull,
-            vcolor=None, texels=None, visible_iou=False, weights=None) -> Dict[str, Tensor]:
+            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0) -> Dict[str, Tensor]:
     """The loop of every refiner over the terms of ``given`` that have planes: one pass per entry of ``taus`` (_schedules) of ONE
     mesh_raster call at the current poses, asked only for what these terms need, and one step from it, the last evaluate-only; a step
     that fails passes its pose on.  Without ``weights`` the step is the single term's own (its 'rms' is the cost carried); with them it
     is joint_align_step ('chi2'), and the last pass's per-term keys are returned too.  -> ``keys``: the last pass's pose, inliers and
     cost, the status of the last step taken (of the evaluation where there is no step), inliers0 / <cost>0 of the first pass; with a
-    term that counts coverage 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' / 'iou0_visible'."""
+    term that counts coverage 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' / 'iou0_visible'.  ``exposure`` with a photometric
+    term: every pass first fits the photograph's per-channel gain and bias to the rendering and rewrites the rendered colours under
+    them (photo_exposure in place, K37; the term's frame map and mask; the fit of the pass before decides with that pass's ``tau``
+    what is kept, the first pass keeps within ``exposure_tau0`` of the plain colours) -> also 'gain' / 'bias' [B,3] and
+    'exposure_status' [B] of the last pass (prefixed with the term's 'photo_' in the joint results)."""
     joint = weights is not None
     cost = "chi2" if joint else "rms"
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -188,9 +192,15 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
               [k for k in term.rendered if k not in mesh]) for i, term in terms]
     step = _STEPS[terms[0][1].name]
     hidden = []
+    lit = next((i for i, t in terms if t is _PHOTO), None) if exposure else None      # the photometric threshold's place in a pass's ``th``
+    fit = {}                                                     # the exposure fit of the pass before
 
     def one_pass(pose, th, last):                                # (a function: the rendered planes are released before the next pass renders)
         r = mesh_raster(verts, faces, pose, intr, **ask)
+        if lit is not None:                                      # (in front of the step: it compares the colours under the photograph's exposure)
+            e = photo_exposure(r["zbuf"], r["rgb"], planes[_PHOTO.plane], tau=th[lit] if fit else exposure_tau0, gain=fit.get("gain"),
+                               bias=fit.get("bias"), frame=frame, mask=masks[_PHOTO.name], inplace=True, workspace=workspace)
+            fit.update(gain=e["gain"], bias=e["bias"], exposure_status=e["status"])
         own = {term.name: dict(kw, **{k: r[k] for k in rendered}, **{term.threshold: th[i]}) for i, term, kw, rendered in fixed}
         if joint:
             got = joint_align_step(pose, intr, weights=weights, damping=damping, evaluate_only=last, workspace=workspace, **own)
@@ -212,6 +222,7 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     res = {k: res[k] for k in keys}
     if joint:
         res.update({k: v for k, v in got.items() if k.startswith(tuple(t.prefix for t in _TERMS))})
+    res.update({(_PHOTO.prefix if joint else "") + k: v for k, v in fit.items()})
     if counting is not None:
         inter, uni = ((counting.prefix if joint else "") + k for k in counting.counts)
         res.update(iou=got[inter].float() / got[uni].float(), iou0=first[inter].float() / first[uni].float())
@@ -295,7 +306,8 @@ PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 @_on_tensor_device
 def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
                 damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-                workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False,
+                exposure_tau0: float = 2.0) -> Dict[str, Tensor]:
     """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
     ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
@@ -303,12 +315,80 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     iters = 0) and 'inliers0' / 'rms0' of the start pose.  A step that fails passes its pose on.  2 (iters + 1) launches besides the
     rasteriser's, bit-identical from run to run, safe under torch.cuda.graph.  ``cull``: the passes render with
     mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] with ``vcolor`` None: the passes colour the mesh from its face texels
-    (mesh_raster(texels=), K35); exactly one of the two."""
+    (mesh_raster(texels=), K35); exactly one of the two.  ``exposure``: the photograph was taken under another exposure, white
+    balance or light than the colours: every pass first fits a gain and a bias per image and channel and renders under them
+    (photo_exposure, K37: three launches more per pass), the first pass over the pixels within ``exposure_tau0`` of the
+    plain colours (2.0 keeps every pixel of colours in [0, 1]), each later one within that pass's ``tau`` of the fit before -> also 'gain'
+    / 'bias' [B,3] and 'exposure_status' [B] int32 of the last pass.  Without it nothing else runs and the keys are those above."""
     op, given = "photo_align", [(_PHOTO, image, tau, mask)]
     if (vcolor is None) == (texels is None):
         raise ValueError("%s: exactly one of vcolor [V,3] and texels= [F,T,3] expected" % op)
     return _refine(op, PHOTO_ALIGN_KEYS, verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
-                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels)
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, exposure=exposure, exposure_tau0=exposure_tau0)
+
+
+# ------------------------------------------------------------------------------------------ K37
+def photo_exposure_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for photo_exposure at B images of H x W (tp_photo_exposure_workspace_bytes, the terms' own size); needs no
+    clearing."""
+    return _workspace_arg("photo_exposure", None, int(_lib.load().tp_photo_exposure_workspace_bytes(B, H, W)), device)
+
+
+PHOTO_EXPOSURE_KEYS = ("gain", "bias", "count", "rms", "status", "flags")
+
+
+@_on_tensor_device
+def photo_exposure(zbuf: Tensor, rgb: Tensor, image: Tensor, *, tau: float, gain: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+                   frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, gain_range=(0.25, 4.0), min_var: float = 1e-6,
+                   apply: bool = True, inplace: bool = False, workspace: Optional[Tensor] = None,
+                   out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The per-image, per-channel gain and bias between B renderings and their photographs, and the renderings under that fit
+    (tp_photo_exposure, K37; the rules are in the header): zbuf [B,H,W] / rgb [B,H,W,3] (mesh_raster's planes at the current poses;
+    taken as they are), image [Ft,H,W,3] (the photograph, channels last; Ft 1 or B, or any Ft with ``frame`` [B] int32), mask
+    [Ft,H,W] uint8 or bool (0: skip the pixel), ``gain`` / ``bias`` [B,3] float32 (the fit of the pass before, which decides with
+    ``tau`` what is kept; None: 1 and 0) -> 'gain' / 'bias' [B,3] (image ~ gain * rgb + bias by least squares over the interior covered
+    pixels the incoming fit explains within ``tau``; the gain clamped into ``gain_range``, 1 for a channel whose variance is not above
+    ``min_var``), 'count' [B] int32, 'rms' [B] (colour units, of the new fit), 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3
+    not finite: gain and bias are then the incoming ones bit for bit), 'flags' [B] int32 (_lib.EXPOSURE_CLAMPED << k,
+    _lib.EXPOSURE_FLAT << k) and, with ``apply``, 'rgb' [B,H,W,3]: gain * rgb + bias on the covered pixels, the rest copied; with
+    ``inplace`` it is ``rgb`` itself, rewritten.  ``workspace``: photo_exposure_workspace(B, H, W); ``out``: any of these tensors to
+    write into (out['gain'] / out['bias'] must not be ``gain`` / ``bias``).  Three launches (two without ``apply``), no atomics,
+    bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "photo_exposure"
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B,H,W] expected, got %s" % (op, tuple(zbuf.shape)))
+    B, H, W = zbuf.shape
+    rgb = _want_gpu(op, rgb, "rgb", torch.float32, (B, H, W, 3))
+    image, frame, mask, Ft = _frame_planes(op, _PHOTO, image, frame, mask, B, H, W, zbuf)
+    gain = None if gain is None else _want_gpu(op, gain, "gain", torch.float32, (B, 3))
+    bias = None if bias is None else _want_gpu(op, bias, "bias", torch.float32, (B, 3))
+    try:
+        lo, hi = (float(x) for x in gain_range)
+    except (TypeError, ValueError):
+        raise ValueError("%s: gain_range must be two host values (min, max), got %r" % (op, gain_range)) from None
+    spec = {"gain": (torch.float32, (B, 3)), "bias": (torch.float32, (B, 3)), "count": (torch.int32, (B,)), "rms": (torch.float32, (B,)),
+            "status": (torch.int32, (B,)), "flags": (torch.int32, (B,))}
+    if apply and inplace:
+        if out is not None and "rgb" in out:
+            raise ValueError("%s: out['rgb'] and inplace=True exclude each other" % op)
+    elif apply:
+        spec["rgb"] = (torch.float32, (B, H, W, 3))
+    res = _outputs(op, out, spec, zbuf.device, partial=True)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_exposure_workspace_bytes(B, H, W)), zbuf.device, align=16)
+    a = _lib.PhotoExposureArgs()
+    a.zbuf, a.rgb, a.image, a.frame, a.mask = zbuf.data_ptr(), rgb.data_ptr(), image.data_ptr(), _ptr(frame), _ptr(mask)
+    a.gain_in, a.bias_in = _ptr(gain), _ptr(bias)
+    a.B, a.Ft, a.H, a.W = B, Ft, H, W
+    a.tau, a.gain_min, a.gain_max, a.min_var = float(tau), lo, hi, float(min_var)
+    for k in PHOTO_EXPOSURE_KEYS:
+        setattr(a, k, res[k].data_ptr())
+    if apply and inplace:
+        res["rgb"] = rgb
+    a.rgb_out = res["rgb"].data_ptr() if apply else None
+    a.workspace = workspace.data_ptr()
+    _call("tp_photo_exposure", a)         # (tau, gain_range, min_var out of range, outputs overlapping inputs: the library's error)
+    return res
 
 
 # ------------------------------------------------------------------------------------------ K31
@@ -520,7 +600,7 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
                 image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
                 iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
                 workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
-                texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
     (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
     one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
@@ -535,7 +615,9 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     last pass's per-term keys of joint_align_step; with ``sdf`` also 'iou' / 'iou0', and with ``visible_iou`` 'iou_visible' /
     'iou0_visible', as silhouette_align.  A step that fails passes its pose on.  Bit-identical from run to run, safe under
     torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] in place of ``vcolor``:
-    the photometric term's renders take their colour from the mesh's face texels (mesh_raster(texels=), K35); at most one of the two."""
+    the photometric term's renders take their colour from the mesh's face texels (mesh_raster(texels=), K35); at most one of the two.
+    ``exposure`` (with ``image``): as photo_align's, for the photometric term -> also 'photo_gain' / 'photo_bias' [B,3] and
+    'photo_exposure_status' [B] int32 of the last pass; without ``image`` it does nothing."""
     op = "joint_align"
     if vcolor is not None and texels is not None:
         raise ValueError("%s: vcolor= or texels=, not both" % op)
@@ -551,4 +633,5 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
         raise ValueError("%s: masks takes the keys %s, got %s" % (op, JOINT_TERMS, sorted(masks)))
     # (the dict has had its cost keys behind inliers0 since K33; JOINT_ALIGN_KEYS names them, not their order)
     return _refine(op, ("pose", "inliers", "status", "inliers0", "chi2", "chi20"), verts, faces, pose, intr, given, taus, damping=damping, frame=frame,
-                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w)
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w, exposure=exposure,
+                   exposure_tau0=exposure_tau0)

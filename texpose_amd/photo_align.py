@@ -51,6 +51,57 @@ def sums_torch(zbuf: Tensor, rgb: Tensor, pose: Tensor, intr: Tensor, image: Ten
     return _gn_torch.normal_sums(B, bi.repeat_interleave(3), J, res.reshape(-1)) + (torch.bincount(bi, minlength=B), pose32)
 
 
+def exposure_torch(zbuf: Tensor, rgb: Tensor, image: Tensor, tau: float, gain: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+                   frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, gain_range=(0.25, 4.0), min_var: float = 1e-6,
+                   apply: bool = True) -> Dict[str, Tensor]:
+    """ops.photo_exposure's rules (include/texpose_amd.h, K37) in plain torch ops in fp64 on the tensors' device: the same arguments
+    -> 'gain' / 'bias' [B,3] float32, 'count' [B] int32, 'rms' [B] float32, 'status', 'flags' [B] int32 and, with ``apply``, 'rgb'
+    [B,H,W,3] float32 (a new tensor).  The sums run in torch's order, not the kernel's: counts, statuses and flags agree, the rest to
+    rounding; 'rgb' is the kernel's bit for bit from the same gain and bias."""
+    f64, f32 = torch.float64, torch.float32
+    B, H, W = zbuf.shape
+    zf, c32, image = zbuf.float(), rgb.float(), image.float()
+    image = image if image.dim() == 4 else image[None]
+    fr = _gn_torch.frames_of(B, image.shape[0], frame, "image must hold 1 or B = %d photographs", zbuf.device)
+    as_f32 = lambda v: float(torch.tensor(v, dtype=f32))
+    tau, lo, hi, min_var = as_f32(tau), as_f32(gain_range[0]), as_f32(gain_range[1]), as_f32(min_var)
+    g_in = torch.ones(B, 3, dtype=f32, device=zbuf.device) if gain is None else gain.float()
+    b_in = torch.zeros(B, 3, dtype=f32, device=zbuf.device) if bias is None else bias.float()
+    covered = (zf > 0) & torch.isfinite(zf)
+    cand = covered.clone()
+    cand[:, :1], cand[:, H - 1:], cand[:, :, :1], cand[:, :, W - 1:] = False, False, False, False
+    cand = _gn_torch.masked(cand, mask, fr)
+    c, o = c32.to(f64), image[fr].to(f64)                                                   # [B,H,W,3]
+    res = o - (g_in.to(f64)[:, None, None, :] * c + b_in.to(f64)[:, None, None, :])
+    keep = cand & torch.isfinite(c).all(-1) & torch.isfinite(o).all(-1) & ((res[..., 0] * res[..., 0] + res[..., 1] * res[..., 1])
+                                                                          + res[..., 2] * res[..., 2] <= tau * tau)
+    k3 = keep[..., None]
+    zero = torch.zeros((), dtype=f64, device=zbuf.device)
+    total = lambda v: torch.where(k3, v, zero).flatten(1, 2).sum(1)                         # [B,3]
+    n = keep.flatten(1).sum(1).to(f64)[:, None]
+    mc, mo = total(c) / n, total(o) / n
+    var, cov, voo = total(c * c) / n - mc * mc, total(c * o) / n - mc * mo, total(o * o) / n - mo * mo
+    live = var > min_var
+    q = cov / torch.where(live, var, torch.ones_like(var))
+    g = torch.where(live, q.clamp(lo, hi), torch.ones_like(q))
+    ch = torch.arange(3, device=zbuf.device)
+    flags = ((live & (g != q)).long() << ch).sum(1) + ((~live).long() << (3 + ch)).sum(1)
+    b = mo - g * mc
+    sse = n * ((voo - 2.0 * (g * cov)) + (g * g) * var)
+    rms = torch.sqrt(((sse[:, 0] + sse[:, 1]) + sse[:, 2]).clamp_min(0.0) / n[:, 0]).to(f32)
+    g32, b32 = g.to(f32), b.to(f32)
+    few = n[:, 0] < _gn_torch.MIN_COUNT
+    fine = torch.isfinite(g32).all(1) & torch.isfinite(b32).all(1) & torch.isfinite(rms)
+    status = torch.where(few, 1, torch.where(fine, 0, 3)).to(torch.int32)
+    ok = (status == 0)[:, None]
+    out = dict(gain=torch.where(ok, g32, g_in), bias=torch.where(ok, b32, b_in), count=n[:, 0].to(torch.int32), rms=rms, status=status,
+               flags=flags.to(torch.int32))
+    if apply:
+        lit = out["gain"][:, None, None, :] * c32                                           # (two fp32 operations)
+        out["rgb"] = torch.where(covered[..., None], lit + out["bias"][:, None, None, :], c32)
+    return out
+
+
 class PhotoRefiner(_MeshRefiner):
     """Photometric alignment for batches of poses of one vertex-coloured mesh at H x W with the mesh on the device and a workspace per
     batch size.
@@ -58,16 +109,19 @@ class PhotoRefiner(_MeshRefiner):
     ``tau`` (one value or ``iters`` + 1 for a coarse-to-fine schedule; 0.5, in the colours' units), ``iters`` (Gauss-Newton steps, 10),
     ``damping`` (relative, 1e-6).  ``refine`` returns pose [B,3,4] ([R|t] model -> camera, mm), inliers [B] (interior covered pixels
     within tau of the photograph), rms [B] (colour units), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was
-    not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose."""
+    not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose.  ``exposure``: every pass first fits
+    the photograph's gain and bias per image and channel (ops.photo_exposure, K37) and ``refine`` also returns gain / bias [B,3] and
+    exposure_status [B]; for photographs whose exposure, white balance or light differ from the colours'."""
     _new_workspace = staticmethod(ops.photo_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, vcolor: Optional[Tensor], H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
-                 damping: float = 1e-6, cull: bool = False, texels: Optional[Tensor] = None):
+                 damping: float = 1e-6, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0):
         super().__init__(verts, faces, H, W, device, cull=cull)
         if (vcolor is None) == (texels is None):
             raise ValueError("PhotoRefiner: exactly one of vcolor [V,3] and texels= [F,T,3] (face texels, K35) expected")
         self._colours(vcolor, texels)
         self.tau, self.iters, self.damping = tau, int(iters), float(damping)
+        self.exposure, self.exposure_tau0 = bool(exposure), float(exposure_tau0)
 
     def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
         """pose [B,3,4], intr [B,3,3] or [3,3], image [Ft,H,W,3] (channels last, the vertex colours' units), frame [B] int32 (the
@@ -77,4 +131,4 @@ class PhotoRefiner(_MeshRefiner):
             raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
         return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
                                         damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull,
-                                        texels=self.texels))
+                                        texels=self.texels, exposure=self.exposure, exposure_tau0=self.exposure_tau0))

@@ -13,7 +13,16 @@ algorithmic bytes, 28 x H x W per pose (rendered depth 4, rendered colour 12, ph
 counted once, as the cache should serve them; a share of peak of the CALL: both launches and the gap between them are inside the
 events); microseconds per rasteriser call with rgb; and microseconds per full ops.photo_align call (10 steps and the final evaluation,
 the rasteriser included) with the share of it the eleven step calls take.  DEPTH_ICP_CONTEXT repeats DESIGN section 19's figures for
-tp_depth_icp_step at 12 bytes per pixel, as context only."""
+tp_depth_icp_step at 12 bytes per pixel, as context only.
+
+    python tools/photo_align_bench.py --exposure [--out profiles/photo_exposure/exposure.json]
+
+times K37 instead (tp_photo_exposure) on the same workload, the photograph under gain (0.75, 0.80, 0.70) and bias
+(0.05, 0.10, 0.08): ops.photo_exposure (fit and apply in place: three launches) against `photo_align.exposure_torch`, whose counts,
+statuses and flags must be equal first, and the full ops.photo_align call with and without exposure=True in the same run, with their
+ratio.  Its algorithmic bytes per pose are 8 x H x W (the rendered depth, read by the fit and by the apply) and 48 per covered
+pixel (the fit reads rendered colour and photograph, the apply reads and writes the rendered colour): most of a frame is background,
+which neither pass reads beyond its depth."""
 import argparse
 import json
 import os
@@ -30,9 +39,47 @@ HBM_PEAK = 8.0e12
 DEPTH_ICP_CONTEXT = {"tp_depth_icp_step_us": {"8": 36.0, "64": 109.1}, "bytes_per_pixel": 12, "source": "DESIGN section 19"}
 
 
+def exposure_row(a, B, H, W, tau, iters, r, image, raster, loop, truth):
+    """One batch size of --exposure: ``r`` the rendering at the start poses, ``image`` the unchanged photographs, ``loop(image, **kw)``
+    the full ops.photo_align call."""
+    import torch
+    from texpose_amd import ops, photo_align
+    dev = image.device
+    gain, bias = torch.tensor([0.75, 0.80, 0.70], device=dev), torch.tensor([0.05, 0.10, 0.08], device=dev)
+    changed = (image * gain + bias).contiguous()
+    ws = ops.photo_exposure_workspace(B, H, W, dev)
+    out = {k: torch.empty((B, 3) if k in ("gain", "bias") else (B,), device=dev, dtype=torch.float32 if k in ("gain", "bias", "rms") else torch.int32)
+           for k in ops.PHOTO_EXPOSURE_KEYS}
+    lit = r["rgb"].clone()                                       # (rewritten by every timed call: the time does not depend on the values)
+    kernel = lambda: ops.photo_exposure(r["zbuf"], lit, changed, tau=2.0, inplace=True, workspace=ws, out=out)
+    plain = lambda: photo_align.exposure_torch(r["zbuf"], r["rgb"], changed, 2.0)
+    got, want = ops.photo_exposure(r["zbuf"], r["rgb"], changed, tau=2.0), plain()
+    if not all(torch.equal(got[k], want[k]) for k in ("count", "status", "flags")):
+        raise SystemExit("photo_align_bench: the two routes disagree at B = %d; nothing was timed" % B)
+    with_fit, without = loop(changed, exposure=True), loop(changed)
+    err = lambda res: float((res["pose"][:, :, 3] - truth[:, :, 3]).norm(dim=1).mean())
+    few = max(3, a.iters // 10)
+    med, times = KB.race({"tp_photo_exposure": kernel, "exposure_torch": plain, "photo_align": lambda: loop(changed),
+                          "photo_align_exposure": lambda: loop(changed, exposure=True), "mesh_raster_rgb": raster},
+                         {"tp_photo_exposure": a.iters, "exposure_torch": few, "photo_align": few, "photo_align_exposure": few, "mesh_raster_rgb": a.iters},
+                         a.warmup, a.repeats)
+    covered = float((r["zbuf"] > 0).float().mean())
+    nbytes = int((8 + 48 * covered) * H * W * B)
+    us = med["tp_photo_exposure"]
+    return dict(B=B, H=H, W=W, tau=tau, iters=iters, us=med, us_all_repeats=times, torch_over_tp_photo_exposure=med["exposure_torch"] / us,
+                algorithmic_bytes=nbytes, bytes_per_second=nbytes / (us * 1e-6), hbm_fraction_of_8TBps=nbytes / (us * 1e-6) / HBM_PEAK,
+                exposure_loop_over_plain_loop=med["photo_align_exposure"] / med["photo_align"],
+                exposure_share_of_its_loop=(iters + 1) * us / med["photo_align_exposure"], counts_equal=True, covered_fraction=covered,
+                count_mean=float(want["count"].float().mean()), gain_max_abs_gap=float((got["gain"] - want["gain"]).abs().max()),
+                gain_recovered_mean=[float(v) for v in with_fit["gain"].mean(0)], translation_error_mm_mean=dict(start=5.0, plain_loop=err(without),
+                                                                                                               exposure_loop=err(with_fit)),
+                final_status_ok=int((with_fit["status"] == 0).sum()))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     KB.add_timing_args(ap, iters=50, warmup=5, repeats=3)
+    ap.add_argument("--exposure", action="store_true", help="time tp_photo_exposure (K37) and the loop with and without exposure=True")
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import ops, photo_align
@@ -64,6 +111,11 @@ def main(argv=None):
         image = torch.where((shot["zbuf"] > 0)[..., None], shot["rgb"], torch.full_like(shot["rgb"], 0.5)).contiguous()
         r = raster()
         ws = ops.photo_align_workspace(B, H, W, dev)
+        if a.exposure:
+            rows.append(exposure_row(a, B, H, W, tau, iters, r, image, raster, lambda im, **kw: ops.photo_align(
+                verts_d, faces_d, vcolor_d, start, K, im, tau=tau, iters=iters, workspace=ws, **kw), truth))
+            print(json.dumps(rows[-1]), flush=True)
+            continue
         out = dict(pose=torch.empty(B, 3, 4, device=dev), inliers=torch.empty(B, dtype=torch.int32, device=dev), rms=torch.empty(B, device=dev),
                    status=torch.empty(B, dtype=torch.int32, device=dev))
         kernel = lambda: ops.photo_align_step(r["zbuf"], r["rgb"], start, K, image, tau=tau, workspace=ws, out=out)
@@ -86,7 +138,7 @@ def main(argv=None):
                          step_pose_max_abs_gap=pose_gap, rms0_mean=float(fin["rms0"].mean()), rms_final_mean=float(fin["rms"].mean()),
                          final_status_ok=int((fin["status"] == 0).sum())))
         print(json.dumps(rows[-1]), flush=True)
-    res = dict(bench="photo_align", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
+    res = dict(bench="photo_exposure" if a.exposure else "photo_align", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
                shader_clock_ghz_before=clock_before, shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start,
                depth_icp_context=DEPTH_ICP_CONTEXT, rows=rows)
     KB.finish(res, a.out)

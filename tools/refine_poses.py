@@ -5,6 +5,7 @@
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
                                  [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster] [--texels [ID=]PATH]
+                                 [--exposure]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -51,7 +52,11 @@ chunks of 256 faces per 16 x 16 tile.  The planes are the same bit for bit, so t
 
 --texels [ID=]PATH (with --rgb): the mesh's face-texel texture, the .texels.npz that bake_texture.py --texel-res
 writes beside its PLY (keyed like --ply).  The photometric renders then take their colour from the texels (K35) instead of the vertex
-colours, --ply may be colourless, and the file is refused if it was baked for other faces than the mesh's."""
+colours, --ply may be colourless, and the file is refused if it was baked for other faces than the mesh's.
+
+--exposure (with --rgb, alone or under --joint): the photographs were taken under another exposure, white balance or
+light than the mesh's colours.  Every pass first fits a gain and a bias per image and channel between rendering and photograph
+(ops.photo_exposure, K37) and compares the colours under them."""
 import argparse
 import csv
 import json
@@ -116,6 +121,7 @@ def main(argv=None):
     ap.add_argument("--weights", type=float, nargs=3, default=None, metavar=("SIL", "RGB", "DEPTH"))
     ap.add_argument("--cull-raster", action="store_true", help="render with the culled rasteriser: the same poses, faster on large meshes")
     ap.add_argument("--texels", action="append", default=[], metavar="[ID=]PATH", help="with --rgb: face texels (bake_texture --texel-res)")
+    ap.add_argument("--exposure", action="store_true", help="with --rgb: fit a gain and a bias per image and channel in every pass")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -142,6 +148,8 @@ def main(argv=None):
         sys.exit("refine_poses: --occluders and --known exclude each other")
     if a.texels and not a.rgb:
         sys.exit("refine_poses: --texels goes with --rgb")
+    if a.exposure and not a.rgb:
+        sys.exit("refine_poses: --exposure goes with --rgb")
     if (a.occluders or a.known) and not a.silhouette:
         sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
@@ -233,13 +241,13 @@ def main(argv=None):
             if a.joint and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=vcolor, texels=texels,
                                              weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
-                                             damping=a.damping, cull=a.cull_raster)
+                                             damping=a.damping, cull=a.cull_raster, exposure=a.exposure)
             if a.silhouette and not a.joint and (outline is None or (outline.H, outline.W) != (H, W)):
                 outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping, cull=a.cull_raster)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
                     refiner = photo_align.PhotoRefiner(verts, faces, vcolor, H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
-                                                       damping=a.damping, cull=a.cull_raster, texels=texels)
+                                                       damping=a.damping, cull=a.cull_raster, texels=texels, exposure=a.exposure)
                 else:
                     refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping, cull=a.cull_raster)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
