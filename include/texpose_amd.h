@@ -1658,6 +1658,46 @@ typedef struct tp_photo_exposure_args {
 size_t tp_photo_exposure_workspace_bytes(int B, int H, int W);  /* 256 * B * ceil(H * W / 1024), rounded up to 16; 0 for non-positive sizes */
 int tp_photo_exposure(const tp_photo_exposure_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K38  one level down an image pyramid, for the photograph, the rendering and the mask of the photometric alignment
+ *      (texpose_amd/ops/refine.py: image_down, surface_down, mask_down; restated in tests/photo_pyramid_ref.py; the project's own step,
+ *      no reference code).  A plane of H x W becomes one of h x w = (H / 2) x (W / 2), rounded down: an odd last
+ *      row or column is only ever a tap.  Coarse pixel (I, J) has its centre at fine coordinate 2 (J + 1/2, I + 1/2), so level l's
+ *      intrinsics are K with rows 0 and 1 times 2^-l, and K30's + .5 pixel-centre convention holds at every level.
+ *      The filter is separable and even: the taps of coarse row I are the fine rows clamp(2 I - 1 + a, 0, H - 1), a = 0 .. 3, those
+ *      of coarse column J the fine columns clamp(2 J - 1 + b, 0, W - 1), b = 0 .. 3, with the weights w = (1, 3, 3, 1) / 8.  In fp64
+ *      from the fp32 inputs, evaluated as written (no contraction), x_ab the tap of row a and column b:
+ *        s_a = ((w_0 x_a0 + w_1 x_a1) + w_2 x_a2) + w_3 x_a3        for a = 0 .. 3
+ *        y   = ((w_0 s_0 + w_1 s_1) + w_2 s_2) + w_3 s_3            rounded to fp32 once
+ *      per channel.  The outputs are a function of the inputs alone: bit-identical from run to run and under graph replay.
+ *      tp_image_down:   image [N,H,W,3] -> [N,h,w,3], y of every channel; non-finite taps propagate as IEEE arithmetic gives
+ *                       (K30 drops such pixels).
+ *      tp_surface_down: zbuf [N,H,W], rgb [N,H,W,3] (K19's planes) -> [N,h,w], [N,h,w,3].  A tap is a surface iff z > 0 and finite
+ *                       (K30's test); a coarse pixel is a surface iff ALL 16 taps are.  There zbuf_out = y of z and rgb_out = y of
+ *                       each channel; everywhere else zbuf_out = -1 and rgb_out = 0 (K19's background), and rgb is not read.  The rim
+ *                       is eroded by the filter's footprint: exactly the coarse pixels whose photographed value mixes in background.
+ *                       With the photograph equal to the rendering composited over any background, a surface pixel of every level
+ *                       holds the same value on both sides bit for bit: the same 16 values through the same arithmetic.
+ *      tp_mask_down:    mask [N,H,W] uint8 -> [N,h,w]: 1 iff all 16 taps are non-zero, else 0.
+ *      One launch each on the stream; no atomics, no allocation, no workspace, no host synchronisation; safe to capture.  No index is
+ *      read from memory and every tap is clamped.  N outside 1 .. 65535, H < 2, W < 2, H * W >= 2^31, null pointers and an output
+ *      overlapping an input (or the other output) are refused (-1, tp_last_error) before anything is launched.
+ *      Left out: other filters or factors than 2, a rasteriser at the reduced size (the rasteriser point-samples
+ *      the texture while the photograph is filtered, and the loop loses images it otherwise solves).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_pyramid_down_args {
+  const float* zbuf;     /* [N,H,W] tp_surface_down: K19's depth, <= 0 / NaN / Inf: no surface; NULL for the other two */
+  const float* rgb;      /* [N,H,W,3] tp_surface_down: K19's colours; tp_image_down: the photograph, channels last; NULL for tp_mask_down */
+  const uint8_t* mask;   /* [N,H,W] tp_mask_down; NULL for the other two */
+  int N, H, W;
+  float* zbuf_out;       /* [N,H/2,W/2] out, tp_surface_down */
+  float* rgb_out;        /* [N,H/2,W/2,3] out, tp_surface_down and tp_image_down */
+  uint8_t* mask_out;     /* [N,H/2,W/2] out, tp_mask_down */
+} tp_pyramid_down_args;
+int tp_image_down(const tp_pyramid_down_args* args, tp_stream_t stream);    /* reads rgb, writes rgb_out */
+int tp_surface_down(const tp_pyramid_down_args* args, tp_stream_t stream);  /* reads zbuf and rgb, writes zbuf_out and rgb_out */
+int tp_mask_down(const tp_pyramid_down_args* args, tp_stream_t stream);     /* reads mask, writes mask_out */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """K29-K33: the render-and-compare pose refiners -- the depth ICP, the photometric alignment, the masks' distance field, the silhouette
 alignment and the joint step of the three -- behind one table of terms: what a term's step takes, asks of the rasteriser and returns
 is said once in ``_TERMS``; one builder fills any term's args struct, one helper sizes every workspace and one driver runs all four
-loops.  K37, the exposure fit that a loop with a photometric term may run in front of each step (photo_exposure), is here too."""
+loops.  K37, the exposure fit that a loop with a photometric term may run in front of each step (photo_exposure), and K38, the image
+pyramid of the photometric loop (image_down, surface_down, mask_down), are here too."""
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -11,7 +12,8 @@ from .. import _lib
 from ._base import Tensor, _call, _f32, _intr_per_view, _lengths, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg
 
 __all__ = ["depth_icp_workspace", "depth_icp_step", "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS",
-           "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "mask_sdf_workspace", "mask_sdf",
+           "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "image_down", "surface_down", "mask_down",
+           "image_pyramid", "mask_pyramid", "mask_sdf_workspace", "mask_sdf",
            "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align",
            "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align"]
 
@@ -139,7 +141,7 @@ def _schedules(op: str, given, iters: int) -> list:
 
 
 def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, given, taus, *, damping, frame, workspace, cull,
-            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0) -> Dict[str, Tensor]:
+            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0, pyramid=None) -> Dict[str, Tensor]:
     """The loop of every refiner over the terms of ``given`` that have planes: one pass per entry of ``taus`` (_schedules) of ONE
     mesh_raster call at the current poses, asked only for what these terms need, and one step from it, the last evaluate-only; a step
     that fails passes its pose on.  Without ``weights`` the step is the single term's own (its 'rms' is the cost carried); with them it
@@ -149,7 +151,10 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     term: every pass first fits the photograph's per-channel gain and bias to the rendering and rewrites the rendered colours under
     them (photo_exposure in place, K37; the term's frame map and mask; the fit of the pass before decides with that pass's ``tau``
     what is kept, the first pass keeps within ``exposure_tau0`` of the plain colours) -> also 'gain' / 'bias' [B,3] and
-    'exposure_status' [B] of the last pass (prefixed with the term's 'photo_' in the joint results)."""
+    'exposure_status' [B] of the last pass (prefixed with the term's 'photo_' in the joint results).  ``pyramid`` (the photometric
+    term alone): steps per level, the coarsest first, adding up to the steps of ``taus``; the photograph's and the mask's pyramids are
+    built once, a pass at level l filters the full-size rendering down l times (surface_down, K38) and steps on the level's planes
+    with the level's intrinsics; the last pass, the evaluation, runs at level 0."""
     joint = weights is not None
     cost = "chi2" if joint else "rms"
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
@@ -192,20 +197,36 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
               [k for k in term.rendered if k not in mesh]) for i, term in terms]
     step = _STEPS[terms[0][1].name]
     hidden = []
+    levels, coarse = [0] * len(taus), {}
+    if pyramid is not None:
+        if joint or [t for _, t in terms] != [_PHOTO]:
+            raise ValueError("%s: pyramid= goes with the photometric term alone" % op)
+        levels = _pass_levels(op, pyramid, len(taus) - 1)
+        photos = image_pyramid(planes[_PHOTO.plane], max(levels) + 1)
+        known = [None] * len(photos) if masks[_PHOTO.name] is None else mask_pyramid(masks[_PHOTO.name], len(photos))
+        for l in range(1, len(photos)):                          # (level l's intrinsics: rows 0 and 1 times 2^-l, exact)
+            scaled = intr.clone()
+            scaled[:, :2] *= 0.5 ** l
+            coarse[l] = (photos[l], known[l], scaled)
     lit = next((i for i, t in terms if t is _PHOTO), None) if exposure else None      # the photometric threshold's place in a pass's ``th``
     fit = {}                                                     # the exposure fit of the pass before
 
-    def one_pass(pose, th, last):                                # (a function: the rendered planes are released before the next pass renders)
+    def one_pass(pose, th, last, level):                         # (a function: the rendered planes are released before the next pass renders)
         r = mesh_raster(verts, faces, pose, intr, **ask)
+        photo, photo_mask, K = coarse[level] if level else (planes.get(_PHOTO.plane), masks.get(_PHOTO.name), intr)
+        for _ in range(level):                                   # (the full-size rendering filtered as the photograph was, never a coarse raster)
+            r = surface_down(r["zbuf"], r["rgb"])
         if lit is not None:                                      # (in front of the step: it compares the colours under the photograph's exposure)
-            e = photo_exposure(r["zbuf"], r["rgb"], planes[_PHOTO.plane], tau=th[lit] if fit else exposure_tau0, gain=fit.get("gain"),
-                               bias=fit.get("bias"), frame=frame, mask=masks[_PHOTO.name], inplace=True, workspace=workspace)
+            e = photo_exposure(r["zbuf"], r["rgb"], photo, tau=th[lit] if fit else exposure_tau0, gain=fit.get("gain"),
+                               bias=fit.get("bias"), frame=frame, mask=photo_mask, inplace=True, workspace=workspace)
             fit.update(gain=e["gain"], bias=e["bias"], exposure_status=e["status"])
         own = {term.name: dict(kw, **{k: r[k] for k in rendered}, **{term.threshold: th[i]}) for i, term, kw, rendered in fixed}
         if joint:
             got = joint_align_step(pose, intr, weights=weights, damping=damping, evaluate_only=last, workspace=workspace, **own)
         else:
-            got = step(pose=pose, intr=intr, damping=damping, evaluate_only=last, workspace=workspace, **own[terms[0][1].name])
+            if level:
+                own[_PHOTO.name].update({_PHOTO.plane: photo, "mask": photo_mask})
+            got = step(pose=pose, intr=K, damping=damping, evaluate_only=last, workspace=workspace, **own[terms[0][1].name])
         if visible_iou and (not hidden or last):                 # (the first and the last rendering)
             z = r["zbuf"]
             hidden.append(((z > 0) & torch.isfinite(z) & unknown).flatten(1).sum(1))
@@ -214,7 +235,7 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     first = status = None
     for it, th in enumerate(taus):
         last = it == len(taus) - 1
-        got = one_pass(pose, th, last)
+        got = one_pass(pose, th, last, levels[it])
         first = got if first is None else first
         status = got["status"] if not last or status is None else status
         pose = got["pose"]
@@ -307,7 +328,7 @@ PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
                 damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
                 workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False,
-                exposure_tau0: float = 2.0) -> Dict[str, Tensor]:
+                exposure_tau0: float = 2.0, pyramid=None) -> Dict[str, Tensor]:
     """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
     ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
@@ -319,12 +340,22 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     balance or light than the colours: every pass first fits a gain and a bias per image and channel and renders under them
     (photo_exposure, K37: three launches more per pass), the first pass over the pixels within ``exposure_tau0`` of the
     plain colours (2.0 keeps every pixel of colours in [0, 1]), each later one within that pass's ``tau`` of the fit before -> also 'gain'
-    / 'bias' [B,3] and 'exposure_status' [B] int32 of the last pass.  Without it nothing else runs and the keys are those above."""
+    / 'bias' [B,3] and 'exposure_status' [B] int32 of the last pass.  Without it nothing else runs and the keys are those above.
+    ``pyramid``: coarse to fine (K38), a tuple of step counts per level, the coarsest first, whose sum must be ``iters``:
+    (4, 3, 3) takes 4 steps at level 2 (a quarter of the size), 3 at level 1 and 3 at level 0.  The photograph's and the mask's
+    pyramids are built once per call (image_pyramid, mask_pyramid); every pass still renders at full size, so ``vcolor``, ``texels``
+    and ``cull`` work unchanged, filters the rendering down to its level (surface_down) and runs the same step on the level's planes
+    with K's rows 0 and 1 times 2^-level; ``exposure`` fits on the level's planes.  ``tau`` keeps its ``iters`` + 1 entries, the final
+    evaluation runs at level 0, and 'inliers0' / 'rms0' are the FIRST pass's, counted at its own level.  It widens the basin where the
+    texture is fine against the start error (on the pinned cases it recovers starts the plain loop loses, and about doubles what the
+    loop tolerates); a level needs enough covered pixels (the pinned cases have 43 - 142 at the coarsest level; 21 - 24 diverge).  None: nothing else runs, bit for bit the call without it."""
     op, given = "photo_align", [(_PHOTO, image, tau, mask)]
     if (vcolor is None) == (texels is None):
         raise ValueError("%s: exactly one of vcolor [V,3] and texels= [F,T,3] expected" % op)
+    if pyramid is not None:
+        _pass_levels(op, pyramid, int(iters))                    # (a host argument: refused before anything touches the device)
     return _refine(op, PHOTO_ALIGN_KEYS, verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
-                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, exposure=exposure, exposure_tau0=exposure_tau0)
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, exposure=exposure, exposure_tau0=exposure_tau0, pyramid=pyramid)
 
 
 # ------------------------------------------------------------------------------------------ K37
@@ -389,6 +420,103 @@ def photo_exposure(zbuf: Tensor, rgb: Tensor, image: Tensor, *, tau: float, gain
     a.workspace = workspace.data_ptr()
     _call("tp_photo_exposure", a)         # (tau, gain_range, min_var out of range, outputs overlapping inputs: the library's error)
     return res
+
+
+# ------------------------------------------------------------------------------------------ K38
+def _down_args(op: str, planes: dict, out: Optional[Dict[str, Tensor]]):
+    """The arguments of one level down for ``planes`` = {name of the args' field: a contiguous GPU tensor [N,H,W] + trailing, taken as
+    it is}: every plane's output [N,H//2,W//2] + trailing goes to the field '<name>_out' -> (the filled struct, {name: output})."""
+    first = next(iter(planes.values()))
+    N, H, W = first.shape[:3]
+    if first.numel() == 0:
+        raise ValueError("%s: empty planes %s" % (op, tuple(first.shape)))
+    res = _outputs(op, out, {k: (t.dtype, (N, H // 2, W // 2) + tuple(t.shape[3:])) for k, t in planes.items()}, first.device, partial=True)
+    a = _lib.PyramidDownArgs()
+    a.N, a.H, a.W = N, H, W
+    for k, t in planes.items():
+        setattr(a, k, t.data_ptr())
+        setattr(a, k + "_out", res[k].data_ptr())
+    return a, res                         # (H < 2, W < 2, N > 65535, an output overlapping an input: the library's error)
+
+
+@_on_tensor_device
+def image_down(image: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """One level down the photograph's pyramid (tp_image_down, K38; the rules are in the header): image [N,H,W,3] float32, channels
+    last, taken as it is -> [N,H//2,W//2,3]: the (1, 3, 3, 1) / 8 filter in rows and columns on clamped taps, fp64 in one stated order,
+    rounded once; non-finite taps propagate.  Level l's intrinsics are K with rows 0 and 1 times 2^-l.  ``out``: the tensor to write
+    into.  One launch, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "image_down"
+    image = _want_gpu(op, image, "image", torch.float32, None)
+    if image.dim() != 4 or image.shape[3] != 3:
+        raise ValueError("%s: image [N,H,W,3] (channels last) expected, got %s" % (op, tuple(image.shape)))
+    a, res = _down_args(op, {"rgb": image}, None if out is None else {"rgb": out})
+    _call("tp_image_down", a)
+    return res["rgb"]
+
+
+@_on_tensor_device
+def surface_down(zbuf: Tensor, rgb: Tensor, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """One level down a rendering (tp_surface_down, K38): zbuf [B,H,W] / rgb [B,H,W,3] (mesh_raster's planes, or this function's;
+    taken as they are) -> 'zbuf' [B,H//2,W//2] and 'rgb' [B,H//2,W//2,3]: a coarse pixel whose 16 taps all have z > 0 and finite holds
+    the filtered depth and colours (image_down's arithmetic), every other one mesh_raster's background (-1 and 0).  Where the photograph
+    is the rendering over any background, the two sides of such a pixel are equal bit for bit at every level.  ``out``: either tensor
+    to write into.  One launch, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "surface_down"
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3:
+        raise ValueError("%s: zbuf [B,H,W] expected, got %s" % (op, tuple(zbuf.shape)))
+    rgb = _want_gpu(op, rgb, "rgb", torch.float32, tuple(zbuf.shape) + (3,))
+    a, res = _down_args(op, {"zbuf": zbuf, "rgb": rgb}, out)
+    _call("tp_surface_down", a)
+    return res
+
+
+@_on_tensor_device
+def mask_down(mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """One level down a mask (tp_mask_down, K38): mask [N,H,W] uint8 or bool -> [N,H//2,W//2] uint8, 1 where all 16 taps are non-zero,
+    else 0: a pixel is used at a level only if nothing it mixes in was masked out.  ``out``: the tensor to write into.  One launch."""
+    op = "mask_down"
+    if torch.is_tensor(mask) and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    mask = _want_gpu(op, mask, "mask", torch.uint8, None)
+    if mask.dim() != 3:
+        raise ValueError("%s: mask [N,H,W] expected, got %s" % (op, tuple(mask.shape)))
+    a, res = _down_args(op, {"mask": mask}, None if out is None else {"mask": out})
+    _call("tp_mask_down", a)
+    return res["mask"]
+
+
+def _pyramid(op: str, down, plane: Tensor, levels: int) -> list:
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError("%s: levels >= 1 expected, got %d" % (op, levels))
+    out = [plane]
+    for _ in range(levels - 1):
+        out.append(down(out[-1]))
+    return out
+
+
+def image_pyramid(image: Tensor, levels: int) -> list:
+    """[image, image_down(image), ...]: ``levels`` entries, the finest first; entry l is the photograph at level l (K38)."""
+    return _pyramid("image_pyramid", image_down, image, levels)
+
+
+def mask_pyramid(mask: Tensor, levels: int) -> list:
+    """[mask, mask_down(mask), ...]: ``levels`` entries, the finest first (K38)."""
+    return _pyramid("mask_pyramid", mask_down, mask, levels)
+
+
+def _pass_levels(op: str, pyramid, iters: int) -> list:
+    """``pyramid`` = steps per level, the coarsest first -> the level of every pass, the final evaluation's (0) included."""
+    try:
+        steps = [int(n) for n in pyramid]
+    except (TypeError, ValueError):
+        raise ValueError("%s: pyramid must be a tuple of step counts per level, the coarsest first, got %r" % (op, pyramid)) from None
+    if not steps or min(steps) < 0 or any(n != p for n, p in zip(steps, pyramid)):
+        raise ValueError("%s: pyramid must be a tuple of step counts (integers >= 0) per level, the coarsest first, got %r" % (op, pyramid))
+    if sum(steps) != iters:
+        raise ValueError("%s: the steps of pyramid %r must add up to iters = %d, got %d" % (op, tuple(pyramid), iters, sum(steps)))
+    return [len(steps) - 1 - k for k, n in enumerate(steps) for _ in range(n)] + [0]
 
 
 # ------------------------------------------------------------------------------------------ K31

@@ -102,6 +102,39 @@ def exposure_torch(zbuf: Tensor, rgb: Tensor, image: Tensor, tau: float, gain: O
     return out
 
 
+def pyramid_torch(*, image: Optional[Tensor] = None, zbuf: Optional[Tensor] = None, rgb: Optional[Tensor] = None,
+                  mask: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """ops.image_down / surface_down / mask_down's rules (include/texpose_amd.h, K38) in plain torch ops in fp64 on the tensors' device,
+    one level down for whichever planes are given: ``image`` [N,H,W,3] -> 'image' [N,H//2,W//2,3]; ``zbuf`` [B,H,W] with ``rgb``
+    [B,H,W,3] -> 'zbuf', 'rgb'; ``mask`` [N,H,W] -> 'mask' uint8.  The sums run in the header's order, every product is a torch op of
+    its own and the weights are dyadic, so the float planes are the kernels' bit for bit (NaN payloads apart)."""
+    f64 = torch.float64
+
+    def taps(n, dev):                                                                       # [n // 2, 4], clamped
+        return (2 * torch.arange(n // 2, device=dev)[:, None] - 1 + torch.arange(4, device=dev)[None, :]).clamp(0, n - 1)
+
+    def gather(x):                                                                          # [N,H,W,C] -> [N,h,4 rows,w,4 columns,C]
+        return x[:, taps(x.shape[1], x.device)][:, :, :, taps(x.shape[2], x.device)]
+
+    def filtered(x):                                                                        # [N,H,W,C] float32 -> [N,h,w,C] float32
+        t = gather(x.float().to(f64))
+        w0, w1 = 0.125, 0.375
+        s = ((w0 * t[:, :, :, :, 0] + w1 * t[:, :, :, :, 1]) + w1 * t[:, :, :, :, 2]) + w0 * t[:, :, :, :, 3]
+        return (((w0 * s[:, :, 0] + w1 * s[:, :, 1]) + w1 * s[:, :, 2]) + w0 * s[:, :, 3]).float()
+
+    out = {}
+    if image is not None:
+        out["image"] = filtered(image)
+    if zbuf is not None:
+        z = zbuf.float()
+        surface = gather(((z > 0) & torch.isfinite(z))[..., None]).all(4).all(2)           # [N,h,w,1]
+        out["zbuf"] = torch.where(surface[..., 0], filtered(z[..., None])[..., 0], torch.full((), -1.0, device=z.device))
+        out["rgb"] = torch.where(surface, filtered(rgb), torch.zeros((), device=z.device))
+    if mask is not None:
+        out["mask"] = gather((mask != 0)[..., None]).all(4).all(2)[..., 0].to(torch.uint8)
+    return out
+
+
 class PhotoRefiner(_MeshRefiner):
     """Photometric alignment for batches of poses of one vertex-coloured mesh at H x W with the mesh on the device and a workspace per
     batch size.
@@ -111,17 +144,23 @@ class PhotoRefiner(_MeshRefiner):
     within tau of the photograph), rms [B] (colour units), status [B] (0 ok, 1 fewer than 6 kept pixels, 3 the last step's system was
     not positive definite: the pose went through unchanged) and inliers0 / rms0 of the start pose.  ``exposure``: every pass first fits
     the photograph's gain and bias per image and channel (ops.photo_exposure, K37) and ``refine`` also returns gain / bias [B,3] and
-    exposure_status [B]; for photographs whose exposure, white balance or light differ from the colours'."""
+    exposure_status [B]; for photographs whose exposure, white balance or light differ from the colours'.  ``pyramid``: coarse to
+    fine (ops.photo_align's ``pyramid``, K38): step counts per level, the coarsest first, adding up to ``iters``; inliers0 / rms0 are
+    then the first pass's, at its own level."""
     _new_workspace = staticmethod(ops.photo_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, vcolor: Optional[Tensor], H: int, W: int, device="cuda:0", *, tau=0.5, iters: int = 10,
-                 damping: float = 1e-6, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0):
+                 damping: float = 1e-6, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0,
+                 pyramid=None):
+        if pyramid is not None:                                  # (a host argument: refused before anything touches the device)
+            ops.refine._pass_levels("PhotoRefiner", pyramid, int(iters))
         super().__init__(verts, faces, H, W, device, cull=cull)
         if (vcolor is None) == (texels is None):
             raise ValueError("PhotoRefiner: exactly one of vcolor [V,3] and texels= [F,T,3] (face texels, K35) expected")
         self._colours(vcolor, texels)
         self.tau, self.iters, self.damping = tau, int(iters), float(damping)
         self.exposure, self.exposure_tau0 = bool(exposure), float(exposure_tau0)
+        self.pyramid = None if pyramid is None else tuple(pyramid)
 
     def refine(self, pose: Tensor, intr: Tensor, image: Tensor, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> AttrDict:
         """pose [B,3,4], intr [B,3,3] or [3,3], image [Ft,H,W,3] (channels last, the vertex colours' units), frame [B] int32 (the
@@ -131,4 +170,4 @@ class PhotoRefiner(_MeshRefiner):
             raise ValueError("PhotoRefiner.refine: photographs of %d x %d x 3 expected, got %s" % (self.H, self.W, tuple(image.shape)))
         return AttrDict(ops.photo_align(self.verts, self.faces, self.vcolor, pose, intr, image, tau=self.tau, iters=self.iters,
                                         damping=self.damping, frame=frame, mask=mask, workspace=self._workspace(pose.shape[0]), cull=self.cull,
-                                        texels=self.texels, exposure=self.exposure, exposure_tau0=self.exposure_tau0))
+                                        texels=self.texels, exposure=self.exposure, exposure_tau0=self.exposure_tau0, pyramid=self.pyramid))

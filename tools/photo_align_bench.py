@@ -22,7 +22,17 @@ times K37 instead (tp_photo_exposure) on the same workload, t
 statuses and flags must be equal first, and the full ops.photo_align call with and without exposure=True in the same run, with their
 ratio.  Its algorithmic bytes per pose are 8 x H x W (the rendered depth, read by the fit and by the apply) and 48 per covered
 pixel (the fit reads rendered colour and photograph, the apply reads and writes the rendered colour): most of a frame is background,
-which neither pass reads beyond its depth."""
+which neither pass reads beyond its depth.
+
+    python tools/photo_align_bench.py --pyramid [--out profiles/photo_pyramid/pyramid.json]
+
+times K38 (tp_surface_down, tp_image_down, tp_mask_down) on the same workload: the down calls of one coarse pass
+(the rendering from level 0 to 1 and from 1 to 2) and of the once-per-call pyramids (photograph and mask, level 0 to 1) against
+`photo_align.pyramid_torch`, whose planes must be equal bit for bit first, and the full ops.photo_align call with and without
+pyramid=(4, 3, 3) in the same run, with their ratio.  Algorithmic bytes per fine pixel of a level: 20 for a rendering (depth 4 and
+colour 12 read, 4 written: a quarter as many pixels of 16 bytes), 15 for a photograph (12 read, 3 written), 1.25 for a mask; each level
+has a quarter of the pixels of the one below.  The rendering's call reads the colours only where a coarse pixel is a surface, so what
+it moves on this workload is reported too: 8 bytes per fine pixel (depth read, background written) and 12 more where it is covered."""
 import argparse
 import json
 import os
@@ -76,11 +86,57 @@ def exposure_row(a, B, H, W, tau, iters, r, image, raster, loop, truth):
                 final_status_ok=int((with_fit["status"] == 0).sum()))
 
 
+def pyramid_row(a, B, H, W, tau, iters, r, image, raster, loop, truth):
+    """One batch size of --pyramid: ``r`` the rendering at the start poses, ``image`` the photographs, ``loop(image, **kw)`` the full
+    ops.photo_align call."""
+    import torch
+    from texpose_amd import ops, photo_align
+    dev = image.device
+    mask = torch.ones(B, H, W, dtype=torch.uint8, device=dev)
+    lvl1 = ops.surface_down(r["zbuf"], r["rgb"])
+    empty = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+    out1, out2 = dict(zbuf=empty(B, H // 2, W // 2), rgb=empty(B, H // 2, W // 2, 3)), dict(zbuf=empty(B, H // 4, W // 4), rgb=empty(B, H // 4, W // 4, 3))
+    out_i, out_m = empty(B, H // 2, W // 2, 3), empty(B, H // 2, W // 2, dtype=torch.uint8)
+    calls = {"tp_surface_down_0_to_1": lambda: ops.surface_down(r["zbuf"], r["rgb"], out=out1),
+             "tp_surface_down_1_to_2": lambda: ops.surface_down(lvl1["zbuf"], lvl1["rgb"], out=out2),
+             "tp_image_down_0_to_1": lambda: ops.image_down(image, out=out_i), "tp_mask_down_0_to_1": lambda: ops.mask_down(mask, out=out_m),
+             "torch_surface_down_0_to_1": lambda: photo_align.pyramid_torch(zbuf=r["zbuf"], rgb=r["rgb"]),
+             "torch_image_down_0_to_1": lambda: photo_align.pyramid_torch(image=image),
+             "photo_align": lambda: loop(image), "photo_align_pyramid": lambda: loop(image, pyramid=(4, 3, 3)), "mesh_raster_rgb": raster}
+    got, want = calls["tp_surface_down_0_to_1"](), calls["torch_surface_down_0_to_1"]()
+    if not (torch.equal(got["zbuf"], want["zbuf"]) and torch.equal(got["rgb"], want["rgb"]) and torch.equal(calls["tp_image_down_0_to_1"](),
+                                                                                                         calls["torch_image_down_0_to_1"]()["image"])):
+        raise SystemExit("photo_align_bench: the two routes disagree at B = %d; nothing was timed" % B)
+    with_pyramid, without = loop(image, pyramid=(4, 3, 3)), loop(image)
+    err = lambda res: float((res["pose"][:, :, 3] - truth[:, :, 3]).norm(dim=1).mean())
+    few = max(3, a.iters // 10)
+    med, times = KB.race(calls, {k: few if k.startswith(("torch", "photo_align")) else a.iters for k in calls}, a.warmup, a.repeats)
+    covered, coarse = float((r["zbuf"] > 0).float().mean()), float((got["zbuf"] > 0).float().mean())
+    pixels = H * W * B
+    full = {"tp_surface_down_0_to_1": 20 * pixels, "tp_surface_down_1_to_2": 20 * pixels // 4, "tp_image_down_0_to_1": 15 * pixels,
+            "tp_mask_down_0_to_1": 5 * pixels // 4}
+    moved = int((8 + 12 * covered) * pixels)
+    rate = {k: v / (med[k] * 1e-6) for k, v in full.items()}
+    pass_us = med["tp_surface_down_0_to_1"] + med["tp_surface_down_1_to_2"]
+    return dict(B=B, H=H, W=W, tau=tau, iters=iters, pyramid=[4, 3, 3], us=med, us_all_repeats=times, planes_equal=True,
+                torch_over_tp_surface_down=med["torch_surface_down_0_to_1"] / med["tp_surface_down_0_to_1"],
+                torch_over_tp_image_down=med["torch_image_down_0_to_1"] / med["tp_image_down_0_to_1"], algorithmic_bytes=full,
+                bytes_per_second=rate, hbm_fraction_of_8TBps={k: v / HBM_PEAK for k, v in rate.items()},
+                surface_down_0_to_1_bytes_moved=moved, surface_down_0_to_1_moved_fraction_of_8TBps=moved / (med["tp_surface_down_0_to_1"] * 1e-6) / HBM_PEAK,
+                level_2_pass_down_us=pass_us, pyramid_loop_over_plain_loop=med["photo_align_pyramid"] / med["photo_align"],
+                raster_share_of_plain_loop=(iters + 1) * med["mesh_raster_rgb"] / med["photo_align"], covered_fraction=covered,
+                covered_fraction_level_1=coarse, translation_error_mm_mean=dict(start=5.0, plain_loop=err(without), pyramid_loop=err(with_pyramid)),
+                final_status_ok=int((with_pyramid["status"] == 0).sum()))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     KB.add_timing_args(ap, iters=50, warmup=5, repeats=3)
     ap.add_argument("--exposure", action="store_true", help="time tp_photo_exposure (K37) and the loop with and without exposure=True")
+    ap.add_argument("--pyramid", action="store_true", help="time the K38 down calls and the loop with and without pyramid=(4, 3, 3)")
     a = ap.parse_args(argv)
+    if a.exposure and a.pyramid:
+        raise SystemExit("photo_align_bench: --exposure or --pyramid, one at a time")
     import torch
     from texpose_amd import ops, photo_align
     if not torch.cuda.is_available():
@@ -111,8 +167,8 @@ def main(argv=None):
         image = torch.where((shot["zbuf"] > 0)[..., None], shot["rgb"], torch.full_like(shot["rgb"], 0.5)).contiguous()
         r = raster()
         ws = ops.photo_align_workspace(B, H, W, dev)
-        if a.exposure:
-            rows.append(exposure_row(a, B, H, W, tau, iters, r, image, raster, lambda im, **kw: ops.photo_align(
+        if a.exposure or a.pyramid:
+            rows.append((exposure_row if a.exposure else pyramid_row)(a, B, H, W, tau, iters, r, image, raster, lambda im, **kw: ops.photo_align(
                 verts_d, faces_d, vcolor_d, start, K, im, tau=tau, iters=iters, workspace=ws, **kw), truth))
             print(json.dumps(rows[-1]), flush=True)
             continue
@@ -138,7 +194,7 @@ def main(argv=None):
                          step_pose_max_abs_gap=pose_gap, rms0_mean=float(fin["rms0"].mean()), rms_final_mean=float(fin["rms"].mean()),
                          final_status_ok=int((fin["status"] == 0).sum())))
         print(json.dumps(rows[-1]), flush=True)
-    res = dict(bench="photo_exposure" if a.exposure else "photo_align", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
+    res = dict(bench="photo_exposure" if a.exposure else "photo_pyramid" if a.pyramid else "photo_align", device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
                shader_clock_ghz_before=clock_before, shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - t_start,
                depth_icp_context=DEPTH_ICP_CONTEXT, rows=rows)
     KB.finish(res, a.out)

@@ -5,7 +5,7 @@
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
                                  [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster] [--texels [ID=]PATH]
-                                 [--exposure]
+                                 [--exposure] [--pyramid N ...]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -56,7 +56,12 @@ colours, --ply may be colourless, and the file is refused if it was baked for ot
 
 --exposure (with --rgb, alone or under --joint): the photographs were taken under another exposure, white balance or
 light than the mesh's colours.  Every pass first fits a gain and a bias per image and channel between rendering and photograph
-(ops.photo_exposure, K37) and compares the colours under them."""
+(ops.photo_exposure, K37) and compares the colours under them.
+
+--pyramid N [N ...] (with --rgb, not under --joint): coarse to fine on an image pyramid, for estimates further off
+than the texture's detail lets the one-pixel gradient see.  The step counts per level, the coarsest first, adding up to --iters-rgb:
+--pyramid 4 3 3 takes 4 steps at a quarter of the size, 3 at half and 3 at full size (ops.photo_align's pyramid=, K38).  The object
+should cover some hundreds of pixels at the coarsest level."""
 import argparse
 import csv
 import json
@@ -122,6 +127,7 @@ def main(argv=None):
     ap.add_argument("--cull-raster", action="store_true", help="render with the culled rasteriser: the same poses, faster on large meshes")
     ap.add_argument("--texels", action="append", default=[], metavar="[ID=]PATH", help="with --rgb: face texels (bake_texture --texel-res)")
     ap.add_argument("--exposure", action="store_true", help="with --rgb: fit a gain and a bias per image and channel in every pass")
+    ap.add_argument("--pyramid", type=int, nargs="+", default=None, metavar="N", help="with --rgb: steps per pyramid level, the coarsest first")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -150,6 +156,10 @@ def main(argv=None):
         sys.exit("refine_poses: --texels goes with --rgb")
     if a.exposure and not a.rgb:
         sys.exit("refine_poses: --exposure goes with --rgb")
+    if a.pyramid and (not a.rgb or a.joint):
+        sys.exit("refine_poses: --pyramid goes with --rgb" + (", and not under --joint" if a.joint else ""))
+    if a.pyramid and (min(a.pyramid) < 0 or sum(a.pyramid) != a.iters_rgb):
+        sys.exit("refine_poses: the steps of --pyramid must be >= 0 and add up to --iters-rgb = %d" % a.iters_rgb)
     if (a.occluders or a.known) and not a.silhouette:
         sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
@@ -247,7 +257,8 @@ def main(argv=None):
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
                     refiner = photo_align.PhotoRefiner(verts, faces, vcolor, H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
-                                                       damping=a.damping, cull=a.cull_raster, texels=texels, exposure=a.exposure)
+                                                       damping=a.damping, cull=a.cull_raster, texels=texels, exposure=a.exposure,
+                                                       pyramid=a.pyramid)
                 else:
                     refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping, cull=a.cull_raster)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
