@@ -1698,6 +1698,81 @@ int tp_image_down(const tp_pyramid_down_args* args, tp_stream_t stream);    /* r
 int tp_surface_down(const tp_pyramid_down_args* args, tp_stream_t stream);  /* reads zbuf and rgb, writes zbuf_out and rgb_out */
 int tp_mask_down(const tp_pyramid_down_args* args, tp_stream_t stream);     /* reads mask, writes mask_out */
 
+/* ------------------------------------------------------------------------------------------
+ * K39  MULTI-VIEW pose refinement: ONE object pose per group of views whose cameras are known (texpose_amd/multiview.py; restated in
+ *      tests/multiview_ref.py; the project's own step, no reference code).
+ *      Views i = 0 .. B-1; cam [B,3,4] C_i = [Rc|tc], world -> camera i, fixed; group [B] int32 in 0 .. Gr-1; model [Gr,3,4] M_g,
+ *      model -> world, the unknowns.  View i is rendered and evaluated at T_i = C_i o M_group[i].
+ *      COMPOSE (tp_pose_compose, a thread per view): T_i = [Rc Rm | Rc tm + tc] in fp64 from the fp32 inputs,
+ *        T[r][c] = (Rc[r][0] M[0][c] + Rc[r][1] M[1][c]) + Rc[r][2] M[2][c]      for c = 0 .. 3, and for c = 3 then + tc[r],
+ *      every dot product left to right as written (no contraction), rounded to fp32 once.  If cam[i] is bit-exactly [I|0] (the words
+ *      of 1.0f on the diagonal, of +0.0f elsewhere) T_i is model[group[i]] bit for bit: a copy, since the arithmetic would turn a -0.0
+ *      into +0.0.  A group id out of range is clamped into 0 .. Gr-1; nothing is read past an array.
+ *      CHANGE OF VARIABLES: K29's step moves a view by x' = exp(w) x + v in the CAMERA frame; perturb M the same way in the WORLD frame
+ *      by d = (w, v).  To first order view i moves by xi_i = A_i d with the 6x6
+ *        A_i = [[Rc, 0], [[tc]x Rc, Rc]]          ([tc]x the cross-product matrix; [tc]x Rc formed with dots as above)
+ *      so with S_i the view's combined sums, H_i its 6x6 matrix and g_i its six J^T r the view contributes
+ *        H'_i = A_i^T H_i A_i,   g'_i = A_i^T g_i,   chi2 and the count unchanged.
+ *      In fp64, A from the fp32 cam: P = H A, then Q = A^T P, each entry a sum over the inner index ascending starting from its first
+ *      product; the upper triangle of Q is taken; g' = A^T g likewise.  A view whose cam is bit-exactly [I|0] is not transformed: its
+ *      sums pass through bit for bit.
+ *      A VIEW'S COMBINED SUMS are K33's, unchanged: every present term is evaluated with evaluate_only = 1 at `pose` (= T, the caller
+ *      composes it), its records gathered in ascending tile order, terms in the order silhouette, photometric, depth, and
+ *      w_a S_a (+ w_b S_b (+ w_c S_c)) formed over the present terms with weight > 0; the count is not weighted.
+ *      A GROUP'S SYSTEM: the member views of group g are member[group_start[g] .. group_start[g+1] - 1] (view indices, ascending inside
+ *      a group); their transformed records are added in that order, the first one assigned; K29's rules (count, pivot rule, damped
+ *      step, fp32 rounding) run unchanged on the sum with the current pose model[g]: fewer than six rows in the whole group: status 1;
+ *      the pivot rule decides between 0 and 3; otherwise the step.  A failed step or evaluate_only returns model[g] bit for bit.  A
+ *      group without members gets status 1, inliers 0, chi2 0, views 0.  views[g]: the member views with a count > 0.
+ *      pose_out (optional) [B,3,4]: the compose rule applied to cam and model_out (model with evaluate_only and no model_out), written
+ *      for every member view.  member and group_start are device arrays: every start, end (start <= end <= B) and member index is
+ *      clamped into range before use.
+ *      With one view per group and every cam exactly [I|0], model_out, status, inliers and chi2 are tp_joint_align_step's on the same
+ *      terms bit for bit, and with one term at weight 1 that term's own step's.
+ *      Launches: each present term's own (as K33), then view_sums (grid B x 64: gather, weight, transform, one 32-double record per
+ *      view into the workspace), group_solve (grid Gr x 64) and, with pose_out, the compose (grid Gr x 64 over the members).  No
+ *      atomics, no allocation, no host synchronisation; bit-identical from run to run.  Safe to capture.
+ *      Refused (-1, tp_last_error) before anything is launched: K33's list (null args; no term, or none with a weight > 0; a bad
+ *      weight or damping; B outside 1 .. 65535; a term whose B differs, or whose H, W or intr differs from another's; two terms
+ *      sharing a workspace; whatever a term's own step refuses) and: Gr outside 1 .. B; null cam, pose, model, member, group_start,
+ *      status, inliers, chi2, views or workspace; a workspace that is not 16-byte aligned; model_out missing without evaluate_only, or
+ *      overlapping model; pose_out overlapping pose or cam; a present term whose pose is not args' pose; the multi-view workspace
+ *      overlapping a term's.  tp_pose_compose refuses null pointers, B outside 1 .. 2^24, Gr < 1 and an out overlapping cam or model.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_pose_compose_args {
+  int B, Gr;
+  const float* cam;          /* [B,3,4] world -> camera */
+  const float* model;        /* [Gr,3,4] model -> world */
+  const int32_t* group;      /* [B] the model of each view; clamped into 0 .. Gr-1 */
+  float* out;                /* [B,3,4] out: cam[i] o model[group[i]] */
+} tp_pose_compose_args;
+int tp_pose_compose(const tp_pose_compose_args* args, tp_stream_t stream);
+
+typedef struct tp_multiview_args {
+  int B, Gr;
+  const float* cam;          /* [B,3,4] world -> camera of each view */
+  const float* pose;         /* [B,3,4] the composed poses every term's planes were rendered at (each term's pose must be this pointer) */
+  const float* model;        /* [Gr,3,4] the current model -> world poses */
+  const int32_t* member;     /* [B] view indices, the groups one after the other, ascending inside a group; clamped */
+  const int32_t* group_start; /* [Gr+1] group g owns member[group_start[g] .. group_start[g+1] - 1]; clamped */
+  float w_sil, w_photo, w_icp; /* finite, >= 0: K33's weights */
+  float damping;             /* finite, >= 0 */
+  int evaluate_only;         /* non-zero: inliers, chi2, status and views of model; no step */
+  float* model_out;          /* [Gr,3,4] out; may be NULL with evaluate_only; must not overlap model */
+  float* pose_out;           /* [B,3,4] out or NULL: cam o model_out per member view; must not overlap pose or cam */
+  int32_t* status;           /* [Gr] out: 0 ok, 1 fewer than 6 kept pixels in the whole group, 3 not positive definite */
+  int32_t* inliers;          /* [Gr] out */
+  float* chi2;               /* [Gr] out */
+  int32_t* views;            /* [Gr] out: member views with a count > 0 */
+  void* workspace;           /* tp_multiview_workspace_bytes(B) bytes, 16-byte aligned; needs no clearing */
+} tp_multiview_args;
+size_t tp_multiview_workspace_bytes(int B);  /* 256 * B; 0 for a non-positive B */
+int tp_multiview_align_step(const tp_multiview_args* mv,
+                            const tp_silhouette_align_args* sil,   /* may be NULL */
+                            const tp_photo_align_args* photo,      /* may be NULL */
+                            const tp_depth_icp_args* icp,          /* may be NULL */
+                            tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

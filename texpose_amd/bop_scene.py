@@ -63,9 +63,11 @@ class BopSceneWriter:
         for sub in ("rgb", "depth", "mask", "mask_visib"):
             os.makedirs(os.path.join(self.root, sub), exist_ok=True)
 
-    def add_views(self, pose, object_ids, info, mask, mask_visib, rgb8, depth16) -> List[int]:
+    def add_views(self, pose, object_ids, info, mask, mask_visib, rgb8, depth16, cam_w2c=None) -> List[int]:
         """pose [B,3,4] (t in NeRF units), object_ids [K] in blend order, info [B,K,10] int32, mask / mask_visib [B,K,H,W] uint8,
-        rgb8 [B,H,W,3] uint8, depth16 [B,H,W] uint16; device tensors or host arrays.  Returns the frame numbers written."""
+        rgb8 [B,H,W,3] uint8, depth16 [B,H,W] uint16; device tensors or host arrays.  ``cam_w2c`` [B,3,4] (world -> camera, t in mm):
+        each frame's camera pose, written as BOP's cam_R_w2c / cam_t_w2c into scene_camera.json (None: the keys are not written).
+        Returns the frame numbers written."""
         from PIL import Image
         pose = torch.as_tensor(pose, dtype=torch.float32) if not torch.is_tensor(pose) else pose.detach().float()
         if pose.dim() == 2:
@@ -78,6 +80,10 @@ class BopSceneWriter:
         info, mask, mask_visib, rgb8, depth16 = (_host(x) for x in (info, mask, mask_visib, rgb8, depth16))
         B, K = rot.shape[0], len(ids)
         H, W = rgb8.shape[1:3]
+        if cam_w2c is not None:
+            cam_w2c = _host(cam_w2c).astype(np.float64)
+            if cam_w2c.shape != (B, 3, 4):
+                raise ValueError("BopSceneWriter.add_views: cam_w2c [B=%d,3,4] expected, got %s" % (B, cam_w2c.shape))
         if info.shape != (B, K, INFO_FIELDS) or mask.shape != (B, K, H, W) or mask_visib.shape != (B, K, H, W) or \
                 rgb8.shape != (B, H, W, 3) or depth16.shape != (B, H, W):
             raise ValueError("BopSceneWriter.add_views: shapes do not agree (B %d, K %d, H %d, W %d)" % (B, K, H, W))
@@ -96,6 +102,8 @@ class BopSceneWriter:
                 Image.fromarray(np.ascontiguousarray(mask[b, k]), "L").save(os.path.join(self.root, "mask", "%06d_%06d.png" % (frame, k)))
                 Image.fromarray(np.ascontiguousarray(mask_visib[b, k]), "L").save(os.path.join(self.root, "mask_visib", "%06d_%06d.png" % (frame, k)))
             self.camera[key] = dict(cam_K=self.cam_K, depth_scale=1000.0 / self.png_per_metre)
+            if cam_w2c is not None:
+                self.camera[key].update(cam_R_w2c=[float(v) for v in cam_w2c[b, :, :3].reshape(9)], cam_t_w2c=[float(v) for v in cam_w2c[b, :, 3]])
             # the meshes share the scene frame: every object of a view carries the view's pose
             self.gt[key] = [dict(obj_id=ids[k], cam_R_m2c=[float(v) for v in rot[b].reshape(9)], cam_t_m2c=[float(v) for v in t_mm[b]])
                             for k in range(K)]

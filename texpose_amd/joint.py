@@ -25,12 +25,11 @@ from .options import AttrDict
 Tensor = torch.Tensor
 
 
-def step_torch(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None,
-               depth: Optional[dict] = None, weights=ops.JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False) -> Dict[str, Tensor]:
-    """ops.joint_align_step's rules (include/texpose_amd.h, K33) in plain torch ops in fp64 on the tensors' device: the terms are the
-    dicts ops.joint_align_step takes -> 'pose' [B,3,4] float32, 'inliers', 'status' [B]
-    int32, 'chi2' [B] float32 and each present term's own evaluation under its prefix ('sil_', 'photo_', 'icp_').  A term that is
-    absent or has weight 0 takes no part in the sum."""
+def sums_torch(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None, depth: Optional[dict] = None,
+               weights=ops.JOINT_WEIGHTS, damping: float = 1e-6):
+    """The combined sums of every image: each present term's ``sums_torch`` at ``pose``, weighted and added over the terms with a
+    weight > 0 -> ((JtJ [B,6,6], Jtr [B,6], cost [B], count [B]) fp64, each present term's own evaluation under its prefix, pose as
+    float32 [B,3,4])."""
     w = ops._joint_weights("step_torch", weights)
     terms = (("sil_", silhouette, w[0], lambda t: _sil.sums_torch(t["zbuf"], pose, intr, t["sdf"], t["tau_px"], t.get("frame"), t.get("mask"))),
              ("photo_", photo, w[1], lambda t: _photo.sums_torch(t["zbuf"], t["rgb"], pose, intr, t["image"], t["tau"], t.get("frame"), t.get("mask"))),
@@ -51,6 +50,16 @@ def step_torch(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None,
         if x > 0:
             part = (x * JtJ, x * Jtr, x * cost, count)
             total = part if total is None else tuple(a + b for a, b in zip(total, part))
+    return total, res, pose32
+
+
+def step_torch(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None,
+               depth: Optional[dict] = None, weights=ops.JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False) -> Dict[str, Tensor]:
+    """ops.joint_align_step's rules (include/texpose_amd.h, K33) in plain torch ops in fp64 on the tensors' device: the terms are the
+    dicts ops.joint_align_step takes -> 'pose' [B,3,4] float32, 'inliers', 'status' [B]
+    int32, 'chi2' [B] float32 and each present term's own evaluation under its prefix ('sil_', 'photo_', 'icp_').  A term that is
+    absent or has weight 0 takes no part in the sum."""
+    total, res, pose32 = sums_torch(pose, intr, silhouette=silhouette, photo=photo, depth=depth, weights=weights, damping=damping)
     out = _gn_torch.solve(*total, pose32, damping, evaluate_only)
     return dict(res, pose=out["pose"], inliers=out["inliers"], status=out["status"], chi2=total[2].float())
 

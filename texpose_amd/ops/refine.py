@@ -15,7 +15,8 @@ __all__ = ["depth_icp_workspace", "depth_icp_step", "DEPTH_ICP_KEYS", "depth_icp
            "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "image_down", "surface_down", "mask_down",
            "image_pyramid", "mask_pyramid", "mask_sdf_workspace", "mask_sdf",
            "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align",
-           "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align"]
+           "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align",
+           "pose_compose", "multiview_group_index", "multiview_align_workspace", "multiview_align_step", "MULTIVIEW_ALIGN_KEYS", "multiview_align"]
 
 
 # ------------------------------------------------------------------------------------------ the terms
@@ -141,7 +142,7 @@ def _schedules(op: str, given, iters: int) -> list:
 
 
 def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, given, taus, *, damping, frame, workspace, cull,
-            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0, pyramid=None) -> Dict[str, Tensor]:
+            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0, pyramid=None, multiview=None) -> Dict[str, Tensor]:
     """The loop of every refiner over the terms of ``given`` that have planes: one pass per entry of ``taus`` (_schedules) of ONE
     mesh_raster call at the current poses, asked only for what these terms need, and one step from it, the last evaluate-only; a step
     that fails passes its pose on.  Without ``weights`` the step is the single term's own (its 'rms' is the cost carried); with them it
@@ -154,11 +155,13 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     'exposure_status' [B] of the last pass (prefixed with the term's 'photo_' in the joint results).  ``pyramid`` (the photometric
     term alone): steps per level, the coarsest first, adding up to the steps of ``taus``; the photograph's and the mask's pyramids are
     built once, a pass at level l filters the full-size rendering down l times (surface_down, K38) and steps on the level's planes
-    with the level's intrinsics; the last pass, the evaluation, runs at level 0."""
+    with the level's intrinsics; the last pass, the evaluation, runs at level 0.  ``multiview`` (K39, with ``weights``): dict(cam [B,3,4],
+    group [B], index) -- ``pose`` is then the MODEL [Gr,3,4], the state the loop carries: every pass composes the B views' poses from it
+    (pose_compose), renders at those and takes multiview_align_step in place of the joint step -> also 'model' and 'views'."""
     joint = weights is not None
     cost = "chi2" if joint else "rms"
-    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose")
-    B = pose.shape[0]
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose" if multiview is None else "model")
+    B = pose.shape[0] if multiview is None else multiview["cam"].shape[0]
     faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
     intr = _intr_per_view(op, intr, B)
     terms, planes, masks = [], {}, {}
@@ -180,7 +183,8 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
         planes[term.plane], frame, masks[term.name], _ = _frame_planes(op, term, planes[term.plane], frame, masks[term.name], B, H, W, pose)
     vcolor = None if vcolor is None else _f32(vcolor.detach(), "vcolor")
     texels = None if texels is None else _f32(texels.detach(), "texels")
-    workspace = _workspace_arg(op, workspace, sum(_term_bytes([t for _, t in terms], B, H, W, 16 if joint else 1)), pose.device, align=16)
+    own_bytes = 0 if multiview is None else int(_lib.load().tp_multiview_workspace_bytes(B))
+    workspace = _workspace_arg(op, workspace, sum(_term_bytes([t for _, t in terms], B, H, W, 16 if joint else 1)) + own_bytes, pose.device, align=16)
     counting = next((t for _, t in terms if t.counts), None)
     if visible_iou:
         if counting is None:
@@ -212,6 +216,8 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     fit = {}                                                     # the exposure fit of the pass before
 
     def one_pass(pose, th, last, level):                         # (a function: the rendered planes are released before the next pass renders)
+        if multiview is not None:                                # (the state is the model; the views' poses follow from it)
+            model, pose = pose, pose_compose(multiview["cam"], pose, multiview["group"])
         r = mesh_raster(verts, faces, pose, intr, **ask)
         photo, photo_mask, K = coarse[level] if level else (planes.get(_PHOTO.plane), masks.get(_PHOTO.name), intr)
         for _ in range(level):                                   # (the full-size rendering filtered as the photograph was, never a coarse raster)
@@ -221,7 +227,10 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
                                bias=fit.get("bias"), frame=frame, mask=photo_mask, inplace=True, workspace=workspace)
             fit.update(gain=e["gain"], bias=e["bias"], exposure_status=e["status"])
         own = {term.name: dict(kw, **{k: r[k] for k in rendered}, **{term.threshold: th[i]}) for i, term, kw, rendered in fixed}
-        if joint:
+        if multiview is not None:
+            got = multiview_align_step(model, multiview["cam"], multiview["group"], intr, weights=weights, damping=damping, evaluate_only=last,
+                                       workspace=workspace, pose=pose, index=multiview["index"], **own)
+        elif joint:
             got = joint_align_step(pose, intr, weights=weights, damping=damping, evaluate_only=last, workspace=workspace, **own)
         else:
             if level:
@@ -238,8 +247,10 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
         got = one_pass(pose, th, last, levels[it])
         first = got if first is None else first
         status = got["status"] if not last or status is None else status
-        pose = got["pose"]
+        pose = got["pose" if multiview is None else "model"]
     res = {"pose": got["pose"], "inliers": got["inliers"], cost: got[cost], "status": status, "inliers0": first["inliers"], cost + "0": first[cost]}
+    if multiview is not None:
+        res.update(model=got["model"], views=got["views"])
     res = {k: res[k] for k in keys}
     if joint:
         res.update({k: v for k, v in got.items() if k.startswith(tuple(t.prefix for t in _TERMS))})
@@ -653,6 +664,45 @@ def joint_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Ten
     return _new_workspace("joint_align", _TERMS[:int(terms)], B, H, W, device)
 
 
+def _step_terms(op: str, pose: Tensor, intr: Tensor, given: dict, damping, out, workspace, tail_bytes: int = 0):
+    """The present terms of a joint or a multi-view step, checked: ``given`` name -> the term's dict or None -> (the three args structs
+    in _TERMS order, None where absent; the per-term outputs under their prefixes; the tensors the structs point into; pose [B,3,4];
+    intr [B,3,3]; the ``tail_bytes`` of the workspace behind the terms' parts as uint8, or None)."""
+    pose = _poses(op, pose, "pose")
+    B = pose.shape[0]
+    intr = _intr_per_view(op, intr, B)
+    shapes = {name: tuple(t["zbuf"].shape) if torch.is_tensor(t.get("zbuf")) else None for name, t in given.items() if t is not None}
+    shape = next(iter(shapes.values()))
+    if len(set(shapes.values())) != 1 or shape is None or len(shape) != 3:
+        raise ValueError("%s: every term needs a zbuf [B,H,W] of one shape, got %r" % (op, shapes))
+    H, W = shape[1:]
+    dev = pose.device
+    present = [term for term in _TERMS if given[term.name] is not None]
+    need = dict(zip(present, _term_bytes(present, B, H, W, 16)))
+    workspace = _workspace_arg(op, workspace, sum(need.values()) + tail_bytes, dev, align=16)
+    raw, offset = workspace.view(torch.uint8).reshape(-1), 0
+    res, structs, alive = {}, [], [workspace]
+    for term in _TERMS:
+        t = given[term.name]
+        if t is None:
+            structs.append(None)
+            continue
+        takes = term.rendered + (term.plane, term.threshold)
+        unknown = set(t) - set(takes) - {"frame", "mask"}
+        missing = [k for k in takes if k not in t]
+        if unknown or missing:
+            raise ValueError("%s: the %s term takes %s, frame and mask; missing %s, unknown %s" % (op, term.name, ", ".join(takes), missing, sorted(unknown)))
+        term_out = None if out is None else {k[len(term.prefix):]: v for k, v in out.items() if k.startswith(term.prefix)}
+        a, r, keep = _term_args(term, "%s (%s)" % (op, term.name), dict({k: t[k] for k in term.rendered}, pose=pose, intr=intr, **{term.plane: t[term.plane]}),
+                                threshold=t[term.threshold], damping=damping, frame=t.get("frame"), mask=t.get("mask"), evaluate_only=True,
+                                workspace=raw[offset:offset + need[term]], out=term_out, with_pose=False)
+        offset += need[term]
+        structs.append(a)
+        alive.append(keep)
+        res.update({term.prefix + k: v for k, v in r.items()})
+    return structs, res, alive, pose, intr, (raw[offset:offset + tail_bytes] if tail_bytes else None)
+
+
 @_on_tensor_device
 def joint_align_step(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None, depth: Optional[dict] = None,
                      weights=JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False, out: Optional[Dict[str, Tensor]] = None,
@@ -677,38 +727,8 @@ def joint_align_step(pose: Tensor, intr: Tensor, *, silhouette: Optional[dict] =
         raise ValueError("%s: no term: give at least one of %s" % (op, ", ".join(name + "=" for name in JOINT_TERMS)))
     if not any(v is not None and x > 0 for v, x in zip(given.values(), w)):
         raise ValueError("%s: no present term has a weight > 0 (weights %r)" % (op, w))
-    pose = _poses(op, pose, "pose")
-    B = pose.shape[0]
-    intr = _intr_per_view(op, intr, B)
-    shapes = {name: tuple(t["zbuf"].shape) if torch.is_tensor(t.get("zbuf")) else None for name, t in given.items() if t is not None}
-    shape = next(iter(shapes.values()))
-    if len(set(shapes.values())) != 1 or shape is None or len(shape) != 3:
-        raise ValueError("%s: every term needs a zbuf [B,H,W] of one shape, got %r" % (op, shapes))
-    H, W = shape[1:]
-    dev = pose.device
-    present = [term for term in _TERMS if given[term.name] is not None]
-    need = dict(zip(present, _term_bytes(present, B, H, W, 16)))
-    workspace = _workspace_arg(op, workspace, sum(need.values()), dev, align=16)
-    raw, offset = workspace.view(torch.uint8).reshape(-1), 0
-    res, structs, alive = {}, [], [workspace]
-    for term in _TERMS:
-        t = given[term.name]
-        if t is None:
-            structs.append(None)
-            continue
-        takes = term.rendered + (term.plane, term.threshold)
-        unknown = set(t) - set(takes) - {"frame", "mask"}
-        missing = [k for k in takes if k not in t]
-        if unknown or missing:
-            raise ValueError("%s: the %s term takes %s, frame and mask; missing %s, unknown %s" % (op, term.name, ", ".join(takes), missing, sorted(unknown)))
-        term_out = None if out is None else {k[len(term.prefix):]: v for k, v in out.items() if k.startswith(term.prefix)}
-        a, r, keep = _term_args(term, "%s (%s)" % (op, term.name), dict({k: t[k] for k in term.rendered}, pose=pose, intr=intr, **{term.plane: t[term.plane]}),
-                                threshold=t[term.threshold], damping=damping, frame=t.get("frame"), mask=t.get("mask"), evaluate_only=True,
-                                workspace=raw[offset:offset + need[term]], out=term_out, with_pose=False)
-        offset += need[term]
-        structs.append(a)
-        alive.append(keep)
-        res.update({term.prefix + k: v for k, v in r.items()})
+    structs, res, _alive, pose, intr, _ = _step_terms(op, pose, intr, given, damping, out, workspace)
+    B, dev = pose.shape[0], pose.device
     joint = _outputs(op, out, {"pose": (torch.float32, (B, 3, 4)), "status": (torch.int32, (B,)), "inliers": (torch.int32, (B,)),
                                "chi2": (torch.float32, (B,))}, dev, partial=True)
     j = _lib.JointAlignArgs()
@@ -763,3 +783,125 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     return _refine(op, ("pose", "inliers", "status", "inliers0", "chi2", "chi20"), verts, faces, pose, intr, given, taus, damping=damping, frame=frame,
                    workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w, exposure=exposure,
                    exposure_tau0=exposure_tau0)
+
+
+# ------------------------------------------------------------------------------------------ K39
+def _group_args(op: str, cam: Tensor, model: Tensor, group: Tensor):
+    """cam [B,3,4], model [Gr,3,4] (1 <= Gr <= B) and group [B] int32 of a multi-view call, checked."""
+    cam, model = _poses(op, cam, "cam"), _poses(op, model, "model")
+    B, Gr = cam.shape[0], model.shape[0]
+    if Gr > B:
+        raise ValueError("%s: model [Gr,3,4] with 1 <= Gr <= B = %d views expected, got %s" % (op, B, tuple(model.shape)))
+    return cam, model, _lengths(op, group, "group", B, cam, required=True)
+
+
+def multiview_group_index(group: Tensor, Gr: int):
+    """group [B] int32 (ids outside 0 .. Gr-1 clamp) -> (member [B] int32: the view indices by group, ascending inside a group;
+    group_start [Gr+1] int32): what tp_multiview_align_step takes.  A stable sort and a searchsorted on the device, no host read."""
+    ids = group.clamp(0, Gr - 1)
+    ordered, member = torch.sort(ids, stable=True)
+    start = torch.searchsorted(ordered, torch.arange(Gr + 1, device=group.device, dtype=ids.dtype))
+    return member.to(torch.int32), start.to(torch.int32)
+
+
+@_on_tensor_device
+def pose_compose(cam: Tensor, model: Tensor, group: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The pose of every view of a multi-view problem (tp_pose_compose, K39; the rules are in the header): cam [B,3,4] (world ->
+    camera), model [Gr,3,4] (model -> world), group [B] int32 (the model of each view; out of range: clamped) -> [B,3,4]: cam[i] o
+    model[group[i]] in fp64, rounded once; a cam of exactly [I|0] copies the model bit for bit.  ``out``: the tensor to write into.
+    One launch, safe under torch.cuda.graph."""
+    op = "pose_compose"
+    cam, model, group = _group_args(op, cam, model, group)
+    B = cam.shape[0]
+    res = torch.empty_like(cam) if out is None else _want_gpu(op, out, "out", torch.float32, (B, 3, 4))
+    a = _lib.PoseComposeArgs()
+    a.B, a.Gr, a.cam, a.model, a.group, a.out = B, model.shape[0], cam.data_ptr(), model.data_ptr(), group.data_ptr(), res.data_ptr()
+    _call("tp_pose_compose", a)           # (out overlapping cam or model: the library's error)
+    return res
+
+
+def multiview_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Tensor:
+    """A workspace for multiview_align_step / multiview_align at B views of H x W with ``terms`` terms present (each term's own part,
+    then tp_multiview_workspace_bytes(B)); needs no clearing."""
+    terms = _TERMS[:int(terms)]
+    return _workspace_arg("multiview_align", None, sum(_term_bytes(terms, B, H, W, 16)) + int(_lib.load().tp_multiview_workspace_bytes(B)), device)
+
+
+@_on_tensor_device
+def multiview_align_step(model: Tensor, cam: Tensor, group: Tensor, intr: Tensor, *, silhouette: Optional[dict] = None, photo: Optional[dict] = None,
+                         depth: Optional[dict] = None, weights=JOINT_WEIGHTS, damping: float = 1e-6, evaluate_only: bool = False,
+                         out: Optional[Dict[str, Tensor]] = None, workspace: Optional[Tensor] = None, pose: Optional[Tensor] = None,
+                         index=None) -> Dict[str, Tensor]:
+    """One MULTI-VIEW Gauss-Newton step: one object pose per group of views with known cameras, all rows of a group's views in one
+    normal system (tp_multiview_align_step, K39; the rules are in the header).  model [Gr,3,4] (model -> world, the unknowns), cam
+    [B,3,4] (world -> camera, fixed), group [B] int32, intr [B,3,3] or one [3,3]; the terms are joint_align_step's dicts with planes
+    rendered at pose_compose(cam, model, group).  -> 'model' [Gr,3,4] (the stepped poses; ``model`` bit for bit with
+    ``evaluate_only`` or a non-zero status), 'pose' [B,3,4] (cam o 'model'), 'status', 'inliers', 'views' [Gr] int32, 'chi2' [Gr], and
+    joint_align_step's per-term keys [B].  ``pose``: the composed poses, where the caller has them (the loop has); ``index``:
+    multiview_group_index(group, Gr), likewise.  ``workspace``: multiview_align_workspace(B, H, W, terms present).  With one view per
+    group and cameras of exactly [I|0] 'model' is joint_align_step's 'pose' bit for bit.  Each term's launches and three more, no
+    atomics, no host read, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "multiview_align_step"
+    w = _joint_weights(op, weights)
+    given = dict(zip(JOINT_TERMS, (silhouette, photo, depth)))
+    if all(v is None for v in given.values()):
+        raise ValueError("%s: no term: give at least one of %s" % (op, ", ".join(name + "=" for name in JOINT_TERMS)))
+    if not any(v is not None and x > 0 for v, x in zip(given.values(), w)):
+        raise ValueError("%s: no present term has a weight > 0 (weights %r)" % (op, w))
+    cam, model, group = _group_args(op, cam, model, group)
+    B, Gr, dev = cam.shape[0], model.shape[0], cam.device
+    pose = pose_compose(cam, model, group) if pose is None else _want_gpu(op, pose, "pose", torch.float32, (B, 3, 4))
+    member, start = multiview_group_index(group, Gr) if index is None else index
+    member, start = _lengths(op, member, "index[0]", B, cam, required=True), _lengths(op, start, "index[1]", Gr + 1, cam, required=True)
+    own_bytes = int(_lib.load().tp_multiview_workspace_bytes(B))
+    structs, res, _alive, pose, intr, tail = _step_terms(op, pose, intr, given, damping, out, workspace, own_bytes)
+    mine = _outputs(op, out, {"model": (torch.float32, (Gr, 3, 4)), "pose": (torch.float32, (B, 3, 4)), "status": (torch.int32, (Gr,)),
+                              "inliers": (torch.int32, (Gr,)), "chi2": (torch.float32, (Gr,)), "views": (torch.int32, (Gr,))}, dev, partial=True)
+    m = _lib.MultiviewArgs()
+    m.B, m.Gr, m.cam, m.pose, m.model = B, Gr, cam.data_ptr(), pose.data_ptr(), model.data_ptr()
+    m.member, m.group_start, m.damping, m.evaluate_only = member.data_ptr(), start.data_ptr(), float(damping), int(bool(evaluate_only))
+    for term, x in zip(_TERMS, w):
+        setattr(m, "w_" + term.prefix[:-1], x)
+    m.model_out, m.pose_out, m.workspace = mine["model"].data_ptr(), mine["pose"].data_ptr(), tail.data_ptr()
+    for k in ("status", "inliers", "chi2", "views"):
+        setattr(m, k, mine[k].data_ptr())
+    _call("tp_multiview_align_step", m, *structs)
+    return dict(mine, **res)
+
+
+MULTIVIEW_ALIGN_KEYS = ("model", "pose", "inliers", "status", "views", "inliers0", "chi2", "chi20")
+
+
+@_on_tensor_device
+def multiview_align(verts: Tensor, faces: Tensor, model: Tensor, cam: Tensor, group: Tensor, intr: Tensor, *, vcolor: Optional[Tensor] = None,
+                    sdf: Optional[Tensor] = None, image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS,
+                    tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None,
+                    masks: Optional[dict] = None, workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
+                    texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0, pyramid=None) -> Dict[str, Tensor]:
+    """Refine ONE pose of one mesh per group of views whose cameras are known (K39): model [Gr,3,4] (model -> world,
+    the start), cam [B,3,4] (world -> camera), group [B] int32, intr [B,3,3] or [3,3]; the measurements and every other keyword are
+    joint_align's, per VIEW.  ``iters`` + 1 passes of pose_compose, ONE mesh_raster call at the composed poses and
+    multiview_align_step, the last with evaluate_only: a view in which the object is half hidden, or whose depth along the axis is
+    loose, is pinned by the group's other views.  One term alone is allowed.  -> 'model' [Gr,3,4], 'pose' [B,3,4] (cam o model),
+    'inliers', 'views' [Gr] int32 and 'chi2' [Gr] of the last pass, 'status' [Gr] of the last step taken, 'inliers0' / 'chi20' of the
+    start, the last pass's per-term keys [B], and 'iou' / 'iou0' (and the visible ones) [B] as joint_align.  A group whose step fails
+    passes its model on.  ``pyramid`` is refused.  Bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "multiview_align"
+    if pyramid is not None:
+        raise ValueError("%s: pyramid= goes with the photometric term alone" % op)
+    if vcolor is not None and texels is not None:
+        raise ValueError("%s: vcolor= or texels=, not both" % op)
+    w = _joint_weights(op, weights)
+    masks = dict(masks or {})
+    given = [(term, p, t, masks.get(term.name)) for term, p, t in zip(_TERMS, (sdf, image, depth), (tau_px, tau, tau_mm))]
+    taus = _schedules(op, given, iters)
+    if sdf is None and image is None and depth is None:
+        raise ValueError("%s: no term: give at least one of sdf=, image=, depth=" % op)
+    if image is not None and vcolor is None and texels is None:
+        raise ValueError("%s: image= needs vcolor=, the mesh's colours [V,3], or texels= [F,T,3]" % op)
+    if set(masks) - set(JOINT_TERMS):
+        raise ValueError("%s: masks takes the keys %s, got %s" % (op, JOINT_TERMS, sorted(masks)))
+    cam, model, group = _group_args(op, cam, model, group)
+    return _refine(op, MULTIVIEW_ALIGN_KEYS, verts, faces, model, intr, given, taus, damping=damping, frame=frame, workspace=workspace, cull=cull,
+                   vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w, exposure=exposure, exposure_tau0=exposure_tau0,
+                   multiview=dict(cam=cam, group=group, index=multiview_group_index(group, model.shape[0])))

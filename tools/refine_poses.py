@@ -5,7 +5,7 @@
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
                                  [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster] [--texels [ID=]PATH]
-                                 [--exposure] [--pyramid N ...]
+                                 [--exposure] [--pyramid N ...] [--multiview]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -61,7 +61,15 @@ light than the mesh's colours.  Every pass first fits a gain and a bias per imag
 --pyramid N [N ...] (with --rgb, not under --joint): coarse to fine on an image pyramid, for estimates further off
 than the texture's detail lets the one-pixel gradient see.  The step counts per level, the coarsest first, adding up to --iters-rgb:
 --pyramid 4 3 3 takes 4 steps at a quarter of the size, 3 at half and 3 at full size (ops.photo_align's pyramid=, K38).  The object
-should cover some hundreds of pixels at the coarsest level."""
+should cover some hundreds of pixels at the coarsest level.
+
+--multiview: the frames of a scene show the SAME rigid objects, and scene_camera.json carries each frame's camera
+pose (cam_R_w2c, cam_t_w2c in mm).  All rows of one object id in one scene are then views of ONE pose in the world frame: they are
+refined together (texpose_amd.multiview, K39), every view's residual rows in one Gauss-Newton system, with the terms named by
+--silhouette, --rgb and --depth (one is enough), --iters-joint steps and --weights as under --joint.  The group starts from the row with
+the highest score (the first on a tie), taken into the world frame; every row is written with its camera's pose of the group's result.
+The tool exits where a frame lacks the camera pose and where one frame holds two rows of one object id (which instance is which across
+frames is then unknown).  --pyramid does not go with it.  Without --multiview nothing changes."""
 import argparse
 import csv
 import json
@@ -128,13 +136,17 @@ def main(argv=None):
     ap.add_argument("--texels", action="append", default=[], metavar="[ID=]PATH", help="with --rgb: face texels (bake_texture --texel-res)")
     ap.add_argument("--exposure", action="store_true", help="with --rgb: fit a gain and a bias per image and channel in every pass")
     ap.add_argument("--pyramid", type=int, nargs="+", default=None, metavar="N", help="with --rgb: steps per pyramid level, the coarsest first")
+    ap.add_argument("--multiview", action="store_true", help="all rows of one object are views of one pose (needs cam_R_w2c / cam_t_w2c)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if not a.device.startswith("cuda"):
         sys.exit("refine_poses: the refinement runs the HIP kernels, which have no CPU route; use --device cuda:N")
-    if a.joint:
-        if a.silhouette + a.rgb + a.depth < 2:
+    if a.multiview and a.silhouette + a.rgb + a.depth < 1:
+        sys.exit("refine_poses: --multiview needs at least one of --silhouette, --rgb and --depth")
+    one_loop = a.joint or a.multiview                            # every named term in ONE loop (K33's sums)
+    if one_loop:
+        if not a.multiview and a.silhouette + a.rgb + a.depth < 2:
             sys.exit("refine_poses: --joint combines at least two of --silhouette, --rgb and --depth")
         for name, values in (("--tau-px", a.tau_px), ("--tau-rgb", a.tau_rgb), ("--tau-mm", a.tau_mm)):
             if len(values) not in (1, a.iters_joint + 1):
@@ -148,7 +160,7 @@ def main(argv=None):
         sys.exit("refine_poses: --tau-rgb takes one value or iters-rgb + 1 = %d values" % (a.iters_rgb + 1))
     if a.silhouette and len(a.tau_px) not in (1, a.iters_sil + 1):
         sys.exit("refine_poses: --tau-px takes one value or iters-sil + 1 = %d values" % (a.iters_sil + 1))
-    if a.rgb and a.depth and not a.joint:
+    if a.rgb and a.depth and not one_loop:
         sys.exit("refine_poses: --depth and --rgb exclude each other")
     if a.occluders and a.known:
         sys.exit("refine_poses: --occluders and --known exclude each other")
@@ -156,15 +168,15 @@ def main(argv=None):
         sys.exit("refine_poses: --texels goes with --rgb")
     if a.exposure and not a.rgb:
         sys.exit("refine_poses: --exposure goes with --rgb")
-    if a.pyramid and (not a.rgb or a.joint):
-        sys.exit("refine_poses: --pyramid goes with --rgb" + (", and not under --joint" if a.joint else ""))
+    if a.pyramid and (not a.rgb or one_loop):
+        sys.exit("refine_poses: --pyramid goes with --rgb" + (", and not under --joint" if a.joint else ", and not with --multiview" if a.multiview else ""))
     if a.pyramid and (min(a.pyramid) < 0 or sum(a.pyramid) != a.iters_rgb):
         sys.exit("refine_poses: the steps of --pyramid must be >= 0 and add up to --iters-rgb = %d" % a.iters_rgb)
     if (a.occluders or a.known) and not a.silhouette:
         sys.exit("refine_poses: --occluders and --known go with --silhouette")
     import torch
     from PIL import Image
-    from texpose_amd import icp, joint, ops, photo_align, silhouette
+    from texpose_amd import icp, joint, multiview, ops, photo_align, silhouette
     from texpose_amd.pose_error import depth_from_png
     from texpose_amd.face_texels import load_texels
     from texpose_amd.surfel import load_ply
@@ -195,10 +207,21 @@ def main(argv=None):
             if str(row[1]) not in cam:
                 sys.exit("refine_poses: frame %d is not in scene_camera.json" % row[1])
             jobs.setdefault(row[2], []).append(i)
+    if a.multiview:                                              # a view needs its camera, a group one row per frame
+        seen = set()
+        for idx in jobs.values():
+            for i in idx:
+                sid, frame, oid = rows[i][:3]
+                if "cam_R_w2c" not in cam[str(frame)] or "cam_t_w2c" not in cam[str(frame)]:
+                    sys.exit("refine_poses: --multiview: frame %d has no cam_R_w2c / cam_t_w2c in scene_camera.json" % frame)
+                if (sid, frame, oid) in seen:
+                    sys.exit("refine_poses: --multiview: frame %d holds two rows of object %d: which instance is which across frames is unknown"
+                             % (frame, oid))
+                seen.add((sid, frame, oid))
     tau = a.tau_mm[0] if len(a.tau_mm) == 1 else a.tau_mm
     tau_rgb = a.tau_rgb[0] if len(a.tau_rgb) == 1 else a.tau_rgb
     tau_px = a.tau_px[0] if len(a.tau_px) == 1 else a.tau_px
-    second = not a.joint and (a.rgb or a.depth or not a.silhouette)          # the depth / RGB refinement runs (after the silhouette's, if any)
+    second = not one_loop and (a.rgb or a.depth or not a.silhouette)          # the depth / RGB refinement runs (after the silhouette's, if any)
     iou_sum, visible_sum = np.zeros(2), np.zeros(2)
     refined = failed = 0
     dev = a.device
@@ -206,8 +229,16 @@ def main(argv=None):
         verts, faces = meshes.get(oid, meshes.get(None))[:2]
         vcolor, texels = meshes.get(oid, meshes.get(None))[2:4] if a.rgb else (None, None)
         refiner = outline = None
-        for s in range(0, len(idx), a.batch):
-            part = idx[s:s + a.batch]
+        parts = [idx[s:s + a.batch] for s in range(0, len(idx), a.batch)]
+        if a.multiview:                                          # whole groups (the rows of one scene id): a batch is closed once it holds --batch rows
+            by_scene, parts = {}, [[]]
+            for i in idx:
+                by_scene.setdefault(rows[i][0], []).append(i)
+            for members in by_scene.values():
+                if parts[-1] and len(parts[-1]) + len(members) > a.batch:
+                    parts.append([])
+                parts[-1] += members
+        for part in parts:
             frames = sorted({rows[i][1] for i in part})
             def masks_of(folder, option):
                 ms = []
@@ -237,10 +268,10 @@ def main(argv=None):
                                 for f in frames]
             read_depth = lambda: [depth_from_png(np.asarray(Image.open(os.path.join(a.scene, "depth", "%06d.png" % f))), float(cam[str(f)]["depth_scale"]))
                                   for f in frames]
-            if a.joint:
+            if one_loop:
                 photos = torch.stack(read_rgb()).to(dev) if a.rgb else None
                 ranges = torch.stack(read_depth()).to(dev) if a.depth else None
-                depth = measured if a.silhouette else photos     # (any of the measured planes: the size)
+                depth = measured if a.silhouette else photos if a.rgb else ranges          # (any of the measured planes: the size)
             else:
                 if a.rgb:
                     planes = read_rgb()
@@ -248,11 +279,11 @@ def main(argv=None):
                     planes = read_depth()
                 depth = torch.stack(planes) if second else measured  # (with --rgb: the photographs [Ft,H,W,3])
             H, W = depth.shape[1:3]
-            if a.joint and (refiner is None or (refiner.H, refiner.W) != (H, W)):
-                refiner = joint.JointRefiner(verts, faces, H, W, dev, vcolor=vcolor, texels=texels,
+            if one_loop and (refiner is None or (refiner.H, refiner.W) != (H, W)):
+                refiner = (multiview.MultiViewRefiner if a.multiview else joint.JointRefiner)(verts, faces, H, W, dev, vcolor=vcolor, texels=texels,
                                              weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
                                              damping=a.damping, cull=a.cull_raster, exposure=a.exposure)
-            if a.silhouette and not a.joint and (outline is None or (outline.H, outline.W) != (H, W)):
+            if a.silhouette and not one_loop and (outline is None or (outline.H, outline.W) != (H, W)):
                 outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping, cull=a.cull_raster)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
@@ -267,7 +298,17 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.time()
             start, K = torch.from_numpy(pose).to(dev), torch.from_numpy(K).to(dev)
-            if a.joint:
+            if a.multiview:
+                w2c = np.stack([np.concatenate([np.array(cam[str(rows[i][1])]["cam_R_w2c"], np.float64).reshape(3, 3),
+                                                np.array(cam[str(rows[i][1])]["cam_t_w2c"], np.float64).reshape(3, 1)], 1) for i in part])
+                scenes = sorted({rows[i][0] for i in part})
+                group = torch.tensor([scenes.index(rows[i][0]) for i in part], dtype=torch.int32, device=dev)
+                w2c = torch.from_numpy(w2c.astype(np.float32)).to(dev)
+                score = torch.tensor([rows[i][3] for i in part], dtype=torch.float64, device=dev)
+                r = refiner.refine(multiview.init_model(start, w2c, group, score, groups=len(scenes)), w2c, group, K, mask_or_sdf=measured, known=known,
+                                   image=photos, depth=ranges, frame=index, masks=None if mask is None else dict(silhouette=mask, photo=mask, depth=mask))
+                r = type(r)(dict(r, status=r["status"][group.long()]))          # (a row's status is its group's)
+            elif a.joint:
                 r = refiner.refine(start, K, mask_or_sdf=measured, known=known, image=photos, depth=ranges, frame=index,
                                    masks=None if mask is None else dict(silhouette=mask, photo=mask, depth=mask))
             elif a.silhouette:
