@@ -1773,6 +1773,85 @@ int tp_multiview_align_step(const tp_multiview_args* mv,
                             const tp_depth_icp_args* icp,          /* may be NULL */
                             tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K40  per-image, per-channel FIRST-ORDER SPHERICAL-HARMONIC shading (ambient + directional) and a bias between a rendering and its
+ *      photograph (texpose_amd/ops/refine.py: photo_lighting; restated in tests/photo_lighting_ref.py; the project's own step, no
+ *      reference code).  K37's sibling for a light that has a direction: face / zbuf / rgb are K19's planes of the
+ *      mesh (verts, faces) at `pose`; the call fits  o_k ~ (l0_k + l1_k n_x + l2_k n_y + l3_k n_z) c_k + beta_k  per image b and
+ *      channel k by least squares over the pixels the light that came in (light_in [B,3,5]: per channel (l0, l1, l2, l3, beta); NULL:
+ *      (1, 0, 0, 0, 0)) explains within tau, n the unit normal of the pixel's FACE in the camera frame, turned towards the camera; where
+ *      rgb_out is given it applies the new light to the rendering.  The model contains K37's (l1 = l2 = l3 = 0).
+ *      Per pixel (row i, column j) of image b, with fr as K37 (frame CLAMPED into [0, Ft)), everything in fp64 from the fp32 inputs,
+ *      evaluated as written (no contraction):
+ *        1.-4. K37's steps 1 - 4: interior, z = zbuf[b,i,j] > 0 and finite, mask[fr,i,j] != 0, the six colours c_k, o_k finite
+ *        5. f = face[b,i,j];  skipped unless 0 <= f < F and all three of faces[f] lie in [0, V)       (nothing is read out of bounds)
+ *        6. v0, v1, v2 = verts[faces[f]];  m = (v1 - v0) x (v2 - v0);  [R|t] = pose[b];
+ *           n_r = (R[r][0] m_x + R[r][1] m_y) + R[r][2] m_z;   d = (n_x n_x + n_y n_y) + n_z n_z;   skipped unless d is finite and > 0;
+ *           n = n / sqrt(d)   (a division per component)
+ *        7. x_r = ((R[r][0] v0_x + R[r][1] v0_y) + R[r][2] v0_z) + t_r;   if (n_x x_x + n_y x_y) + n_z x_z > 0 then n = -n
+ *        8. per channel the regressors x = (c, c n_x, c n_y, c n_z, 1): entry 0 is c itself
+ *        9. with (l, beta) = light_in[b,k]:  p_k = (((l0 x_0 + l1 x_1) + l2 x_2) + l3 x_3) + beta;  r_k = o_k - p_k;
+ *           kept iff (r_0^2 + r_1^2) + r_2^2 <= tau * tau
+ *      Steps 5 - 7 are the pixel's VALID NORMAL (they read neither colours nor the mask); K19's normal plane is not used.
+ *      64 sums over the kept pixels: [0] n (+ 1 per pixel) and, for channel k, [1 + 21 k ..]: the 15 products x_i x_j, j >= i,
+ *      row-major, the 5 products x_i o, and o o.  K30's / K37's order: a thread owns four consecutive flat pixels (ascending), a
+ *      workgroup 1024; butterfly sums inside a wave, the four waves in ascending order, one 64-double record per workgroup, the
+ *      records of an image in ascending order.  No atomics; the outputs are a function of the inputs alone, bit-identical from run
+ *      to run and under graph replay.
+ *      Per image and channel, in fp64 as written, A the 5 x 5 matrix of the 15 sums, r the 5, Soo the last:
+ *        Cholesky of A with K29's pivot rule (a pivot must be finite, > 1e-10 x its diagonal entry and > 0), L y = r, L^T x = y, every
+ *        inner sum in ascending index order starting from the entry itself.  x is ACCEPTED iff the factorisation passes, all five
+ *        values are finite, gain_min <= x_0 <= gain_max and sqrt((x_1^2 + x_2^2) + x_3^2) <= x_0 (the shading is non-negative for
+ *        every normal).  Otherwise K37's closed form on the sub-sums Sc = A[0][4], So = r[4], Scc = A[0][0], Sco = r[0] (and n):
+ *        mc, mo, var, cov, the clamp, the flat rule and b = mo - g mc exactly as K37 states them, x = (g, 0, 0, 0, b), and
+ *        TP_LIGHTING_FALLBACK << k is set in flags beside K37's TP_EXPOSURE_CLAMPED << k / TP_EXPOSURE_FLAT << k; where the kept sets
+ *        agree g and b are K37's bit for bit.
+ *        xr = (((x_0 r_0 + x_1 r_1) + x_2 r_2) + x_3 r_3) + x_4 r_4;  (Ax)_i likewise over row i;  xAx likewise over x_i (Ax)_i;
+ *        sse_k = (Soo - 2 xr) + xAx
+ *      count = n;  rms = sqrt(max(0, (sse_0 + sse_1) + sse_2) / n) (NaN at n = 0);  status = 1 where n < 6; else 3 where one of the 15
+ *      coefficients or rms rounded to fp32 is not finite; else 0.  light = the 15 coefficients rounded to fp32 where status == 0;
+ *      otherwise light_in bit for bit ((1, 0, 0, 0, 0) where NULL).  flags are those of the fit just made whatever the status.
+ *      Apply, where rgb_out is given: a pixel with zbuf > 0 and finite (border pixels included) becomes
+ *        s = ((l0 + l1 n_x) + l2 n_y) + l3 n_z   in fp64 from the fp32 light just written and the pixel's valid normal, rounded to fp32
+ *            ONCE; s = l0 itself where the pixel has no valid normal
+ *        rgb_out[b,i,j,k] = s * rgb[b,i,j,k] + beta   as two fp32 operations (a product, then a sum)
+ *      so a light without a directional part gives K37's apply bit for bit.  Every other pixel is copied bit for bit, and with
+ *      rgb_out == rgb is not written.
+ *      Three launches on the stream (reduce, solve, apply; two without rgb_out).  Refused (-1, tp_last_error) before anything is
+ *      launched: K37's list (sizes, Ft without frame, tau, gain_min / gain_max, min_var, null pointers, workspace alignment, an rgb_out
+ *      overlapping rgb without being rgb, light overlapping light_in) and null verts, faces, face or pose and V <= 0 or F <= 0.
+ *      No input value causes an access out of bounds: frame is clamped, face and the vertex indices are checked before use.  No
+ *      allocation, no host synchronisation; outputs and workspace must not overlap inputs otherwise.  Safe to capture.
+ *      Left out: second-order SH, interpolated vertex normals, shadows and speculars, a light shared by the views of a group,
+ *      eliminating the light inside the pose step's system, a ridge term (DESIGN section 30 says why none was needed).
+ * ------------------------------------------------------------------------------------------ */
+#define TP_LIGHTING_FALLBACK 64  /* flags: << k, channel k took K37's closed form (with its TP_EXPOSURE_CLAMPED / TP_EXPOSURE_FLAT << k) */
+typedef struct tp_photo_lighting_args {
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3]; a face with an index outside [0, V) has no normal */
+  const int32_t* face;       /* [B,H,W] K19's face index at the current poses; outside [0, F): no normal */
+  const float* zbuf;         /* [B,H,W] K19's depth at the current poses: <= 0 or NaN: background */
+  const float* rgb;          /* [B,H,W,3] K19's colours at the current poses */
+  const float* pose;         /* [B,3,4] the poses the planes were rendered at */
+  const float* image;        /* [Ft,H,W,3] the photograph, channels last */
+  const int32_t* frame;      /* [B] index into image (and mask), or NULL: b when Ft == B, 0 when Ft == 1 */
+  const uint8_t* mask;       /* [Ft,H,W] or NULL; 0: the pixel is skipped */
+  const float* light_in;     /* [B,3,5] or NULL ((1, 0, 0, 0, 0)): the light the keep rule judges by */
+  int V, F, B, Ft, H, W;
+  float tau;                 /* finite, > 0 */
+  float gain_min, gain_max;  /* 0 < gain_min <= 1 <= gain_max, finite: the range of l0 */
+  float min_var;             /* finite, >= 0: K37's, for a channel that falls back */
+  float* light;              /* [B,3,5] out; must not overlap light_in */
+  int32_t* count;            /* [B] out */
+  float* rms;                /* [B] out, colour units */
+  int32_t* status;           /* [B] out: 0 ok, 1 fewer than 6 kept pixels, 3 not finite */
+  int32_t* flags;            /* [B] out: TP_LIGHTING_FALLBACK << k | TP_EXPOSURE_CLAMPED << k | TP_EXPOSURE_FLAT << k */
+  float* rgb_out;            /* [B,H,W,3] out, rgb itself (in place) or NULL (fit only) */
+  void* workspace;           /* tp_photo_lighting_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_photo_lighting_args;
+size_t tp_photo_lighting_workspace_bytes(int B, int H, int W);  /* 512 * B * ceil(H * W / 1024); 0 for non-positive sizes */
+int tp_photo_lighting(const tp_photo_lighting_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

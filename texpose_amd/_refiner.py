@@ -24,8 +24,9 @@ class _MeshRefiner:
         self._sdf_workspaces: Dict[int, Tensor] = {}
 
     def _workspace(self, B: int) -> Tensor:
-        if B not in self._workspaces:
-            self._workspaces[B] = type(self)._new_workspace(B, self.H, self.W, self.device)
+        if B not in self._workspaces:                # (a refiner with lighting=True: its fit, K40, runs in the same bytes and may need more)
+            extra = {"lighting": True} if getattr(self, "lighting", False) else {}
+            self._workspaces[B] = type(self)._new_workspace(B, self.H, self.W, self.device, **extra)
         return self._workspaces[B]
 
     def _colours(self, vcolor, texels) -> None:

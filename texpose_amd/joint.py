@@ -70,19 +70,22 @@ class JointRefiner(_MeshRefiner):
 
     ``weights`` (w_sil, w_photo, w_icp; ops.JOINT_WEIGHTS), ``tau_px`` / ``tau`` / ``tau_mm`` (each term's threshold, one value or
     ``iters`` + 1), ``iters`` (Gauss-Newton steps, 20), ``damping`` (relative, 1e-6), ``exposure`` (the photometric term fits the
-    photograph's gain and bias per image and channel in every pass: ops.photo_exposure, K37).  ``refine`` returns ops.joint_align's dict."""
+    photograph's gain and bias per image and channel in every pass: ops.photo_exposure, K37) or, in its place, ``lighting`` (ambient +
+    directional shading on the faces' normals and a bias: ops.photo_lighting, K40).  ``refine`` returns ops.joint_align's dict."""
     _new_workspace = staticmethod(ops.joint_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, vcolor: Optional[Tensor] = None,
                  weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, cull: bool = False,
-                 texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0):
+                 texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0, lighting: bool = False):
+        if exposure and lighting:                                # (host arguments: refused before anything touches the device)
+            raise ValueError("JointRefiner: exposure= and lighting= exclude each other (the lighting model contains the exposure's)")
         super().__init__(verts, faces, H, W, device, cull=cull)
         if vcolor is not None and texels is not None:
             raise ValueError("JointRefiner: vcolor= or texels=, not both")
         self._colours(vcolor, texels)
         self.weights = ops._joint_weights("JointRefiner", weights)
         self.tau_px, self.tau, self.tau_mm, self.iters, self.damping = tau_px, tau, tau_mm, int(iters), float(damping)
-        self.exposure, self.exposure_tau0 = bool(exposure), float(exposure_tau0)
+        self.exposure, self.exposure_tau0, self.lighting = bool(exposure), float(exposure_tau0), bool(lighting)
 
     def refine(self, pose: Tensor, intr: Tensor, *, mask_or_sdf: Optional[Tensor] = None, known: Optional[Tensor] = None,
                image: Optional[Tensor] = None, depth: Optional[Tensor] = None, frame: Optional[Tensor] = None,
@@ -110,4 +113,5 @@ class JointRefiner(_MeshRefiner):
         return AttrDict(ops.joint_align(self.verts, self.faces, pose, intr, vcolor=self.vcolor, texels=self.texels, sdf=planes, image=image, depth=depth,
                                         weights=self.weights, tau_px=self.tau_px, tau=self.tau, tau_mm=self.tau_mm, iters=self.iters,
                                         damping=self.damping, frame=frame, masks=masks, workspace=self._workspace(pose.shape[0]),
-                                        visible_iou=known is not None, cull=self.cull, exposure=self.exposure, exposure_tau0=self.exposure_tau0))
+                                        visible_iou=known is not None, cull=self.cull, exposure=self.exposure, exposure_tau0=self.exposure_tau0,
+                                        lighting=self.lighting))

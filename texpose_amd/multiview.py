@@ -100,20 +100,22 @@ def init_model(pose: Tensor, cam: Tensor, group: Tensor, score: Optional[Tensor]
 
 class MultiViewRefiner(_MeshRefiner):
     """Multi-view refinement for batches of views of one mesh at H x W with the mesh (and its colours) on the device and a workspace per
-    batch size; the keywords are JointRefiner's.  ``refine`` returns ops.multiview_align's dict: 'model' [Gr,3,4], the per-view 'pose'
+    batch size; the keywords are JointRefiner's (``lighting`` fits one light per VIEW).  ``refine`` returns ops.multiview_align's dict: 'model' [Gr,3,4], the per-view 'pose'
     [B,3,4], and the rest."""
     _new_workspace = staticmethod(ops.multiview_align_workspace)
 
     def __init__(self, verts: Tensor, faces: Tensor, H: int, W: int, device="cuda:0", *, vcolor: Optional[Tensor] = None,
                  weights=ops.JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, cull: bool = False,
-                 texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0):
+                 texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0, lighting: bool = False):
+        if exposure and lighting:                                # (host arguments: refused before anything touches the device)
+            raise ValueError("MultiViewRefiner: exposure= and lighting= exclude each other (the lighting model contains the exposure's)")
         super().__init__(verts, faces, H, W, device, cull=cull)
         if vcolor is not None and texels is not None:
             raise ValueError("MultiViewRefiner: vcolor= or texels=, not both")
         self._colours(vcolor, texels)
         self.weights = ops._joint_weights("MultiViewRefiner", weights)
         self.tau_px, self.tau, self.tau_mm, self.iters, self.damping = tau_px, tau, tau_mm, int(iters), float(damping)
-        self.exposure, self.exposure_tau0 = bool(exposure), float(exposure_tau0)
+        self.exposure, self.exposure_tau0, self.lighting = bool(exposure), float(exposure_tau0), bool(lighting)
 
     def refine(self, model: Tensor, cam: Tensor, group: Tensor, intr: Tensor, *, mask_or_sdf: Optional[Tensor] = None,
                known: Optional[Tensor] = None, image: Optional[Tensor] = None, depth: Optional[Tensor] = None,
@@ -137,4 +139,5 @@ class MultiViewRefiner(_MeshRefiner):
         return AttrDict(ops.multiview_align(self.verts, self.faces, model, cam, group, intr, vcolor=self.vcolor, texels=self.texels, sdf=planes,
                                             image=image, depth=depth, weights=self.weights, tau_px=self.tau_px, tau=self.tau, tau_mm=self.tau_mm,
                                             iters=self.iters, damping=self.damping, frame=frame, masks=masks, workspace=self._workspace(cam.shape[0]),
-                                            visible_iou=known is not None, cull=self.cull, exposure=self.exposure, exposure_tau0=self.exposure_tau0))
+                                            visible_iou=known is not None, cull=self.cull, exposure=self.exposure, exposure_tau0=self.exposure_tau0,
+                                            lighting=self.lighting))

@@ -1,8 +1,9 @@
 """K29-K33: the render-and-compare pose refiners -- the depth ICP, the photometric alignment, the masks' distance field, the silhouette
 alignment and the joint step of the three -- behind one table of terms: what a term's step takes, asks of the rasteriser and returns
 is said once in ``_TERMS``; one builder fills any term's args struct, one helper sizes every workspace and one driver runs all four
-loops.  K37, the exposure fit that a loop with a photometric term may run in front of each step (photo_exposure), and K38, the image
-pyramid of the photometric loop (image_down, surface_down, mask_down), are here too."""
+loops.  K37, the exposure fit that a loop with a photometric term may run in front of each step (photo_exposure), its sibling K40 for
+a light with a direction (photo_lighting), and K38, the image pyramid of the photometric loop (image_down, surface_down, mask_down),
+are here too."""
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -12,7 +13,8 @@ from .. import _lib
 from ._base import Tensor, _call, _f32, _intr_per_view, _lengths, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg
 
 __all__ = ["depth_icp_workspace", "depth_icp_step", "DEPTH_ICP_KEYS", "depth_icp", "photo_align_workspace", "photo_align_step", "PHOTO_ALIGN_KEYS",
-           "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "image_down", "surface_down", "mask_down",
+           "photo_align", "photo_exposure_workspace", "photo_exposure", "PHOTO_EXPOSURE_KEYS", "photo_lighting_workspace", "photo_lighting",
+           "PHOTO_LIGHTING_KEYS", "image_down", "surface_down", "mask_down",
            "image_pyramid", "mask_pyramid", "mask_sdf_workspace", "mask_sdf",
            "mask_known_from_others", "silhouette_align_workspace", "silhouette_align_step", "SILHOUETTE_ALIGN_KEYS", "silhouette_align",
            "JOINT_TERMS", "JOINT_WEIGHTS", "_joint_weights", "joint_align_workspace", "joint_align_step", "JOINT_ALIGN_KEYS", "joint_align",
@@ -52,8 +54,12 @@ def _term_bytes(terms, B: int, H: int, W: int, align: int = 1) -> list:
     return [(int(getattr(lib, t.workspace_bytes)(B, H, W)) + align - 1) // align * align for t in terms]
 
 
-def _new_workspace(op: str, terms, B: int, H: int, W: int, device) -> Tensor:
-    return _workspace_arg(op, None, sum(_term_bytes(terms, B, H, W)), device)
+def _new_workspace(op: str, terms, B: int, H: int, W: int, device, lighting: bool = False, tail_bytes: int = 0, align: int = 1) -> Tensor:
+    """``lighting``: for a loop with lighting=True, whose fit (K40) runs in the same bytes and may need more than the terms."""
+    need = sum(_term_bytes(terms, B, H, W, align)) + tail_bytes
+    if lighting:
+        need = max(need, int(_lib.load().tp_photo_lighting_workspace_bytes(B, H, W)))
+    return _workspace_arg(op, None, need, device)
 
 
 def _frame_planes(op: str, term: _Term, planes: Tensor, frame: Optional[Tensor], mask: Optional[Tensor], B: int, H: int, W: int, like: Tensor):
@@ -142,7 +148,7 @@ def _schedules(op: str, given, iters: int) -> list:
 
 
 def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, given, taus, *, damping, frame, workspace, cull,
-            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0, pyramid=None, multiview=None) -> Dict[str, Tensor]:
+            vcolor=None, texels=None, visible_iou=False, weights=None, exposure=False, exposure_tau0=2.0, pyramid=None, multiview=None, lighting=False) -> Dict[str, Tensor]:
     """The loop of every refiner over the terms of ``given`` that have planes: one pass per entry of ``taus`` (_schedules) of ONE
     mesh_raster call at the current poses, asked only for what these terms need, and one step from it, the last evaluate-only; a step
     that fails passes its pose on.  Without ``weights`` the step is the single term's own (its 'rms' is the cost carried); with them it
@@ -157,7 +163,16 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     built once, a pass at level l filters the full-size rendering down l times (surface_down, K38) and steps on the level's planes
     with the level's intrinsics; the last pass, the evaluation, runs at level 0.  ``multiview`` (K39, with ``weights``): dict(cam [B,3,4],
     group [B], index) -- ``pose`` is then the MODEL [Gr,3,4], the state the loop carries: every pass composes the B views' poses from it
-    (pose_compose), renders at those and takes multiview_align_step in place of the joint step -> also 'model' and 'views'."""
+    (pose_compose), renders at those and takes multiview_align_step in place of the joint step -> also 'model' and 'views'.
+    ``lighting`` with a photometric term, in place of ``exposure`` (its model contains K37's; both: ValueError): every pass also asks
+    the rasteriser for the face index and first fits ambient + directional shading and a bias per image and channel on the faces' own
+    normals (photo_lighting in place, K40; kept within that pass's ``tau`` of the light before, the first pass within
+    ``exposure_tau0`` of the plain colours) -> also 'light' [B,3,5], 'lighting_status' and 'lighting_flags' [B] of the last pass
+    (prefixed as above).  With ``pyramid`` the fit and the apply run on the FULL-SIZE rendering against the full-size photograph and
+    mask, before surface_down: normals need no pyramid, and the lit rendering is filtered as the photograph was.  The workspace must
+    then also hold tp_photo_lighting_workspace_bytes."""
+    if exposure and lighting:                                    # (a host argument: refused before anything touches the device)
+        raise ValueError("%s: exposure= and lighting= exclude each other (the lighting model contains the exposure's)" % op)
     joint = weights is not None
     cost = "chi2" if joint else "rms"
     verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose" if multiview is None else "model")
@@ -184,7 +199,11 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
     vcolor = None if vcolor is None else _f32(vcolor.detach(), "vcolor")
     texels = None if texels is None else _f32(texels.detach(), "texels")
     own_bytes = 0 if multiview is None else int(_lib.load().tp_multiview_workspace_bytes(B))
-    workspace = _workspace_arg(op, workspace, sum(_term_bytes([t for _, t in terms], B, H, W, 16 if joint else 1)) + own_bytes, pose.device, align=16)
+    need = sum(_term_bytes([t for _, t in terms], B, H, W, 16 if joint else 1)) + own_bytes
+    relit = bool(lighting) and any(t is _PHOTO for _, t in terms)
+    if relit:                                                    # (the fit's records are twice a term's: it runs before the step, in the same bytes)
+        need = max(need, int(_lib.load().tp_photo_lighting_workspace_bytes(B, H, W)))
+    workspace = _workspace_arg(op, workspace, need, pose.device, align=16)
     counting = next((t for _, t in terms if t.counts), None)
     if visible_iou:
         if counting is None:
@@ -193,7 +212,7 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
         if frame is not None:
             unknown = unknown[frame.clamp(0, unknown.shape[0] - 1).long()]
     colour = any(t.colour for _, t in terms)
-    ask = dict(H=H, W=W, vcolor=vcolor if colour else None, texels=texels if colour else None, face_ids=any(t.face_ids for _, t in terms),
+    ask = dict(H=H, W=W, vcolor=vcolor if colour else None, texels=texels if colour else None, face_ids=relit or any(t.face_ids for _, t in terms),
                normals=False, cull=cull)
     from .scene import mesh_raster                               # (looked up per call: tests and tools replace ops.scene.mesh_raster)
     mesh = dict(verts=verts, faces=faces)
@@ -212,14 +231,19 @@ def _refine(op: str, keys: tuple, verts: Tensor, faces: Tensor, pose: Tensor, in
             scaled = intr.clone()
             scaled[:, :2] *= 0.5 ** l
             coarse[l] = (photos[l], known[l], scaled)
-    lit = next((i for i, t in terms if t is _PHOTO), None) if exposure else None      # the photometric threshold's place in a pass's ``th``
-    fit = {}                                                     # the exposure fit of the pass before
+    photo_at = next((i for i, t in terms if t is _PHOTO), None)  # the photometric threshold's place in a pass's ``th``
+    lit = photo_at if exposure else None
+    fit = {}                                                     # the exposure (or lighting) fit of the pass before
 
     def one_pass(pose, th, last, level):                         # (a function: the rendered planes are released before the next pass renders)
         if multiview is not None:                                # (the state is the model; the views' poses follow from it)
             model, pose = pose, pose_compose(multiview["cam"], pose, multiview["group"])
         r = mesh_raster(verts, faces, pose, intr, **ask)
         photo, photo_mask, K = coarse[level] if level else (planes.get(_PHOTO.plane), masks.get(_PHOTO.name), intr)
+        if relit:                                                # (on the full-size rendering, whatever the level: in front of surface_down)
+            e = photo_lighting(verts, faces, r["face"], r["zbuf"], r["rgb"], pose, planes[_PHOTO.plane], tau=th[photo_at] if fit else exposure_tau0,
+                               light=fit.get("light"), frame=frame, mask=masks[_PHOTO.name], inplace=True, workspace=workspace)
+            fit.update(light=e["light"], lighting_status=e["status"], lighting_flags=e["flags"])
         for _ in range(level):                                   # (the full-size rendering filtered as the photograph was, never a coarse raster)
             r = surface_down(r["zbuf"], r["rgb"])
         if lit is not None:                                      # (in front of the step: it compares the colours under the photograph's exposure)
@@ -309,9 +333,10 @@ def depth_icp(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, depth: T
 
 
 # ------------------------------------------------------------------------------------------ K30
-def photo_align_workspace(B: int, H: int, W: int, device) -> Tensor:
-    """A workspace for photo_align_step / photo_align at B images of H x W (tp_photo_align_workspace_bytes); needs no clearing."""
-    return _new_workspace("photo_align", (_PHOTO,), B, H, W, device)
+def photo_align_workspace(B: int, H: int, W: int, device, lighting: bool = False) -> Tensor:
+    """A workspace for photo_align_step / photo_align at B images of H x W (tp_photo_align_workspace_bytes); needs no clearing.
+    ``lighting``: for photo_align(lighting=True), whose fit needs tp_photo_lighting_workspace_bytes."""
+    return _new_workspace("photo_align", (_PHOTO,), B, H, W, device, lighting)
 
 
 @_on_tensor_device
@@ -339,7 +364,7 @@ PHOTO_ALIGN_KEYS = ("pose", "inliers", "rms", "status", "inliers0", "rms0")
 def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr: Tensor, image: Tensor, *, tau=0.5, iters: int = 10,
                 damping: float = 1e-6, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None,
                 workspace: Optional[Tensor] = None, cull: bool = False, texels: Optional[Tensor] = None, exposure: bool = False,
-                exposure_tau0: float = 2.0, pyramid=None) -> Dict[str, Tensor]:
+                exposure_tau0: float = 2.0, pyramid=None, lighting: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one vertex-coloured mesh against a photograph (the rules are in the header, K30): ``iters`` + 1 passes of
     mesh_raster at the current poses (depth and colour, H x W = image's) followed by photo_align_step, the last with evaluate_only.
     ``tau``: one value, or ``iters`` + 1 host values for a coarse-to-fine schedule (the last is the final evaluation's).  -> 'pose'
@@ -359,14 +384,24 @@ def photo_align(verts: Tensor, faces: Tensor, vcolor: Tensor, pose: Tensor, intr
     with K's rows 0 and 1 times 2^-level; ``exposure`` fits on the level's planes.  ``tau`` keeps its ``iters`` + 1 entries, the final
     evaluation runs at level 0, and 'inliers0' / 'rms0' are the FIRST pass's, counted at its own level.  It widens the basin where the
     texture is fine against the start error (on the pinned cases it recovers starts the plain loop loses, and about doubles what the
-    loop tolerates); a level needs enough covered pixels (the pinned cases have 43 - 142 at the coarsest level; 21 - 24 diverge).  None: nothing else runs, bit for bit the call without it."""
+    loop tolerates); a level needs enough covered pixels (the pinned cases have 43 - 142 at the coarsest level; 21 - 24 diverge).  None: nothing else runs, bit for bit the call without it.
+    ``lighting``: the photograph was taken under a light with a DIRECTION (a lamp on one side), which no gain and bias can absorb: every
+    pass first fits ambient + directional shading (first-order spherical harmonics on the faces' own normals) and a bias per image and
+    channel and renders under them (photo_lighting, K40: three launches more per pass, and the passes render the face index too; DESIGN
+    section 30), kept as ``exposure`` keeps (``exposure_tau0``, then the pass's ``tau`` under the light before) -> also 'light' [B,3,5]
+    (per channel l0, l1, l2, l3, beta), 'lighting_status' and 'lighting_flags' [B] int32 of the last pass.  The model contains
+    ``exposure``'s: the two together are refused.  With ``pyramid`` the fit runs at full size, before the rendering is filtered down.
+    ``workspace`` must then be photo_align_workspace(B, H, W, device, lighting=True).  False: nothing else runs."""
     op, given = "photo_align", [(_PHOTO, image, tau, mask)]
+    if exposure and lighting:
+        raise ValueError("%s: exposure= and lighting= exclude each other (the lighting model contains the exposure's)" % op)
     if (vcolor is None) == (texels is None):
         raise ValueError("%s: exactly one of vcolor [V,3] and texels= [F,T,3] expected" % op)
     if pyramid is not None:
         _pass_levels(op, pyramid, int(iters))                    # (a host argument: refused before anything touches the device)
     return _refine(op, PHOTO_ALIGN_KEYS, verts, faces, pose, intr, given, _schedules(op, given, iters), damping=damping, frame=frame,
-                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, exposure=exposure, exposure_tau0=exposure_tau0, pyramid=pyramid)
+                   workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, exposure=exposure, exposure_tau0=exposure_tau0, pyramid=pyramid,
+                   lighting=lighting)
 
 
 # ------------------------------------------------------------------------------------------ K37
@@ -430,6 +465,78 @@ def photo_exposure(zbuf: Tensor, rgb: Tensor, image: Tensor, *, tau: float, gain
     a.rgb_out = res["rgb"].data_ptr() if apply else None
     a.workspace = workspace.data_ptr()
     _call("tp_photo_exposure", a)         # (tau, gain_range, min_var out of range, outputs overlapping inputs: the library's error)
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K40
+def photo_lighting_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for photo_lighting at B images of H x W (tp_photo_lighting_workspace_bytes: twice a term's); needs no clearing."""
+    return _workspace_arg("photo_lighting", None, int(_lib.load().tp_photo_lighting_workspace_bytes(B, H, W)), device)
+
+
+PHOTO_LIGHTING_KEYS = ("light", "count", "rms", "status", "flags")
+
+
+@_on_tensor_device
+def photo_lighting(verts: Tensor, faces: Tensor, face: Tensor, zbuf: Tensor, rgb: Tensor, pose: Tensor, image: Tensor, *, tau: float,
+                   light: Optional[Tensor] = None, frame: Optional[Tensor] = None, mask: Optional[Tensor] = None, gain_range=(0.25, 4.0),
+                   min_var: float = 1e-6, apply: bool = True, inplace: bool = False, workspace: Optional[Tensor] = None,
+                   out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """Ambient + directional shading and a bias per image and channel between B renderings and their photographs, and the renderings
+    under that fit (tp_photo_lighting, K40; the rules are in the header): verts [V,3], faces [F,3] int32, face / zbuf [B,H,W] and rgb
+    [B,H,W,3] (mesh_raster's planes of the mesh at ``pose``; taken as they are: a face index or a vertex index out of range gives a
+    pixel without a normal, never a read out of bounds), pose [B,3,4], image / frame / mask as photo_exposure's, ``light`` [B,3,5]
+    float32 (per channel l0, l1, l2, l3, beta: the light of the pass before, which decides with ``tau`` what is kept; None: (1, 0, 0,
+    0, 0)) -> 'light' [B,3,5] (image ~ (l0 + l1 n_x + l2 n_y + l3 n_z) rgb + beta by least squares over the kept pixels, n the
+    face's unit normal in the camera frame, towards the camera; a channel whose 5 x 5 system fails the pivot rule, or whose solution
+    leaves ``gain_range`` in l0 or has |(l1, l2, l3)| > l0, takes photo_exposure's gain and bias with l1 = l2 = l3 = 0), 'count' [B]
+    int32, 'rms' [B], 'status' [B] int32 (0 ok, 1 fewer than 6 kept pixels, 3 not finite: the light is then the incoming one bit for
+    bit), 'flags' [B] int32 (_lib.LIGHTING_FALLBACK << k beside photo_exposure's bits) and, with ``apply``, 'rgb' [B,H,W,3]: the
+    shading times rgb plus beta on the covered pixels (the ambient form l0 rgb + beta where a pixel has no normal), the rest copied;
+    with ``inplace`` it is ``rgb`` itself, rewritten.  ``workspace``: photo_lighting_workspace(B, H, W); ``out``: any of these tensors
+    to write into (out['light'] must not be ``light``).  Three launches (two without ``apply``), no atomics, bit-identical from run to
+    run, safe under torch.cuda.graph."""
+    op = "photo_lighting"
+    verts = _points(op, verts, "verts")
+    faces = _want_gpu(op, faces, "faces", torch.int32, None)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise ValueError("%s: faces [F,3] expected, got %s" % (op, tuple(faces.shape)))
+    zbuf = _want_gpu(op, zbuf, "zbuf", torch.float32, None)
+    if zbuf.dim() != 3 or zbuf.numel() == 0:
+        raise ValueError("%s: zbuf [B,H,W] expected, got %s" % (op, tuple(zbuf.shape)))
+    B, H, W = zbuf.shape
+    face = _want_gpu(op, face, "face", torch.int32, (B, H, W))
+    rgb = _want_gpu(op, rgb, "rgb", torch.float32, (B, H, W, 3))
+    pose = _poses(op, pose, "pose")
+    if pose.shape[0] != B:
+        raise ValueError("%s: pose [B=%d,3,4] expected, got %s" % (op, B, tuple(pose.shape)))
+    image, frame, mask, Ft = _frame_planes(op, _PHOTO, image, frame, mask, B, H, W, zbuf)
+    light = None if light is None else _want_gpu(op, light, "light", torch.float32, (B, 3, 5))
+    try:
+        lo, hi = (float(x) for x in gain_range)
+    except (TypeError, ValueError):
+        raise ValueError("%s: gain_range must be two host values (min, max), got %r" % (op, gain_range)) from None
+    spec = {"light": (torch.float32, (B, 3, 5)), "count": (torch.int32, (B,)), "rms": (torch.float32, (B,)), "status": (torch.int32, (B,)),
+            "flags": (torch.int32, (B,))}
+    if apply and inplace:
+        if out is not None and "rgb" in out:
+            raise ValueError("%s: out['rgb'] and inplace=True exclude each other" % op)
+    elif apply:
+        spec["rgb"] = (torch.float32, (B, H, W, 3))
+    res = _outputs(op, out, spec, zbuf.device, partial=True)
+    workspace = _workspace_arg(op, workspace, int(_lib.load().tp_photo_lighting_workspace_bytes(B, H, W)), zbuf.device, align=16)
+    a = _lib.PhotoLightingArgs()
+    a.verts, a.faces, a.face, a.zbuf, a.rgb, a.pose = (t.data_ptr() for t in (verts, faces, face, zbuf, rgb, pose))
+    a.image, a.frame, a.mask, a.light_in = image.data_ptr(), _ptr(frame), _ptr(mask), _ptr(light)
+    a.V, a.F, a.B, a.Ft, a.H, a.W = verts.shape[0], faces.shape[0], B, Ft, H, W
+    a.tau, a.gain_min, a.gain_max, a.min_var = float(tau), lo, hi, float(min_var)
+    for k in PHOTO_LIGHTING_KEYS:
+        setattr(a, k, res[k].data_ptr())
+    if apply and inplace:
+        res["rgb"] = rgb
+    a.rgb_out = res["rgb"].data_ptr() if apply else None
+    a.workspace = workspace.data_ptr()
+    _call("tp_photo_lighting", a)         # (tau, gain_range, min_var out of range, outputs overlapping inputs: the library's error)
     return res
 
 
@@ -658,10 +765,10 @@ def _joint_weights(op: str, weights) -> tuple:
     return w
 
 
-def joint_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Tensor:
+def joint_align_workspace(B: int, H: int, W: int, device, terms: int = 3, lighting: bool = False) -> Tensor:
     """A workspace for joint_align_step / joint_align at B images of H x W with ``terms`` terms present (each term's own
-    ``*_workspace_bytes``, one after the other); needs no clearing."""
-    return _new_workspace("joint_align", _TERMS[:int(terms)], B, H, W, device)
+    ``*_workspace_bytes``, one after the other); needs no clearing.  ``lighting``: for joint_align(lighting=True)."""
+    return _new_workspace("joint_align", _TERMS[:int(terms)], B, H, W, device, lighting)
 
 
 def _step_terms(op: str, pose: Tensor, intr: Tensor, given: dict, damping, out, workspace, tail_bytes: int = 0):
@@ -748,7 +855,8 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
                 image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS, tau_px=4.0, tau=0.5, tau_mm=20.0,
                 iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None, masks: Optional[dict] = None,
                 workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
-                texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0) -> Dict[str, Tensor]:
+                texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0,
+                lighting: bool = False) -> Dict[str, Tensor]:
     """Refine B poses of one mesh against whichever of the measured outline (``sdf`` [Ft,H,W], mask_sdf's field), the photograph
     (``image`` [Ft,H,W,3], with the mesh's ``vcolor`` [V,3]) and the measured depth (``depth`` [Ft,H,W], mm) are given, ALL rows in
     one Gauss-Newton system per step (K33): ``iters`` + 1 passes of ONE mesh_raster call at the current poses, asked
@@ -765,8 +873,12 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     torch.cuda.graph.  ``cull``: the passes render with mesh_raster(cull=True), same bits.  ``texels`` [F,T,3] in place of ``vcolor``:
     the photometric term's renders take their colour from the mesh's face texels (mesh_raster(texels=), K35); at most one of the two.
     ``exposure`` (with ``image``): as photo_align's, for the photometric term -> also 'photo_gain' / 'photo_bias' [B,3] and
-    'photo_exposure_status' [B] int32 of the last pass; without ``image`` it does nothing."""
+    'photo_exposure_status' [B] int32 of the last pass; without ``image`` it does nothing.  ``lighting`` (with ``image``): as
+    photo_align's, in place of ``exposure`` (both: refused) -> also 'photo_light' [B,3,5], 'photo_lighting_status' and
+    'photo_lighting_flags' [B] int32; ``workspace`` must then be joint_align_workspace(..., lighting=True)."""
     op = "joint_align"
+    if exposure and lighting:
+        raise ValueError("%s: exposure= and lighting= exclude each other (the lighting model contains the exposure's)" % op)
     if vcolor is not None and texels is not None:
         raise ValueError("%s: vcolor= or texels=, not both" % op)
     w = _joint_weights(op, weights)
@@ -782,7 +894,7 @@ def joint_align(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, vco
     # (the dict has had its cost keys behind inliers0 since K33; JOINT_ALIGN_KEYS names them, not their order)
     return _refine(op, ("pose", "inliers", "status", "inliers0", "chi2", "chi20"), verts, faces, pose, intr, given, taus, damping=damping, frame=frame,
                    workspace=workspace, cull=cull, vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w, exposure=exposure,
-                   exposure_tau0=exposure_tau0)
+                   exposure_tau0=exposure_tau0, lighting=lighting)
 
 
 # ------------------------------------------------------------------------------------------ K39
@@ -820,11 +932,10 @@ def pose_compose(cam: Tensor, model: Tensor, group: Tensor, out: Optional[Tensor
     return res
 
 
-def multiview_align_workspace(B: int, H: int, W: int, device, terms: int = 3) -> Tensor:
+def multiview_align_workspace(B: int, H: int, W: int, device, terms: int = 3, lighting: bool = False) -> Tensor:
     """A workspace for multiview_align_step / multiview_align at B views of H x W with ``terms`` terms present (each term's own part,
-    then tp_multiview_workspace_bytes(B)); needs no clearing."""
-    terms = _TERMS[:int(terms)]
-    return _workspace_arg("multiview_align", None, sum(_term_bytes(terms, B, H, W, 16)) + int(_lib.load().tp_multiview_workspace_bytes(B)), device)
+    then tp_multiview_workspace_bytes(B)); needs no clearing.  ``lighting``: for multiview_align(lighting=True)."""
+    return _new_workspace("multiview_align", _TERMS[:int(terms)], B, H, W, device, lighting, int(_lib.load().tp_multiview_workspace_bytes(B)), 16)
 
 
 @_on_tensor_device
@@ -877,7 +988,8 @@ def multiview_align(verts: Tensor, faces: Tensor, model: Tensor, cam: Tensor, gr
                     sdf: Optional[Tensor] = None, image: Optional[Tensor] = None, depth: Optional[Tensor] = None, weights=JOINT_WEIGHTS,
                     tau_px=4.0, tau=0.5, tau_mm=20.0, iters: int = 20, damping: float = 1e-6, frame: Optional[Tensor] = None,
                     masks: Optional[dict] = None, workspace: Optional[Tensor] = None, visible_iou: bool = False, cull: bool = False,
-                    texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0, pyramid=None) -> Dict[str, Tensor]:
+                    texels: Optional[Tensor] = None, exposure: bool = False, exposure_tau0: float = 2.0, pyramid=None,
+                    lighting: bool = False) -> Dict[str, Tensor]:
     """Refine ONE pose of one mesh per group of views whose cameras are known (K39): model [Gr,3,4] (model -> world,
     the start), cam [B,3,4] (world -> camera), group [B] int32, intr [B,3,3] or [3,3]; the measurements and every other keyword are
     joint_align's, per VIEW.  ``iters`` + 1 passes of pose_compose, ONE mesh_raster call at the composed poses and
@@ -885,8 +997,11 @@ def multiview_align(verts: Tensor, faces: Tensor, model: Tensor, cam: Tensor, gr
     loose, is pinned by the group's other views.  One term alone is allowed.  -> 'model' [Gr,3,4], 'pose' [B,3,4] (cam o model),
     'inliers', 'views' [Gr] int32 and 'chi2' [Gr] of the last pass, 'status' [Gr] of the last step taken, 'inliers0' / 'chi20' of the
     start, the last pass's per-term keys [B], and 'iou' / 'iou0' (and the visible ones) [B] as joint_align.  A group whose step fails
-    passes its model on.  ``pyramid`` is refused.  Bit-identical from run to run, safe under torch.cuda.graph."""
+    passes its model on.  ``pyramid`` is refused.  Bit-identical from run to run, safe under torch.cuda.graph.  ``lighting``: as
+    joint_align's, one light per VIEW (a light shared by a group's views is left out), fitted at the view's composed pose."""
     op = "multiview_align"
+    if exposure and lighting:
+        raise ValueError("%s: exposure= and lighting= exclude each other (the lighting model contains the exposure's)" % op)
     if pyramid is not None:
         raise ValueError("%s: pyramid= goes with the photometric term alone" % op)
     if vcolor is not None and texels is not None:
@@ -904,4 +1019,4 @@ def multiview_align(verts: Tensor, faces: Tensor, model: Tensor, cam: Tensor, gr
     cam, model, group = _group_args(op, cam, model, group)
     return _refine(op, MULTIVIEW_ALIGN_KEYS, verts, faces, model, intr, given, taus, damping=damping, frame=frame, workspace=workspace, cull=cull,
                    vcolor=vcolor, texels=texels, visible_iou=visible_iou, weights=w, exposure=exposure, exposure_tau0=exposure_tau0,
-                   multiview=dict(cam=cam, group=group, index=multiview_group_index(group, model.shape[0])))
+                   multiview=dict(cam=cam, group=group, index=multiview_group_index(group, model.shape[0])), lighting=lighting)

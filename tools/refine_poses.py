@@ -5,7 +5,7 @@
     python tools/refine_poses.py --scene SCENE_DIR --ply [ID=]PATH [--ply ID=PATH ...] --est RESULTS.csv --out REFINED.csv
                                  [--silhouette [--occluders | --known DIR] [--depth | --rgb]] [--rgb]
                                  [--joint [--iters-joint N] [--weights SIL RGB DEPTH]] [--cull-raster] [--texels [ID=]PATH]
-                                 [--exposure] [--pyramid N ...] [--multiview]
+                                 [--exposure | --lighting] [--pyramid N ...] [--multiview]
 
 --scene: a BOP scene folder with scene_camera.json (cam_K and depth_scale per frame) and depth/{frame:06d}.png (16 bit; 0: no
 measurement).  --est: scene_id,im_id,obj_id,score,R,t,time rows (the file tools/pnp_poses.py writes); --scene-id keeps the rows of one
@@ -57,6 +57,10 @@ colours, --ply may be colourless, and the file is refused if it was baked for ot
 --exposure (with --rgb, alone or under --joint): the photographs were taken under another exposure, white balance or
 light than the mesh's colours.  Every pass first fits a gain and a bias per image and channel between rendering and photograph
 (ops.photo_exposure, K37) and compares the colours under them.
+
+--lighting (with --rgb, alone, under --joint or with --multiview; not together with --exposure, whose model it
+contains): the photographs were taken under a light with a direction, a lamp on one side of the object.  Every pass first fits ambient +
+directional shading on the faces' normals and a bias per image and channel (ops.photo_lighting, K40) and compares the colours under them.
 
 --pyramid N [N ...] (with --rgb, not under --joint): coarse to fine on an image pyramid, for estimates further off
 than the texture's detail lets the one-pixel gradient see.  The step counts per level, the coarsest first, adding up to --iters-rgb:
@@ -135,6 +139,7 @@ def main(argv=None):
     ap.add_argument("--cull-raster", action="store_true", help="render with the culled rasteriser: the same poses, faster on large meshes")
     ap.add_argument("--texels", action="append", default=[], metavar="[ID=]PATH", help="with --rgb: face texels (bake_texture --texel-res)")
     ap.add_argument("--exposure", action="store_true", help="with --rgb: fit a gain and a bias per image and channel in every pass")
+    ap.add_argument("--lighting", action="store_true", help="with --rgb: fit ambient + directional shading and a bias per image and channel in every pass")
     ap.add_argument("--pyramid", type=int, nargs="+", default=None, metavar="N", help="with --rgb: steps per pyramid level, the coarsest first")
     ap.add_argument("--multiview", action="store_true", help="all rows of one object are views of one pose (needs cam_R_w2c / cam_t_w2c)")
     ap.add_argument("--batch", type=int, default=64)
@@ -168,6 +173,10 @@ def main(argv=None):
         sys.exit("refine_poses: --texels goes with --rgb")
     if a.exposure and not a.rgb:
         sys.exit("refine_poses: --exposure goes with --rgb")
+    if a.lighting and not a.rgb:
+        sys.exit("refine_poses: --lighting goes with --rgb")
+    if a.lighting and a.exposure:
+        sys.exit("refine_poses: --lighting or --exposure, not both (the lighting model contains the exposure's)")
     if a.pyramid and (not a.rgb or one_loop):
         sys.exit("refine_poses: --pyramid goes with --rgb" + (", and not under --joint" if a.joint else ", and not with --multiview" if a.multiview else ""))
     if a.pyramid and (min(a.pyramid) < 0 or sum(a.pyramid) != a.iters_rgb):
@@ -282,14 +291,14 @@ def main(argv=None):
             if one_loop and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 refiner = (multiview.MultiViewRefiner if a.multiview else joint.JointRefiner)(verts, faces, H, W, dev, vcolor=vcolor, texels=texels,
                                              weights=a.weights or ops.JOINT_WEIGHTS, tau_px=tau_px, tau=tau_rgb, tau_mm=tau, iters=a.iters_joint,
-                                             damping=a.damping, cull=a.cull_raster, exposure=a.exposure)
+                                             damping=a.damping, cull=a.cull_raster, exposure=a.exposure, lighting=a.lighting)
             if a.silhouette and not one_loop and (outline is None or (outline.H, outline.W) != (H, W)):
                 outline = silhouette.SilhouetteRefiner(verts, faces, H, W, dev, tau_px=tau_px, iters=a.iters_sil, damping=a.damping, cull=a.cull_raster)
             if second and (refiner is None or (refiner.H, refiner.W) != (H, W)):
                 if a.rgb:
                     refiner = photo_align.PhotoRefiner(verts, faces, vcolor, H, W, dev, tau=tau_rgb, iters=a.iters_rgb,
                                                        damping=a.damping, cull=a.cull_raster, texels=texels, exposure=a.exposure,
-                                                       pyramid=a.pyramid)
+                                                       pyramid=a.pyramid, lighting=a.lighting)
                 else:
                     refiner = icp.DepthRefiner(verts, faces, H, W, dev, tau_mm=tau, iters=a.iters, damping=a.damping, cull=a.cull_raster)
             pose = np.stack([np.concatenate([rows[i][4], rows[i][5].reshape(3, 1)], 1) for i in part]).astype(np.float32)
