@@ -1852,6 +1852,57 @@ typedef struct tp_photo_lighting_args {
 size_t tp_photo_lighting_workspace_bytes(int B, int H, int W);  /* 512 * B * ceil(H * W / 1024); 0 for non-positive sizes */
 int tp_photo_lighting(const tp_photo_lighting_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K41  the per-pixel step between K35's shading and K36's adjoint when face texels are fitted as an ALBEDO under one first-order SH
+ *      light per view (texpose_amd/ops/scene.py: face_texel_light; texpose_amd/face_texels.py: FaceTexelFitter(lighting=True); restated
+ *      in tests/face_texel_light_ref.py; the project's own step, no reference code).  The fitter minimises
+ *        sum_b sum_p m_p | s_b(n_p) * (S x)_p + beta_b - I_p |^2 + lam |x - prior|^2
+ *      over the node colours x and the lights; with the lights fixed its normal equations are (S^T D S + lam) x = S^T m s (I - beta) +
+ *      lam prior with D = m s^2, and this call turns S x (or S p) into what the adjoint consumes.  face is K19's plane of the mesh
+ *      (verts, faces) at `pose`, light [B,3,5] per channel (l0, l1, l2, l3, beta) as K40 writes it, colour [B,H,W,3] K35's shading.
+ *      Per pixel p of image b and channel k:
+ *        covered iff 0 <= face < F;  m = weight[p] (1 where weight is NULL)
+ *        the pixel is OFF -- and writes +0 to grad and diag and adds nothing to the sums -- where it is not covered, where m is not
+ *        finite or m <= 0, and where one of its three colours (or, in residual mode, of its three image values) is not finite
+ *        s_k = K40's apply shading: ((l0 + l1 n_x) + l2 n_y) + l3 n_z in fp64 from the fp32 light and the pixel's VALID NORMAL (K40's
+ *              steps 5 - 7), rounded to fp32 ONCE; l0 itself where the pixel has no valid normal
+ *        everything below is fp32, one rounding per operation, evaluated as written (no contraction):
+ *        a_k = m * s_k
+ *        residual mode (image given):  q_k = s_k * c_k;  p_k = q_k + beta_k  (K40's two operations: p is its applied rendering bit
+ *                                      for bit);  e_k = I_k - p_k;  grad_k = a_k * e_k
+ *        operator mode (image NULL):   q_k = s_k * c_k;  grad_k = a_k * q_k
+ *        diag_k = a_k * s_k   (where diag is given: the diagonal D of the operator; one adjoint of it is the preconditioner)
+ *      Every pixel of grad (and diag) is written: the outputs need no clearing and are a function of the inputs alone.
+ *      sums [B,2] (residual mode only): [0] the sum over the pixels that are on of (double)m * (((double)e_0 e_0 + (double)e_1 e_1) +
+ *      (double)e_2 e_2), [1] the sum of (double)m, in fp64 in K30's order: a thread owns four consecutive flat pixels (ascending), a
+ *      workgroup 1024; butterfly sums inside a wave, the four waves in ascending order, one record of two doubles per (image, tile)
+ *      in the workspace, and a second kernel that adds an image's records in ascending tile order.  No atomics: bit-identical from
+ *      run to run and under graph replay.
+ *      One launch on the stream, two with sums.  Refused (-1, tp_last_error) before anything is launched: a non-positive size, B >
+ *      65535, H * W >= 2^31, a null verts, faces, face, pose, light, colour or grad, sums without image, sums without a workspace or
+ *      with one that is not 8-byte aligned, and an output (grad, diag, sums, the workspace) that overlaps an input or another output.
+ *      No input value causes an access out of bounds: face and the vertex indices are checked before use as in K40.  No allocation,
+ *      no host synchronisation.  Safe to capture.
+ *      Left out: the shading fused into K35 / K36 themselves, one light for several views, second-order SH, a robust loss.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_face_texel_light_args {
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3]; a face with an index outside [0, V) has no normal */
+  const int32_t* face;       /* [B,H,W] K19's face plane (any values); outside [0, F): not covered */
+  const float* pose;         /* [B,3,4] the poses the plane was rendered at */
+  const float* light;        /* [B,3,5] per channel (l0, l1, l2, l3, beta) */
+  const float* colour;       /* [B,H,W,3] S x (residual mode) or S p (operator mode) */
+  const float* image;        /* [B,H,W,3] the photographs, or NULL: operator mode */
+  const float* weight;       /* [B,H,W] m, or NULL: 1 */
+  int V, F, B, H, W;
+  float* grad;               /* [B,H,W,3] out */
+  float* diag;               /* [B,H,W,3] out or NULL */
+  double* sums;              /* [B,2] out or NULL; residual mode only */
+  void* workspace;           /* with sums: tp_face_texel_light_workspace_bytes(B, H, W) bytes, 8-byte aligned; needs no clearing */
+} tp_face_texel_light_args;
+size_t tp_face_texel_light_workspace_bytes(int B, int H, int W);  /* 16 * B * ceil(H * W / 1024); 0 for non-positive sizes */
+int tp_face_texel_light(const tp_face_texel_light_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,55 +17,14 @@
 #include "tp_common.h"
 #include "pose_gn.h"
 #include "pose_terms.h"
+#include "face_normal.h"
 
 namespace {
 constexpr int kLitRecord = 64;                         // n, then per channel 15 (x x^T, upper triangle, row-major) + 5 (x o) + o o
 constexpr int kLitChannel = 21;
 constexpr int kLitMinCount = 6;
 
-__device__ __forceinline__ bool finite3(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 __device__ __forceinline__ bool covered(float z) { return z > 0.f && isfinite(z); }
-
-// the four values of a thread's pixels from p0 on, `past` beyond the plane
-template <bool VEC, class T, class T4>
-__device__ __forceinline__ void load_four(const T* p, int64_t p0, int64_t plane, T past, T (&v)[kGnPix]) {
-#pragma unroll
-  for (int k = 0; k < kGnPix; ++k) v[k] = past;
-  if constexpr (VEC) {
-    if (p0 < plane) {                                                            // (plane % 4 == 0: the four are inside together)
-      const T4 q = *reinterpret_cast<const T4*>(p + p0);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kGnPix; ++k)
-      if (p0 + k < plane) v[k] = p[p0 + k];
-  }
-}
-
-// The valid normal of face f at the pose T [12] (steps 5 - 7 of the header): false where f or one of its vertex indices is out of
-// range or the normal has no finite positive length; nothing is read out of bounds.
-__device__ __forceinline__ bool face_normal(const float* verts, const int32_t* faces, int V, int F, int f, const float* T, V3& n) {
-  if (f < 0 || f >= F) return false;
-  const int32_t* idx = faces + (int64_t)f * 3;
-  const int i0 = idx[0], i1 = idx[1], i2 = idx[2];
-  if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) return false;
-  const float *p0 = verts + (int64_t)i0 * 3, *p1 = verts + (int64_t)i1 * 3, *p2 = verts + (int64_t)i2 * 3;
-  const V3 v0 = {(double)p0[0], (double)p0[1], (double)p0[2]}, v1 = {(double)p1[0], (double)p1[1], (double)p1[2]},
-           v2 = {(double)p2[0], (double)p2[1], (double)p2[2]};
-  const V3 m = cross(v1 - v0, v2 - v0);
-  const V3 r0 = {(double)T[0], (double)T[1], (double)T[2]}, r1 = {(double)T[4], (double)T[5], (double)T[6]},
-           r2 = {(double)T[8], (double)T[9], (double)T[10]};
-  V3 u = {dot(r0, m), dot(r1, m), dot(r2, m)};
-  const double d = dot(u, u);
-  if (!(isfinite(d) && d > 0.0)) return false;
-  const double len = sqrt(d);
-  u = {u.x / len, u.y / len, u.z / len};
-  const V3 xc = {dot(r0, v0) + (double)T[3], dot(r1, v0) + (double)T[7], dot(r2, v0) + (double)T[11]};
-  if (dot(u, xc) > 0.0) u = {-u.x, -u.y, -u.z};
-  n = u;
-  return true;
-}
 
 // One channel's 21 sums over the thread's kept pixels, the wave's butterfly and lane 0's store; the caller's wave has a kept pixel
 template <int CH>
@@ -318,17 +277,6 @@ __global__ __launch_bounds__(tp::kWave) void lighting_solve_kernel(tp_photo_ligh
   a.flags[b] = bits[0] | bits[1] | bits[2];
 }
 
-// the three shadings of a covered pixel: fp64 from the fp32 light and the valid normal, rounded once; l0 itself without a normal
-__device__ __forceinline__ void shade_of(const tp_photo_lighting_args& a, const float (&l)[15], int f, const float* T, float (&s)[3]) {
-  V3 n;
-  const bool valid = face_normal(a.verts, a.faces, a.V, a.F, f, T, n);
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float* q = l + 5 * ch;
-    s[ch] = valid ? (float)((((double)q[0] + (double)q[1] * n.x) + (double)q[2] * n.y) + (double)q[3] * n.z) : q[0];
-  }
-}
-
 // INPLACE: rgb_out is rgb; a pixel without a surface is then not written
 template <bool VEC, bool INPLACE>
 __global__ __launch_bounds__(kGnBlock) void lighting_apply_kernel(tp_photo_lighting_args a) {
@@ -365,7 +313,7 @@ __global__ __launch_bounds__(kGnBlock) void lighting_apply_kernel(tp_photo_light
     for (int k = 0; k < kGnPix; ++k) {
       if (!(cov >> k & 1u)) continue;
       float s[3];
-      shade_of(a, l, fs[k], T, s);
+      shade_of(a.verts, a.faces, a.V, a.F, l, fs[k], T, s);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = tp::add_rn(tp::mul_rn(s[ch], v[3 * k + ch]), l[5 * ch + 4]);
     }
@@ -388,7 +336,7 @@ __global__ __launch_bounds__(kGnBlock) void lighting_apply_kernel(tp_photo_light
       const bool on = cov >> k & 1u;
       if (INPLACE && !on) continue;
       float s[3] = {0.f, 0.f, 0.f};
-      if (on) shade_of(a, l, pf[p0 + k], T, s);
+      if (on) shade_of(a.verts, a.faces, a.V, a.F, l, pf[p0 + k], T, s);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
         const float c = pc[(p0 + k) * 3 + ch];

@@ -14,6 +14,8 @@ Gradients with respect to the texture come from K36 (tp_face_texel_shade_bwd, DE
 shading: ``autograd_ops.face_texel_shade`` (per-slot texels), ``shade_nodes`` (node colours shared between faces) and
 ``FaceTexelFitter``, which fits the node colours to photographs by preconditioned conjugate gradients on the quantity the refiners
 consume: the difference between the shaded render and the photograph.  No gradients with respect to pose or vertices, first order only.
+``FaceTexelFitter(lighting=True)`` (K41 tp_face_texel_light) fits the colours as an albedo under one first-order
+SH light per view, for photographs whose light differs from view to view.
 """
 from __future__ import annotations
 
@@ -209,12 +211,27 @@ class FaceTexelFitter:
     ``weight``: the lumped diagonal of S^T S).  S x is ops.face_texel_shade, S^T g is ops.face_texel_shade_bwd with the node index:
     deterministic, so a fit is bit-identical from run to run.  An iteration is one shade and one adjoint over the stored views for the
     step and one more shade for the training rms it reports.  A quadratic loss only (a robust loss goes through ``shade_nodes`` and
-    an optimiser); the result is not clamped: the caller does that."""
+    an optimiser); the result is not clamped: the caller does that.
 
-    def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", lam: float = 0.1, iters: int = 4, cull: bool = False):
+    ``lighting=True`` (K41) fits x as an ALBEDO under one first-order SH light per stored view: it minimises
+        sum_b sum_p m_p |s_b(n_p) (S x)_p + beta_b - I_p|^2 + lam |x - prior|^2
+    over x and the lights (l0, l1, l2, l3, beta per view and channel; s = l0 + l1 n_x + l2 n_y + l3 n_z on the face's normal, as
+    ops.photo_lighting) by ``rounds`` alternations: a light step (ops.photo_lighting of the unlit render S x against each photograph,
+    ``tau0`` in round 0 and ``tau`` afterwards, l0 within ``gain_range``) and ``iters`` conjugate-gradient steps on (S^T m s^2 S + lam) x
+    = S^T m s (I - beta) + lam prior, restarted from the current x, preconditioned per node and channel with S^T (m s^2) + lam; between
+    shade and adjoint sits ops.face_texel_light.  From round 1 on a view whose light fit fails (status != 0) or falls back to the
+    ambient-only form in a channel keeps the light it had.  The gauge (x scaled by a, every l0 .. l3 by 1 / a) is pinned by the prior
+    alone; the result's ``gain`` is the mean l0 per channel, for a caller who wants to normalise.  ``lighting=False`` is the fit above."""
+
+    def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", lam: float = 0.1, iters: int = 4, cull: bool = False,
+                 lighting: bool = False, rounds: int = 6, tau: float = 0.5, tau0: float = 2.0, gain_range=(0.25, 4.0)):
         self.R, self.T, self.H, self.W = int(R), texel_count(R), int(H), int(W)
         if not (lam > 0 and int(iters) >= 0):
             raise ValueError("FaceTexelFitter: lam > 0 and iters >= 0 expected")
+        if lighting and not (int(rounds) >= 1 and tau > 0 and tau0 > 0):
+            raise ValueError("FaceTexelFitter: rounds >= 1, tau > 0 and tau0 > 0 expected with lighting")
+        self.lighting, self.rounds, self.tau, self.tau0 = bool(lighting), int(rounds), float(tau), float(tau0)
+        self.gain_range = tuple(float(g) for g in gain_range)
         self.lam, self.iters, self.cull, self.device = float(lam), int(iters), bool(cull), torch.device(device)
         self.verts_host = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
         self.faces_host = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
@@ -224,7 +241,8 @@ class FaceTexelFitter:
         self.faces = torch.from_numpy(self.faces_host).to(self.device)
         self.node_index = torch.from_numpy(self.node_index_host).to(self.device)
         self._node_index32 = self.node_index.to(torch.int32)
-        self._views = []                                 # (face, rgb, weight, pose, intr) per add_views call
+        self._faces_lit = self.faces.contiguous()        # (K40 and K41 take the faces as they are: a PLY reader may hand over a strided view)
+        self._views = []                                 # (face, rgb, weight, pose, intr) per add_views call; + (zbuf, mask) with lighting
 
     @property
     def views(self) -> int:
@@ -237,7 +255,7 @@ class FaceTexelFitter:
         """rgb [B,H,W,3] photographs, pose_mm [B,3,4] (t in mm), intr [B,3,3] or [3,3]; ``face`` [B,H,W] int32: the base mesh's face
         plane at those poses (None: rasterised here); ``weight`` [B,H,W] per pixel (None: 1 on covered pixels whose four neighbours are
         covered too, 0 elsewhere: the rim pixels of a photograph mix in background).  Face plane, photograph and weight stay on the
-        device until reset(): 20 bytes per pixel."""
+        device until reset(): 20 bytes per pixel (with lighting 25: the depth plane the light step reads as "covered" and its mask)."""
         pose = torch.as_tensor(pose_mm, dtype=torch.float32).to(self.device).contiguous()
         B = pose.shape[0]
         K = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
@@ -245,15 +263,22 @@ class FaceTexelFitter:
         rgb = torch.as_tensor(rgb).detach().to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(rgb.shape) != (B, self.H, self.W, 3):
             raise ValueError("FaceTexelFitter.add_views: rgb %s expected, got %s" % ((B, self.H, self.W, 3), tuple(rgb.shape)))
+        zbuf = None
         if face is None:
-            face = ops.mesh_raster(self.verts, self.faces, pose, K, H=self.H, W=self.W, normals=False, cull=self.cull)["face"]
+            planes = ops.mesh_raster(self.verts, self.faces, pose, K, H=self.H, W=self.W, normals=False, cull=self.cull)
+            face, zbuf = planes["face"], planes["zbuf"]
         face = torch.as_tensor(face).to(device=self.device, dtype=torch.int32).contiguous()
         if tuple(face.shape) != (B, self.H, self.W):
             raise ValueError("FaceTexelFitter.add_views: face %s expected, got %s" % ((B, self.H, self.W), tuple(face.shape)))
         if weight is None:
             weight = inner_coverage(face, self.faces.shape[0]).float()
         weight = torch.as_tensor(weight).detach().to(device=self.device, dtype=torch.float32).reshape(B, self.H, self.W).contiguous()
-        self._views.append((face, rgb, weight, pose, K))
+        if not self.lighting:
+            self._views.append((face, rgb, weight, pose, K))
+            return
+        if zbuf is None:                                 # (the light step reads depth only as "covered")
+            zbuf = torch.where((face >= 0) & (face < self.faces.shape[0]), 1.0, -1.0).float()
+        self._views.append((face, rgb, weight, pose, K, zbuf.contiguous(), (weight > 0).to(torch.uint8)))
 
     def _shade(self, view, x: Tensor) -> Tensor:
         return ops.face_texel_shade(view[0], self.verts, self.faces, x[self.node_index], view[3], view[4])
@@ -270,10 +295,14 @@ class FaceTexelFitter:
             sse = sse + ((e * e).sum(-1) * view[2]).double().sum()
         return sse
 
-    def fit(self, prior: Optional[Tensor] = None, start: Optional[Tensor] = None) -> AttrDict:
+    def fit(self, prior: Optional[Tensor] = None, start: Optional[Tensor] = None, lights: Optional[Tensor] = None, light_step: bool = True) -> AttrDict:
         """``prior`` [U,3] (e.g. FaceTexelBaker's vcolor_sub; None: 0.5), ``start`` [U,3] (None: the prior) -> AttrDict(texels [F,T,3],
         nodes [U,3], coverage [U], rms [iters + 1]: sqrt(sum m |S x - I|^2 / (3 sum m)) at the start and after every iteration (a device
-        tensor), on_prior: the number of nodes with coverage < lam, which the prior decides)."""
+        tensor), on_prior: the number of nodes with coverage < lam, which the prior decides).  With lighting: ``lights`` [views,3,5] are the
+        lights to start from (None: (1, 0, 0, 0, 0)), ``light_step=False`` keeps them through every round (a fit under known lights), and
+        the result gains light, lighting_status, lighting_flags and gain (see _fit_lit)."""
+        if not self.lighting and (lights is not None or not light_step):
+            raise ValueError("FaceTexelFitter.fit: lights and light_step belong to lighting=True")
         if not self._views:
             raise ValueError("FaceTexelFitter.fit: no views (add_views first)")
         dev, U, lam = self.device, self.U, self.lam
@@ -289,6 +318,12 @@ class FaceTexelFitter:
         prior = nodes_arg(prior, "prior", torch.full((U, 3), 0.5, device=dev))
         x = nodes_arg(start, "start", prior).clone()
         dot = lambda a, b: (a.double() * b.double()).sum()
+        if self.lighting:
+            if lights is not None:
+                lights = torch.as_tensor(lights).detach().to(device=dev, dtype=torch.float32)
+                if tuple(lights.shape) != (self.views, 3, 5):
+                    raise ValueError("FaceTexelFitter.fit: lights [views=%d,3,5] expected, got %s" % (self.views, tuple(lights.shape)))
+            return self._fit_lit(prior, x, dot, lights, bool(light_step))
         # r = b - A x = S^T m (I - S x) + lam (prior - x); the first adjoint also gives the coverage
         r, coverage = lam * (prior - x), torch.zeros(U, device=dev)
         sse, total = torch.zeros((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.float64)
@@ -316,6 +351,72 @@ class FaceTexelFitter:
             sses.append(self._sse(x))
         rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
         return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()))
+
+
+    def _lit(self, view, colour: Tensor, light: Tensor, **kw):
+        return ops.face_texel_light(view[0], self.verts, self._faces_lit, colour, view[3], light, weight=view[2], **kw)
+
+    def _fit_lit(self, prior: Tensor, x: Tensor, dot, start_lights: Optional[Tensor], light_step: bool) -> AttrDict:
+        """fit() with lighting: as its result, rms [rounds * iters + 1] being that of the lit residual (after the first light step and after
+        every iteration), plus light [views,3,5], lighting_status / lighting_flags [views] (ops.photo_lighting's, of the last round) and
+        gain [3].  Scalars stay 0-dim fp64 device tensors; nothing is read back inside the loop."""
+        dev, U, lam = self.device, self.U, self.lam
+        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
+        fallback = 7 * ops._lib.LIGHTING_FALLBACK
+        sizes = [v[0].shape[0] for v in self._views]
+        identity = torch.tensor([1.0, 0.0, 0.0, 0.0, 0.0], device=dev)
+        lights = [None if light_step else identity.expand(b, 3, 5).contiguous() for b in sizes] if start_lights is None \
+            else [t.contiguous() for t in start_lights.split(sizes)]
+        status, flags = ([torch.zeros(b, device=dev, dtype=torch.int32) for b in sizes] for _ in range(2))
+        coverage, sses, total = None, [], zero
+
+        def lit_sse(x):
+            sums = zero.new_zeros(2)
+            for i, view in enumerate(self._views):
+                sums = sums + self._lit(view, self._shade(view, x), lights[i], image=view[1], sums=True)["sums"].sum(0)
+            return sums[0]
+
+        for rnd in range(self.rounds):
+            # the light step, then r = S^T m s (I - (s S x + beta)) + lam (prior - x) and the preconditioner under the new lights
+            r, pre, sums = lam * (prior - x), torch.zeros(U, 3, device=dev), zero.new_zeros(2)
+            first_cover = torch.zeros(U, device=dev) if coverage is None else None
+            for i, view in enumerate(self._views):
+                c = self._shade(view, x)
+                if light_step:
+                    fit = ops.photo_lighting(self.verts, self._faces_lit, view[0], view[5], c, view[3], view[1], tau=self.tau0 if rnd == 0 else self.tau,
+                                             light=lights[i], mask=view[6], gain_range=self.gain_range, apply=False)
+                    failed = (fit["flags"] & fallback) != 0          # (status != 0: photo_lighting itself returns the incoming light)
+                    keep = fit["light"] if rnd == 0 else torch.where(failed[:, None, None], lights[i], fit["light"])
+                    lights[i], status[i], flags[i] = keep, fit["status"], fit["flags"]
+                out = self._lit(view, c, lights[i], image=view[1], diag=True, sums=True)
+                if first_cover is not None:
+                    g, w = self._adjoint(view, out["grad"], weight=True)
+                    first_cover = first_cover + w
+                else:
+                    g = self._adjoint(view, out["grad"])
+                r, pre, sums = r + g, pre + self._adjoint(view, out["diag"]), sums + out["sums"].sum(0)
+            if coverage is None:
+                coverage, total = first_cover, sums[1]
+                sses.append(sums[0])
+            m_inv = 1.0 / (pre + lam)
+            z = r * m_inv
+            p, rz = z.clone(), dot(r, z)
+            for _ in range(self.iters):
+                ap = lam * p
+                for i, view in enumerate(self._views):
+                    ap = ap + self._adjoint(view, self._lit(view, self._shade(view, p), lights[i])["grad"])
+                pap = dot(p, ap)
+                alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
+                x, r = x + alpha.float() * p, r - alpha.float() * ap
+                z = r * m_inv
+                rz_new = dot(r, z)
+                beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
+                p, rz = z + beta.float() * p, rz_new
+                sses.append(lit_sse(x))
+        rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
+        light = torch.cat(lights)
+        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()),
+                        light=light, lighting_status=torch.cat(status), lighting_flags=torch.cat(flags), gain=light[:, :, 0].double().mean(0).float())
 
 
 def inner_coverage(face: Tensor, F: int) -> Tensor:

@@ -8,7 +8,8 @@ from .. import _lib
 from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_device, _outputs, _points, _poses, _ptr, _want_gpu, _workspace_arg)
 
 __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
-           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade", "face_texel_shade_bwd"]
+           "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade", "face_texel_shade_bwd",
+           "face_texel_light_workspace", "face_texel_light"]
 
 
 # ------------------------------------------------------------------------------------------ K19
@@ -343,3 +344,56 @@ def face_texel_shade_bwd(face: Tensor, verts: Tensor, faces: Tensor, grad_rgb: T
     a.workspace, a.grad, a.weight = ws.data_ptr(), grad.data_ptr(), _ptr(wsum)
     _call("tp_face_texel_shade_bwd", a)
     return (grad, wsum) if weight else grad
+
+
+# ------------------------------------------------------------------------------------------ K41
+def face_texel_light_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for face_texel_light(sums=True) at B images of H x W (tp_face_texel_light_workspace_bytes); needs no clearing."""
+    return _workspace_arg("face_texel_light", None, int(_lib.load().tp_face_texel_light_workspace_bytes(B, H, W)), device)
+
+
+@_on_tensor_device
+def face_texel_light(face: Tensor, verts: Tensor, faces: Tensor, colour: Tensor, pose: Tensor, light: Tensor, *, image: Optional[Tensor] = None,
+                     weight: Optional[Tensor] = None, diag: bool = False, sums: bool = False, workspace: Optional[Tensor] = None,
+                     out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The per-pixel step between face_texel_shade and face_texel_shade_bwd when the texels are an albedo under one first-order SH light
+    per view (tp_face_texel_light, K41; the rule is in the header): face [B,H,W] int32 (taken as it is), verts [V,3], faces [F,3] int32,
+    colour [B,H,W,3] (face_texel_shade of the node colours, or of a search direction), pose [B,3,4], light [B,3,5] (per channel l0, l1,
+    l2, l3, beta, as photo_lighting returns it), ``weight`` [B,H,W] m (None: 1).  With s the shading of photo_lighting's apply:
+    ``image`` [B,H,W,3] given (residual mode): 'grad' = m s (image - (s colour + beta)); ``image`` None (operator mode): 'grad' = m s
+    (s colour).  ``diag``: also 'diag' = m s s, all [B,H,W,3] float32.  ``sums`` (residual mode): 'sums' [B,2] float64, sum m |image -
+    (s colour + beta)|^2 and sum m per image.  A pixel without a face in [0, F), with m not finite or <= 0, or with a non-finite colour or
+    image value gets zeros and adds nothing.  ``workspace``: face_texel_light_workspace(B, H, W), used with ``sums``; ``out``: any of these
+    tensors to write into.  One launch (two with ``sums``), no atomics, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "face_texel_light"
+    _want_gpu(op, face, "face", torch.int32, None)
+    if face.dim() != 3 or face.numel() == 0:
+        raise ValueError("%s: face [B,H,W] expected, got %s" % (op, tuple(face.shape)))
+    B, H, W = face.shape
+    verts = _points(op, verts, "verts")
+    faces = _want_gpu(op, faces, "faces", torch.int32, None)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise ValueError("%s: faces [F,3] expected, got %s" % (op, tuple(faces.shape)))
+    colour = _want_gpu(op, colour, "colour", torch.float32, (B, H, W, 3))
+    pose = _poses(op, pose, "pose", B)
+    light = _want_gpu(op, light, "light", torch.float32, (B, 3, 5))
+    image = None if image is None else _want_gpu(op, image, "image", torch.float32, (B, H, W, 3))
+    weight = None if weight is None else _want_gpu(op, weight, "weight", torch.float32, (B, H, W))
+    if sums and image is None:
+        raise ValueError("%s: sums=True needs image (residual mode)" % op)
+    spec = {"grad": (torch.float32, (B, H, W, 3))}
+    if diag:
+        spec["diag"] = (torch.float32, (B, H, W, 3))
+    if sums:
+        spec["sums"] = (torch.float64, (B, 2))
+    res = _outputs(op, out, spec, face.device, partial=True)
+    a = _lib.FaceTexelLightArgs()
+    a.verts, a.faces, a.face, a.pose, a.light, a.colour = (t.data_ptr() for t in (verts, faces, face, pose, light, colour))
+    a.image, a.weight = _ptr(image), _ptr(weight)
+    a.V, a.F, a.B, a.H, a.W = verts.shape[0], faces.shape[0], B, H, W
+    a.grad, a.diag, a.sums = res["grad"].data_ptr(), _ptr(res.get("diag")), _ptr(res.get("sums"))
+    if sums:
+        workspace = _workspace_arg(op, workspace, int(_lib.load().tp_face_texel_light_workspace_bytes(B, H, W)), face.device, align=8)
+        a.workspace = workspace.data_ptr()
+    _call("tp_face_texel_light", a)       # (outputs overlapping inputs or each other: the library's error)
+    return res

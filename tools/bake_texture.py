@@ -22,7 +22,13 @@ as the prior (weight L, default 0.1), minimise the difference between the texel 
 The fitted texels, clamped to [0, 1], are what <out>.texels.npz holds and the PLY's vertex colours are the fitted corner nodes; the
 report gains 'fit' (iters, lam, rms_before, rms_after, on_prior: nodes too little seen to leave the prior); --verify prints and stores
 the PSNR through the baked and through the fitted texels.  Without --fit nothing changes.
-Out of scope: texture atlases, view-dependent textures, photographs."""
+--fit-photos NPZ (with --fit): the fit runs against the photographs of an .npz with rgb [N,H,W,3] in [0, 1], pose [N,3,4] (object to
+camera, t in mm) and intr [3,3] or [N,3,3] instead of the checkpoint's renders (inner pixels of the mesh's own coverage, weight 1); the
+bake of the checkpoint's renders stays the prior and the start.  --fit-lighting [ROUNDS] (default 6): the texels are
+fitted as an albedo under one first-order SH light per view (FaceTexelFitter(lighting=True), K41 tp_face_texel_light), ROUNDS
+alternations of a light step and ITERS steps of CG; for photographs taken under lights that differ from view to view.  The report's
+'fit' gains 'rms' (the whole series) and, with --fit-lighting, 'lighting' (rounds, light [N,3,5], status, flags, gain).
+Out of scope: texture atlases, view-dependent textures, reading a BOP scene's photographs (--fit-photos takes an .npz)."""
 import argparse
 import json
 import os
@@ -48,6 +54,9 @@ def main(argv=None):
     ap.add_argument("--texel-res", type=int, default=None, metavar="R", help="also write <out>.texels.npz: face texels of resolution R")
     ap.add_argument("--fit", type=int, default=None, metavar="ITERS", help="with --texel-res: fit the texels to the views by ITERS steps of CG")
     ap.add_argument("--fit-lambda", type=float, default=0.1, metavar="L", help="weight of the baked texture as the fit's prior")
+    ap.add_argument("--fit-photos", default=None, metavar="NPZ", help="with --fit: fit to these photographs (rgb, pose in mm, intr)")
+    ap.add_argument("--fit-lighting", type=int, nargs="?", const=6, default=None, metavar="ROUNDS",
+                    help="with --fit: fit an albedo under one SH-1 light per view, ROUNDS alternations (default 6)")
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--samples", type=int, default=None, help="nerf.sample_intvs")
@@ -69,6 +78,10 @@ def main(argv=None):
         ap.error("--texel-res R needs R in 1 .. 64")
     if a.fit is not None and (a.texel_res is None or a.fit < 1 or not a.fit_lambda > 0):
         ap.error("--fit ITERS needs --texel-res R, ITERS >= 1 and --fit-lambda L > 0")
+    if a.fit is None and (a.fit_photos is not None or a.fit_lighting is not None):
+        ap.error("--fit-photos and --fit-lighting need --fit ITERS")
+    if a.fit_lighting is not None and a.fit_lighting < 1:
+        ap.error("--fit-lighting ROUNDS needs ROUNDS >= 1")
     import torch
     from texpose_amd import checkpoint as ck, ops
     from texpose_amd import face_texels as ft
@@ -110,7 +123,8 @@ def main(argv=None):
     # with --texel-res the nodes of the subdivided mesh are baked; its first V rows are the mesh's vertices, so the PLY comes from them
     texel_baker = None if a.texel_res is None else ft.FaceTexelBaker(verts, faces, a.texel_res, a.H, a.W, a.device, **thresholds)
     baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds) if texel_baker is None else texel_baker.nodes
-    fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit)
+    lit = dict(lighting=True, rounds=a.fit_lighting) if a.fit_lighting is not None else {}
+    fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit, **lit)
     light = torch.tensor(a.light_index, device=dev)
     kept = []                                                         # (rgb, mask) of every view, for --verify
     torch.cuda.synchronize(dev)
@@ -129,13 +143,24 @@ def main(argv=None):
                 rgb[i] = ret.rgb_static.view(a.H, a.W, 3)
                 weight[i] = ret.opacity_static.view(a.H, a.W)
             baker.add_views(rgb, tb.poses_to_mm(p, scale), k, zbuf=sb.zbuf[0], weight=weight)      # (the base mesh's depth planes)
-            if fitter is not None:
+            if fitter is not None and a.fit_photos is None:
                 pose_mm = tb.poses_to_mm(p, scale).contiguous()
                 face = ops.mesh_raster(fitter.verts, fitter.faces, pose_mm, k, H=a.H, W=a.W, normals=False)["face"]
                 inside = sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)
                 fitter.add_views(rgb.clamp(0, 1), pose_mm, k, face=face, weight=(ft.inner_coverage(face, len(faces)) & inside).float())
             if a.verify:
                 kept.append((rgb, sb.object_mask.view(n, a.H, a.W) & (sb.zbuf[0] > 0)))
+        if fitter is not None and a.fit_photos is not None:
+            photos = np.load(a.fit_photos)
+            prgb = np.asarray(photos["rgb"], dtype=np.float32)
+            ppose = np.asarray(photos["pose"], dtype=np.float32).reshape(-1, 3, 4)
+            pintr = np.asarray(photos["intr"], dtype=np.float32)
+            if prgb.shape != (len(ppose), a.H, a.W, 3) or pintr.shape not in ((3, 3), (len(ppose), 3, 3)):
+                sys.exit("bake_texture: --fit-photos holds rgb %s, pose %s and intr %s; rgb [N,%d,%d,3], pose [N,3,4] and intr [3,3] or [N,3,3] expected"
+                         % (prgb.shape, ppose.shape, pintr.shape, a.H, a.W))
+            for c in range(0, len(ppose), a.chunk):
+                fitter.add_views(torch.from_numpy(prgb[c:c + a.chunk]), torch.from_numpy(ppose[c:c + a.chunk]),
+                                 torch.from_numpy(pintr if pintr.ndim == 2 else pintr[c:c + a.chunk]))
     V = len(verts)
     texels = None
     if texel_baker is None:
@@ -149,7 +174,11 @@ def main(argv=None):
         got = fitter.fit(prior=sub.vcolor_sub, start=sub.vcolor_sub)
         nodes = got.nodes.clamp(0, 1)
         texels, res.vcolor = ft.texels_from_nodes(nodes, fitter.node_index), nodes[:V].contiguous()
-        fit = dict(iters=a.fit, lam=a.fit_lambda, rms_before=float(got.rms[0]), rms_after=float(got.rms[-1]), on_prior=got.on_prior)
+        fit = dict(iters=a.fit, lam=a.fit_lambda, rms_before=float(got.rms[0]), rms_after=float(got.rms[-1]), on_prior=got.on_prior,
+                   rms=[float(v) for v in got.rms.tolist()], views=fitter.views, photos=a.fit_photos)
+        if a.fit_lighting is not None:
+            fit["lighting"] = dict(rounds=a.fit_lighting, light=got.light.tolist(), status=got.lighting_status.tolist(),
+                                   flags=got.lighting_flags.tolist(), gain=got.gain.tolist())
     torch.cuda.synchronize(dev)
     seconds = time.perf_counter() - t0
     ops.check_mlp_status(dev)
@@ -167,6 +196,9 @@ def main(argv=None):
         report["fit"] = fit
         print("bake_texture: fit of %d nodes, %d iterations, lambda %g: training rms %.5f -> %.5f, %d nodes on the prior"
               % (len(texel_baker.verts_sub), a.fit, a.fit_lambda, fit["rms_before"], fit["rms_after"], fit["on_prior"]))
+        if a.fit_lighting is not None:
+            print("bake_texture: %d rounds under one light per view: mean ambient gain %s, %d of %d light fits ok"
+                  % (a.fit_lighting, " ".join("%.3f" % g for g in fit["lighting"]["gain"]), sum(s == 0 for s in fit["lighting"]["status"]), fitter.views))
     if a.verify:
         base_verts, base_faces = (baker.verts, baker.faces) if texel_baker is None else (texel_baker.verts, texel_baker.faces)
 

@@ -26,7 +26,22 @@ many calls after a warm-up, three repeats per route, alternating, medians; the s
     python tools/face_texel_bench.py --fit [--out profiles/face_texel_fit/adjoint.json]
 
 Each adjoint row carries the forward's time of the same run and the atomic bytes per second: 9 (12 with the coverage) 64-bit atomics, 72
-(96) bytes, per covered pixel.  Before anything is timed the identity <shade(t), g> = <t, adjoint(g)> is checked in fp64 on the host."""
+(96) bytes, per covered pixel.  Before anything is timed the identity <shade(t), g> = <t, adjoint(g)> is checked in fp64 on the host.
+
+--fit --lighting: the lit fit instead (K41 tp_face_texel_light), on the same workload, the R = 8 render relit view by
+view as the photographs:
+
+  light B=n <mode>   ops.face_texel_light on n views: "residual" (image given), "+sums", "operator" (no image), "+diag"
+  torch B=n <mode>   the same rule composed in torch -- the comparator, not the code under test: the shading plane from
+                     ops.photo_lighting's apply of an all-ones rendering (a fit that keeps nothing applies the incoming light), then the
+                     elementwise passes; checked bit for bit against the fused call before anything is timed
+  fit R=4 ...        FaceTexelFitter.fit plain with 0 and 1 iteration, and lit (one round) with 0 and 1 iteration and without the
+                     light step: the differences are one plain iteration, one lit iteration and one light step
+
+    python tools/face_texel_bench.py --fit --lighting [--out profiles/face_texel_light/light.json]
+
+Each K41 row carries the bytes it moves (8 B per pixel for face and weight, 12 B per pixel for grad, 12 more with diag, 12 B per covered
+pixel for colour and 12 more for image) and their share of 8 TB/s."""
 import argparse
 import json
 import os
@@ -50,6 +65,7 @@ def main(argv=None):
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--fit", action="store_true", help="time the adjoint (K36) and one fitter iteration instead")
+    ap.add_argument("--lighting", action="store_true", help="with --fit: time K41 and the lit fit instead")
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import face_texels as FT, ops, texture_bake as TB
@@ -69,8 +85,10 @@ def main(argv=None):
     base = raster(vcolor=vcol)
     covered = base["zbuf"] > 0
     n_cov = int(covered.sum())
+    if a.lighting and not a.fit:
+        ap.error("--lighting comes with --fit")
     if a.fit:
-        return bench_fit(a, locals())
+        return (bench_light if a.lighting else bench_fit)(a, locals())
     routes, iters, checks, meshes = {"base": lambda: raster(vcolor=vcol), "base cull": lambda: raster(vcolor=vcol, cull=True)}, {}, {}, {}
     heavy = max(2, a.iters // 10)
     for R in (1, 4, 8):
@@ -169,6 +187,105 @@ def bench_fit(a, env):
                covered_share=n_cov / (B * H * W), iters=a.iters, warmup=a.warmup, repeats=a.repeats, shader_clock_ghz_before=env["clock_before"],
                shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - env["t_start"], textures=meshes, checks=checks,
                fit_iteration_us=med["fit R=4 iters=1"] - med["fit R=4 iters=0"], rows=rows)
+    KB.finish(res, a.out)
+
+
+def bench_light(a, env):
+    import torch
+    from texpose_amd import face_texels as FT, ops
+    dev, B, H, W, pose, K, verts, faces = (env[k] for k in ("dev", "B", "H", "W", "pose", "K", "verts", "faces"))
+    v_np, f_np, colour, n_cov = (env[k] for k in ("v_np", "f_np", "colour", "n_cov"))
+    F = len(f_np)
+    face = ops.mesh_raster(verts, faces, pose, K, H=H, W=W, normals=False)["face"]
+    covered = (face >= 0) & (face < F)
+    zbuf = torch.where(covered, 1.0, -1.0).float()
+    nothing = torch.zeros(B, H, W, dtype=torch.uint8, device=dev)
+    vs, _, ni = FT.subdivide(v_np, f_np, 8)
+    texels = torch.from_numpy(FT.texels_from_nodes(colour(vs), ni)).to(dev)
+    unlit = ops.face_texel_shade(face, verts, faces, texels, pose, K)
+    rs = np.random.RandomState(0)                                    # one light per view: ambient, a directional part of 0.45 of it, a bias
+    amb = np.array([0.70, 0.75, 0.65]) * rs.uniform(0.8, 1.25, (B, 1))
+    d = rs.randn(B, 3)
+    d[:, 2] = -np.abs(d[:, 2]) - 0.3
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    light = torch.from_numpy(np.concatenate([amb[:, :, None], 0.45 * amb[:, :, None] * d[:, None, :],
+                                             (np.array([0.05, 0.10, 0.08]) * rs.uniform(0, 1, (B, 1)))[:, :, None]], 2).astype(np.float32)).to(dev)
+    apply = lambda rgb, l, n: ops.photo_lighting(verts, faces, face[:n], zbuf[:n], rgb, pose[:n], rgb, tau=0.5, light=l, mask=nothing[:n])["rgb"]
+    photo = apply(unlit, light, B)
+    weight = FT.inner_coverage(face, F).float()
+    colour_plane = (unlit * 0.9).contiguous()                        # a rendering that leaves a residual
+    unbiased = light.clone()
+    unbiased[:, :, 4] = 0.0
+    ones = torch.ones(B, H, W, 3, device=dev)
+    off = torch.zeros((), device=dev)
+    on = (covered & (weight > 0))[..., None]                         # (an uncovered or unweighted pixel is +0, whatever the products' signs)
+
+    def composed(n, image, diag=False, sums=False):
+        s = apply(ones[:n], unbiased[:n], n)
+        ms = weight[:n, ..., None] * s
+        q = s * colour_plane[:n]
+        out = {}
+        if image:
+            e = photo[:n] - (q + light[:n, None, None, :, 4])
+            out["grad"] = torch.where(on[:n], ms * e, off)
+            if sums:
+                e64 = e.double()
+                t = weight[:n].double() * ((e64[..., 0] * e64[..., 0] + e64[..., 1] * e64[..., 1]) + e64[..., 2] * e64[..., 2])
+                out["sums"] = torch.stack([(t * covered[:n]).sum((1, 2)), (weight[:n].double() * covered[:n]).sum((1, 2))], 1)
+        else:
+            out["grad"] = torch.where(on[:n], ms * q, off)
+        if diag:
+            out["diag"] = torch.where(on[:n], ms * s, off)
+        return out
+
+    routes, checks = {}, {}
+    modes = {"residual": dict(image=True), "residual +sums": dict(image=True, sums=True), "residual +diag +sums": dict(image=True, diag=True, sums=True),
+             "operator": dict(image=False), "operator +diag": dict(image=False, diag=True)}
+    for n in (B, 8):
+        outs = dict(grad=torch.empty(n, H, W, 3, device=dev), diag=torch.empty(n, H, W, 3, device=dev), sums=torch.empty(n, 2, device=dev, dtype=torch.float64))
+        ws = ops.face_texel_light_workspace(n, H, W, dev)
+        for name, m in modes.items():
+            kw = dict(image=photo[:n] if m["image"] else None, weight=weight[:n], diag=m.get("diag", False), sums=m.get("sums", False))
+            fused = lambda n=n, kw=kw, outs=outs, ws=ws: ops.face_texel_light(face[:n], verts, faces, colour_plane[:n], pose[:n], light[:n], workspace=ws,
+                                                                              out={k: outs[k] for k in ("grad",) + (("diag",) if kw["diag"] else ()) + (("sums",) if kw["sums"] else ())}, **kw)
+            torch_way = lambda n=n, m=m: composed(n, m["image"], m.get("diag", False), m.get("sums", False))
+            got, want = fused(), torch_way()
+            equal = {k: bool(torch.equal(got[k].view(torch.int32), want[k].view(torch.int32))) if k != "sums"
+                     else float(((got[k] - want[k]).abs() / want[k].abs().clamp_min(1e-300)).max()) for k in got}
+            checks["B=%d %s" % (n, name)] = equal
+            if not all(v is True or (v is not False and v <= 1e-12) for v in equal.values()):
+                raise SystemExit("face_texel_bench: B = %d %s: the fused call and the torch composition disagree (%s); nothing was timed" % (n, name, equal))
+            routes["light B=%d %s" % (n, name)] = fused
+            routes["torch B=%d %s" % (n, name)] = torch_way
+    def fitter(**kw):
+        f = FT.FaceTexelFitter(v_np, f_np, 4, H, W, dev, **kw)
+        for c in range(0, B, 16):
+            f.add_views(photo[c:c + 16], pose[c:c + 16], K[c:c + 16], face=face[c:c + 16])
+        return f
+
+    for iters in (0, 1):
+        routes["fit R=4 plain iters=%d" % iters] = fitter(iters=iters).fit
+        routes["fit R=4 lit rounds=1 iters=%d" % iters] = fitter(iters=iters, lighting=True, rounds=1).fit
+    held = fitter(iters=0, lighting=True, rounds=1)
+    routes["fit R=4 lit rounds=1 iters=0 no light step"] = lambda: held.fit(lights=light, light_step=False)
+    med, times = KB.race(routes, a.iters, a.warmup, a.repeats)
+    rows = []
+    for name in routes:
+        row = dict(route=name, us_per_call=med[name], us_all_repeats=times[name])
+        if name.startswith("light"):
+            n = int(name.split("B=")[1].split()[0])
+            cov = int(covered[:n].sum())
+            moved = n * H * W * (8 + 12 + (12 if "+diag" in name else 0)) + cov * (24 if "residual" in name else 12)
+            row.update(bytes_moved=moved, share_of_8_tb_per_s=moved / (med[name] * 1e-6) / 8e12, torch_us_same_run=med["torch" + name[5:]],
+                       speedup_over_torch=med["torch" + name[5:]] / med[name])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    res = dict(bench="face_texel_light", device=torch.cuda.get_device_name(0), V=len(v_np), F=F, B=B, H=H, W=W, covered_pixels=n_cov,
+               covered_share=n_cov / (B * H * W), iters=a.iters, warmup=a.warmup, repeats=a.repeats, shader_clock_ghz_before=env["clock_before"],
+               shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - env["t_start"], checks=checks,
+               plain_iteration_us=med["fit R=4 plain iters=1"] - med["fit R=4 plain iters=0"],
+               lit_iteration_us=med["fit R=4 lit rounds=1 iters=1"] - med["fit R=4 lit rounds=1 iters=0"],
+               light_step_us=med["fit R=4 lit rounds=1 iters=0"] - med["fit R=4 lit rounds=1 iters=0 no light step"], rows=rows)
     KB.finish(res, a.out)
 
 
