@@ -1903,6 +1903,58 @@ typedef struct tp_face_texel_light_args {
 size_t tp_face_texel_light_workspace_bytes(int B, int H, int W);  /* 16 * B * ceil(H * W / 1024); 0 for non-positive sizes */
 int tp_face_texel_light(const tp_face_texel_light_args* args, tp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K42  robust (IRLS) weights of a photometric residual, scaled per image by an EXACT median found on the device (texpose_amd/ops/
+ *      scene.py: robust_weight; texpose_amd/face_texels.py: FaceTexelFitter(robust=...); restated in tests/robust_weight_ref.py; the
+ *      project's own step, no reference code).  model and image are [B,H,W,3] fp32, weight [B,H,W] the base weight
+ *      (NULL: 1 everywhere).  Per pixel p of image b, evaluated as written (no contraction):
+ *        1. e_k = (double)image_k - (double)model_k;  q = (float)(((e_0 e_0 + e_1 e_1) + e_2 e_2) / 3.0): fp64, rounded once.
+ *        2. the pixel is COUNTED iff its base weight is finite and > 0, its six colour values are finite and q is finite.  A pixel
+ *           that is not counted gets out = +0.
+ *        3. count[b] = n, the number of counted pixels; median_q[b] = the exact LOWER median of q over them: the element of rank
+ *           (n - 1) / 2 (integer division, 0-based, ascending); 0 for n = 0.
+ *        4. s2 = fmax((1.4826 * 1.4826) * (double)median_q[b], (double)sigma_min * sigma_min);  with scale_in given:
+ *           s2 = fmax((double)scale_in[b] * scale_in[b], (double)sigma_min * sigma_min), the median is not computed and median_q[b] =
+ *           0.  scale[b] = (float)sqrt(s2), for reporting.
+ *        5. u2 = (double)q / (((double)c * c) * s2);
+ *           TP_ROBUST_TUKEY: w = u2 < 1 ? (1 - u2) * (1 - u2) : 0        (no square root: comparable bit for bit)
+ *           TP_ROBUST_HUBER: w = u2 <= 1 ? 1 : 1 / sqrt(u2)
+ *           out = (float)((double)base * w)
+ *      The median without a sort and without float atomics: q >= 0, and the bit pattern of a non-negative fp32 is monotone in its
+ *      value, so a three-level radix select on the bits (the upper 11, the next 11, the last 10) finds the element of the rank
+ *      exactly.  The first pass forms q, stores its bits in the workspace (all ones for a pixel that is not counted) and counts the
+ *      upper 11 bits; the second and third pass read the stored bits and count the next digit of the keys that carry the prefix found
+ *      so far.  Each pass counts into a histogram in LDS per workgroup and adds its non-zero bins to the image's histogram with
+ *      INTEGER atomics: sums of integers do not depend on the order of arrival.  One small launch per level (one workgroup per
+ *      image) scans the histogram for the bin that holds the rank.  Every output is a function of the inputs alone: bit-identical
+ *      from run to run and under graph replay.
+ *      Eight launches on the stream (clear, 3 x (count, search), weight); two with scale_in (clear, weight: q is formed in the weight
+ *      pass and count[b] is added up with integer atomics).  The workspace needs no clearing.  Refused (-1, tp_last_error) before
+ *      anything is launched: a non-positive size, B > 65535, H * W >= 2^31, a null model, image, out, median_q, scale or count, an
+ *      unknown kind, c or sigma_min not finite or <= 0, without scale_in a null workspace or one that is not 16-byte aligned, and an
+ *      output (out, median_q, scale, count, the workspace) that overlaps an input or another output.  No input value causes an access
+ *      out of bounds.  No allocation, no host synchronisation.  Safe to capture.
+ *      Left out: a median of the absolute residual per channel, a scale shared between images, other rho functions (Cauchy, Welsch).
+ * ------------------------------------------------------------------------------------------ */
+enum { TP_ROBUST_TUKEY = 0, TP_ROBUST_HUBER = 1 };
+typedef struct tp_robust_weight_args {
+  const float* model;        /* [B,H,W,3] the rendering (S x) */
+  const float* image;        /* [B,H,W,3] the photographs */
+  const float* weight;       /* [B,H,W] base weight, or NULL: 1 */
+  const float* scale_in;     /* [B] sigma per image, or NULL: 1.4826 * sqrt(median q) */
+  int B, H, W;
+  int kind;                  /* TP_ROBUST_TUKEY or TP_ROBUST_HUBER */
+  float c;                   /* the tuning constant, in units of sigma: 4.685 (Tukey), 1.345 (Huber) are the usual ones */
+  float sigma_min;           /* the floor of sigma: 1 / 255 is one step of an 8-bit photograph */
+  float* out;                /* [B,H,W] out: base weight * robust weight */
+  float* median_q;           /* [B] out */
+  float* scale;              /* [B] out: sigma */
+  int32_t* count;            /* [B] out: counted pixels */
+  void* workspace;           /* without scale_in: tp_robust_weight_workspace_bytes(B, H, W) bytes, 16-byte aligned; needs no clearing */
+} tp_robust_weight_args;
+size_t tp_robust_weight_workspace_bytes(int B, int H, int W);  /* 4 * B * H * W rounded up to 16, + 20512 * B; 0 for non-positive sizes */
+int tp_robust_weight(const tp_robust_weight_args* args, tp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ shading: ``autograd_ops.face_texel_shade`` (per-slot texels), ``shade_nodes`` (n
 ``FaceTexelFitter``, which fits the node colours to photographs by preconditioned conjugate gradients on the quantity the refiners
 consume: the difference between the shaded render and the photograph.  No gradients with respect to pose or vertices, first order only.
 ``FaceTexelFitter(lighting=True)`` (K41 tp_face_texel_light) fits the colours as an albedo under one first-order
-SH light per view, for photographs whose light differs from view to view.
+SH light per view, for photographs whose light differs from view to view.  ``FaceTexelFitter(robust="tukey")`` (K42 tp_robust_weight,
+DESIGN.md section 32) reweights the pixels round by round, for photographs with occluders and highlights.
 """
 from __future__ import annotations
 
@@ -210,8 +211,16 @@ class FaceTexelFitter:
     gradients preconditioned with M = coverage + lam, coverage the per-node sum of shading weights over all covered pixels (K36's
     ``weight``: the lumped diagonal of S^T S).  S x is ops.face_texel_shade, S^T g is ops.face_texel_shade_bwd with the node index:
     deterministic, so a fit is bit-identical from run to run.  An iteration is one shade and one adjoint over the stored views for the
-    step and one more shade for the training rms it reports.  A quadratic loss only (a robust loss goes through ``shade_nodes`` and
-    an optimiser); the result is not clamped: the caller does that.
+    step and one more shade for the training rms it reports.  A quadratic loss by default; ``robust`` = "tukey" or "huber" fits by
+    iteratively reweighted least squares instead (below), and any other loss goes through ``shade_nodes`` and an optimiser.  The result
+    is not clamped: the caller does that.
+
+    ``robust`` (K42): for photographs that carry what no texture explains (an occluder, a highlight, a patch of
+    background).  ``robust_rounds`` rounds, each of which weights every pixel of every stored view by ops.robust_weight of the current
+    residual (Tukey's biweight with c = 4.685, or Huber's weight with c = 1.345, or ``robust_c``; in units of sigma = 1.4826 sqrt(median of
+    the mean squared colour error) per view, at least ``sigma_min``) times the view's own weight, and then runs ``iters`` conjugate-
+    gradient steps on the weighted system from the current x, preconditioned with S^T (w) + lam.  The result gains scale, kept and
+    robust_count per view (see _fit_robust).  Not together with ``lighting=True``.
 
     ``lighting=True`` (K41) fits x as an ALBEDO under one first-order SH light per stored view: it minimises
         sum_b sum_p m_p |s_b(n_p) (S x)_p + beta_b - I_p|^2 + lam |x - prior|^2
@@ -224,10 +233,22 @@ class FaceTexelFitter:
     alone; the result's ``gain`` is the mean l0 per channel, for a caller who wants to normalise.  ``lighting=False`` is the fit above."""
 
     def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", lam: float = 0.1, iters: int = 4, cull: bool = False,
-                 lighting: bool = False, rounds: int = 6, tau: float = 0.5, tau0: float = 2.0, gain_range=(0.25, 4.0)):
+                 lighting: bool = False, rounds: int = 6, tau: float = 0.5, tau0: float = 2.0, gain_range=(0.25, 4.0),
+                 robust: Optional[str] = None, robust_c: Optional[float] = None, robust_rounds: int = 6, sigma_min: float = 1.0 / 255.0):
         self.R, self.T, self.H, self.W = int(R), texel_count(R), int(H), int(W)
         if not (lam > 0 and int(iters) >= 0):
             raise ValueError("FaceTexelFitter: lam > 0 and iters >= 0 expected")
+        if robust is not None:
+            if robust not in ops.ROBUST_KINDS:
+                raise ValueError("FaceTexelFitter: robust %r is none of None, %s" % (robust, ", ".join(map(repr, sorted(ops.ROBUST_KINDS)))))
+            if lighting:
+                raise ValueError("FaceTexelFitter: robust weights under lighting=True are left out (DESIGN.md section 32): pass weights from "
+                                 "ops.robust_weight through add_views(weight=) instead")
+            c = ops.ROBUST_KINDS[robust][1] if robust_c is None else float(robust_c)
+            if not (int(robust_rounds) >= 1 and np.isfinite(c) and c > 0 and np.isfinite(sigma_min) and sigma_min > 0):
+                raise ValueError("FaceTexelFitter: robust_rounds >= 1, robust_c > 0 and sigma_min > 0 expected with robust")
+            self.robust_c, self.robust_rounds, self.sigma_min = c, int(robust_rounds), float(sigma_min)
+        self.robust = robust
         if lighting and not (int(rounds) >= 1 and tau > 0 and tau0 > 0):
             raise ValueError("FaceTexelFitter: rounds >= 1, tau > 0 and tau0 > 0 expected with lighting")
         self.lighting, self.rounds, self.tau, self.tau0 = bool(lighting), int(rounds), float(tau), float(tau0)
@@ -324,6 +345,8 @@ class FaceTexelFitter:
                 if tuple(lights.shape) != (self.views, 3, 5):
                     raise ValueError("FaceTexelFitter.fit: lights [views=%d,3,5] expected, got %s" % (self.views, tuple(lights.shape)))
             return self._fit_lit(prior, x, dot, lights, bool(light_step))
+        if self.robust is not None:
+            return self._fit_robust(prior, x, dot)
         # r = b - A x = S^T m (I - S x) + lam (prior - x); the first adjoint also gives the coverage
         r, coverage = lam * (prior - x), torch.zeros(U, device=dev)
         sse, total = torch.zeros((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.float64)
@@ -352,6 +375,68 @@ class FaceTexelFitter:
         rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
         return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()))
 
+    def _fit_robust(self, prior: Tensor, x: Tensor, dot) -> AttrDict:
+        """fit() with robust=...: ``robust_rounds`` rounds of iteratively reweighted least squares.  A round takes the weights w =
+        ops.robust_weight(S x, photograph, weight=m) of every stored view at the current x, then ``iters`` conjugate-gradient steps on
+        (S^T w S + lam) x = S^T w I + lam prior, restarted from x and preconditioned with S^T (w) + lam (the adjoint of the weight plane).
+        As fit()'s result, rms [robust_rounds * iters + 1] being sqrt(sum w |S x - I|^2 / (3 sum w)) under the round's own weights (at the
+        start and after every iteration), plus scale [views] (sigma per view), kept [views] = sum w / sum m and robust_count [views], all
+        of the last round.  Scalars stay 0-dim fp64 device tensors; nothing is read back inside the loop."""
+        dev, U, lam = self.device, self.U, self.lam
+        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
+        spaces = [ops.robust_weight_workspace(v[0].shape[0], self.H, self.W, dev) for v in self._views]
+        coverage, rms = None, []
+
+        def weighted_sse(x, ws):
+            sse = zero
+            for view, w in zip(self._views, ws):
+                e = self._shade(view, x) - view[1]
+                sse = sse + torch.where(w > 0, (e * e).sum(-1) * w, torch.zeros_like(w)).double().sum()
+            return sse
+
+        for rnd in range(self.robust_rounds):
+            # the weights at the current x, then r = S^T w (I - S x) + lam (prior - x) and the preconditioner under them
+            r, pre, sse, total = lam * (prior - x), torch.zeros(U, 3, device=dev), zero, zero
+            first_cover = torch.zeros(U, device=dev) if coverage is None else None
+            ws, fits = [], []
+            for view, space in zip(self._views, spaces):
+                model = self._shade(view, x)
+                fit = ops.robust_weight(model, view[1], weight=view[2], kind=self.robust, c=self.robust_c, sigma_min=self.sigma_min, workspace=space)
+                w = fit["weight"]
+                on = (w > 0)[..., None]
+                e = torch.where(on, view[1] - model, torch.zeros_like(model))
+                if first_cover is not None:                      # (the coverage is that of the plain fit: it does not look at the values)
+                    g, cover = self._adjoint(view, e * w[..., None], weight=True)
+                    r, first_cover = r + g, first_cover + cover
+                else:
+                    r = r + self._adjoint(view, e * w[..., None])
+                pre = pre + self._adjoint(view, w[..., None].expand(-1, -1, -1, 3).contiguous())
+                sse, total = sse + ((e * e).sum(-1) * w).double().sum(), total + w.double().sum()
+                ws.append(w)
+                fits.append(fit)
+            if coverage is None:
+                coverage = first_cover
+                rms.append(torch.sqrt(sse / (3.0 * total).clamp_min(1e-300)))
+            m_inv = 1.0 / (pre + lam)
+            z = r * m_inv
+            p, rz = z.clone(), dot(r, z)
+            for _ in range(self.iters):
+                ap = lam * p
+                for view, w in zip(self._views, ws):
+                    ap = ap + self._adjoint(view, self._shade(view, p) * w[..., None])
+                pap = dot(p, ap)
+                alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
+                x, r = x + alpha.float() * p, r - alpha.float() * ap
+                z = r * m_inv
+                rz_new = dot(r, z)
+                beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
+                p, rz = z + beta.float() * p, rz_new
+                rms.append(torch.sqrt(weighted_sse(x, ws) / (3.0 * total).clamp_min(1e-300)))
+        base = torch.cat([torch.where(v[2] > 0, v[2], torch.zeros_like(v[2])).double().sum((1, 2)) for v in self._views])
+        kept = (torch.cat([w.double().sum((1, 2)) for w in ws]) / base.clamp_min(1e-300)).float()
+        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=torch.stack(rms).float(),
+                        on_prior=int((coverage < lam).sum()), scale=torch.cat([f["scale"] for f in fits]), kept=kept,
+                        robust_count=torch.cat([f["count"] for f in fits]))
 
     def _lit(self, view, colour: Tensor, light: Tensor, **kw):
         return ops.face_texel_light(view[0], self.verts, self._faces_lit, colour, view[3], light, weight=view[2], **kw)

@@ -1,4 +1,5 @@
-"""K19-K22, K27, K35, K36: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake, the face-texel shading and its adjoint."""
+"""K19-K22, K27, K35, K36, K41, K42: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake, the face-texel shading, its
+adjoint, its lighting step and the robust weights of its residual."""
 import math
 from typing import Dict, Optional, Tuple
 
@@ -9,7 +10,7 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_dev
 
 __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
            "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade", "face_texel_shade_bwd",
-           "face_texel_light_workspace", "face_texel_light"]
+           "face_texel_light_workspace", "face_texel_light", "ROBUST_KINDS", "robust_weight_workspace", "robust_weight"]
 
 
 # ------------------------------------------------------------------------------------------ K19
@@ -396,4 +397,49 @@ def face_texel_light(face: Tensor, verts: Tensor, faces: Tensor, colour: Tensor,
         workspace = _workspace_arg(op, workspace, int(_lib.load().tp_face_texel_light_workspace_bytes(B, H, W)), face.device, align=8)
         a.workspace = workspace.data_ptr()
     _call("tp_face_texel_light", a)       # (outputs overlapping inputs or each other: the library's error)
+    return res
+
+
+# ------------------------------------------------------------------------------------------ K42
+ROBUST_KINDS = {"tukey": (_lib.ROBUST_TUKEY, 4.685), "huber": (_lib.ROBUST_HUBER, 1.345)}      # name -> (the header's constant, the default c)
+
+
+def robust_weight_workspace(B: int, H: int, W: int, device) -> Tensor:
+    """A workspace for robust_weight at B images of H x W (tp_robust_weight_workspace_bytes); needs no clearing."""
+    return _workspace_arg("robust_weight", None, int(_lib.load().tp_robust_weight_workspace_bytes(B, H, W)), device)
+
+
+@_on_tensor_device
+def robust_weight(model: Tensor, image: Tensor, *, weight: Optional[Tensor] = None, kind: str = "tukey", c: Optional[float] = None,
+                  sigma_min: float = 1.0 / 255.0, scale_in: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+                  out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    """The weights of one round of iteratively reweighted least squares on a photometric residual (tp_robust_weight, K42; the rule is in
+    the header): model and image [B,H,W,3] float32, ``weight`` [B,H,W] the base weight (None: 1).  Per pixel q = mean over the channels
+    of (image - model)^2; per image sigma = max(1.4826 sqrt(median q), ``sigma_min``), the median being the exact lower median over the
+    pixels that count (base weight finite and > 0, every colour finite) -- or ``scale_in`` [B] where given, and no median is taken;
+    u^2 = q / (c sigma)^2; ``kind`` 'tukey': (1 - u^2)^2 inside u < 1, 0 outside; 'huber': 1 inside, 1 / u outside; ``c`` None: 4.685 and
+    1.345.  Returns 'weight' [B,H,W] float32 (base x robust; 0 where the pixel does not count), 'median_q' [B], 'scale' [B] (sigma) float32
+    and 'count' [B] int32.  ``workspace``: robust_weight_workspace(B, H, W), used without ``scale_in``; ``out``: any of these tensors to
+    write into.  Integer atomics only: bit-identical from run to run; nothing is read back; safe under torch.cuda.graph."""
+    op = "robust_weight"
+    if kind not in ROBUST_KINDS:
+        raise ValueError("%s: kind %r is none of %s" % (op, kind, sorted(ROBUST_KINDS)))
+    _want_gpu(op, model, "model", torch.float32, None)
+    if model.dim() != 4 or model.shape[3] != 3 or model.numel() == 0:
+        raise ValueError("%s: model [B,H,W,3] expected, got %s" % (op, tuple(model.shape)))
+    B, H, W = model.shape[:3]
+    image = _want_gpu(op, image, "image", torch.float32, (B, H, W, 3))
+    weight = None if weight is None else _want_gpu(op, weight, "weight", torch.float32, (B, H, W))
+    scale_in = None if scale_in is None else _want_gpu(op, scale_in, "scale_in", torch.float32, (B,))
+    res = _outputs(op, out, {"weight": (torch.float32, (B, H, W)), "median_q": (torch.float32, (B,)), "scale": (torch.float32, (B,)),
+                             "count": (torch.int32, (B,))}, model.device, partial=True)
+    a = _lib.RobustWeightArgs()
+    a.model, a.image, a.weight, a.scale_in = model.data_ptr(), image.data_ptr(), _ptr(weight), _ptr(scale_in)
+    a.B, a.H, a.W, a.kind = B, H, W, ROBUST_KINDS[kind][0]
+    a.c, a.sigma_min = float(ROBUST_KINDS[kind][1] if c is None else c), float(sigma_min)
+    a.out, a.median_q, a.scale, a.count = (res[k].data_ptr() for k in ("weight", "median_q", "scale", "count"))
+    if scale_in is None:
+        workspace = _workspace_arg(op, workspace, int(_lib.load().tp_robust_weight_workspace_bytes(B, H, W)), model.device, align=16)
+        a.workspace = workspace.data_ptr()
+    _call("tp_robust_weight", a)          # (bad c or sigma_min, outputs overlapping inputs or each other: the library's error)
     return res

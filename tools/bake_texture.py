@@ -28,6 +28,9 @@ bake of the checkpoint's renders stays the prior and the start.  --fit-lighting 
 fitted as an albedo under one first-order SH light per view (FaceTexelFitter(lighting=True), K41 tp_face_texel_light), ROUNDS
 alternations of a light step and ITERS steps of CG; for photographs taken under lights that differ from view to view.  The report's
 'fit' gains 'rms' (the whole series) and, with --fit-lighting, 'lighting' (rounds, light [N,3,5], status, flags, gain).
+--fit-robust [tukey|huber] (default tukey) with --fit-robust-rounds N (default 6): the fit reweights every pixel round
+by round by the robust weight of its residual (FaceTexelFitter(robust=...), K42 tp_robust_weight), for photographs with occluders or
+highlights; N rounds of ITERS steps; 'fit' gains 'robust' (kind, rounds, scale and kept per view).  Not together with --fit-lighting.
 Out of scope: texture atlases, view-dependent textures, reading a BOP scene's photographs (--fit-photos takes an .npz)."""
 import argparse
 import json
@@ -57,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--fit-photos", default=None, metavar="NPZ", help="with --fit: fit to these photographs (rgb, pose in mm, intr)")
     ap.add_argument("--fit-lighting", type=int, nargs="?", const=6, default=None, metavar="ROUNDS",
                     help="with --fit: fit an albedo under one SH-1 light per view, ROUNDS alternations (default 6)")
+    ap.add_argument("--fit-robust", nargs="?", const="tukey", default=None, choices=("tukey", "huber"),
+                    help="with --fit: reweight the pixels round by round with Tukey's (default) or Huber's weight of their residual")
+    ap.add_argument("--fit-robust-rounds", type=int, default=None, metavar="N", help="with --fit-robust: rounds of reweighting (default 6)")
     ap.add_argument("--H", type=int, default=480)
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--samples", type=int, default=None, help="nerf.sample_intvs")
@@ -82,6 +88,12 @@ def main(argv=None):
         ap.error("--fit-photos and --fit-lighting need --fit ITERS")
     if a.fit_lighting is not None and a.fit_lighting < 1:
         ap.error("--fit-lighting ROUNDS needs ROUNDS >= 1")
+    if a.fit is None and (a.fit_robust is not None or a.fit_robust_rounds is not None):
+        ap.error("--fit-robust and --fit-robust-rounds need --fit ITERS")
+    if a.fit_robust is not None and a.fit_lighting is not None:
+        ap.error("--fit-robust does not go together with --fit-lighting (DESIGN section 32, left out)")
+    if a.fit_robust_rounds is not None and (a.fit_robust is None or a.fit_robust_rounds < 1):
+        ap.error("--fit-robust-rounds N needs --fit-robust and N >= 1")
     import torch
     from texpose_amd import checkpoint as ck, ops
     from texpose_amd import face_texels as ft
@@ -124,6 +136,8 @@ def main(argv=None):
     texel_baker = None if a.texel_res is None else ft.FaceTexelBaker(verts, faces, a.texel_res, a.H, a.W, a.device, **thresholds)
     baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds) if texel_baker is None else texel_baker.nodes
     lit = dict(lighting=True, rounds=a.fit_lighting) if a.fit_lighting is not None else {}
+    if a.fit_robust is not None:
+        lit = dict(robust=a.fit_robust, robust_rounds=6 if a.fit_robust_rounds is None else a.fit_robust_rounds)
     fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit, **lit)
     light = torch.tensor(a.light_index, device=dev)
     kept = []                                                         # (rgb, mask) of every view, for --verify
@@ -179,6 +193,9 @@ def main(argv=None):
         if a.fit_lighting is not None:
             fit["lighting"] = dict(rounds=a.fit_lighting, light=got.light.tolist(), status=got.lighting_status.tolist(),
                                    flags=got.lighting_flags.tolist(), gain=got.gain.tolist())
+        if a.fit_robust is not None:
+            fit["robust"] = dict(kind=a.fit_robust, rounds=fitter.robust_rounds, scale=got.scale.tolist(), kept=got.kept.tolist(),
+                                 count=got.robust_count.tolist())
     torch.cuda.synchronize(dev)
     seconds = time.perf_counter() - t0
     ops.check_mlp_status(dev)
@@ -199,6 +216,10 @@ def main(argv=None):
         if a.fit_lighting is not None:
             print("bake_texture: %d rounds under one light per view: mean ambient gain %s, %d of %d light fits ok"
                   % (a.fit_lighting, " ".join("%.3f" % g for g in fit["lighting"]["gain"]), sum(s == 0 for s in fit["lighting"]["status"]), fitter.views))
+        if a.fit_robust is not None:
+            print("bake_texture: %d rounds of %s weights: sigma per view %.4f .. %.4f, weight kept per view %.3f .. %.3f"
+                  % (fit["robust"]["rounds"], a.fit_robust, min(fit["robust"]["scale"]), max(fit["robust"]["scale"]), min(fit["robust"]["kept"]),
+                     max(fit["robust"]["kept"])))
     if a.verify:
         base_verts, base_faces = (baker.verts, baker.faces) if texel_baker is None else (texel_baker.verts, texel_baker.faces)
 

@@ -41,7 +41,23 @@ view as the photographs:
     python tools/face_texel_bench.py --fit --lighting [--out profiles/face_texel_light/light.json]
 
 Each K41 row carries the bytes it moves (8 B per pixel for face and weight, 12 B per pixel for grad, 12 more with diag, 12 B per covered
-pixel for colour and 12 more for image) and their share of 8 TB/s."""
+pixel for colour and 12 more for image) and their share of 8 TB/s.
+
+--fit --robust: the robust weights instead (K42 tp_robust_weight), on the same workload: the R = 8 render as the
+photographs, the R = 4 render as the model, the inner pixels as the base weight:
+
+  robust B=n <kind>      ops.robust_weight on n views (8 and all): "tukey", "huber", "tukey scale_in" (no median), and "tukey perfect fit"
+                         (model = photograph: every q is 0, every key of a wave lands in one histogram bin at every level)
+  torch B=n tukey        the same rule composed in torch -- the comparator, not the code under test: q in fp64, torch.kthvalue per image
+                         over the counted pixels (which reads each image's count back), the weight in fp64; checked bit for bit against the
+                         call before anything is timed
+  fit R=4 ...            FaceTexelFitter.fit plain and robust (one round) with 0 iterations: the difference is one weight step
+
+    python tools/face_texel_bench.py --fit --robust [--out profiles/robust_weight/robust.json]
+
+Each K42 row carries the bytes its passes move -- 52 B per pixel: 24 B model and image, 4 B weight and 4 B of key written by the first pass,
+4 B of key read by each of the second and third, 4 B key, 4 B weight and 4 B out by the last (44 B without a weight, 36 B with scale_in: one
+pass) -- and their share of 8 TB/s, the floor if every pass went to HBM."""
 import argparse
 import json
 import os
@@ -66,6 +82,7 @@ def main(argv=None):
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--fit", action="store_true", help="time the adjoint (K36) and one fitter iteration instead")
     ap.add_argument("--lighting", action="store_true", help="with --fit: time K41 and the lit fit instead")
+    ap.add_argument("--robust", action="store_true", help="with --fit: time K42 and the robust fit's weight step instead")
     a = ap.parse_args(argv)
     import torch
     from texpose_amd import face_texels as FT, ops, texture_bake as TB
@@ -87,8 +104,10 @@ def main(argv=None):
     n_cov = int(covered.sum())
     if a.lighting and not a.fit:
         ap.error("--lighting comes with --fit")
+    if a.robust and (not a.fit or a.lighting):
+        ap.error("--robust comes with --fit and without --lighting")
     if a.fit:
-        return (bench_light if a.lighting else bench_fit)(a, locals())
+        return (bench_robust if a.robust else bench_light if a.lighting else bench_fit)(a, locals())
     routes, iters, checks, meshes = {"base": lambda: raster(vcolor=vcol), "base cull": lambda: raster(vcolor=vcol, cull=True)}, {}, {}, {}
     heavy = max(2, a.iters // 10)
     for R in (1, 4, 8):
@@ -286,6 +305,85 @@ def bench_light(a, env):
                plain_iteration_us=med["fit R=4 plain iters=1"] - med["fit R=4 plain iters=0"],
                lit_iteration_us=med["fit R=4 lit rounds=1 iters=1"] - med["fit R=4 lit rounds=1 iters=0"],
                light_step_us=med["fit R=4 lit rounds=1 iters=0"] - med["fit R=4 lit rounds=1 iters=0 no light step"], rows=rows)
+    KB.finish(res, a.out)
+
+
+def bench_robust(a, env):
+    import torch
+    from texpose_amd import face_texels as FT, ops
+    dev, B, H, W, pose, K, verts, faces = (env[k] for k in ("dev", "B", "H", "W", "pose", "K", "verts", "faces"))
+    v_np, f_np, colour, n_cov = (env[k] for k in ("v_np", "f_np", "colour", "n_cov"))
+    F = len(f_np)
+    face = ops.mesh_raster(verts, faces, pose, K, H=H, W=W, normals=False)["face"]
+
+    def shade(R):
+        vs, _, ni = FT.subdivide(v_np, f_np, R)
+        return ops.face_texel_shade(face, verts, faces, torch.from_numpy(FT.texels_from_nodes(colour(vs), ni)).to(dev), pose, K)
+
+    photo, model = shade(8), shade(4)
+    weight = FT.inner_coverage(face, F).float()
+    sigma = torch.full((B,), 0.03, device=dev)
+    c_tukey, sigma_min = 4.685, 1.0 / 255.0
+
+    def composed(n):
+        """the header's rule for Tukey's weight, image by image"""
+        e = photo[:n].double() - model[:n].double()
+        q = (((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]) / 3.0).float()
+        counted = torch.isfinite(weight[:n]) & (weight[:n] > 0) & torch.isfinite(q)
+        out, med, cnt = torch.zeros(n, H, W, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev, dtype=torch.int32)
+        for b in range(n):
+            qb = q[b][counted[b]]
+            cnt[b] = qb.numel()
+            if qb.numel():
+                med[b] = torch.kthvalue(qb, (qb.numel() - 1) // 2 + 1).values
+        s2 = torch.clamp_min((1.4826 * 1.4826) * med.double(), float(np.float32(sigma_min)) ** 2)
+        u2 = q.double() / ((float(np.float32(c_tukey)) ** 2) * s2)[:, None, None]
+        w = torch.where(u2 < 1.0, (1.0 - u2) * (1.0 - u2), torch.zeros_like(u2))
+        out = torch.where(counted, (weight[:n].double() * w).float(), out)
+        return dict(weight=out, median_q=med, scale=torch.sqrt(s2).float(), count=cnt)
+
+    routes, checks, moved = {}, {}, {}
+    for n in (B, 8):
+        ws = ops.robust_weight_workspace(n, H, W, dev)
+        outs = dict(weight=torch.empty(n, H, W, device=dev), median_q=torch.empty(n, device=dev), scale=torch.empty(n, device=dev),
+                    count=torch.empty(n, device=dev, dtype=torch.int32))
+        call = lambda n=n, ws=ws, outs=outs, m=model, **kw: ops.robust_weight(m[:n], photo[:n], weight=weight[:n], workspace=ws, out=outs, **kw)
+        got, want = {k: v.clone() for k, v in call().items()}, composed(n)
+        equal = {k: bool(torch.equal(got[k].view(torch.int32), want[k].view(torch.int32))) for k in ("weight", "median_q", "count")}
+        checks["B=%d tukey" % n] = dict(equal, median_q=got["median_q"].tolist()[:4], kept=float(got["weight"].sum() / weight[:n].sum()))
+        if not all(equal.values()):
+            raise SystemExit("face_texel_bench: B = %d: the call and the torch composition disagree (%s); nothing was timed" % (n, equal))
+        routes["robust B=%d tukey" % n] = call
+        routes["robust B=%d huber" % n] = lambda call=call: call(kind="huber")
+        routes["robust B=%d tukey scale_in" % n] = lambda call=call, n=n: call(scale_in=sigma[:n])
+        routes["robust B=%d tukey perfect fit" % n] = lambda call=call: call(m=photo)
+        routes["torch B=%d tukey" % n] = lambda n=n: composed(n)
+        for name in ("tukey", "huber", "tukey perfect fit"):
+            moved["robust B=%d %s" % (n, name)] = 52 * n * H * W
+        moved["robust B=%d tukey scale_in" % n] = 36 * n * H * W
+
+    def fitter(**kw):
+        f = FT.FaceTexelFitter(v_np, f_np, 4, H, W, dev, iters=0, **kw)
+        for c in range(0, B, 16):
+            f.add_views(photo[c:c + 16], pose[c:c + 16], K[c:c + 16], face=face[c:c + 16])
+        return f
+
+    routes["fit R=4 plain iters=0"] = fitter().fit
+    routes["fit R=4 robust rounds=1 iters=0"] = fitter(robust="tukey", robust_rounds=1).fit
+    med, times = KB.race(routes, a.iters, a.warmup, a.repeats)
+    rows = []
+    for name in routes:
+        row = dict(route=name, us_per_call=med[name], us_all_repeats=times[name])
+        if name in moved:
+            row.update(bytes_moved=moved[name], share_of_8_tb_per_s=moved[name] / (med[name] * 1e-6) / 8e12)
+        if name.endswith(" tukey") and name.startswith("robust"):
+            row.update(torch_us_same_run=med["torch" + name[6:]], speedup_over_torch=med["torch" + name[6:]] / med[name])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    res = dict(bench="robust_weight", device=torch.cuda.get_device_name(0), V=len(v_np), F=F, B=B, H=H, W=W, covered_pixels=n_cov,
+               covered_share=n_cov / (B * H * W), weighted_share=float(weight.sum()) / (B * H * W), iters=a.iters, warmup=a.warmup, repeats=a.repeats,
+               shader_clock_ghz_before=env["clock_before"], shader_clock_ghz_after=KB.shader_clock(), seconds=time.time() - env["t_start"], checks=checks,
+               weight_step_us=med["fit R=4 robust rounds=1 iters=0"] - med["fit R=4 plain iters=0"], rows=rows)
     KB.finish(res, a.out)
 
 
