@@ -131,22 +131,14 @@ def inner_coverage(face, F):
     return inner
 
 
-def fit_loop(views, prior, start, lam, iters, dtype=np.float64):
-    """FaceTexelFitter.fit: ``iters`` steps of conjugate gradients on (S^T m S + lam) x = S^T m I + lam prior, preconditioned with
-    coverage + lam -> dict(nodes, coverage, rms [iters + 1]).  ``dtype``: the precision of the vectors (the scalars stay fp64)."""
-    x, prior = np.array(start, dtype=dtype), np.asarray(prior, dtype=dtype)
+def pcg(x, r, m_inv, apply, after_step, iters, dtype=np.float64):
+    """``iters`` steps of preconditioned conjugate gradients from x, whose residual b - A x is r: ``apply(p)`` is A p, ``m_inv`` the inverse
+    of the diagonal preconditioner, ``after_step(x)`` is called after every step -> x.  The vectors are ``dtype``, the scalars fp64."""
     dot = lambda a, b: float((a.astype(np.float64) * b.astype(np.float64)).sum())
-    S = lambda v: views.shade(v.astype(np.float64)).astype(dtype)
-    St = lambda g: views.adjoint(g.astype(np.float64)).astype(dtype)
-    m, total = views.m.astype(dtype)[:, None], float(views.m.sum())
-    rms_of = lambda v: float(np.sqrt((views.m[:, None] * (S(v).astype(np.float64) - views.rgb) ** 2).sum() / (3.0 * total)))
-    coverage = views.coverage()
-    m_inv = (1.0 / (coverage[:, None] + lam)).astype(dtype)
-    r = St(m * (views.rgb.astype(dtype) - S(x))) + dtype(lam) * (prior - x)
     z = r * m_inv
-    p, rz, rms = z.copy(), dot(r, z), [rms_of(x)]
+    p, rz = z.copy(), dot(r, z)
     for _ in range(iters):
-        ap = St(m * S(p)) + dtype(lam) * p
+        ap = apply(p)
         pap = dot(p, ap)
         alpha = rz / pap if pap > 0 else 0.0
         x, r = x + dtype(alpha) * p, r - dtype(alpha) * ap
@@ -154,7 +146,23 @@ def fit_loop(views, prior, start, lam, iters, dtype=np.float64):
         rz_new = dot(r, z)
         beta = rz_new / rz if rz > 0 else 0.0
         p, rz = z + dtype(beta) * p, rz_new
-        rms.append(rms_of(x))
+        after_step(x)
+    return x
+
+
+def fit_loop(views, prior, start, lam, iters, dtype=np.float64):
+    """FaceTexelFitter.fit: ``iters`` steps of conjugate gradients on (S^T m S + lam) x = S^T m I + lam prior, preconditioned with
+    coverage + lam -> dict(nodes, coverage, rms [iters + 1]).  ``dtype``: the precision of the vectors (the scalars stay fp64)."""
+    x, prior = np.array(start, dtype=dtype), np.asarray(prior, dtype=dtype)
+    S = lambda v: views.shade(v.astype(np.float64)).astype(dtype)
+    St = lambda g: views.adjoint(g.astype(np.float64)).astype(dtype)
+    m, total = views.m.astype(dtype)[:, None], float(views.m.sum())
+    rms_of = lambda v: float(np.sqrt((views.m[:, None] * (S(v).astype(np.float64) - views.rgb) ** 2).sum() / (3.0 * total)))
+    coverage = views.coverage()
+    m_inv = (1.0 / (coverage[:, None] + lam)).astype(dtype)
+    r = St(m * (views.rgb.astype(dtype) - S(x))) + dtype(lam) * (prior - x)
+    rms = [rms_of(x)]
+    x = pcg(x, r, m_inv, lambda p: St(m * S(p)) + dtype(lam) * p, lambda v: rms.append(rms_of(v)), iters, dtype)
     return dict(nodes=x, coverage=coverage, rms=np.array(rms))
 
 

@@ -76,7 +76,6 @@ def lit_fit_loop(views, planes, prior, start, lam, iters, rounds, tau=0.5, tau0=
     B, H, W = face.shape
     F = len(faces)
     valid = views.valid.reshape(B, H, W)
-    dot = lambda a, b: float((a.astype(np.float64) * b.astype(np.float64)).sum())
     S = lambda v: views.shade(v.astype(np.float64)).astype(dtype)
     St = lambda g: views.adjoint(g.astype(np.float64)).astype(dtype)
     m, total = views.m.astype(dtype)[:, None], float(views.m.sum())
@@ -104,18 +103,7 @@ def lit_fit_loop(views, planes, prior, start, lam, iters, rounds, tau=0.5, tau0=
             rms.append(rms_of(x))
         r = St(m * s * resid(x)) + dtype(lam) * (prior - x)
         m_inv = (1.0 / (St(m * s * s) + dtype(lam))).astype(dtype)
-        z = r * m_inv
-        p, rz = z.copy(), dot(r, z)
-        for _ in range(iters):
-            ap = St(m * s * (s * S(p))) + dtype(lam) * p
-            pap = dot(p, ap)
-            alpha = rz / pap if pap > 0 else 0.0
-            x, r = x + dtype(alpha) * p, r - dtype(alpha) * ap
-            z = r * m_inv
-            rz_new = dot(r, z)
-            bet = rz_new / rz if rz > 0 else 0.0
-            p, rz = z + dtype(bet) * p, rz_new
-            rms.append(rms_of(x))
+        x = FIT.pcg(x, r, m_inv, lambda p: St(m * s * (s * S(p))) + dtype(lam) * p, lambda v: rms.append(rms_of(v)), iters, dtype)
     return dict(nodes=x, coverage=views.coverage(), light=light, status=status, flags=flags, gain=light[:, :, 0].astype(np.float64).mean(0),
                 rms=np.array(rms))
 

@@ -5,6 +5,8 @@ import os
 
 import numpy as np
 
+import face_texel_fit_ref as FIT
+
 TUKEY, HUBER = "tukey", "huber"
 DEFAULT_C = {TUKEY: 4.685, HUBER: 1.345}
 SIGMA_MIN = np.float32(1.0 / 255.0)
@@ -114,7 +116,6 @@ def robust_fit_loop(views, rgb, weight, prior, start, lam=LAM, iters=ITERS, roun
     valid = views.valid
     rgb32, base32 = np.asarray(rgb, np.float32), np.asarray(weight, np.float32)
     x, prior = np.array(start, dtype=dtype), np.asarray(prior, dtype=dtype)
-    dot = lambda a, b: float((a.astype(np.float64) * b.astype(np.float64)).sum())
     S = lambda v: views.shade(v.astype(np.float64)).astype(dtype)
     St = lambda g: views.adjoint(g.astype(np.float64)).astype(dtype)
     image = views.rgb.astype(dtype)
@@ -131,18 +132,7 @@ def robust_fit_loop(views, rgb, weight, prior, start, lam=LAM, iters=ITERS, roun
         pre = np.bincount(views.dest.reshape(-1), (views.w * w64[:, None]).reshape(-1), views.U) if weighted_preconditioner else coverage
         m_inv = (1.0 / (pre[:, None] + lam)).astype(dtype)
         r = St(w * (image - S(x))) + dtype(lam) * (prior - x)
-        z = r * m_inv
-        p, rz = z.copy(), dot(r, z)
-        for _ in range(iters):
-            ap = St(w * S(p)) + dtype(lam) * p
-            pap = dot(p, ap)
-            alpha = rz / pap if pap > 0 else 0.0
-            x, r = x + dtype(alpha) * p, r - dtype(alpha) * ap
-            z = r * m_inv
-            rz_new = dot(r, z)
-            beta = rz_new / rz if rz > 0 else 0.0
-            p, rz = z + dtype(beta) * p, rz_new
-            rms.append(rms_of(x))
+        x = FIT.pcg(x, r, m_inv, lambda p: St(w * S(p)) + dtype(lam) * p, lambda v: rms.append(rms_of(v)), iters, dtype)
     kept = fit["weight"].astype(np.float64).sum((1, 2)) / np.maximum(np.where(base32 > 0, base32, 0).astype(np.float64).sum((1, 2)), 1e-300)
     return dict(nodes=x, coverage=coverage, rms=np.array(rms), scale=fit["scale"], kept=kept, count=fit["count"])
 

@@ -20,7 +20,7 @@ DESIGN.md section 32) reweights the pixels round by round, for photographs with 
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -157,21 +157,28 @@ def nodes_from_texels(texels, node_index, U: Optional[int] = None) -> np.ndarray
     return out
 
 
-class FaceTexelBaker:
+class _TexelMesh:
+    """What FaceTexelBaker and FaceTexelFitter share: the base mesh, its subdivision at resolution R and the device copies."""
+
+    def _set_mesh(self, verts, faces, R: int, device) -> None:
+        self.R, self.T, self.device = int(R), texel_count(R), torch.device(device)
+        self.verts_host = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+        self.faces_host = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+        self.verts_sub, self.faces_sub, self.node_index_host = subdivide(self.verts_host, self.faces_host, self.R)
+        self.verts = torch.from_numpy(self.verts_host).to(self.device)
+        self.faces = torch.from_numpy(self.faces_host).to(self.device)
+        self.node_index = torch.from_numpy(self.node_index_host).to(self.device)
+
+
+class FaceTexelBaker(_TexelMesh):
     """Accumulates views of one mesh into a face-texel texture of resolution R: the vertex bake (TextureBaker, K27) on the U unique
     nodes of ``subdivide``, with the normals vertex_normals(verts_sub, faces_sub) and the depth planes of the BASE mesh.  The texture
     is continuous across edges by construction: the faces at an edge index the same nodes."""
 
     def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", **thresholds):
-        self.R, self.T = int(R), texel_count(R)
-        self.verts_host = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-        self.faces_host = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
-        self.verts_sub, self.faces_sub, self.node_index_host = subdivide(self.verts_host, self.faces_host, self.R)
+        self._set_mesh(verts, faces, R, device)
         self.nodes = TextureBaker(self.verts_sub, self.faces_sub, H, W, device, **thresholds)
-        self.device, self.H, self.W = self.nodes.device, self.nodes.H, self.nodes.W
-        self.verts = torch.from_numpy(self.verts_host).to(self.device)
-        self.faces = torch.from_numpy(self.faces_host).to(self.device)
-        self.node_index = torch.from_numpy(self.node_index_host).to(self.device)
+        self.H, self.W = self.nodes.H, self.nodes.W
 
     @property
     def views(self) -> int:
@@ -204,38 +211,55 @@ def shade_nodes(face: Tensor, verts: Tensor, faces: Tensor, nodes: Tensor, node_
     return autograd_ops.face_texel_shade_nodes(face, verts, faces, nodes, torch.as_tensor(node_index, device=nodes.device), pose, intr)
 
 
-class FaceTexelFitter:
+class _View(NamedTuple):
+    """One add_views call of FaceTexelFitter, on the device until reset(); zbuf and mask with lighting only: the depth plane the light
+    step reads as "covered" and its mask (weight > 0)."""
+    face: Tensor
+    rgb: Tensor
+    weight: Tensor
+    pose: Tensor
+    intr: Tensor
+    zbuf: Optional[Tensor] = None
+    mask: Optional[Tensor] = None
+
+
+class FaceTexelFitter(_TexelMesh):
     """Fits the U node colours x of a face-texel texture of resolution R to photographs: minimises
         sum_p m_p |(S x)_p - I_p|^2 + lam |x - prior|^2
-    over the stored views, S the shading rule of K35 on the node colours (texels = x[node_index]), by ``iters`` steps of conjugate
-    gradients preconditioned with M = coverage + lam, coverage the per-node sum of shading weights over all covered pixels (K36's
-    ``weight``: the lumped diagonal of S^T S).  S x is ops.face_texel_shade, S^T g is ops.face_texel_shade_bwd with the node index:
-    deterministic, so a fit is bit-identical from run to run.  An iteration is one shade and one adjoint over the stored views for the
-    step and one more shade for the training rms it reports.  A quadratic loss by default; ``robust`` = "tukey" or "huber" fits by
-    iteratively reweighted least squares instead (below), and any other loss goes through ``shade_nodes`` and an optimiser.  The result
-    is not clamped: the caller does that.
+    over the stored views, S the shading rule of K35 on the node colours (texels = x[node_index]).  S x is ops.face_texel_shade, S^T g
+    is ops.face_texel_shade_bwd with the node index: deterministic, so a fit is bit-identical from run to run.  The result is not
+    clamped: the caller does that.
 
-    ``robust`` (K42): for photographs that carry what no texture explains (an occluder, a highlight, a patch of
-    background).  ``robust_rounds`` rounds, each of which weights every pixel of every stored view by ops.robust_weight of the current
-    residual (Tukey's biweight with c = 4.685, or Huber's weight with c = 1.345, or ``robust_c``; in units of sigma = 1.4826 sqrt(median of
-    the mean squared colour error) per view, at least ``sigma_min``) times the view's own weight, and then runs ``iters`` conjugate-
-    gradient steps on the weighted system from the current x, preconditioned with S^T (w) + lam.  The result gains scale, kept and
-    robust_count per view (see _fit_robust).  Not together with ``lighting=True``.
+    The loop, common to the three modes: a round is one pass over the stored views -- shade, the mode's pixel step, adjoint -- that
+    gives the right-hand side, the preconditioner and the error sums (the first pass also yields the coverage: the per-node sum of
+    shading weights over all covered pixels, K36's ``weight``, the lumped diagonal of S^T S), and then ``iters`` steps of preconditioned
+    conjugate gradients (_pcg) restarted from the current x.  An iteration is one shade and one adjoint over the stored views for the
+    step and one more shade for the training rms it reports.
+
+    The plain fit (a quadratic loss, the default) is one round, preconditioned with M = coverage + lam.  Any loss that is none of the
+    three modes goes through ``shade_nodes`` and an optimiser.
+
+    ``robust`` = "tukey" or "huber" (K42) fits by iteratively reweighted least squares, for photographs that carry
+    what no texture explains (an occluder, a highlight, a patch of background).  ``robust_rounds`` rounds, each of which weights every
+    pixel of every stored view by ops.robust_weight of the current residual (Tukey's biweight with c = 4.685, or Huber's weight with c =
+    1.345, or ``robust_c``; in units of sigma = 1.4826 sqrt(median of the mean squared colour error) per view, at least ``sigma_min``)
+    times the view's own weight, and solves the weighted system, preconditioned with S^T (w) + lam.  The result gains scale, kept and
+    robust_count per view (see _robust_mode).  Not together with ``lighting=True``.
 
     ``lighting=True`` (K41) fits x as an ALBEDO under one first-order SH light per stored view: it minimises
         sum_b sum_p m_p |s_b(n_p) (S x)_p + beta_b - I_p|^2 + lam |x - prior|^2
     over x and the lights (l0, l1, l2, l3, beta per view and channel; s = l0 + l1 n_x + l2 n_y + l3 n_z on the face's normal, as
     ops.photo_lighting) by ``rounds`` alternations: a light step (ops.photo_lighting of the unlit render S x against each photograph,
-    ``tau0`` in round 0 and ``tau`` afterwards, l0 within ``gain_range``) and ``iters`` conjugate-gradient steps on (S^T m s^2 S + lam) x
-    = S^T m s (I - beta) + lam prior, restarted from the current x, preconditioned per node and channel with S^T (m s^2) + lam; between
-    shade and adjoint sits ops.face_texel_light.  From round 1 on a view whose light fit fails (status != 0) or falls back to the
-    ambient-only form in a channel keeps the light it had.  The gauge (x scaled by a, every l0 .. l3 by 1 / a) is pinned by the prior
-    alone; the result's ``gain`` is the mean l0 per channel, for a caller who wants to normalise.  ``lighting=False`` is the fit above."""
+    ``tau0`` in round 0 and ``tau`` afterwards, l0 within ``gain_range``) and the round's conjugate-gradient steps on (S^T m s^2 S + lam) x
+    = S^T m s (I - beta) + lam prior, preconditioned per node and channel with S^T (m s^2) + lam; between shade and adjoint sits
+    ops.face_texel_light.  From round 1 on a view whose light fit fails (status != 0) or falls back to the ambient-only form in a channel
+    keeps the light it had.  The gauge (x scaled by a, every l0 .. l3 by 1 / a) is pinned by the prior alone; the result's ``gain`` is
+    the mean l0 per channel, for a caller who wants to normalise (see _lit_mode)."""
 
     def __init__(self, verts, faces, R: int, H: int, W: int, device="cuda:0", lam: float = 0.1, iters: int = 4, cull: bool = False,
                  lighting: bool = False, rounds: int = 6, tau: float = 0.5, tau0: float = 2.0, gain_range=(0.25, 4.0),
                  robust: Optional[str] = None, robust_c: Optional[float] = None, robust_rounds: int = 6, sigma_min: float = 1.0 / 255.0):
-        self.R, self.T, self.H, self.W = int(R), texel_count(R), int(H), int(W)
+        self.T, self.H, self.W = texel_count(R), int(H), int(W)        # (R is checked before the other arguments)
         if not (lam > 0 and int(iters) >= 0):
             raise ValueError("FaceTexelFitter: lam > 0 and iters >= 0 expected")
         if robust is not None:
@@ -253,21 +277,16 @@ class FaceTexelFitter:
             raise ValueError("FaceTexelFitter: rounds >= 1, tau > 0 and tau0 > 0 expected with lighting")
         self.lighting, self.rounds, self.tau, self.tau0 = bool(lighting), int(rounds), float(tau), float(tau0)
         self.gain_range = tuple(float(g) for g in gain_range)
-        self.lam, self.iters, self.cull, self.device = float(lam), int(iters), bool(cull), torch.device(device)
-        self.verts_host = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-        self.faces_host = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
-        self.verts_sub, self.faces_sub, self.node_index_host = subdivide(self.verts_host, self.faces_host, self.R)
+        self.lam, self.iters, self.cull = float(lam), int(iters), bool(cull)
+        self._set_mesh(verts, faces, R, device)
         self.U = len(self.verts_sub)
-        self.verts = torch.from_numpy(self.verts_host).to(self.device)
-        self.faces = torch.from_numpy(self.faces_host).to(self.device)
-        self.node_index = torch.from_numpy(self.node_index_host).to(self.device)
         self._node_index32 = self.node_index.to(torch.int32)
         self._faces_lit = self.faces.contiguous()        # (K40 and K41 take the faces as they are: a PLY reader may hand over a strided view)
-        self._views = []                                 # (face, rgb, weight, pose, intr) per add_views call; + (zbuf, mask) with lighting
+        self._views = []                                 # one _View per add_views call
 
     @property
     def views(self) -> int:
-        return sum(v[0].shape[0] for v in self._views)
+        return sum(v.face.shape[0] for v in self._views)
 
     def reset(self) -> None:
         self._views = []
@@ -295,33 +314,26 @@ class FaceTexelFitter:
             weight = inner_coverage(face, self.faces.shape[0]).float()
         weight = torch.as_tensor(weight).detach().to(device=self.device, dtype=torch.float32).reshape(B, self.H, self.W).contiguous()
         if not self.lighting:
-            self._views.append((face, rgb, weight, pose, K))
+            self._views.append(_View(face, rgb, weight, pose, K))
             return
         if zbuf is None:                                 # (the light step reads depth only as "covered")
             zbuf = torch.where((face >= 0) & (face < self.faces.shape[0]), 1.0, -1.0).float()
-        self._views.append((face, rgb, weight, pose, K, zbuf.contiguous(), (weight > 0).to(torch.uint8)))
+        self._views.append(_View(face, rgb, weight, pose, K, zbuf.contiguous(), (weight > 0).to(torch.uint8)))
 
-    def _shade(self, view, x: Tensor) -> Tensor:
-        return ops.face_texel_shade(view[0], self.verts, self.faces, x[self.node_index], view[3], view[4])
+    def _shade(self, view: _View, x: Tensor) -> Tensor:
+        return ops.face_texel_shade(view.face, self.verts, self.faces, x[self.node_index], view.pose, view.intr)
 
-    def _adjoint(self, view, g: Tensor, weight: bool = False):
-        return ops.face_texel_shade_bwd(view[0], self.verts, self.faces, g, view[3], view[4], R=self.R, node_index=self._node_index32, U=self.U,
-                                        weight=weight)
-
-    def _sse(self, x: Tensor) -> Tensor:
-        """sum_p m_p |(S x)_p - I_p|^2 over the views, fp64, 0-dim"""
-        sse = torch.zeros((), device=self.device, dtype=torch.float64)
-        for view in self._views:
-            e = self._shade(view, x) - view[1]
-            sse = sse + ((e * e).sum(-1) * view[2]).double().sum()
-        return sse
+    def _adjoint(self, view: _View, g: Tensor, weight: bool = False):
+        return ops.face_texel_shade_bwd(view.face, self.verts, self.faces, g, view.pose, view.intr, R=self.R, node_index=self._node_index32,
+                                        U=self.U, weight=weight)
 
     def fit(self, prior: Optional[Tensor] = None, start: Optional[Tensor] = None, lights: Optional[Tensor] = None, light_step: bool = True) -> AttrDict:
         """``prior`` [U,3] (e.g. FaceTexelBaker's vcolor_sub; None: 0.5), ``start`` [U,3] (None: the prior) -> AttrDict(texels [F,T,3],
-        nodes [U,3], coverage [U], rms [iters + 1]: sqrt(sum m |S x - I|^2 / (3 sum m)) at the start and after every iteration (a device
-        tensor), on_prior: the number of nodes with coverage < lam, which the prior decides).  With lighting: ``lights`` [views,3,5] are the
-        lights to start from (None: (1, 0, 0, 0, 0)), ``light_step=False`` keeps them through every round (a fit under known lights), and
-        the result gains light, lighting_status, lighting_flags and gain (see _fit_lit)."""
+        nodes [U,3], coverage [U], rms [rounds * iters + 1]: sqrt(sum w |residual|^2 / (3 sum w)) under the mode's weights at the start and
+        after every iteration (a device tensor; rounds is 1, ``robust_rounds`` or ``rounds``), on_prior: the number of nodes with coverage <
+        lam, which the prior decides) plus the mode's own keys (_robust_mode, _lit_mode).  With lighting: ``lights`` [views,3,5] are the lights to
+        start from (None: (1, 0, 0, 0, 0)) and ``light_step=False`` keeps them through every round (a fit under known lights).  Scalars stay
+        0-dim fp64 device tensors; nothing but on_prior is read back."""
         if not self.lighting and (lights is not None or not light_step):
             raise ValueError("FaceTexelFitter.fit: lights and light_step belong to lighting=True")
         if not self._views:
@@ -338,170 +350,147 @@ class FaceTexelFitter:
 
         prior = nodes_arg(prior, "prior", torch.full((U, 3), 0.5, device=dev))
         x = nodes_arg(start, "start", prior).clone()
-        dot = lambda a, b: (a.double() * b.double()).sum()
-        if self.lighting:
-            if lights is not None:
-                lights = torch.as_tensor(lights).detach().to(device=dev, dtype=torch.float32)
-                if tuple(lights.shape) != (self.views, 3, 5):
-                    raise ValueError("FaceTexelFitter.fit: lights [views=%d,3,5] expected, got %s" % (self.views, tuple(lights.shape)))
-            return self._fit_lit(prior, x, dot, lights, bool(light_step))
-        if self.robust is not None:
-            return self._fit_robust(prior, x, dot)
-        # r = b - A x = S^T m (I - S x) + lam (prior - x); the first adjoint also gives the coverage
-        r, coverage = lam * (prior - x), torch.zeros(U, device=dev)
-        sse, total = torch.zeros((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.float64)
-        for view in self._views:
-            e = view[1] - self._shade(view, x)
-            g, w = self._adjoint(view, e * view[2][..., None], weight=True)
-            r, coverage = r + g, coverage + w
-            sse, total = sse + ((e * e).sum(-1) * view[2]).double().sum(), total + view[2].double().sum()
-        m_inv = 1.0 / (coverage[:, None] + lam)
-        z = r * m_inv
-        p, rz = z.clone(), dot(r, z)
-        sses = [sse]
-        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
-        for _ in range(self.iters):
+        if lights is not None:
+            lights = torch.as_tensor(lights).detach().to(device=dev, dtype=torch.float32)
+            if tuple(lights.shape) != (self.views, 3, 5):
+                raise ValueError("FaceTexelFitter.fit: lights [views=%d,3,5] expected, got %s" % (self.views, tuple(lights.shape)))
+        mode = self._lit_mode(lights, bool(light_step)) if self.lighting else self._robust_mode() if self.robust is not None else self._plain_mode()
+        zero = torch.zeros((), device=dev, dtype=torch.float64)
+        coverage, total, errors = torch.zeros(U, device=dev), zero, []       # errors: (sum w |residual|^2, sum w) per rms entry
+
+        def apply(p):                                    # A p = S^T D S p + lam p, D the mode's pixel step under the round's weights or lights
             ap = lam * p
-            for view in self._views:
-                ap = ap + self._adjoint(view, self._shade(view, p) * view[2][..., None])
-            pap = dot(p, ap)
-            alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
-            x, r = x + alpha.float() * p, r - alpha.float() * ap
-            z = r * m_inv
-            rz_new = dot(r, z)
-            beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
-            p, rz = z + beta.float() * p, rz_new
-            sses.append(self._sse(x))
-        rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
-        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()))
+            for i, view in enumerate(self._views):
+                ap = ap + self._adjoint(view, mode.between(i, view, self._shade(view, p)))
+            return ap
 
-    def _fit_robust(self, prior: Tensor, x: Tensor, dot) -> AttrDict:
-        """fit() with robust=...: ``robust_rounds`` rounds of iteratively reweighted least squares.  A round takes the weights w =
-        ops.robust_weight(S x, photograph, weight=m) of every stored view at the current x, then ``iters`` conjugate-gradient steps on
-        (S^T w S + lam) x = S^T w I + lam prior, restarted from x and preconditioned with S^T (w) + lam (the adjoint of the weight plane).
-        As fit()'s result, rms [robust_rounds * iters + 1] being sqrt(sum w |S x - I|^2 / (3 sum w)) under the round's own weights (at the
-        start and after every iteration), plus scale [views] (sigma per view), kept [views] = sum w / sum m and robust_count [views], all
-        of the last round.  Scalars stay 0-dim fp64 device tensors; nothing is read back inside the loop."""
-        dev, U, lam = self.device, self.U, self.lam
-        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
-        spaces = [ops.robust_weight_workspace(v[0].shape[0], self.H, self.W, dev) for v in self._views]
-        coverage, rms = None, []
-
-        def weighted_sse(x, ws):
+        def after_step(x):
             sse = zero
-            for view, w in zip(self._views, ws):
-                e = self._shade(view, x) - view[1]
-                sse = sse + torch.where(w > 0, (e * e).sum(-1) * w, torch.zeros_like(w)).double().sum()
-            return sse
+            for i, view in enumerate(self._views):
+                sse = sse + mode.sse(i, view, self._shade(view, x))
+            errors.append((sse, total))
 
-        for rnd in range(self.robust_rounds):
-            # the weights at the current x, then r = S^T w (I - S x) + lam (prior - x) and the preconditioner under them
-            r, pre, sse, total = lam * (prior - x), torch.zeros(U, 3, device=dev), zero, zero
-            first_cover = torch.zeros(U, device=dev) if coverage is None else None
-            ws, fits = [], []
-            for view, space in zip(self._views, spaces):
-                model = self._shade(view, x)
-                fit = ops.robust_weight(model, view[1], weight=view[2], kind=self.robust, c=self.robust_c, sigma_min=self.sigma_min, workspace=space)
-                w = fit["weight"]
-                on = (w > 0)[..., None]
-                e = torch.where(on, view[1] - model, torch.zeros_like(model))
-                if first_cover is not None:                      # (the coverage is that of the plain fit: it does not look at the values)
-                    g, cover = self._adjoint(view, e * w[..., None], weight=True)
-                    r, first_cover = r + g, first_cover + cover
+        for rnd in range(mode.rounds):
+            # one pass over the views: r = b - A x = S^T (the mode's residual) + lam (prior - x), the preconditioner and the error sums
+            r, pre, sse, round_total = lam * (prior - x), None, zero, zero
+            for i, view in enumerate(self._views):
+                grad, diag, err, weight = mode.residual(rnd, i, view, self._shade(view, x))
+                if rnd == 0:                             # the first adjoint also gives the coverage (it does not look at the values)
+                    g, cover = self._adjoint(view, grad, weight=True)
+                    coverage = coverage + cover
                 else:
-                    r = r + self._adjoint(view, e * w[..., None])
-                pre = pre + self._adjoint(view, w[..., None].expand(-1, -1, -1, 3).contiguous())
-                sse, total = sse + ((e * e).sum(-1) * w).double().sum(), total + w.double().sum()
-                ws.append(w)
-                fits.append(fit)
-            if coverage is None:
-                coverage = first_cover
-                rms.append(torch.sqrt(sse / (3.0 * total).clamp_min(1e-300)))
-            m_inv = 1.0 / (pre + lam)
-            z = r * m_inv
-            p, rz = z.clone(), dot(r, z)
-            for _ in range(self.iters):
-                ap = lam * p
-                for view, w in zip(self._views, ws):
-                    ap = ap + self._adjoint(view, self._shade(view, p) * w[..., None])
-                pap = dot(p, ap)
-                alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
-                x, r = x + alpha.float() * p, r - alpha.float() * ap
-                z = r * m_inv
-                rz_new = dot(r, z)
-                beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
-                p, rz = z + beta.float() * p, rz_new
-                rms.append(torch.sqrt(weighted_sse(x, ws) / (3.0 * total).clamp_min(1e-300)))
-        base = torch.cat([torch.where(v[2] > 0, v[2], torch.zeros_like(v[2])).double().sum((1, 2)) for v in self._views])
-        kept = (torch.cat([w.double().sum((1, 2)) for w in ws]) / base.clamp_min(1e-300)).float()
-        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=torch.stack(rms).float(),
-                        on_prior=int((coverage < lam).sum()), scale=torch.cat([f["scale"] for f in fits]), kept=kept,
-                        robust_count=torch.cat([f["count"] for f in fits]))
+                    g = self._adjoint(view, grad)
+                if diag is not None:
+                    pre = (torch.zeros(U, 3, device=dev) if pre is None else pre) + self._adjoint(view, diag)
+                r, sse, round_total = r + g, sse + err, round_total + weight
+            if rnd == 0 or mode.total_per_round:
+                total = round_total
+            if rnd == 0:
+                errors.append((sse, total))
+            m_inv = 1.0 / ((coverage[:, None] if pre is None else pre) + lam)
+            x = _pcg(x, r, m_inv, apply, after_step, self.iters)
+        sse, total = (torch.stack(t) for t in zip(*errors))
+        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage,
+                        rms=torch.sqrt(sse / (3.0 * total).clamp_min(1e-300)).float(), on_prior=int((coverage < lam).sum()), **mode.extras())
 
-    def _lit(self, view, colour: Tensor, light: Tensor, **kw):
-        return ops.face_texel_light(view[0], self.verts, self._faces_lit, colour, view[3], light, weight=view[2], **kw)
+    # A mode of fit() supplies: rounds; residual(rnd, i, view, model), which first takes view i's weights or light for the round at model =
+    # S x -> (the plane whose adjoint goes into r, the plane whose adjoint is the view's term of the preconditioner or None: the coverage
+    # serves, sum w |residual|^2, sum w); between(i, view, shaded): the pixel step between shade and adjoint in A p; sse(i, view, model):
+    # sum w |residual|^2 at a new x; total_per_round: whether sum w is the round's own; extras(): the result's further keys.
+    def _plain_mode(self) -> AttrDict:
+        """The quadratic fit: one round, a pixel weighs its view's m."""
+        def residual(rnd, i, view, model):
+            e = view.rgb - model
+            return e * view.weight[..., None], None, ((e * e).sum(-1) * view.weight).double().sum(), view.weight.double().sum()
 
-    def _fit_lit(self, prior: Tensor, x: Tensor, dot, start_lights: Optional[Tensor], light_step: bool) -> AttrDict:
-        """fit() with lighting: as its result, rms [rounds * iters + 1] being that of the lit residual (after the first light step and after
-        every iteration), plus light [views,3,5], lighting_status / lighting_flags [views] (ops.photo_lighting's, of the last round) and
-        gain [3].  Scalars stay 0-dim fp64 device tensors; nothing is read back inside the loop."""
-        dev, U, lam = self.device, self.U, self.lam
-        zero, one = torch.zeros((), device=dev, dtype=torch.float64), torch.ones((), device=dev, dtype=torch.float64)
-        fallback = 7 * ops._lib.LIGHTING_FALLBACK
-        sizes = [v[0].shape[0] for v in self._views]
+        def sse(i, view, model):
+            e = model - view.rgb
+            return ((e * e).sum(-1) * view.weight).double().sum()
+
+        return AttrDict(rounds=1, total_per_round=False, residual=residual, between=lambda i, view, shaded: shaded * view.weight[..., None],
+                        sse=sse, extras=dict)
+
+    def _robust_mode(self) -> AttrDict:
+        """robust=...: iteratively reweighted least squares.  A round takes the weights w = ops.robust_weight(S x, photograph, weight=m) of
+        every stored view at the current x; its system is (S^T w S + lam) x = S^T w I + lam prior, preconditioned with S^T (w) + lam (the
+        adjoint of the weight plane), and its rms is that under the round's own weights.  The result gains scale [views] (sigma per view),
+        kept [views] = sum w / sum m and robust_count [views], all of the last round."""
+        spaces = [ops.robust_weight_workspace(v.face.shape[0], self.H, self.W, self.device) for v in self._views]
+        ws, fits = [None] * len(spaces), [None] * len(spaces)
+
+        def residual(rnd, i, view, model):
+            fits[i] = ops.robust_weight(model, view.rgb, weight=view.weight, kind=self.robust, c=self.robust_c, sigma_min=self.sigma_min,
+                                        workspace=spaces[i])
+            w = ws[i] = fits[i]["weight"]
+            e = torch.where((w > 0)[..., None], view.rgb - model, torch.zeros_like(model))
+            return e * w[..., None], w[..., None].expand(-1, -1, -1, 3).contiguous(), ((e * e).sum(-1) * w).double().sum(), w.double().sum()
+
+        def sse(i, view, model):
+            e = model - view.rgb
+            return torch.where(ws[i] > 0, (e * e).sum(-1) * ws[i], torch.zeros_like(ws[i])).double().sum()
+
+        def extras():
+            base = torch.cat([torch.where(v.weight > 0, v.weight, torch.zeros_like(v.weight)).double().sum((1, 2)) for v in self._views])
+            kept = (torch.cat([w.double().sum((1, 2)) for w in ws]) / base.clamp_min(1e-300)).float()
+            return dict(scale=torch.cat([f["scale"] for f in fits]), kept=kept, robust_count=torch.cat([f["count"] for f in fits]))
+
+        return AttrDict(rounds=self.robust_rounds, total_per_round=True, residual=residual, between=lambda i, view, shaded: shaded * ws[i][..., None],
+                        sse=sse, extras=extras)
+
+    def _lit_mode(self, start_lights: Optional[Tensor], light_step: bool) -> AttrDict:
+        """lighting=True: a round first takes each view's light (ops.photo_lighting of the unlit render S x against the photograph, unless
+        ``light_step`` is off); from round 1 a failed or fallback light keeps the one before.  Its system is (S^T m s^2 S + lam) x = S^T m s
+        (I - beta) + lam prior, preconditioned with S^T (m s^2) + lam; ops.face_texel_light sits between shade and adjoint and sums the lit
+        residual, so rms is that of the lit residual (after the first light step and after every iteration; sum m is round 0's).  The result
+        gains light [views,3,5], lighting_status / lighting_flags [views] (ops.photo_lighting's, of the last round) and gain [3]."""
+        dev, fallback = self.device, 7 * ops._lib.LIGHTING_FALLBACK
+        sizes = [v.face.shape[0] for v in self._views]
         identity = torch.tensor([1.0, 0.0, 0.0, 0.0, 0.0], device=dev)
         lights = [None if light_step else identity.expand(b, 3, 5).contiguous() for b in sizes] if start_lights is None \
             else [t.contiguous() for t in start_lights.split(sizes)]
         status, flags = ([torch.zeros(b, device=dev, dtype=torch.int32) for b in sizes] for _ in range(2))
-        coverage, sses, total = None, [], zero
 
-        def lit_sse(x):
-            sums = zero.new_zeros(2)
-            for i, view in enumerate(self._views):
-                sums = sums + self._lit(view, self._shade(view, x), lights[i], image=view[1], sums=True)["sums"].sum(0)
-            return sums[0]
+        def lit(i, view, colour, **kw):
+            return ops.face_texel_light(view.face, self.verts, self._faces_lit, colour, view.pose, lights[i], weight=view.weight, **kw)
 
-        for rnd in range(self.rounds):
-            # the light step, then r = S^T m s (I - (s S x + beta)) + lam (prior - x) and the preconditioner under the new lights
-            r, pre, sums = lam * (prior - x), torch.zeros(U, 3, device=dev), zero.new_zeros(2)
-            first_cover = torch.zeros(U, device=dev) if coverage is None else None
-            for i, view in enumerate(self._views):
-                c = self._shade(view, x)
-                if light_step:
-                    fit = ops.photo_lighting(self.verts, self._faces_lit, view[0], view[5], c, view[3], view[1], tau=self.tau0 if rnd == 0 else self.tau,
-                                             light=lights[i], mask=view[6], gain_range=self.gain_range, apply=False)
-                    failed = (fit["flags"] & fallback) != 0          # (status != 0: photo_lighting itself returns the incoming light)
-                    keep = fit["light"] if rnd == 0 else torch.where(failed[:, None, None], lights[i], fit["light"])
-                    lights[i], status[i], flags[i] = keep, fit["status"], fit["flags"]
-                out = self._lit(view, c, lights[i], image=view[1], diag=True, sums=True)
-                if first_cover is not None:
-                    g, w = self._adjoint(view, out["grad"], weight=True)
-                    first_cover = first_cover + w
-                else:
-                    g = self._adjoint(view, out["grad"])
-                r, pre, sums = r + g, pre + self._adjoint(view, out["diag"]), sums + out["sums"].sum(0)
-            if coverage is None:
-                coverage, total = first_cover, sums[1]
-                sses.append(sums[0])
-            m_inv = 1.0 / (pre + lam)
-            z = r * m_inv
-            p, rz = z.clone(), dot(r, z)
-            for _ in range(self.iters):
-                ap = lam * p
-                for i, view in enumerate(self._views):
-                    ap = ap + self._adjoint(view, self._lit(view, self._shade(view, p), lights[i])["grad"])
-                pap = dot(p, ap)
-                alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
-                x, r = x + alpha.float() * p, r - alpha.float() * ap
-                z = r * m_inv
-                rz_new = dot(r, z)
-                beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
-                p, rz = z + beta.float() * p, rz_new
-                sses.append(lit_sse(x))
-        rms = torch.sqrt(torch.stack(sses) / (3.0 * total).clamp_min(1e-300)).float()
-        light = torch.cat(lights)
-        return AttrDict(texels=texels_from_nodes(x, self.node_index), nodes=x, coverage=coverage, rms=rms, on_prior=int((coverage < lam).sum()),
-                        light=light, lighting_status=torch.cat(status), lighting_flags=torch.cat(flags), gain=light[:, :, 0].double().mean(0).float())
+        def residual(rnd, i, view, model):
+            if light_step:
+                fit = ops.photo_lighting(self.verts, self._faces_lit, view.face, view.zbuf, model, view.pose, view.rgb, tau=self.tau0 if rnd == 0 else self.tau,
+                                         light=lights[i], mask=view.mask, gain_range=self.gain_range, apply=False)
+                failed = (fit["flags"] & fallback) != 0          # (status != 0: photo_lighting itself returns the incoming light)
+                keep = fit["light"] if rnd == 0 else torch.where(failed[:, None, None], lights[i], fit["light"])
+                lights[i], status[i], flags[i] = keep, fit["status"], fit["flags"]
+            out = lit(i, view, model, image=view.rgb, diag=True, sums=True)
+            sums = out["sums"].sum(0)
+            return out["grad"], out["diag"], sums[0], sums[1]
+
+        def extras():
+            light = torch.cat(lights)
+            return dict(light=light, lighting_status=torch.cat(status), lighting_flags=torch.cat(flags), gain=light[:, :, 0].double().mean(0).float())
+
+        return AttrDict(rounds=self.rounds, total_per_round=False, residual=residual, between=lambda i, view, shaded: lit(i, view, shaded)["grad"],
+                        sse=lambda i, view, model: lit(i, view, model, image=view.rgb, sums=True)["sums"].sum(0)[0], extras=extras)
+
+
+def _pcg(x: Tensor, r: Tensor, m_inv: Tensor, apply, after_step, iters: int) -> Tensor:
+    """``iters`` steps of preconditioned conjugate gradients from x, whose residual b - A x is r -> x.  ``apply(p)`` is A p, ``m_inv`` the
+    inverse of the diagonal preconditioner, ``after_step(x)`` is called after every step.  The scalars are 0-dim fp64 device tensors and a
+    vanishing denominator gives a zero step: nothing is read back."""
+    dot = lambda a, b: (a.double() * b.double()).sum()
+    zero, one = torch.zeros((), device=x.device, dtype=torch.float64), torch.ones((), device=x.device, dtype=torch.float64)
+    z = r * m_inv
+    p, rz = z.clone(), dot(r, z)
+    for _ in range(iters):
+        ap = apply(p)
+        pap = dot(p, ap)
+        alpha = torch.where(pap > 0, rz / torch.where(pap > 0, pap, one), zero)
+        x, r = x + alpha.float() * p, r - alpha.float() * ap
+        z = r * m_inv
+        rz_new = dot(r, z)
+        beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, one), zero)
+        p, rz = z + beta.float() * p, rz_new
+        after_step(x)
+    return x
 
 
 def inner_coverage(face: Tensor, F: int) -> Tensor:

@@ -135,10 +135,10 @@ def main(argv=None):
     # with --texel-res the nodes of the subdivided mesh are baked; its first V rows are the mesh's vertices, so the PLY comes from them
     texel_baker = None if a.texel_res is None else ft.FaceTexelBaker(verts, faces, a.texel_res, a.H, a.W, a.device, **thresholds)
     baker = tb.TextureBaker(verts, faces, a.H, a.W, a.device, **thresholds) if texel_baker is None else texel_baker.nodes
-    lit = dict(lighting=True, rounds=a.fit_lighting) if a.fit_lighting is not None else {}
+    fit_mode = dict(lighting=True, rounds=a.fit_lighting) if a.fit_lighting is not None else {}
     if a.fit_robust is not None:
-        lit = dict(robust=a.fit_robust, robust_rounds=6 if a.fit_robust_rounds is None else a.fit_robust_rounds)
-    fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit, **lit)
+        fit_mode = dict(robust=a.fit_robust, robust_rounds=6 if a.fit_robust_rounds is None else a.fit_robust_rounds)
+    fitter = None if a.fit is None else ft.FaceTexelFitter(verts, faces, a.texel_res, a.H, a.W, a.device, lam=a.fit_lambda, iters=a.fit, **fit_mode)
     light = torch.tensor(a.light_index, device=dev)
     kept = []                                                         # (rgb, mask) of every view, for --verify
     torch.cuda.synchronize(dev)
