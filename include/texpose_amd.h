@@ -1532,7 +1532,8 @@ int tp_joint_align_step(const tp_joint_align_args* j,
  *      step is fp64, evaluated as written (no contraction), and rounded to fp32 once.  rgb = (0, 0, 0), and nothing else is read,
  *      for face < 0 or >= F, a vertex index outside 0 .. V-1, a vertex with z <= 0 or a non-finite camera-frame coordinate, |area| <=
  *      1e-10 or not finite, and any non-finite w_k or colour.  Nothing is read out of bounds for any face plane or pose.  Point
- *      sampling: no minification filter.  One launch, one thread per pixel; no LDS, no atomics, no workspace, no allocation, no host
+ *      sampling (the minification filter is K43's tp_face_texel_shade_mip, below, not this entry point).  One launch, one thread
+ *      per pixel; no LDS, no atomics, no workspace, no allocation, no host
  *      synchronisation; the output is a function of the inputs alone.  Non-positive sizes, R outside 1 .. TP_FACE_TEXEL_MAX_R,
  *      H * W >= 2^31, F * T >= 2^31, B * ceil(H W / 256) >= 2^31 and null pointers are refused (-1, tp_last_error) and launch
  *      nothing.  Safe to capture.
@@ -1576,7 +1577,8 @@ int tp_face_texel_shade(const tp_face_texel_shade_args* args, tp_stream_t stream
  *      Four launches on the stream (one memset of the workspace, maximum, scatter, finalise), one thread per pixel; no host
  *      synchronisation, no allocation; safe to capture.  Everything K35 refuses, B H W > 2^25, U <= 0 with a node index, 3 N >= 2^31,
  *      a null or not 8-byte aligned workspace and a null grad_rgb or grad are refused (-1, tp_last_error) and launch nothing.
- *      Left out: gradients with respect to the pose or the vertices, second order, one R per face, a minification filter.
+ *      Left out: gradients with respect to the pose or the vertices, second order, one R per face, the adjoint of K43's
+ *      minification filter (the forward has one since K43, below).
  * ------------------------------------------------------------------------------------------ */
 typedef struct tp_face_texel_shade_bwd_args {
   const float* verts;        /* [V,3] as K35 */
@@ -1954,6 +1956,74 @@ typedef struct tp_robust_weight_args {
 } tp_robust_weight_args;
 size_t tp_robust_weight_workspace_bytes(int B, int H, int W);  /* 4 * B * H * W rounded up to 16, + 20512 * B; 0 for non-positive sizes */
 int tp_robust_weight(const tp_robust_weight_args* args, tp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K43  mip levels of a face-texel texture: a minification filter for K35's shading (texpose_amd/face_texels.py: mip_slots, build_mips,
+ *      TexelMips; texpose_amd/ops/scene.py: face_texel_mip_reduce, face_texel_shade_mip; restated in tests/face_texel_mip_ref.py; the
+ *      project's own step, no reference code).
+ *      The chain.  Level 0 is K35's texture [F, T(R), 3].  Level l has resolution R_l = R >> l and exists while R_(l-1) is even: L
+ *      levels need R % 2^(L-1) == 0.  Coarse node (I, J) of a face is fine node (2I, 2J) of the same face; every other fine node is
+ *      the midpoint of one coarse lattice edge.  The chain is ONE packed fp32 buffer: level l is a contiguous [F, T(R_l), 3] block at
+ *      element offset 3 F sum_{k<l} T(R_k); tp_face_texel_mip_elems(F, R, L) is its size in elements (0 for F <= 0, R outside 1 ..
+ *      TP_FACE_TEXEL_MAX_R, L < 1, R % 2^(L-1) != 0 or F sum T(R_k) >= 2^31).
+ *
+ * K43a tp_face_texel_mip_reduce: one level down, Rf (even) -> Rc = Rf / 2.  The filter is the normalised transpose of linear
+ *      prolongation (full weighting on the triangular lattice), written per coarse CELL so that it needs no valence and is the same
+ *      rule at mesh vertices, edges and open boundaries.  The slots (f Tc + n, Tc = T(Rc)) that name one unique node u of the coarse
+ *      grid come as a CSR pair: slot_list[slot_ptr[u] .. slot_ptr[u+1] - 1] (face_texels.mip_slots builds it from subdivide's
+ *      node_index by a stable argsort, so that the slots of a node ascend).  For node u, acc[3] = 0 and wacc = 0 in fp64; for every
+ *      slot s = f Tc + n of u in list order, n decoded to (I, J), the six directions d_0 .. d_5 = (1,0), (0,1), (-1,1), (-1,0), (0,-1),
+ *      (1,-1), and k = 0 .. 5 in order: where both (I,J) + d_k and (I,J) + d_((k+1)%6) are nodes of the coarse grid (i, j >= 0, i + j
+ *      <= Rc) the pair is a coarse cell of f at this corner, and per channel
+ *        acc  = acc + ((2 x(2I,2J) + 3 x((2I,2J) + d_k)) + 3 x((2I,2J) + d_((k+1)%6))),   wacc = wacc + 8,
+ *      x face f's OWN fine texels (fp32 -> fp64), every product and sum fp64 as written.  The value (float)(acc / wacc) is written to
+ *      every slot of u.  On a closed manifold that is x_c / 4 + 3/4 of the mean of the incident edge midpoints, whatever the valence;
+ *      a constant texture comes back bit for bit; a non-finite texel propagates.  Entries of slot_list outside 0 .. F Tc - 1 are
+ *      skipped and never dereferenced, and a range of slot_ptr is cut to 0 .. F Tc; a node without a valid slot writes nothing.  The
+ *      call first clears `coarse` (one asynchronous memset), then one launch, one thread per unique node: no atomics, no float
+ *      reduction across threads, no workspace, no host synchronisation; the output is a function of the inputs alone (for a slot_list
+ *      that names every slot at most once).  Safe to capture.  Refused (-1, tp_last_error), nothing launched: null pointers, F <= 0,
+ *      U <= 0, Rf odd or outside 2 .. TP_FACE_TEXEL_MAX_R, F T(Rf) >= 2^31.
+ *
+ * K43b tp_face_texel_shade_mip: K35 with a level chosen and blended per pixel.  Arguments as K35, with `mips` (the packed chain) in
+ *      the place of texels, L its number of levels, and footprint, finite and > 0: a multiplier on the texel density (an LOD bias of
+ *      log2(footprint) / 2; 1 is the rule as derived).  Per pixel: K35's step 1 gives w_0, w_1, w_2 (once; the SAME device function as
+ *      K35, texpose_amd/csrc/face_texel_cell.h) and, from the values it has formed already,
+ *        d = (((double)footprint (double)(R R)) |(iz_0 iz_1) iz_2|) / (|area| ((|S| |S|) |S|)),   iz_k = 1 / z_k, S = (t_0 + t_1) + t_2
+ *      before the clamp: the texel cells of level 0 per pixel, the determinant of d(R w_1, R w_2) / d(px, py) -- 1 / area for the
+ *      screen barycentrics times iz_0 iz_1 iz_2 / S^3 for the perspective map.  Level selection, without a transcendental:
+ *        d <= 1, L = 1 or d not finite:  level 0 alone; only level 0 is read and the colour is K35's expression exactly;
+ *        otherwise e = ilogb(d), l0 = min(e >> 1, L - 1);   l0 = L - 1:  level L - 1 alone;
+ *        otherwise t = (ldexp(d, -2 l0) - 1) / 3  (an exact scaling, one subtraction, one division; 0 <= t < 1);  t = 0: level l0
+ *        alone; else c = (1 - t) c_l0 + t c_(l0+1) per channel in fp64.
+ *      Each c_l is K35's step 2 and three-product sum on level l's texels at R_l under the same w.  Rounded to fp32 once.  The zero
+ *      rules and out-of-bounds guarantees are K35's; a non-finite colour at a level that is read gives zero.  One launch, one thread
+ *      per pixel, 256 per workgroup, K35's grid; no LDS, no atomics, no workspace, no host synchronisation; safe to capture.
+ *      Refused: everything K35 refuses, tp_face_texel_mip_elems(F, R, L) == 0 and a footprint that is not finite or <= 0.
+ *      Left out: the adjoint of the mip shade and the refiners / the fitter's forward on it, an anisotropic footprint (the area
+ *      measure under-filters at grazing angles), one R per face.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tp_face_texel_mip_reduce_args {
+  const float* fine;         /* [F,T(Rf),3] */
+  const int32_t* slot_ptr;   /* [U+1] */
+  const int32_t* slot_list;  /* [F*T(Rf/2)] (any values: entries outside 0 .. F*T(Rf/2)-1 are skipped) */
+  int F, Rf, U;
+  float* coarse;             /* [F,T(Rf/2),3] out; cleared by the call */
+} tp_face_texel_mip_reduce_args;
+typedef struct tp_face_texel_shade_mip_args {
+  const float* verts;        /* [V,3] as K35 */
+  const int32_t* faces;      /* [F,3] */
+  const float* mips;         /* the packed chain: tp_face_texel_mip_elems(F, R, L) floats */
+  const float* pose;         /* [B,3,4] */
+  const float* intr;         /* [B,3,3] */
+  const int32_t* face;       /* [B,H,W] K19's face plane (any values) */
+  int B, H, W, V, F, R, L;
+  float footprint;           /* finite, > 0; 1: the rule as derived */
+  float* rgb;                /* [B,H,W,3] out */
+} tp_face_texel_shade_mip_args;
+int64_t tp_face_texel_mip_elems(int F, int R, int L);     /* 3 F sum_{l<L} T(R >> l); 0 for anything refused */
+int tp_face_texel_mip_reduce(const tp_face_texel_mip_reduce_args* args, tp_stream_t stream);
+int tp_face_texel_shade_mip(const tp_face_texel_shade_mip_args* args, tp_stream_t stream);
 
 #ifdef __cplusplus
 }

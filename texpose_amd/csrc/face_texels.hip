@@ -22,7 +22,8 @@
 //
 // K36 tp_face_texel_shade_bwd: the adjoint of K35 with respect to the texels (restated in tests/face_texel_fit_ref.py).
 // K35 is linear in the texels: a pixel that it shades by rule reads three slots n_a, n_b, n_c of its face f with the weights w_a, w_b,
-// w_c of step 2 (face_texel_cell below, the ONE source of steps 1 and 2 for both kernels).  The adjoint adds w_k g_p (3 channels) to the
+// w_c of step 2 (face_texel_cell of face_texel_cell.h, the ONE source of steps 1 and 2 for K35, K36 and K43b).  The adjoint adds w_k g_p (3
+// channels) to the
 // destination d(f, n_k): the slot f T + n_k itself, or node_index[f T + n_k] where a node index is given (entries outside 0 .. U-1 are
 // skipped); `weight` is the same sum with g = 1 (the coverage: the lumped diagonal of S^T S).  A pixel contributes nothing where K35
 // writes zeros by its geometric rules, and nothing where a component of its grad_rgb is not finite.  K35's "non-finite colour -> zero"
@@ -44,68 +45,10 @@
 // One thread per pixel, 256 per workgroup, the image index uniform over the workgroup, no LDS.  A background pixel returns after one
 // 4-byte load; a pixel whose gradient is all zeros (a masked one) after 16 bytes unless the coverage is wanted.
 #include "tp_common.h"
+#include "face_texel_cell.h"
 
 namespace {
 constexpr int kShadeBlock = 256;
-
-// Steps 1 and 2 of the rule for pixel (row i, column j) under face f, 0 <= f < F: the three slots of the face's T texels and their weights,
-// in the order the forward adds them (A, B, C).  false: the pixel is one that K35 shades to zero by rule.
-struct TexelCell {
-  int n[3];
-  double w[3];
-};
-
-__device__ __forceinline__ bool face_texel_cell(const float* __restrict__ verts, const int32_t* __restrict__ faces, const float* P, const float* K,
-                                                int V, int R, int f, int i, int j, TexelCell& cell) {
-  double u[3], v[3], iz[3];
-  for (int k = 0; k < 3; ++k) {
-    const int vi = faces[3 * (int64_t)f + k];
-    if (vi < 0 || vi >= V) return false;
-    const double X = verts[3 * (int64_t)vi], Y = verts[3 * (int64_t)vi + 1], Z = verts[3 * (int64_t)vi + 2];
-    double c[3];
-    for (int r = 0; r < 3; ++r) c[r] = (double)P[4 * r] * X + (double)P[4 * r + 1] * Y + (double)P[4 * r + 2] * Z + (double)P[4 * r + 3];
-    if (!(c[2] > 0.0) || !isfinite(c[0]) || !isfinite(c[1]) || !isfinite(c[2])) return false;
-    const double q0 = (double)K[0] * c[0] + (double)K[1] * c[1] + (double)K[2] * c[2];
-    const double q1 = (double)K[3] * c[0] + (double)K[4] * c[1] + (double)K[5] * c[2];
-    const double q2 = (double)K[6] * c[0] + (double)K[7] * c[1] + (double)K[8] * c[2];
-    u[k] = q0 / q2;
-    v[k] = q1 / q2;
-    iz[k] = 1.0 / c[2];
-  }
-  const double area = (u[1] - u[0]) * (v[2] - v[0]) - (v[1] - v[0]) * (u[2] - u[0]);
-  if (!(isfinite(area) && fabs(area) > 1e-10)) return false;
-  const double px = (double)j + 0.5, py = (double)i + 0.5;
-  double t[3], w[3];
-  for (int k = 0; k < 3; ++k) {
-    const int s = (k + 1) % 3, e = (k + 2) % 3;       // b_k: the edge opposite vertex k, from vertex s to vertex e
-    const double ex = u[e] - u[s], ey = v[e] - v[s];
-    t[k] = ((ex * (py - v[s]) - ey * (px - u[s])) / area) * iz[k];
-  }
-  const double sum = (t[0] + t[1]) + t[2];
-  for (int k = 0; k < 3; ++k) {
-    w[k] = t[k] / sum;
-    w[k] = w[k] < 0.0 ? 0.0 : w[k];
-  }
-  const double s2 = (w[0] + w[1]) + w[2];
-  for (int k = 0; k < 3; ++k) w[k] = w[k] / s2;
-  if (!(isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]))) return false;     // (then every w_k is in [0, 1])
-  const double ta = (double)R * w[1], tb = (double)R * w[2];
-  int ci = (int)floor(ta), cj = (int)floor(tb);
-  ci = ci < R - 1 ? ci : R - 1;
-  cj = cj < R - 1 - ci ? cj : R - 1 - ci;
-  const double fa = ta - (double)ci, fb = tb - (double)cj;
-  const bool upper = fa + fb > 1.0 && ci + cj <= R - 2;
-  // node (i, j) at j (R + 1) - j (j - 1) / 2 + i; the row above starts R + 1 - j further on
-  const int n00 = cj * (R + 1) - (cj * (cj - 1)) / 2 + ci;
-  const int n01 = n00 + (R + 1 - cj);                   // (i, j + 1)
-  cell.n[0] = upper ? n01 + 1 : n00;                    // (i + 1, j + 1) or (i, j)
-  cell.n[1] = n00 + 1;                                  // (i + 1, j)
-  cell.n[2] = n01;                                      // (i, j + 1)
-  cell.w[0] = upper ? (fa + fb) - 1.0 : (1.0 - fa) - fb;
-  cell.w[1] = upper ? 1.0 - fb : fa;
-  cell.w[2] = upper ? 1.0 - fa : fb;
-  return true;
-}
 
 __global__ __launch_bounds__(kShadeBlock) void face_texel_shade_kernel(tp_face_texel_shade_args a, int blocks_per_image, int T) {
   const int b = (int)(blockIdx.x / (unsigned)blocks_per_image);                  // workgroup-uniform
@@ -120,11 +63,7 @@ __global__ __launch_bounds__(kShadeBlock) void face_texel_shade_kernel(tp_face_t
     const int i = (int)(rem / a.W), j = (int)(rem - (int64_t)i * a.W);
     TexelCell cell;
     if (face_texel_cell(a.verts, a.faces, a.pose + 12 * (int64_t)b, a.intr + 9 * (int64_t)b, a.V, a.R, f, i, j, cell)) {
-      const float* tex = a.texels + 3 * ((int64_t)f * T);
-      const float* A = tex + 3 * (int64_t)cell.n[0];
-      const float* Bn = tex + 3 * (int64_t)cell.n[1];
-      const float* Cn = tex + 3 * (int64_t)cell.n[2];
-      for (int c = 0; c < 3; ++c) col[c] = (cell.w[0] * (double)A[c] + cell.w[1] * (double)Bn[c]) + cell.w[2] * (double)Cn[c];
+      face_texel_colour(a.texels + 3 * ((int64_t)f * T), cell, col);
       if (!(isfinite(col[0]) && isfinite(col[1]) && isfinite(col[2]))) col[0] = col[1] = col[2] = 0.0;
     }
   }

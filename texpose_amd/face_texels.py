@@ -7,8 +7,10 @@ of the base mesh while the colour becomes R x finer along each edge.  The nodes 
 subdivided R times (``subdivide``), which is how a texture is baked -- ``FaceTexelBaker`` runs the unchanged vertex bake (K27) on those
 points -- and what the shading is tested against: texels on the base mesh equal vertex colours on the subdivided one.
 
-Point sampling only (no minification filter: pick R with ``resolution_for`` so that a texel is about a pixel), one R per mesh, no UV
-atlas.
+``ops.face_texel_shade`` point-samples (pick R with ``resolution_for`` so that a texel is about a pixel).  Where one texture is seen
+over a range of distances, ``build_mips`` makes the chain of coarser levels (K43a) and ``ops.face_texel_shade_mip`` /
+``ops.mesh_raster(texel_mips=)`` shade through it, choosing and blending two levels per pixel (K43b).  One R per
+mesh, no UV atlas.
 
 Gradients with respect to the texture come from K36 (tp_face_texel_shade_bwd), the deterministic adjoint of the
 shading: ``autograd_ops.face_texel_shade`` (per-slot texels), ``shade_nodes`` (node colours shared between faces) and
@@ -137,6 +139,71 @@ def subdivide(verts, faces, R: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]
                 cells.append((n(i + 1, j), n(i + 1, j + 1), n(i, j + 1)))
     faces_sub = node_index[:, np.array(cells, dtype=np.int64)].reshape(-1, 3).astype(np.int32)
     return verts_sub, faces_sub, node_index
+
+
+def mip_levels(R: int) -> int:
+    """The number of levels the chain of a texture of resolution R can have: level l has R >> l and exists while the one before is
+    even, so 1 + the number of times 2 divides R (64 -> 7, 6 -> 2, an odd R -> 1)."""
+    texel_count(R)
+    R, L = int(R), 1
+    while R % 2 == 0:
+        R, L = R // 2, L + 1
+    return L
+
+
+def mip_slots(verts, faces, Rc: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The slots of every unique node of the grid of resolution Rc as a CSR pair, for ops.face_texel_mip_reduce INTO that grid ->
+    (slot_ptr [U+1] int32, slot_list [F T(Rc)] int32): node u is named by the slots slot_list[slot_ptr[u] : slot_ptr[u+1]] (f T + n,
+    ascending), from ``subdivide``'s node_index by a stable argsort."""
+    node_index = subdivide(verts, faces, Rc)[2].reshape(-1)
+    U = int(node_index.max()) + 1 if node_index.size else 0
+    slot_list = np.argsort(node_index, kind="stable").astype(np.int32)
+    slot_ptr = np.concatenate([[0], np.cumsum(np.bincount(node_index, minlength=U))]).astype(np.int32)
+    return slot_ptr, slot_list
+
+
+class TexelMips:
+    """The mip chain of a face-texel texture on the device: ``R`` (level 0's resolution), ``L`` levels, ``F`` faces and ``packed``,
+    ONE float32 buffer in which level l is the contiguous [F, T(R >> l), 3] block at element offset 3 F sum_{k<l} T(R >> k).
+    ``level(l)`` is a view of it."""
+
+    def __init__(self, R: int, L: int, F: int, packed: Tensor):
+        self.R, self.L, self.F, self.packed = int(R), int(L), int(F), packed
+        self._offsets = np.concatenate([[0], np.cumsum([3 * self.F * texel_count(self.R >> l) for l in range(self.L)])])
+        if not 1 <= self.L <= mip_levels(self.R) or packed.dim() != 1 or packed.numel() != int(self._offsets[-1]):
+            raise ValueError("TexelMips: R = %d allows 1 .. %d levels and L = %d of them over %d faces hold %d values, got %d"
+                             % (self.R, mip_levels(self.R), self.L, self.F, int(self._offsets[-1]), packed.numel()))
+
+    def level(self, l: int) -> Tensor:
+        """Level l as [F, T(R >> l), 3] (a view of ``packed``)."""
+        if not 0 <= int(l) < self.L:
+            raise ValueError("TexelMips.level: level in 0 .. %d expected, got %r" % (self.L - 1, l))
+        return self.packed[int(self._offsets[l]):int(self._offsets[l + 1])].view(self.F, texel_count(self.R >> int(l)), 3)
+
+
+def build_mips(verts, faces, texels, levels: Optional[int] = None) -> TexelMips:
+    """The mip chain of ``texels`` [F,T(R),3] (a tensor on the device, or anything torch.as_tensor takes: then on cuda:0) over the mesh
+    (verts, faces) they belong to -> TexelMips with ``levels`` levels (None: as many as R allows, ``mip_levels``).  Level 0 is the
+    texture itself; every further level is one ops.face_texel_mip_reduce (K43a) of the one before, with the CSR of ``mip_slots``.
+    Nothing is stored on disk: save_texels keeps level 0 and the chain is rebuilt from it in milliseconds."""
+    t = texels if torch.is_tensor(texels) else torch.as_tensor(np.asarray(texels, dtype=np.float32))
+    t = t.detach().to(device=t.device if t.is_cuda else "cuda:0", dtype=torch.float32).contiguous()
+    f = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int32).reshape(-1, 3)
+    v = (verts.detach().cpu().numpy() if torch.is_tensor(verts) else np.asarray(verts)).astype(np.float32).reshape(-1, 3)
+    if t.dim() != 3 or t.shape[0] != len(f) or t.shape[2] != 3:
+        raise ValueError("build_mips: texels [F=%d,T,3] expected, got %s" % (len(f), tuple(t.shape)))
+    R = resolution_of(t.shape[1])
+    L = mip_levels(R) if levels is None else int(levels)
+    if not 1 <= L <= mip_levels(R):
+        raise ValueError("build_mips: R = %d allows 1 .. %d levels, got %r" % (R, mip_levels(R), levels))
+    sizes = [3 * len(f) * texel_count(R >> l) for l in range(L)]
+    mips = TexelMips(R, L, len(f), torch.empty(sum(sizes), device=t.device))
+    mips.level(0).copy_(t)
+    for l in range(1, L):
+        slot_ptr, slot_list = mip_slots(v, f, R >> l)
+        ops.face_texel_mip_reduce(mips.level(l - 1), torch.from_numpy(slot_ptr).to(t.device), torch.from_numpy(slot_list).to(t.device),
+                                  out=mips.level(l))
+    return mips
 
 
 def texels_from_nodes(colour_sub, node_index):

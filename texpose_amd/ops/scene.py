@@ -1,5 +1,5 @@
-"""K19-K22, K27, K35, K36, K41, K42: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake, the face-texel shading, its
-adjoint, its lighting step and the robust weights of its residual."""
+"""K19-K22, K27, K35, K36, K41, K42, K43: the mesh rasteriser, the surfel maps, the BOP scene writers, the texture bake, the face-texel
+shading, its adjoint, its lighting step, the robust weights of its residual and its mip levels."""
 import math
 from typing import Dict, Optional, Tuple
 
@@ -10,7 +10,8 @@ from ._base import (Tensor, _call, _f32, _float3, _intr_per_view, _on_tensor_dev
 
 __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_finish", "SCENE_SOURCES", "SCENE_BOUNDS_KEYS", "scene_bounds",
            "SCENE_INFO_KEYS", "scene_annotate", "view_images", "texture_bake_workspace", "texture_bake", "face_texel_shade", "face_texel_shade_bwd",
-           "face_texel_light_workspace", "face_texel_light", "ROBUST_KINDS", "robust_weight_workspace", "robust_weight"]
+           "face_texel_light_workspace", "face_texel_light", "ROBUST_KINDS", "robust_weight_workspace", "robust_weight", "face_texel_mip_reduce",
+           "face_texel_shade_mip"]
 
 
 # ------------------------------------------------------------------------------------------ K19
@@ -18,7 +19,7 @@ __all__ = ["mesh_raster", "normals_from_depth", "SURFEL_FINISH_KEYS", "surfel_fi
 def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: int, W: int, vcolor: Optional[Tensor] = None,
                 nocs_norm: Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]] = None,
                 face_ids: bool = True, normals: bool = True, zbuf_out: Optional[Tensor] = None, cull: bool = False,
-                texels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                texels: Optional[Tensor] = None, texel_mips=None) -> Dict[str, Tensor]:
     """Hard rasterisation of one mesh at B poses (tp_mesh_raster).  verts [V,3] and pose [B,3,4] ([R|t], t) in the same units (mm),
     faces [F,3] int, intr [B,3,3] or [3,3].  Returns zbuf [B,H,W] (-1 on background) and, as asked, face [B,H,W] int32, rgb
     (``vcolor`` [V,3] given), nocs (``nocs_norm`` = (centre, max-abs) per axis given) and normal, each [B,H,W,3].
@@ -26,9 +27,13 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     ``cull``: tp_mesh_raster_culled, which skips whole chunks of 256 faces per 16 x 16 tile by their union box: the same planes bit for
     bit, one launch more (K34).
     ``texels`` [F,T(R),3] instead of ``vcolor``: rgb comes from the per-face texel texture (face_texel_shade on the face plane, which
-    is then rendered and returned whatever ``face_ids`` says; K35)."""
-    if texels is not None and vcolor is not None:
+    is then rendered and returned whatever ``face_ids`` says; K35).
+    ``texel_mips`` (face_texels.build_mips of this mesh's texels) in the place of ``texels``, or beside the texels it was built from:
+    rgb comes from face_texel_shade_mip, the shading with a minification filter (K43)."""
+    if (texels is not None or texel_mips is not None) and vcolor is not None:
         raise ValueError("mesh_raster: vcolor or texels, not both")
+    if texel_mips is not None and texels is not None and (texels.dim() != 3 or texels.shape[1] != (texel_mips.R + 1) * (texel_mips.R + 2) // 2):
+        raise ValueError("mesh_raster: texel_mips of resolution %d were not built from texels %s" % (texel_mips.R, tuple(texels.shape)))
     verts, pose = _f32(verts, "verts"), _f32(pose, "pose")
     if pose.dim() == 2:
         pose = pose[None]
@@ -45,7 +50,7 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
     a.verts, a.faces, a.pose, a.intr = verts.data_ptr(), faces.data_ptr(), pose.data_ptr(), intr.data_ptr()
     a.B, a.H, a.W, a.V, a.F = B, H, W, V, F
     out = {"zbuf": torch.empty(B, H, W, device=dev) if zbuf_out is None else _want_gpu("mesh_raster", zbuf_out, "zbuf_out", torch.float32, (B, H, W))}
-    if face_ids or texels is not None:
+    if face_ids or texels is not None or texel_mips is not None:
         out["face"] = torch.empty(B, H, W, device=dev, dtype=torch.int32)
     if vcolor is not None:
         vcolor = _f32(vcolor, "vcolor")
@@ -67,7 +72,9 @@ def mesh_raster(verts: Tensor, faces: Tensor, pose: Tensor, intr: Tensor, *, H: 
         _call("tp_mesh_raster_culled", a)
     else:
         _call("tp_mesh_raster", a)
-    if texels is not None:
+    if texel_mips is not None:
+        out["rgb"] = face_texel_shade_mip(out["face"], verts, faces, texel_mips, pose, intr)
+    elif texels is not None:
         out["rgb"] = face_texel_shade(out["face"], verts, faces, texels, pose, intr)
     return out
 
@@ -443,3 +450,75 @@ def robust_weight(model: Tensor, image: Tensor, *, weight: Optional[Tensor] = No
         a.workspace = workspace.data_ptr()
     _call("tp_robust_weight", a)          # (bad c or sigma_min, outputs overlapping inputs or each other: the library's error)
     return res
+
+
+# ------------------------------------------------------------------------------------------ K43
+@_on_tensor_device
+def face_texel_mip_reduce(texels: Tensor, slot_ptr: Tensor, slot_list: Tensor, *, out: Optional[Tensor] = None) -> Tensor:
+    """One mip level down (tp_face_texel_mip_reduce, K43a; the rule is in the header): texels [F,T(Rf),3] with Rf even, the CSR pair
+    of the COARSE grid's unique nodes (face_texels.mip_slots(verts, faces, Rf // 2): slot_ptr [U+1], slot_list [F T(Rf/2)], any
+    integer type) -> [F,T(Rf/2),3] float32.  ``out``: the tensor to write into (e.g. a level of the packed chain).  One memset and
+    one launch, no workspace, bit-identical from run to run, safe under torch.cuda.graph."""
+    op = "face_texel_mip_reduce"
+    if not torch.is_tensor(texels) or not texels.is_cuda:
+        raise ValueError("%s: texels must be a GPU tensor" % op)
+    texels = _f32(texels.detach(), "texels")
+    F, Tf = (texels.shape[0], texels.shape[1]) if texels.dim() == 3 else (0, 0)
+    Rf = (math.isqrt(8 * Tf + 1) - 3) // 2
+    lib = _lib.load()
+    if F == 0 or tuple(texels.shape) != (F, Tf, 3) or lib.tp_face_texel_count(Rf) != Tf or Rf % 2:
+        raise ValueError("%s: texels [F,T,3] with T = (R + 1)(R + 2) / 2 for an even R in 2 .. %d expected, got %s"
+                         % (op, _lib.FACE_TEXEL_MAX_R, tuple(texels.shape)))
+    Tc = int(lib.tp_face_texel_count(Rf // 2))
+    for t, name in ((slot_ptr, "slot_ptr"), (slot_list, "slot_list")):
+        if not torch.is_tensor(t) or t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
+            raise ValueError("%s: %s must be a one-dimensional integer tensor" % (op, name))
+    if slot_ptr.numel() < 2 or slot_list.numel() != F * Tc:
+        raise ValueError("%s: slot_ptr [U+1] and slot_list [F T(R/2) = %d] expected, got %d and %d entries"
+                         % (op, F * Tc, slot_ptr.numel(), slot_list.numel()))
+    slot_ptr = slot_ptr.to(device=texels.device, dtype=torch.int32).contiguous()
+    slot_list = slot_list.to(device=texels.device, dtype=torch.int32).contiguous()
+    coarse = torch.empty(F, Tc, 3, device=texels.device) if out is None else _want_gpu(op, out, "out", torch.float32, (F, Tc, 3))
+    a = _lib.FaceTexelMipReduceArgs()
+    a.fine, a.slot_ptr, a.slot_list, a.coarse = texels.data_ptr(), slot_ptr.data_ptr(), slot_list.data_ptr(), coarse.data_ptr()
+    a.F, a.Rf, a.U = F, Rf, slot_ptr.numel() - 1
+    _call("tp_face_texel_mip_reduce", a)
+    return coarse
+
+
+@_on_tensor_device
+def face_texel_shade_mip(face: Tensor, verts: Tensor, faces: Tensor, mips, pose: Tensor, intr: Tensor, *, footprint: float = 1.0,
+                         out: Optional[Tensor] = None) -> Tensor:
+    """face_texel_shade with a minification filter (tp_face_texel_shade_mip, K43b; the rule is in the header): ``mips`` is the chain
+    face_texels.build_mips made of this mesh's texels (anything with ``packed`` -- the packed float32 levels on the device --, ``R``
+    and ``L``); the other arguments are face_texel_shade's.  Per pixel the texel density d (level-0 cells per pixel, closed form) picks
+    two adjacent levels and blends them; a magnified pixel (d <= 1) is face_texel_shade's pixel bit for bit.  ``footprint`` > 0
+    multiplies d (an LOD bias of log2(footprint) / 2).  One launch, no workspace, bit-identical from run to run, safe under
+    torch.cuda.graph.  Not differentiable."""
+    op = "face_texel_shade_mip"
+    _want_gpu(op, face, "face", torch.int32, None)
+    if face.dim() != 3 or face.numel() == 0:
+        raise ValueError("%s: face [B,H,W] expected, got %s" % (op, tuple(face.shape)))
+    B, H, W = face.shape
+    verts, pose = _points(op, verts, "verts"), _poses(op, pose, "pose", B)
+    intr = _intr_per_view(op, intr, B)
+    faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+    V, F = verts.shape[0], faces.shape[0]
+    if tuple(faces.shape) != (F, 3) or F == 0:
+        raise ValueError("%s: faces [F,3] expected, got %s" % (op, tuple(faces.shape)))
+    packed, R, L = (getattr(mips, k, None) for k in ("packed", "R", "L"))
+    if not torch.is_tensor(packed) or R is None or L is None:
+        raise ValueError("%s: mips must carry packed, R and L (face_texels.build_mips)" % op)
+    packed = _want_gpu(op, packed.detach(), "mips.packed", torch.float32, None)
+    need = int(_lib.load().tp_face_texel_mip_elems(F, int(R), int(L)))
+    if need == 0 or packed.dim() != 1 or packed.numel() != need:
+        raise ValueError("%s: mips of R = %r, L = %r with %d values do not belong to a mesh of %d faces (%d values expected)"
+                         % (op, R, L, packed.numel(), F, need))
+    if not (math.isfinite(footprint) and footprint > 0):
+        raise ValueError("%s: footprint must be finite and > 0, got %r" % (op, footprint))
+    rgb = torch.empty(B, H, W, 3, device=face.device) if out is None else _want_gpu(op, out, "out", torch.float32, (B, H, W, 3))
+    a = _lib.FaceTexelShadeMipArgs()
+    a.verts, a.faces, a.mips, a.pose, a.intr, a.face = (t.data_ptr() for t in (verts, faces, packed, pose, intr, face))
+    a.B, a.H, a.W, a.V, a.F, a.R, a.L, a.footprint, a.rgb = B, H, W, V, F, int(R), int(L), float(footprint), rgb.data_ptr()
+    _call("tp_face_texel_shade_mip", a)
+    return rgb

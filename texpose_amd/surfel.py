@@ -221,8 +221,9 @@ def calibrate_pose(pose: torch.Tensor, depth_scale: float) -> torch.Tensor:
 class SurfelRenderer:
     """The colour + NOCS renders and normals of compute_surfelinfo for one CAD mesh at batches of poses (one tp_mesh_raster call)."""
 
-    def __init__(self, verts, faces, vcolor=None, H: int = 480, W: int = 640, device="cuda:0", cull: bool = False, texels=None):
-        if vcolor is not None and texels is not None:
+    def __init__(self, verts, faces, vcolor=None, H: int = 480, W: int = 640, device="cuda:0", cull: bool = False, texels=None,
+                 texel_mips=None):
+        if vcolor is not None and (texels is not None or texel_mips is not None):
             raise ValueError("SurfelRenderer: vcolor or texels, not both")
         self.device = torch.device(device)
         self.cull = bool(cull)                 # render with ops.mesh_raster(cull=True): the same bits (K34; DESIGN section 24)
@@ -233,6 +234,8 @@ class SurfelRenderer:
         self.vcolor = None if vcolor is None else torch.as_tensor(np.asarray(vcolor, dtype=np.float32)).to(self.device)
         # [F,T,3] face texels (K35): rgb from ops.mesh_raster(texels=) instead of the vertex colours
         self.texels = None if texels is None else torch.as_tensor(texels, dtype=torch.float32).to(self.device).contiguous()
+        # face_texels.build_mips of the texels (K43): rgb through the minification filter, over the range of depths
+        self.texel_mips = texel_mips
 
     def _raster(self, pose, intr, depth_scale: float):
         pose = torch.as_tensor(pose, dtype=torch.float32).to(self.device)
@@ -240,7 +243,7 @@ class SurfelRenderer:
             pose = pose[None]
         intr = torch.as_tensor(intr, dtype=torch.float32).to(self.device)
         return ops.mesh_raster(self.verts, self.faces, calibrate_pose(pose, depth_scale), intr, H=self.H, W=self.W, vcolor=self.vcolor,
-                               texels=self.texels, nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True, cull=self.cull)
+                               texels=self.texels, texel_mips=self.texel_mips, nocs_norm=(self.nocs_center, self.nocs_scale), face_ids=False, normals=True, cull=self.cull)
 
     def __call__(self, pose, intr, depth_scale: float) -> AttrDict:
         """pose [B,3,4] (t in nerf.depth.scale units, like pose_init), intr [B,3,3] or [3,3] ->

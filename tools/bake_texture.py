@@ -16,6 +16,9 @@ prints (and stores) the PSNR against the NeRF views inside the mask; nothing is 
 the vertices along every edge, no UV unwrap) from the same views and write it as <out>.texels.npz beside the PLY (texels, R and the
 faces it belongs to; refine_poses.py --texels reads it).  The PLY still holds the vertex colours, now the texture's corner nodes;
 --verify then re-renders through the texels, and the report gains 'texels' (R, nodes, coloured, filled, unseen, file).
+--texel-mips [L] (with --texel-res): build the texture's mip chain (face_texels.build_mips, K43; L levels, default as
+many as R allows) and let --verify re-render through ops.mesh_raster(texel_mips=), the shading with a minification filter; the report's
+'texels' gains 'mip_levels'.  The files written are the same: the chain is rebuilt from level 0 wherever it is wanted.
 --fit ITERS [--fit-lambda L] (with --texel-res): the views also go into a face_texels.FaceTexelFitter (inner pixels
 of the mask, weight 1), and after the bake ITERS steps of preconditioned conjugate gradients from the baked nodes, with the baked nodes
 as the prior (weight L, default 0.1), minimise the difference between the texel render and the views (K36 tp_face_texel_shade_bwd).
@@ -55,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--report", default=None, metavar="JSON")
     ap.add_argument("--verify", action="store_true", help="re-render the baked mesh and print the PSNR against the NeRF views")
     ap.add_argument("--texel-res", type=int, default=None, metavar="R", help="also write <out>.texels.npz: face texels of resolution R")
+    ap.add_argument("--texel-mips", type=int, nargs="?", const=0, default=None, metavar="L",
+                    help="with --texel-res: --verify renders through the texture's mip chain of L levels (default: all R allows)")
     ap.add_argument("--fit", type=int, default=None, metavar="ITERS", help="with --texel-res: fit the texels to the views by ITERS steps of CG")
     ap.add_argument("--fit-lambda", type=float, default=0.1, metavar="L", help="weight of the baked texture as the fit's prior")
     ap.add_argument("--fit-photos", default=None, metavar="NPZ", help="with --fit: fit to these photographs (rgb, pose in mm, intr)")
@@ -82,6 +87,10 @@ def main(argv=None):
         ap.error("--sphere N needs N >= 1 and --distance-mm D > 0")
     if a.texel_res is not None and not 1 <= a.texel_res <= 64:
         ap.error("--texel-res R needs R in 1 .. 64")
+    if a.texel_mips is not None:
+        allowed = 0 if a.texel_res is None else (a.texel_res & -a.texel_res).bit_length()      # 1 + the number of times 2 divides R
+        if not 0 <= a.texel_mips <= allowed or (a.texel_mips == 0 and a.texel_res is None):
+            ap.error("--texel-mips [L] needs --texel-res R and 1 <= L <= %d (R must be a multiple of 2^(L-1))" % max(allowed, 1))
     if a.fit is not None and (a.texel_res is None or a.fit < 1 or not a.fit_lambda > 0):
         ap.error("--fit ITERS needs --texel-res R, ITERS >= 1 and --fit-lambda L > 0")
     if a.fit is None and (a.fit_photos is not None or a.fit_lighting is not None):
@@ -209,6 +218,8 @@ def main(argv=None):
         U = len(texel_baker.verts_sub)
         report["texels"] = dict(R=a.texel_res, per_face=int(texels.shape[1]), nodes=U, coloured=float(sub.seen.sum()) / U, filled=sub.filled,
                                 unseen=sub.unseen, file=texel_file)
+        if a.texel_mips is not None:
+            report["texels"]["mip_levels"] = a.texel_mips or ft.mip_levels(a.texel_res)
     if fit is not None:
         report["fit"] = fit
         print("bake_texture: fit of %d nodes, %d iterations, lambda %g: training rms %.5f -> %.5f, %d nodes on the prior"
@@ -225,10 +236,12 @@ def main(argv=None):
 
         def rerender(texels):
             se, px = 0.0, 0
+            mips = None if texels is None or a.texel_mips is None else ft.build_mips(base_verts, base_faces, texels, a.texel_mips or None)
             with torch.no_grad():
                 for c, (rgb, mask) in zip(range(0, N, a.chunk), kept):
                     r = ops.mesh_raster(base_verts, base_faces, tb.poses_to_mm(pose[c:c + a.chunk], scale).contiguous(), intr[c:c + a.chunk],
-                                        H=a.H, W=a.W, vcolor=res.vcolor if texels is None else None, texels=texels, face_ids=False, normals=False)
+                                        H=a.H, W=a.W, vcolor=res.vcolor if texels is None else None, texels=texels, texel_mips=mips, face_ids=False,
+                                        normals=False)
                     m = mask & (r["zbuf"] > 0)
                     se += float((((r["rgb"] - rgb.clamp(0, 1)) ** 2).sum(-1) * m).double().sum())
                     px += int(m.sum())
